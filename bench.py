@@ -323,6 +323,29 @@ def time_stages(faces, textures, S, eps, g_rgb, g_alpha, g_depth, iters, k6_flag
 time_stages.band_kernel = {}
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs: float32 values written in all (under 64 MB with the .npy headers)
+DUMP_SEED = 0
+
+
+def dump_sample(arrays):
+    """--dump-outputs: {name: tensor} -> {name: (float32 array, full shape, full element count)} within DUMP_BYTES in all.  The
+    smaller arrays are taken whole; the budget left is shared evenly by the larger ones, each of which gives the elements at
+    sorted(np.random.default_rng(DUMP_SEED).choice(numel, k, replace=False)) of its flattened values: the same elements in every
+    run of the same shapes, so that the outputs of two builds compare element for element."""
+    out, left = {}, DUMP_BYTES // 4
+    names = sorted(arrays, key=lambda name: arrays[name].numel())
+    for i, name in enumerate(names):
+        t = arrays[name].detach()
+        n = t.numel()
+        k = min(n, left // (len(names) - i))
+        left -= k
+        if k < n:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(n, k, replace=False))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        out[name] = (t.float().cpu().numpy(), tuple(arrays[name].shape), n)
+    return out
+
+
 def time_step(step, dev, steps, warmup):
     for _ in range(warmup):
         step()
@@ -749,7 +772,12 @@ def main():
                     help='teapot: the metric\'s configuration (BASELINE.json configs[1] at batch 64); c4: BASELINE.json configs[3], '
                          '512 random meshes x 10 240 faces, texture_size 4, 256x256 textured RGB, the meshes split over the GPUs '
                          '(--gather: the all-gather of the rendered shards the configuration names)')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='after the timed steps, write what the last timed step returned (rgb, '
+                    'alpha, depth, grad_faces, grad_textures; rgb_gathered with --gather) as DIR/<name>.npy, float32, under 64 MB in '
+                    'all (a fixed seeded sample of the larger arrays: bench.dump_sample); rank 0 (its shard) in an N > 1 run')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
     c4 = args.workload == 'c4'
     if c4:  # (the job is the configuration's 512 meshes, 4 x 4 x 4 textures, RGB only; the headline's extra rows do not apply)
         args.batch = C4_MESHES if args.batch == 64 else args.batch
@@ -804,7 +832,7 @@ def main():
     gather = args.gather and dist is not None
     last = {}
 
-    def make_step(f, t, size, grads, with_gather=False, exact=None, ref=None, total=G):
+    def make_step(f, t, size, grads, with_gather=False, exact=None, ref=None, total=G, keep_outputs=False):
         def step():
             f.grad = None
             t.grad = None
@@ -816,10 +844,14 @@ def main():
                 last['gathered'] = nrd.all_gather_images(outs[0].detach(), total=total)
             torch.autograd.backward([o for o in outs if o is not None], [g for g in grads if g is not None])
             last['fi'] = fn.face_index_map
+            if keep_outputs and last.get('keep'):  # (detached: a kept autograd graph would carry this step's AccumulateGrad
+                last['outs'] = [None if o is None else o.detach() for o in outs]  # nodes into the next, which breaks a capture)
         return step
 
     grads = (g_rgb, g_alpha, g_depth)
-    step = make_step(faces, textures, S, grads, with_gather=gather, ref=z_ref)
+    # (--dump-outputs: the timed step keeps its outputs in its last timed call only -- timed(keep_last=True) -- so that no step
+    # holds a previous step's outputs and every step runs as without the flag)
+    step = make_step(faces, textures, S, grads, with_gather=gather, ref=z_ref, keep_outputs=bool(args.dump_outputs))
     local_step = make_step(faces, textures, S, grads, ref=z_ref)  # rank-local work only: no collective inside
 
     def barrier():
@@ -832,7 +864,9 @@ def main():
     run, mode = step, 'eager'
     if args.graph and not gather:
         from neural_renderer_amd.graph import capture
+        last['keep'] = True  # (a replay rewrites the outputs of the captured call: those are the ones to keep)
         run, mode = capture(step, dev), 'hipgraph'
+        last['keep'] = False
 
     # Timing protocol: all ranks leave a barrier + device synchronize together, each times ITS OWN K steps up to its own
     # device synchronize (wall clock, and HIP events on the launch stream as a cross-check), then a second barrier closes the
@@ -843,8 +877,9 @@ def main():
     # behind 30: 0.367).  W warm-up steps of 0.4 ms do not get there, so the same step runs untimed for --prewarm-ms before
     # the W warm-up steps and the K timed ones (reported in `timing.prewarm`).
     # (Rank-local steps only: the loop is bounded by time, so the ranks run different numbers of them -- no collective inside.)
-    def timed(run_fn, pre_fn):
-        """(seconds for K steps: MAX over ranks, rank-local HIP-event ms per step, pre-warm steps)."""
+    def timed(run_fn, pre_fn, keep_last=False):
+        """(seconds for K steps: MAX over ranks, rank-local HIP-event ms per step, pre-warm steps).  keep_last: the K-th step keeps
+        its outputs (last['outs'], --dump-outputs)."""
         n_pre, t_pre = 0, time.perf_counter()
         if args.prewarm_ms > 0:  # (one-time costs of the very first calls -- allocations, kernel attributes -- are not device work)
             pre_fn()
@@ -861,8 +896,11 @@ def main():
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         ev0.record()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             run_fn()
+        last['keep'] = keep_last
+        run_fn()
+        last['keep'] = False
         ev1.record()
         torch.cuda.synchronize(dev)
         seconds = time.perf_counter() - t0
@@ -880,7 +918,13 @@ def main():
     cold_elapsed, _, _ = timed(run, local_step if gather else run)
     args.prewarm_ms = keep_prewarm
     cold_ms = cold_elapsed / args.steps * 1e3
-    elapsed, event_ms_per_step, prewarm_steps = timed(run, local_step if gather else run)
+    elapsed, event_ms_per_step, prewarm_steps = timed(run, local_step if gather else run, keep_last=True)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # the last timed step's results, before any other step overwrites them
+        outs = dict(zip(('rgb', 'alpha', 'depth'), last['outs']), grad_faces=faces.grad, grad_textures=textures.grad)
+        if gather:
+            outs['rgb_gathered'] = last['gathered']
+        dumped = dump_sample({k: v for k, v in outs.items() if v is not None})
     eager_ms = None
     if mode == 'hipgraph':  # also report the eager number
         eager_ms = time_step(local_step, dev, args.steps, 2)
@@ -1125,6 +1169,14 @@ def main():
                        'cpu_affinity': ('pinned to one L3 group: %d logical CPUs from %d' % (len(pinned), min(pinned))) if pinned else 'not pinned',
                        'backend': (dist.get_backend() if dist is not None else None)},
         }
+        if dumped is not None:
+            os.makedirs(args.dump_outputs, exist_ok=True)
+            for name, (a, _, _) in dumped.items():
+                np.save(os.path.join(args.dump_outputs, name + '.npy'), a)
+            line['dump_outputs'] = {
+                'dir': args.dump_outputs, 'dtype': 'float32', 'seed': DUMP_SEED,
+                'arrays': {name: {'shape': list(shape), 'elements': int(a.size), 'of': n, 'sampled': bool(a.size < n)}
+                           for name, (a, shape, n) in dumped.items()}}
         print(json.dumps(line))
     if dist is not None:
         dist.barrier()

@@ -68,6 +68,63 @@ def test_bench_json_line():
     assert d['timing']['backend'] is None and d['timing']['rank0_hip_event_ms_per_step'] > 0
 
 
+def _bench_dump(out_dir, extra):
+    out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4',
+                          '--cpu-sample-views', '0', '--stage-iters', '2', '--prewarm-ms', '0', '--dump-outputs', str(out_dir)] + extra,
+                         cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    return json.loads(lines[0])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes what the last timed step returned; the timed step's inputs do not depend on what the run does after it
+    (the full run -- extra rows, HIP-graph capture of the step included -- and a --light one), hence the same outputs."""
+    import numpy as np
+    d = _bench_dump(tmp_path / 'a', [])
+    assert len(d['extra_rows']) == 5 and all(x['ms_per_step'] > 0 for x in d['extra_rows'])  # (the graph row ran: no capture failure)
+    _bench_dump(tmp_path / 'b', ['--light'])
+    assert d['steps'] == 3 and d['ms_per_step'] > 0
+    S, F = d['config']['image_size'], d['config']['num_faces']
+    shapes = {'rgb': [4, S, S, 3], 'alpha': [4, S, S], 'depth': [4, S, S], 'grad_faces': [4, F, 3, 3], 'grad_textures': [4, F, 2, 2, 2, 3]}
+    assert {k: v['shape'] for k, v in d['dump_outputs']['arrays'].items()} == shapes
+    got = {}
+    for run in ('a', 'b'):
+        got[run] = {name: np.load(str(tmp_path / run / (name + '.npy'))) for name in shapes}
+    assert sum(os.path.getsize(str(tmp_path / 'a' / (n + '.npy'))) for n in shapes) <= 64e6
+    for name, shape in shapes.items():
+        a, b = got['a'][name], got['b'][name]
+        assert a.dtype == np.float32 and list(a.shape) == shape and np.isfinite(a).all(), name  # 4 views: no sampling
+        if name == 'grad_faces':  # (double atomics: the order of arrival may move an entry by one ulp)
+            np.testing.assert_allclose(a, b, rtol=1e-6, atol=1e-6 * np.abs(b).max())
+        else:
+            np.testing.assert_array_equal(a, b, err_msg=name)
+    assert got['a']['alpha'].max() == 1.0 and got['a']['alpha'].min() == 0.0 and np.abs(got['a']['grad_faces']).max() > 0
+
+
+def test_dump_sample_stays_within_64_mb():
+    """bench.dump_sample at the headline shapes (64 views at 256 x 256): the sample fits the budget, is the seeded subset, and is
+    the same on every call; arrays that fit are taken whole."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    B, F, S = 64, 4928, 256
+    arrays = {'rgb': torch.arange(B * S * S * 3, dtype=torch.float32).reshape(B, S, S, 3), 'alpha': torch.rand(B, S, S),
+              'depth': torch.rand(B, S, S), 'grad_faces': torch.rand(B, F, 3, 3), 'grad_textures': torch.rand(B, F, 2, 2, 2, 3)}
+    a, b = bench.dump_sample(arrays), bench.dump_sample(arrays)
+    assert set(a) == set(arrays) and sum(v[0].nbytes for v in a.values()) <= bench.DUMP_BYTES < 64e6 - 1024
+    for name, (v, shape, n) in a.items():
+        assert v.dtype == np.float32 and shape == tuple(arrays[name].shape) and n == arrays[name].numel()
+        np.testing.assert_array_equal(v, b[name][0])
+    np.testing.assert_array_equal(a['grad_faces'][0], arrays['grad_faces'].numpy())  # fits: whole, in its shape
+    idx = a['rgb'][0].astype(np.int64)  # rgb holds its own flat indices: the sample is sorted, distinct, seeded
+    assert len(idx) < arrays['rgb'].numel() and (np.diff(idx) > 0).all()
+    np.testing.assert_array_equal(idx, np.sort(np.random.default_rng(bench.DUMP_SEED).choice(B * S * S * 3, len(idx), replace=False)))
+
+
 def test_bench_refuses_to_run_without_a_gpu():
     import torch
     if torch.cuda.is_available():

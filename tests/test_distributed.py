@@ -75,7 +75,10 @@ def _worker(rank, world, port, total, out_q):
 
 
 @pytest.mark.parametrize('total', [8, 5])
-def test_two_process_gloo(total):
+def test_two_process_gloo(total, monkeypatch):
+    # CPU ranks on every machine: with a GPU visible, init_from_env would put rank r on device r, which a one-GPU box lacks
+    monkeypatch.setenv('HIP_VISIBLE_DEVICES', '-1')
+    monkeypatch.setenv('CUDA_VISIBLE_DEVICES', '-1')
     ctx = mp.get_context('spawn')
     q = ctx.Queue()
     port = _free_port()
