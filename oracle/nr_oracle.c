@@ -509,17 +509,74 @@ API void oracle_forward_background_alpha(const int32_t *face_index_map, float *r
  * float arithmetic, but the running sums are kept in double and rounded once at the end.  It isolates the
  * per-term arithmetic (what a parallel implementation must reproduce) from the order-dependent float
  * summation noise of the reference's serial loop; tests use both forms.
+ * Term magnitudes (NOT the reference; tests/helpers.py `entrywise` turns them into per-entry error bounds), through
+ * oracle_backward_pixel_map_mags (oracle_backward_pixel_map keeps its signature of oracle_version 4).  mag_a, mag_m
+ * [B*F*9] double and mag_n [B*F*9] may be NULL (then nothing else changes, bit for bit); otherwise they are fully written:
+ *   mag_a  sum of |term| over the terms the reference forms (:651, :656, :722, :727),
+ *   mag_m  sum over the same visits of (sum_c (|I_c| + |ref_c| + 2 kappa_b) |g_c| + (|a| + |a_ref| + 2) |g_a|) / |dist|:
+ *          the magnitudes that enter a term before its colour difference cancels.  kappa_b is the largest colour magnitude
+ *          of image b (the background included: rgb_map holds it on uncovered pixels), so mag_m also covers a difference
+ *          formed as P - sum (ref_c - K_c) g_c around any colour K of the image.  Visits that :647 / :717 skip
+ *          (diff_grad <= 0) still add here: a kernel whose diff rounds to the other side of 0 keeps such a term,
+ *          Alpha only (no rgb), the colours are exactly 0 or 1 (K5, :449): alpha - alpha_ref is -1, 0 or 1 and diff_grad is
+ *          exact in any evaluation, so every kernel takes the same visits with the same diff and only the rounding of
+ *          diff / dist remains: mag_m adds |term| over the visits taken (mag_m = mag_a),
+ *   mag_n  the number of terms formed (the terms of mag_a).
  */
-API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index_map, const float *rgb_map,
-                                   const float *alpha_map, const float *grad_rgb_map,
-                                   const float *grad_alpha_map, float *grad_faces, int batch_size, int num_faces,
-                                   int image_size, double eps, int return_rgb, int return_alpha,
-                                   long long *visit_counter, int accumulate_double)
+static inline float k6_dist(const float p[3][2], int vertex, int d0, int d1, float d1_cross, int is, double eps)
+{
+    /* :649-650 (vertex 0, against p[1]) / :654-655 (vertex 1, against p[0]) */
+    const float den = vertex == 0 ? p[1][0] - (float)d0 : (float)d0 - p[0][0];
+    float dist = (float)((double)((p[1][0] - p[0][0]) / den * ((float)d1 - d1_cross)) * 2. / is);
+    return (0 < dist) ? (float)((double)dist + eps) : (float)((double)dist - eps);
+}
+
+/* one visit of a sweep: the terms of :648-657 / :719-728 (taken unless diff_grad <= 0) and their magnitudes */
+static inline void k6_visit(float diff_grad, double smag, const float p[3][2], const int pi[3], int axis, int d0, int d1,
+                            float d1_cross, int is, double eps, float *grad_face, double *grad_face_d, double *ma,
+                            double *mm, int32_t *mn)
+{
+    const int take = !(diff_grad <= 0); /* :647 / :717 (a NaN diff goes through) */
+    if (!take && !mm) return;
+    for (int v = 0; v < 2; v++) {
+        if (p[1 - v][0] == (float)d0) continue; /* :648 / :653 */
+        const float dist = k6_dist(p, v, d0, d1, d1_cross, is, eps);
+        const int k = pi[v] * 3 + (1 - axis);
+        if (take) {
+            const float term = diff_grad / dist; /* :651 / :656 */
+            grad_face[k] -= term;
+            grad_face_d[k] -= (double)term;
+            if (ma) { ma[k] += fabs((double)term); mn[k] += 1; }
+        }
+        /* (alpha only: smag < 0 stands for |diff|, see oracle_backward_pixel_map_mags) */
+        if (mm) mm[k] += smag < 0 ? (take ? fabs((double)(diff_grad / dist)) : 0.) : smag / fabs((double)dist);
+    }
+}
+
+API void oracle_backward_pixel_map_mags(const float *faces, const int32_t *face_index_map, const float *rgb_map,
+                                        const float *alpha_map, const float *grad_rgb_map,
+                                        const float *grad_alpha_map, float *grad_faces, int batch_size, int num_faces,
+                                        int image_size, double eps, int return_rgb, int return_alpha,
+                                        long long *visit_counter, int accumulate_double, double *mag_a, double *mag_m,
+                                        int32_t *mag_n)
 {
     const int is = image_size;
     const long n = (long)batch_size * num_faces;
     long long visits = 0;
+    const int mags = mag_a && mag_m && mag_n;
+    if (mags) {
+        memset(mag_a, 0, sizeof(double) * 9 * (size_t)n);
+        memset(mag_m, 0, sizeof(double) * 9 * (size_t)n);
+        memset(mag_n, 0, sizeof(int32_t) * 9 * (size_t)n);
+    }
     if ((!return_rgb) && (!return_alpha)) return; /* :523 */
+    double *kappa = 0; /* largest colour magnitude per image (mag_m) */
+    if (mags && return_rgb) {
+        kappa = (double *)calloc((size_t)batch_size, sizeof(double));
+        for (int b = 0; b < batch_size; b++)
+            for (long j = (long)b * is * is * 3; j < (long)(b + 1) * is * is * 3; j++)
+                if (fabs((double)rgb_map[j]) > kappa[b]) kappa[b] = fabs((double)rgb_map[j]);
+    }
 #pragma omp parallel for schedule(dynamic, 16) reduction(+ : visits) num_threads(NTHREADS)
     for (long i = 0; i < n; i++) {
         const int bn = (int)(i / num_faces);
@@ -527,6 +584,9 @@ API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index
         const float *face = faces + i * 9;
         float grad_face[9] = {0};
         double grad_face_d[9] = {0};
+        double *ma = mags ? mag_a + i * 9 : 0, *mm = mags ? mag_m + i * 9 : 0;
+        int32_t *mn = mags ? mag_n + i * 9 : 0;
+        const double kap = kappa ? kappa[bn] : 0;
 
         if (is_backside(face)) continue; /* :540 */
 
@@ -600,24 +660,24 @@ API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index
                         long idx = map_index_from;
                         for (int d1 = d1_from; d1 <= d1_to; d1++, idx += map_offset) {
                             float diff_grad = 0;
+                            double smag = 0;
                             visits++;
                             if (return_alpha) diff_grad += (alpha_map[idx] - alpha_in) * grad_alpha_map[idx];
                             if (return_rgb)
                                 for (int k = 0; k < 3; k++)
                                     diff_grad += (rgb_map[idx * 3 + k] - rgb_in[k]) * grad_rgb_map[idx * 3 + k];
-                            if (diff_grad <= 0) continue; /* :647 */
-                            if (p[1][0] != (float)d0) {   /* :648-652 */
-                                float dist = (float)((double)((p[1][0] - p[0][0]) / (p[1][0] - (float)d0) *
-                                                              ((float)d1 - d1_cross)) * 2. / is);
-                                dist = (0 < dist) ? (float)((double)dist + eps) : (float)((double)dist - eps);
-                                { const float term = diff_grad / dist; grad_face[pi[0] * 3 + (1 - axis)] -= term; grad_face_d[pi[0] * 3 + (1 - axis)] -= (double)term; }
+                            if (mags && !return_rgb) smag = -1;
+                            else if (mags) {
+                                if (return_alpha)
+                                    smag += (fabs((double)alpha_map[idx]) + fabs((double)alpha_in) + 2.) *
+                                            fabs((double)grad_alpha_map[idx]);
+                                if (return_rgb)
+                                    for (int k = 0; k < 3; k++)
+                                        smag += (fabs((double)rgb_map[idx * 3 + k]) + fabs((double)rgb_in[k]) + 2. * kap) *
+                                                fabs((double)grad_rgb_map[idx * 3 + k]);
                             }
-                            if (p[0][0] != (float)d0) { /* :653-657 */
-                                float dist = (float)((double)((p[1][0] - p[0][0]) / ((float)d0 - p[0][0]) *
-                                                              ((float)d1 - d1_cross)) * 2. / is);
-                                dist = (0 < dist) ? (float)((double)dist + eps) : (float)((double)dist - eps);
-                                { const float term = diff_grad / dist; grad_face[pi[1] * 3 + (1 - axis)] -= term; grad_face_d[pi[1] * 3 + (1 - axis)] -= (double)term; }
-                            }
+                            /* :647-657 */
+                            k6_visit(diff_grad, smag, p, pi, axis, d0, d1, d1_cross, is, eps, grad_face, grad_face_d, ma, mm, mn);
                         }
                     }
 
@@ -646,23 +706,23 @@ API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index
                             visits++;
                             if (face_index_map[idx] != fn) continue; /* :707 */
                             float diff_grad = 0;
+                            double smag = 0;
                             if (return_alpha) diff_grad += (alpha_map[idx] - alpha_out) * grad_alpha_map[idx];
                             if (return_rgb)
                                 for (int k = 0; k < 3; k++)
                                     diff_grad += (rgb_map[idx * 3 + k] - rgb_out[k]) * grad_rgb_map[idx * 3 + k];
-                            if (diff_grad <= 0) continue; /* :717 */
-                            if (p[1][0] != (float)d0) {   /* :719-723 */
-                                float dist = (float)((double)((p[1][0] - p[0][0]) / (p[1][0] - (float)d0) *
-                                                              ((float)d1 - d1_cross)) * 2. / is);
-                                dist = (0 < dist) ? (float)((double)dist + eps) : (float)((double)dist - eps);
-                                { const float term = diff_grad / dist; grad_face[pi[0] * 3 + (1 - axis)] -= term; grad_face_d[pi[0] * 3 + (1 - axis)] -= (double)term; }
+                            if (mags && !return_rgb) smag = -1;
+                            else if (mags) {
+                                if (return_alpha)
+                                    smag += (fabs((double)alpha_map[idx]) + fabs((double)alpha_out) + 2.) *
+                                            fabs((double)grad_alpha_map[idx]);
+                                if (return_rgb)
+                                    for (int k = 0; k < 3; k++)
+                                        smag += (fabs((double)rgb_map[idx * 3 + k]) + fabs((double)rgb_out[k]) + 2. * kap) *
+                                                fabs((double)grad_rgb_map[idx * 3 + k]);
                             }
-                            if (p[0][0] != (float)d0) { /* :724-728 */
-                                float dist = (float)((double)((p[1][0] - p[0][0]) / ((float)d0 - p[0][0]) *
-                                                              ((float)d1 - d1_cross)) * 2. / is);
-                                dist = (0 < dist) ? (float)((double)dist + eps) : (float)((double)dist - eps);
-                                { const float term = diff_grad / dist; grad_face[pi[1] * 3 + (1 - axis)] -= term; grad_face_d[pi[1] * 3 + (1 - axis)] -= (double)term; }
-                            }
+                            /* :717-728 */
+                            k6_visit(diff_grad, smag, p, pi, axis, d0, d1, d1_cross, is, eps, grad_face, grad_face_d, ma, mm, mn);
                         }
                     }
                 }
@@ -670,19 +730,34 @@ API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index
         }
         for (int k = 0; k < 9; k++) grad_faces[i * 9 + k] = accumulate_double ? (float)grad_face_d[k] : grad_face[k]; /* :736 */
     }
+    free(kappa);
     if (visit_counter) *visit_counter = visits;
+}
+
+/* The entry point as it was before the magnitudes (oracle_version <= 4): callers built against it keep working. */
+API void oracle_backward_pixel_map(const float *faces, const int32_t *face_index_map, const float *rgb_map,
+                                   const float *alpha_map, const float *grad_rgb_map,
+                                   const float *grad_alpha_map, float *grad_faces, int batch_size, int num_faces,
+                                   int image_size, double eps, int return_rgb, int return_alpha,
+                                   long long *visit_counter, int accumulate_double)
+{
+    oracle_backward_pixel_map_mags(faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, grad_faces,
+                                   batch_size, num_faces, image_size, eps, return_rgb, return_alpha, visit_counter,
+                                   accumulate_double, 0, 0, 0);
 }
 
 /* ------------------------------------------------------------------------------------------------
  * K7: rasterize.py:750-792 -- scatter of grad_rgb into the 8 sampled texels (accumulates).
  */
-API void oracle_backward_textures(const int32_t *face_index_map, const float *sampling_weight_map,
-                                  const int32_t *sampling_index_map, const float *grad_rgb_map,
-                                  float *grad_textures, int batch_size, int num_faces, int image_size,
-                                  int texture_size, double *acc_d)
+API void oracle_backward_textures_mags(const int32_t *face_index_map, const float *sampling_weight_map,
+                                       const int32_t *sampling_index_map, const float *grad_rgb_map,
+                                       float *grad_textures, int batch_size, int num_faces, int image_size,
+                                       int texture_size, double *acc_d, double *mag_a, int32_t *mag_n)
 {
     /* acc_d != NULL (NOT the reference): accumulate into this double buffer [same shape as grad_textures]
-     * instead of grad_textures; see the note on accumulate_double at K6. */
+     * instead of grad_textures; see the note on accumulate_double at K6.
+     * mag_a / mag_n (NOT the reference; both or neither, same shape as grad_textures, accumulated like acc_d): the sum of
+     * |term| and the number of terms per element (see K6). */
     const int is = image_size;
     const int nf = num_faces;
     const int ts = texture_size;
@@ -701,22 +776,37 @@ API void oracle_backward_textures(const int32_t *face_index_map, const float *sa
                 for (int k = 0; k < 3; k++) {
                     const float term = w * grad_rgb_map[i * 3 + k]; /* :780 */
                     if (acc_d) acc_d[toff + isc * 3 + k] += (double)term; else grad_texture[isc * 3 + k] += term;
+                    if (mag_a) { mag_a[toff + isc * 3 + k] += fabs((double)term); mag_n[toff + isc * 3 + k] += 1; }
                 }
             }
         }
     }
 }
 
+/* the pre-magnitude entry point (oracle_version <= 4) */
+API void oracle_backward_textures(const int32_t *face_index_map, const float *sampling_weight_map,
+                                  const int32_t *sampling_index_map, const float *grad_rgb_map,
+                                  float *grad_textures, int batch_size, int num_faces, int image_size,
+                                  int texture_size, double *acc_d)
+{
+    oracle_backward_textures_mags(face_index_map, sampling_weight_map, sampling_index_map, grad_rgb_map, grad_textures,
+                                  batch_size, num_faces, image_size, texture_size, acc_d, 0, 0);
+}
+
 /* ------------------------------------------------------------------------------------------------
  * K8: rasterize.py:794-847 -- analytic gradient of the depth map w.r.t. the winning face (accumulates
  * on top of what K6 stored, :881-883).
  */
-API void oracle_backward_depth_map(const float *faces, const float *depth_map, const int32_t *face_index_map,
-                                   const float *face_inv_map, const float *weight_map,
-                                   const float *grad_depth_map, float *grad_faces, int batch_size, int num_faces,
-                                   int image_size, double *acc_d)
+API void oracle_backward_depth_map_mags(const float *faces, const float *depth_map, const int32_t *face_index_map,
+                                        const float *face_inv_map, const float *weight_map,
+                                        const float *grad_depth_map, float *grad_faces, int batch_size, int num_faces,
+                                        int image_size, double *acc_d, double *mag_a, double *mag_m, int32_t *mag_n)
 {
-    /* acc_d != NULL (NOT the reference): add the terms to this double buffer [B*F*9] instead of grad_faces. */
+    /* acc_d != NULL (NOT the reference): add the terms to this double buffer [B*F*9] instead of grad_faces.
+     * mag_a / mag_m / mag_n (NOT the reference; all or none, [B*F*9], accumulated): per entry the sum of |term|, of the
+     * magnitudes that enter a term, and the number of terms (see K6).  For z (:826) a term is one product chain: mag_m adds
+     * |term|.  For x, y (:830-837) the term's factor tmp_l = sum_m -face_inv[m][l] / z_m cancels: mag_m adds
+     * |grad_depth * w_k * depth^2 * is / 2| * sum_m |face_inv[m][l] / z_m|. */
     const int is = image_size;
     const int nf = num_faces;
 #pragma omp parallel for schedule(dynamic, 1) num_threads(NTHREADS)
@@ -732,12 +822,18 @@ API void oracle_backward_depth_map(const float *faces, const float *depth_map, c
             const float grad_depth = grad_depth_map[i];
             float *grad_face = grad_faces + ((long)bn * nf + fn) * 9;
             double *grad_face_d = acc_d ? acc_d + ((long)bn * nf + fn) * 9 : 0;
+            const long mo = ((long)bn * nf + fn) * 9;
 
             /* :824-827 */
             for (int k = 0; k < 3; k++) {
                 const float z_k = face[3 * k + 2];
                 const float term = grad_depth * weight[k] * depth2 / (z_k * z_k);
                 if (grad_face_d) grad_face_d[3 * k + 2] += (double)term; else grad_face[3 * k + 2] += term;
+                if (mag_a) {
+                    mag_a[mo + 3 * k + 2] += fabs((double)term);
+                    mag_m[mo + 3 * k + 2] += fabs((double)term);
+                    mag_n[mo + 3 * k + 2] += 1;
+                }
             }
 
             /* :830-837 */
@@ -749,9 +845,26 @@ API void oracle_backward_depth_map(const float *faces, const float *depth_map, c
                 {
                     const float term = -grad_depth * tmp[l] * weight[k] * depth2 * (float)is / 2.0f;
                     if (grad_face_d) grad_face_d[3 * k + l] += (double)term; else grad_face[3 * k + l] += term;
+                    if (mag_a) {
+                        double sm = 0;
+                        for (int m = 0; m < 3; m++) sm += fabs((double)face_inv[3 * m + l] / (double)face[3 * m + 2]);
+                        mag_a[mo + 3 * k + l] += fabs((double)term);
+                        mag_m[mo + 3 * k + l] += fabs((double)grad_depth * weight[k] * depth2 * is / 2.) * sm;
+                        mag_n[mo + 3 * k + l] += 1;
+                    }
                 }
         }
     }
 }
 
-API int oracle_version(void) { return 4; }
+/* the pre-magnitude entry point (oracle_version <= 4) */
+API void oracle_backward_depth_map(const float *faces, const float *depth_map, const int32_t *face_index_map,
+                                   const float *face_inv_map, const float *weight_map,
+                                   const float *grad_depth_map, float *grad_faces, int batch_size, int num_faces,
+                                   int image_size, double *acc_d)
+{
+    oracle_backward_depth_map_mags(faces, depth_map, face_index_map, face_inv_map, weight_map, grad_depth_map, grad_faces,
+                                   batch_size, num_faces, image_size, acc_d, 0, 0, 0);
+}
+
+API int oracle_version(void) { return 5; }

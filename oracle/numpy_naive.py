@@ -158,10 +158,11 @@ def _dist(p0x, p1x, den, d1, d1_cross, s, eps):
     return np.where(0 < d, d.astype(f64) + eps, d.astype(f64) - eps).astype(f32)
 
 
-def backward_pixel_map(faces, fi, rgb, alpha, g_rgb, g_alpha, eps):
+def backward_pixel_map(faces, fi, rgb, alpha, g_rgb, g_alpha, eps, magnitudes=False):
     """K6 (rasterize.py:517-748).  rgb / alpha (and their gradients) may be None.  Every term is the reference's float32
     arithmetic; the per-face sums are accumulated in float64 and rounded once (compare with the C oracle's
-    accumulate_double form)."""
+    accumulate_double form).  magnitudes=True returns (grad, A, N): per entry the sum of |term| (float64) and the number of
+    terms formed (compare with the C oracle's mag_a / mag_n)."""
     faces = np.ascontiguousarray(faces, f32)
     bs, nf = faces.shape[:2]
     s = fi.shape[1]
@@ -176,6 +177,8 @@ def backward_pixel_map(faces, fi, rgb, alpha, g_rgb, g_alpha, eps):
     gim = np.concatenate(grads, axis=-1)
     nc = img.shape[-1]
     grad = np.zeros((bs, nf, 3, 3), f64)
+    mag_a = np.zeros((bs, nf, 3, 3), f64)
+    mag_n = np.zeros((bs, nf, 3, 3), np.int64)
     grid = np.arange(s, dtype=np.int64)
 
     def channel_diff(line, gline, ref):
@@ -247,8 +250,13 @@ def backward_pixel_map(faces, fi, rgb, alpha, g_rgb, g_alpha, eps):
                             # vertex pi[0]: :648-652 / :719-723 ; vertex pi[1]: :653-657 / :724-728
                             for vert, den, on in ((pi[0], a1x - fd0, a1x != fd0), (pi[1], fd0 - a0x, a0x != fd0)):
                                 dist = _dist(a0x, a1x, den, grid, d1_cross, s, eps)
-                                term = np.where(mask & on[:, None], (diff / dist).astype(f64), 0.0)
+                                taken = mask & on[:, None]
+                                term = np.where(taken, (diff / dist).astype(f64), 0.0)
                                 np.subtract.at(grad[bn, :, vert, 1 - axis], sel, term.sum(axis=1))
+                                np.add.at(mag_a[bn, :, vert, 1 - axis], sel, np.abs(term).sum(axis=1))
+                                np.add.at(mag_n[bn, :, vert, 1 - axis], sel, taken.sum(axis=1))
     out = grad.astype(f32)
     out[:, :, :, 2] = 0
+    if magnitudes:
+        return out, mag_a, mag_n
     return out

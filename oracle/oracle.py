@@ -50,7 +50,7 @@ def lib():
     if _lib is None:
         build()
         _lib = ctypes.CDLL(_LIB)
-        if _lib.oracle_version() < 4:  # a stale prebuilt library
+        if _lib.oracle_version() < 5:  # a stale prebuilt library
             build(force=True)
             _lib = ctypes.CDLL(_LIB)
         env = os.environ.get('NR_ORACLE_THREADS')
@@ -184,9 +184,13 @@ class Rasterize(object):
         depth_r = self.depth_map.copy() if self.return_depth else None
         return rgb_r, alpha_r, depth_r
 
-    def backward(self, grad_rgb=None, grad_alpha=None, grad_depth=None, accumulate_double=False, skip_textures=False):
+    def backward(self, grad_rgb=None, grad_alpha=None, grad_depth=None, accumulate_double=False, skip_textures=False,
+                 magnitudes=False):
         """accumulate_double: keep K6's running sums in double (NOT the reference; see nr_oracle.c).
-        skip_textures: leave K7 out (its output stays zero) -- for callers that only want grad_faces of a huge mesh."""
+        skip_textures: leave K7 out (its output stays zero) -- for callers that only want grad_faces of a huge mesh.
+        magnitudes: also return a dict of per-entry term magnitudes (NOT the reference; nr_oracle.c at K6 / K7 / K8):
+        'A', 'M' (float64) and 'N' (int32) of K6 for every grad_faces entry, 'A8', 'M8', 'N8' of K8 when depth is returned,
+        'At', 'Nt' of K7 when rgb is returned and K7 runs.  The gradients themselves do not change, bit for bit."""
         L = lib()
         bs, nf, s = self.batch_size, self.num_faces, self.image_size
         # :851-855
@@ -204,36 +208,47 @@ class Rasterize(object):
             g_depth = _f32(grad_depth) if grad_depth is not None else np.zeros_like(self.depth_map)
             assert g_depth.shape == self.depth_map.shape
 
+        _f64p = ctypes.POINTER(ctypes.c_double)
+        mags = {}
+        if magnitudes:
+            mags = dict(A=np.zeros(self.faces.shape, np.float64), M=np.zeros(self.faces.shape, np.float64),
+                        N=np.zeros(self.faces.shape, np.int32))
         # :881 backward_pixel_map_gpu
         visits = ctypes.c_longlong(0)
-        L.oracle_backward_pixel_map(
+        L.oracle_backward_pixel_map_mags(
             _p(self.faces, _f32p), _p(self.face_index_map, _i32p), _p(self.rgb_map, _f32p),
             _p(self.alpha_map, _f32p), _p(g_rgb, _f32p), _p(g_alpha, _f32p), _p(self.grad_faces, _f32p),
             bs, nf, s, ctypes.c_double(self.eps), int(self.return_rgb), int(self.return_alpha),
-            ctypes.byref(visits), int(accumulate_double))
+            ctypes.byref(visits), int(accumulate_double),
+            _p(mags.get('A'), _f64p), _p(mags.get('M'), _f64p), _p(mags.get('N'), _i32p))
         self.visits = visits.value
-        _f64p = ctypes.POINTER(ctypes.c_double)
         # :882 backward_textures_gpu
         if self.return_rgb and not skip_textures:
             acc = np.zeros(self.grad_textures.shape, np.float64) if accumulate_double else None
-            L.oracle_backward_textures(
+            if magnitudes:
+                mags['At'] = np.zeros(self.grad_textures.shape, np.float64)
+                mags['Nt'] = np.zeros(self.grad_textures.shape, np.int32)
+            L.oracle_backward_textures_mags(
                 _p(self.face_index_map, _i32p), _p(self.sampling_weight_map, _f32p),
                 _p(self.sampling_index_map, _i32p), _p(g_rgb, _f32p), _p(self.grad_textures, _f32p),
-                bs, nf, s, self.texture_size, _p(acc, _f64p))
+                bs, nf, s, self.texture_size, _p(acc, _f64p), _p(mags.get('At'), _f64p), _p(mags.get('Nt'), _i32p))
             if acc is not None:
                 self.grad_textures = acc.astype(np.float32)
         # :883 backward_depth_map_gpu
         if self.return_depth:
             acc = self.grad_faces.astype(np.float64) if accumulate_double else None
-            L.oracle_backward_depth_map(
+            if magnitudes:
+                for k, t in (('A8', np.float64), ('M8', np.float64), ('N8', np.int32)):
+                    mags[k] = np.zeros(self.faces.shape, t)
+            L.oracle_backward_depth_map_mags(
                 _p(self.faces, _f32p), _p(self.depth_map, _f32p), _p(self.face_index_map, _i32p),
                 _p(self.face_inv_map, _f32p), _p(self.weight_map, _f32p), _p(g_depth, _f32p),
-                _p(self.grad_faces, _f32p), bs, nf, s, _p(acc, _f64p))
+                _p(self.grad_faces, _f32p), bs, nf, s, _p(acc, _f64p),
+                _p(mags.get('A8'), _f64p), _p(mags.get('M8'), _f64p), _p(mags.get('N8'), _i32p))
             if acc is not None:
                 self.grad_faces = acc.astype(np.float32)
-        if self.return_rgb:
-            return self.grad_faces, self.grad_textures
-        return self.grad_faces,
+        out = (self.grad_faces, self.grad_textures) if self.return_rgb else (self.grad_faces,)
+        return out + (mags,) if magnitudes else out
 
 
 # ----------------------------------------------------------------------------------------------------

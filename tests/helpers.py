@@ -76,6 +76,125 @@ def rel_err(a, b, floor=None):
     return float((np.abs(a - b) / np.maximum(np.abs(b), floor)).max()) if b.size else 0.0
 
 
+# ------------------------------------------------------------------------------------------------------------------------
+# Entrywise bounds: every gradient entry against its own term magnitudes (oracle Rasterize.backward(magnitudes=True))
+U = 2.0 ** -24   # float32 unit roundoff
+UD = 2.0 ** -53  # float64 unit roundoff
+# Per-term constants c1 of the two default-mode band kernels (first-order roundings counted in entrywise's docstring,
+# plus one for the second-order products)
+C1_ROW = 22
+C1_FAST = 24
+# Longest float partial sum a lane forms before its sum goes to double
+M_ROW = 32   # k_bpm_row: a lane's even / odd segment terms, <= 8 at raster 256 and <= 32 at 1024, the largest raster it serves
+M_FAST = 49  # k_bpm_fast: <= 3 pieces of 15 pixels in one float sum (a class-U super-piece), then a float tree over <= 16
+             # pieces of a run of lanes (depth 4): 45 + 4
+MODES = ('exact', 'row', 'fast', 'default', 'global', 'textures')
+
+
+def gamma(n, u=U):
+    """Higham's gamma_n = n u / (1 - n u): |fl(sum of n terms in any order) - sum| <= gamma_{n-1} * sum |terms|."""
+    n = np.asarray(n, np.float64)
+    return n * u / (1.0 - n * u)
+
+
+def _ulp(x):
+    return np.spacing(np.abs(np.asarray(x, np.float64)).astype(np.float32)).astype(np.float64)
+
+
+def entrywise_bound(ref_d, mags, mode, got=None):
+    """Per-entry bound on |got - ref_d| for `mode`; see entrywise."""
+    ref_d = np.asarray(ref_d, np.float64)
+    big = np.abs(ref_d) if got is None else np.maximum(np.abs(ref_d), np.abs(np.asarray(got, np.float64)))
+    ulp = _ulp(big)
+    if mode == 'textures':
+        a, n = mags['At'], mags['Nt']
+        return ulp + gamma(n) * a
+    a, m, n = mags['A'], mags['M'], mags['N']
+    double_sums = 2 * UD * n * a
+    if mode in ('exact', 'global'):
+        b = ulp + double_sums
+    elif mode == 'row':
+        b = ulp + double_sums + C1_ROW * U * m + gamma(M_ROW) * a
+    elif mode == 'fast':
+        b = ulp + double_sums + C1_FAST * U * m + gamma(M_FAST) * a
+    elif mode == 'default':
+        b = ulp + double_sums + np.maximum(C1_ROW * U * m + gamma(M_ROW) * a, C1_FAST * U * m + gamma(M_FAST) * a)
+    else:
+        raise ValueError(mode)
+    if 'A8' in mags:
+        x8 = mags['M8'].copy()
+        x8[..., 2] = mags['A8'][..., 2]
+        b = b + gamma(mags['N8'] + 1) * (a + x8) + ulp
+    return b
+
+
+def entrywise(got, ref_d, mags, mode):
+    """Every gradient entry against a bound built from its OWN terms, not from the largest gradient of the call (rel_err's floor).
+
+    `ref_d` is the oracle's output with its float terms summed in double (Rasterize.backward(accumulate_double=True)), `mags`
+    the dict of Rasterize.backward(magnitudes=True) on the same inputs: per grad_faces entry A = sum |term|, M = sum of the
+    magnitudes entering each term before its colour difference cancels (nr_oracle.c, K6), N = number of terms; A8 / M8 / N8
+    the same for K8's terms; At / Nt per grad_textures element (K7).  Returns (worst |got - ref_d| / bound, indices of the
+    entries above their bound).  Entries where got, ref_d or the bound is not finite are skipped (the NaN pattern is
+    asserted where the tests compare gradients).  u = 2^-24, u_d = 2^-53, gamma_n = n u / (1 - n u).
+
+    grad_faces, by `mode` (K6's kernels: neural_renderer_amd/csrc/nr_backward_pixel_map.hip):
+      'exact' -- NR_FLAG_EXACT_GRADIENT on either band kernel (include/nr_hip.h:79-93: the reference's operations one by one,
+          every sum in double): the terms are the oracle's bits, so only the two double sums differ, each by <= N u_d A
+          (any order), and each side rounds its double to float once:  ulp(ref_d) + 2 u_d N A.
+      'global' -- k_bpm_global (NR_FLAG_K6_GLOBAL, rasters whose band does not fit in LDS): the reference's terms
+          (nr_backward_pixel_map.hip:190-195) in per-lane double sums, stored without atomics: the exact mode's bound.
+      'row' -- k_bpm_row, default mode.  Per term, against the oracle's float term (first order, S = sum_c (|I_c| + |ref_c| +
+          2 kappa) |g_c| of the pixel, so that M = sum S / |dist|):
+            diff: P formed in double and rounded once (u S), ref_c - K_c rounded (u S), four fused multiply-adds
+                (:2026-2031, 4 u S) -> 6 u S; the oracle's sum_c (I_c - ref_c) g_c (nr_oracle.c, K6): a subtraction, a
+                product and an add per channel (the first add onto 0 exact) -> 5 u S;
+            dist: t = fma(sdir, d1, -sdir cross) is the reference's subtraction (same bits); |c| 2/S (2 u: the product
+                and 2/S when S is no power of two), fma(|c| 2/S, |t|, eps) (u), eps in float (u) -> 4 u; the oracle's c t,
+                x 2/S, +- eps -> 3 u;
+            reciprocal: v_rcp_f32 <= 1 ulp = 2 u (:2038; phase A's recip_n with a Newton step, :1697-1699, less); the
+                oracle's division u.
+          |term - term_ref| <= (6 + 5) u S / |dist| + (4 + 3 + 2 + 1) u |term| <= 21 u S / |dist|: C1_ROW = 22 with the
+          second-order products.  A visit that one side skips (diff <= 0) and the other keeps has |diff| within those
+          roundings of 0 and is covered the same way: M counts skipped visits too.  Sums: fma(dm, rcp, a) into a lane's
+          float partial sums of <= M_ROW terms (gamma_M_ROW A), the rest in double (u_d N A per side), one rounding to float:
+            ulp(ref_d) + 2 u_d N A + C1_ROW u M + gamma_M_ROW A.
+      'fast' -- k_bpm_fast, default mode (NR_FLAG_K6_LEGACY, the scan path NR_FLAG_K6_SCAN, overflow images, rasters above
+          k_bpm_row's): the colour difference from b - ref or c - ref, one product and three fused multiply-adds
+          (:1002-1022, 5 u S; the oracle 5 u S); t = (d1 - cross) + k, two roundings of one sign (:1043, :1066: 2 u against the
+          reference's one, 3 u apart), c 2/S (2 u), fma (u), eps (u); the oracle 3 u; v_rcp_f32 without a Newton step
+          (nr_k6_tune.h NR_K6_NEWTON = 0: 2 u), the oracle's division (u): (5 + 5) u S / |dist| + (3 + 4 + 3 + 2 + 1) u |term|
+          <= 23 u S / |dist|: C1_FAST = 24.  Float sums of <= M_FAST terms (:1073-1077 and the run sums), double above:
+            ulp(ref_d) + 2 u_d N A + C1_FAST u M + gamma_M_FAST A.
+      'default' -- the default mode where either band kernel may serve an image (k_bpm_row hands overflow images to
+          k_bpm_fast): the larger of the two.
+    With K8 (depth; `mags` has A8): its terms are the reference's expressions (nr_backward_gather.hip:293-299 against
+    nr_oracle.c K8), added in float in any order together with K6's rounded total (atomics, :548-549), so the bound grows
+    by gamma_{N8+1} (A + X8) + ulp, X8 = M8 for x, y (tmp_l cancels) and A8 for z.
+    'textures' (grad_textures, K7): one product per term, the reference's (rasterize.py:780), float partial sums and
+    atomics in any order:  ulp(ref) + gamma_Nt At.
+    """
+    got = np.asarray(got, np.float64)
+    ref_d = np.asarray(ref_d, np.float64)
+    bound = entrywise_bound(ref_d, mags, mode, got)
+    ok = np.isfinite(got) & np.isfinite(ref_d) & np.isfinite(bound)
+    ratio = np.zeros(got.shape, np.float64)
+    with np.errstate(divide='ignore', invalid='ignore'):
+        ratio[ok] = np.abs(got[ok] - ref_d[ok]) / bound[ok]
+    ratio[ok & (bound == 0) & (got != ref_d)] = np.inf
+    ratio[ok & (bound == 0) & (got == ref_d)] = 0.0
+    worst = float(ratio.max()) if ratio.size else 0.0
+    return worst, np.argwhere(ratio > 1)
+
+
+def above_1e4(got, ref_d):
+    """Number of entries more than 1e-4 off elementwise (relative to the entry itself; exact zeros of ref_d excluded)."""
+    got = np.asarray(got, np.float64)
+    ref_d = np.asarray(ref_d, np.float64)
+    ok = np.isfinite(got) & np.isfinite(ref_d) & (ref_d != 0)
+    return int((np.abs(got[ok] - ref_d[ok]) > 1e-4 * np.abs(ref_d[ok])).sum())
+
+
 _display = None
 
 

@@ -46,13 +46,14 @@ def _compare(faces, textures, S, eps, modes, seed, bg=(0.0, 0.0, 0.0), double_te
     g_depth = rng.normal(size=shape).astype(np.float32) if depth else None
     t0 = time.time()
     if double_textures:
-        ref = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True)
-        ref_gf, ref_gt = ref[0], (ref[1] if rgb else None)
+        ref = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, magnitudes=True)
+        ref_gf, ref_gt, mags = ref[0], (ref[1] if rgb else None), ref[-1]
     else:
         # grad_textures of a 655 360 x 8^3 x 3 tensor: float sums (4 GB) instead of a double twin (8 GB); K6 / K8 in double
         ref_gt = fn.backward(g_rgb, g_alpha, g_depth)[1].copy() if rgb else None
         keep = fn.return_rgb
-        ref_gf = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, skip_textures=True)[0]
+        out = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, skip_textures=True, magnitudes=True)
+        ref_gf, mags = out[0], out[-1]
     t_bwd = time.time() - t0
     out = {}
     # (default mode: k_bpm_row, then the same terms on k_bpm_fast -- NR_FLAG_K6_LEGACY 128 --, then the exact mode)
@@ -65,12 +66,20 @@ def _compare(faces, textures, S, eps, modes, seed, bg=(0.0, 0.0, 0.0), double_te
         out[flags] = dict(err=err, max_abs_err=float(np.abs(gf - ref_gf).max()), max_abs=float(np.abs(ref_gf).max()),
                           frac_within_1e4=float(np.mean(np.abs(gf[ok] - ref_gf[ok]) <= RTOL * np.abs(ref_gf[ok]))))
         assert err <= (max(bound, 1e-5) if depth else bound), (flags, err)
+        # every entry against its own term magnitudes (helpers.entrywise)
+        mode = {0: 'default', 128: 'fast', EXACT: 'exact'}[flags]
+        worst, bad = H.entrywise(gf, ref_gf, mags, mode)
+        out[flags].update(entrywise_worst=worst, above_1e4_elementwise=H.above_1e4(gf, ref_gf))
         if rgb:
             gt = abi.host(gt)
             e_t = H.rel_err(gt, ref_gt)
             out[flags]['grad_textures_err'] = e_t
             assert e_t <= RTOL, e_t
+            if 'At' in mags:
+                out[flags]['grad_textures_entrywise_worst'] = H.entrywise(gt, ref_gt, mags, 'textures')[0]
             del gt
+        assert worst <= 1, (flags, mode, worst, len(bad), [tuple(i) for i in bad[:5]])
+        assert out[flags].get('grad_textures_entrywise_worst', 0.0) <= 1, (flags, out[flags])
     report('full_size', S=S, B=int(faces.shape[0]), F=int(faces.shape[1]), modes=list(modes), oracle_fwd_s=t_fwd,
            oracle_bwd_s=t_bwd, threads=O.get_threads(), covered=int((fi >= 0).sum()), visits=fn.visits,
            default=out[0], k_bpm_fast=out[128], exact=out[EXACT])

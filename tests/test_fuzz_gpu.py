@@ -20,8 +20,10 @@ EXTRA_SEEDS = [int(x) for x in os.environ.get('NR_FUZZ_EXTRA_SEEDS', '').split()
 @pytest.mark.parametrize('seed', [1, 2, 3, 6, 118] + EXTRA_SEEDS)  # (6: the scene at the metric's worst case, see the bound below;
 # 118: a crossing point half an ulp below a pixel centre -- the out sweep's second pixel, which k_bpm_row's first version dropped)
 def test_fuzz_unusual_parameters(seed):
+    from test_hip_parity import report
     rng = np.random.default_rng(seed)
     failures = []
+    worst, above = {}, {}
     for it in range(60):
         B = int(rng.integers(1, 4))
         F = int(rng.integers(1, 50))
@@ -53,7 +55,7 @@ def test_fuzz_unusual_parameters(seed):
         g = [rng.normal(size=x.shape).astype(np.float32) for x in (fn.rgb_map, fn.alpha_map, fn.depth_map)]
         if rng.uniform() < 0.3:
             g[0][rng.uniform(size=g[0].shape) < 0.5] = 0
-        ref_gf, ref_gt = fn.backward(*g, accumulate_double=True)
+        ref_gf, ref_gt, mags = fn.backward(*g, accumulate_double=True, magnitudes=True)
         # default K6 numerics (staged and fused entry points; the default mode runs k_bpm_row; 128: NR_FLAG_K6_LEGACY -- the same
         # terms on k_bpm_fast) within the north star's 1e-4 of the reference's terms summed exactly, PLUS twice the reference's
         # own float-summation noise on the scene (its serial float sums against the same exact sum) -- the allowance the float
@@ -100,8 +102,19 @@ def test_fuzz_unusual_parameters(seed):
             ok = np.isfinite(ref_gt) & np.isfinite(gt)
             if ok.any() and H.rel_err(gt[ok], ref_gt[ok]) > 1e-4:
                 msg.append('%s: grad_textures %.2e' % (name, H.rel_err(gt[ok], ref_gt[ok])))
+            # every entry against its own term magnitudes (helpers.entrywise), in the mode of the kernel that ran
+            mode = 'exact' if name.endswith('exact') else ('fast' if name.endswith('legacy') else 'default')
+            w_f, bad_f = H.entrywise(gf, ref_gf, mags, mode)
+            w_t, bad_t = H.entrywise(gt, ref_gt, mags, 'textures')
+            worst[name] = max(worst.get(name, 0.0), w_f)
+            worst[name + ' grad_textures'] = max(worst.get(name + ' grad_textures', 0.0), w_t)
+            above[name] = above.get(name, 0) + H.above_1e4(gf, ref_gf)
+            if w_f > 1 or w_t > 1:
+                msg.append('%s: entrywise grad_faces %.3g at %s, grad_textures %.3g at %s' % (
+                    name, w_f, [tuple(i) for i in bad_f[:3]], w_t, [tuple(i) for i in bad_t[:3]]))
         if msg:
             failures.append((it, dict(B=B, F=F, S=S, ts=ts, eps=eps, near=near, far=far, flags=flags), msg))
+    report('fuzz_unusual_parameters', seed=seed, entrywise_worst=worst, above_1e4_elementwise=above)
     assert not failures, failures
 
 
@@ -109,8 +122,10 @@ def test_fuzz_unusual_parameters(seed):
 def test_fuzz_dense_scenes(seed):
     """Larger random scenes (up to 3000 faces, raster sizes up to 256 incl. non-powers of two, random output modes): several
     scan passes and line windows per band, accumulator-slot overflow, the large-face queue of the forward."""
+    from test_hip_parity import report
     rng = np.random.default_rng(seed)
     failures = []
+    worst, above = {}, {}
     for it in range(8):
         B = int(rng.integers(1, 3))
         F = int(rng.choice([200, 700, 1500, 3000]))
@@ -130,7 +145,8 @@ def test_fuzz_dense_scenes(seed):
         g_rgb = rng.normal(size=(B, S, S, 3)).astype(np.float32) if rgb else None
         g_alpha = rng.normal(size=(B, S, S)).astype(np.float32) if alpha else None
         g_depth = rng.normal(size=(B, S, S)).astype(np.float32) if depth else None
-        ref = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True)
+        ref = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, magnitudes=True)
+        mags = ref[-1]
         for name, run, bound in (('backward', abi.backward, 1e-4), ('backward_fused', abi.backward_fused, 1e-4),
                                  ('backward_fused_exact', lambda *a: abi.backward_fused(*a, k6_flags=2), 1e-5)):
             gf, gt = run(fw, g_rgb, g_alpha, g_depth)
@@ -141,8 +157,17 @@ def test_fuzz_dense_scenes(seed):
                 e = H.rel_err(abi.host(gt), ref[1])
                 if not e <= 1e-4:
                     msg.append('%s: grad_textures %.2e' % (name, e))
+            # every entry against its own term magnitudes (helpers.entrywise)
+            w_f, bad_f = H.entrywise(abi.host(gf), ref[0], mags, 'exact' if name.endswith('exact') else 'default')
+            w_t = H.entrywise(abi.host(gt), ref[1], mags, 'textures')[0] if rgb else 0.0
+            worst[name] = max(worst.get(name, 0.0), w_f, w_t)
+            above[name] = above.get(name, 0) + H.above_1e4(abi.host(gf), ref[0])
+            if w_f > 1 or w_t > 1:
+                msg.append('%s: entrywise grad_faces %.3g at %s, grad_textures %.3g' % (name, w_f, [tuple(i) for i in bad_f[:3]],
+                                                                                        w_t))
         if msg:
             failures.append((it, dict(B=B, F=F, S=S, ts=ts, eps=eps, modes=modes), msg))
+    report('fuzz_dense_scenes', seed=seed, entrywise_worst=worst, above_1e4_elementwise=above)
     assert not failures, failures
 
 
@@ -241,7 +266,8 @@ def test_fuzz_default_k6_error_levels(seed):
         scale = float(rng.choice([1.0, 100.0]))
         g_rgb = (scale * rng.normal(size=(B, S, S, 3))).astype(np.float32) if rgb else None
         g_alpha = (scale * rng.normal(size=(B, S, S))).astype(np.float32) if alpha else None
-        ref = fn.backward(g_rgb, g_alpha, None, accumulate_double=True)[0]
+        out = fn.backward(g_rgb, g_alpha, None, accumulate_double=True, magnitudes=True)
+        ref, mags = out[0], out[-1]
         noise = H.rel_err(fn.backward(g_rgb, g_alpha, None)[0], ref)  # the reference's own serial float sums against the exact sum
         gf = abi.host(abi.backward_fused(fw, g_rgb, g_alpha, None)[0])                 # the default mode: k_bpm_row
         gp = abi.host(abi.backward_fused(fw, g_rgb, g_alpha, None, k6_flags=128)[0])   # k_bpm_fast (NR_FLAG_K6_LEGACY)
@@ -255,6 +281,16 @@ def test_fuzz_default_k6_error_levels(seed):
         bound = 1e-4 + 2 * noise
         if not e_def <= bound or not e_px <= bound or not e_exact <= 2e-6:
             failures.append((it, family, dict(S=S, eps=eps, rgb=rgb, alpha=alpha, F=F), e_def, e_px, e_exact, noise))
+        # every entry against its own term magnitudes (helpers.entrywise): is the noise allowance above only cancellation?
+        for run, got, mode in (('default', gf, 'default'), ('k_bpm_fast', gp, 'fast'), ('exact', ge, 'exact')):
+            w, bad = H.entrywise(got, ref, mags, mode)
+            key = '%s %s entrywise' % (family, run)
+            worst[key] = max(worst.get(key, 0.0), w)
+            key = '%s %s above_1e4_elementwise' % (family, run)
+            worst[key] = worst.get(key, 0) + H.above_1e4(got, ref)
+            if w > 1:
+                failures.append((it, family, dict(S=S, eps=eps, rgb=rgb, alpha=alpha, F=F), run, 'entrywise %.3g' % w,
+                                 [tuple(i) for i in bad[:3]]))
     report('fuzz_default_k6_error_levels', seed=seed, worst=worst)
     assert not failures, failures
 

@@ -232,6 +232,16 @@ def grads_for(fn, rng, rgb=True, alpha=True, depth=True):
     return g_rgb, g_alpha, g_depth
 
 
+def k6_mode(flags):
+    """helpers.entrywise's mode for a K6 call with these flags: k_bpm_global's (NR_FLAG_K6_GLOBAL), the exact mode's, k_bpm_fast's
+    (NR_FLAG_K6_LEGACY, NR_FLAG_K6_SCAN) or the default mode's, where either band kernel may serve an image."""
+    if flags & K6_GLOBAL:
+        return 'global'
+    if flags & EXACT:
+        return 'exact'
+    return 'fast' if flags & (K6_LEGACY | K6_SCAN) else 'default'
+
+
 def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts_bg=(0.2, 0.4, 0.6), k6_flags=0, near=0.1,
                    far=100):
     rgb, alpha, depth = modes
@@ -250,10 +260,19 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
     ref = fn.backward(g_rgb, g_alpha, g_depth)
     ref_gf, ref_gt = ref[0].copy(), (ref[1].copy() if rgb else None)
     # same per-pixel float terms, sums carried in double: isolates term arithmetic from summation order
-    ref_dd = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True)
-    ref_d, ref_gt_d = ref_dd[0].copy(), (ref_dd[1].copy() if rgb else None)
+    ref_dd = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, magnitudes=True)
+    ref_d, ref_gt_d, mags = ref_dd[0].copy(), (ref_dd[1].copy() if rgb else None), ref_dd[-1]
     noise = H.rel_err(ref_gf, ref_d)       # the reference's own serial-float-sum rounding noise
     err_f = None
+
+    def entrywise(got, flags, what):
+        """every entry against its own term magnitudes (helpers.entrywise), in the mode of the kernel that ran"""
+        mode = k6_mode(flags)
+        worst, bad = H.entrywise(got, ref_d, mags, mode)
+        report('check_backward_entrywise', S=S, modes=list(modes), flags=flags, run=what, mode=mode, entrywise_worst=worst,
+               above_1e4_elementwise=H.above_1e4(got, ref_d))
+        assert worst <= 1, '%s (flags %d, %s): %d entries beyond their entrywise bound, worst %.3g at %s' % (
+            what, flags, mode, len(bad), worst, [tuple(i) for i in bad[:5]])
     # default kernel and NR_FLAG_EXACT_GRADIENT; with and without the forward's visible-face flags (same bits)
     for flags, bound in ((k6_flags, K6_BOUND_DEFAULT), (k6_flags | EXACT, K6_BOUND_EXACT)):
         gf, gt = abi.backward(fw, g_rgb, g_alpha, g_depth, use_sampling_maps=residual_maps,
@@ -272,6 +291,7 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
             bound = K6_BOUND_EXACT
         assert err_d <= bound, 'grad_faces vs double-summed oracle: %g (flags %d)' % (err_d, flags)
         assert err_f <= RTOL + 2 * noise, 'grad_faces rel err %g (reference summation noise %g)' % (err_f, noise)
+        entrywise(gf, flags, 'backward')
         # back faces and z (when depth is off) are exactly zero, like the reference
         if not depth:
             assert np.all(gf[..., 2] == 0)
@@ -281,6 +301,7 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
             # same terms either way; what can differ is the order of the line records, hence which segment sums share a float
             # run sum before the double atomics (and the order of K8's float adds): a few 1e-7 of the largest gradient
             assert H.rel_err(abi.host(gf2), gf) <= SAME_TERMS
+            entrywise(abi.host(gf2), flags, 'backward_without_visible')
             # the band kernel's second way to its line records (in-kernel face scan, the fallback of images whose records
             # exceed the buffer): same terms again, in both arithmetic modes
             gf3, _ = abi.backward(fw, g_rgb, g_alpha, g_depth, use_sampling_maps=residual_maps,
@@ -291,6 +312,7 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
             # the same quantity; the exact mode's terms are the same bits on either kernel)
             same_kernel = bool(flags & (EXACT | K6_GLOBAL | K6_LEGACY))
             assert H.rel_err(gf3, gf) <= (SAME_TERMS if same_kernel else K6_BOUND_DEFAULT)
+            entrywise(gf3, flags | K6_SCAN, 'backward_scan')
             # ... and the same mode on the other band kernel (the call above ran k_bpm_row wherever its band fits;
             # NR_FLAG_K6_LEGACY: k_bpm_fast): against the oracle and against k_bpm_row's
             if not (flags & (K6_GLOBAL | K6_SCAN | K6_LEGACY | K6_PX)):
@@ -303,6 +325,7 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
                     report('check_backward_' + kname, S=S, modes=list(modes), flags=flags | kflag, err_vs_double_sum=err_k,
                            vs_default=H.rel_err(gf4, gf))
                     assert err_k <= bound, 'grad_faces (%s) vs double-summed oracle: %g' % (kname, err_k)
+                    entrywise(gf4, flags | kflag, 'backward_' + kname)
                     # (two kernels, two ways to round a term -- k_bpm_fast steps t = d1 - d1_cross by additions of 1 along a
                     # piece and forms sum (I - ref) g, k_bpm_row subtracts per pixel like the reference and forms the colour
                     # difference from centred sums: not the same terms in another order, so not SAME_TERMS; each kernel is
@@ -325,6 +348,10 @@ def check_backward(faces, textures, S, eps, modes, seed, residual_maps=False, ts
         assert H.rel_err(gt, ref_gt_d) <= RTOL, 'grad_textures vs double-summed oracle'
         err_t = H.rel_err(gt, ref_gt)
         assert err_t <= RTOL + 2 * noise_t, 'grad_textures rel err %g (summation noise %g)' % (err_t, noise_t)
+        worst_t, bad_t = H.entrywise(gt, ref_gt_d, mags, 'textures')
+        report('check_backward_entrywise', S=S, modes=list(modes), run='grad_textures', mode='textures',
+               entrywise_worst=worst_t, above_1e4_elementwise=H.above_1e4(gt, ref_gt_d))
+        assert worst_t <= 1, 'grad_textures: %d elements beyond their entrywise bound, worst %.3g' % (len(bad_t), worst_t)
     return err_f
 
 
@@ -436,11 +463,17 @@ def test_big_faces_every_gather_path(ts, eps):
     fw = abi.forward(faces, textures, S, 0.1, 100.0, eps, (0.3, 0.1, 0.2), 0, True, True, True)
     check_forward(fw, fn)
     g_rgb, g_alpha, g_depth = grads_for(fn, rng)
-    ref_gf, ref_gt = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True)
+    ref_gf, ref_gt, mags = fn.backward(g_rgb, g_alpha, g_depth, accumulate_double=True, magnitudes=True)
     for run in (abi.backward, abi.backward_fused):
         gf, gt = run(fw, g_rgb, g_alpha, g_depth)
         assert H.rel_err(abi.host(gt), ref_gt) <= RTOL, run.__name__
         assert H.rel_err(abi.host(gf), ref_gf) <= K6_BOUND_DEFAULT, run.__name__
+        w_f, bad_f = H.entrywise(abi.host(gf), ref_gf, mags, 'default')
+        w_t, bad_t = H.entrywise(abi.host(gt), ref_gt, mags, 'textures')
+        report('big_faces_entrywise', ts=ts, eps=eps, run=run.__name__, entrywise_worst=w_f, entrywise_worst_textures=w_t,
+               above_1e4_elementwise=H.above_1e4(abi.host(gf), ref_gf))
+        assert w_f <= 1, '%s: grad_faces entries beyond their bound: %s' % (run.__name__, [tuple(i) for i in bad_f[:5]])
+        assert w_t <= 1, '%s: grad_textures elements beyond their bound: %s' % (run.__name__, [tuple(i) for i in bad_t[:5]])
 
 
 @pytest.mark.parametrize('S', [384, 512, 768, 1024])
@@ -451,6 +484,29 @@ def test_band_width_classes(S):
     faces = H.random_scene(rng, 1, 400, spread=0.7, size=0.15)
     textures = rng.uniform(0, 1, (1, 400, 2, 2, 2, 3)).astype(np.float32)
     check_backward(faces, textures, S, 1e-3, (True, True, True), seed=301 + S)
+
+
+@pytest.mark.parametrize('S', [480, 481, 513, 576, 577, 600, 777, 832, 833, 1000])
+def test_band_kernel_edges(S):
+    """Band-kernel paths that the soak compares only kernel against kernel, here against the oracle entry by entry
+    (check_backward's entrywise bounds): rasters whose two row chunks are unequal (513, 600, 777, 1000: row_chunk), the team
+    threshold (lines of 32 or more segments share windows from 481: window_team), the edges of k_bpm_fast's 80 KB band shape
+    (576 / 577 and 832 / 833: band_shape; check_backward runs k_bpm_fast behind NR_FLAG_K6_LEGACY).  One image, a few hundred
+    small faces."""
+    rng = np.random.default_rng(5000 + S)
+    faces = H.random_scene(rng, 1, 300, spread=0.7, size=0.12)
+    textures = rng.uniform(0, 1, (1, 300, 2, 2, 2, 3)).astype(np.float32)
+    check_backward(faces, textures, S, 1e-3, (True, True, S % 2 == 0), seed=5001 + S)
+
+
+@pytest.mark.parametrize('B', [1, 4, 32])
+def test_row_band_widths(B):
+    """k_bpm_row's band width at raster 256 follows the launch's workgroup count (row_band_config: ROW_MIN_WGS 4096 and
+    ROW_MIN_WGS_1 1024 workgroups of 2 B S / W): one-line bands for 1 image, two-line bands for 4, four-line bands for 32."""
+    rng = np.random.default_rng(6000 + B)
+    faces = H.random_scene(rng, B, 120, spread=0.7, size=0.15)
+    textures = rng.uniform(0, 1, (B, 120, 2, 2, 2, 3)).astype(np.float32)
+    check_backward(faces, textures, 256, 1e-3, (True, True, False), seed=6001 + B)
 
 
 @pytest.mark.parametrize('S', [4096, 6000])
@@ -593,9 +649,12 @@ def test_global_memory_k6_fallback():
     fn = oracle_forward(faces, textures, 96, 0.1, 100, 1e-3, (0.2, 0.4, 0.6), rgb, alpha, depth)
     fw = abi.forward(faces, textures, 96, 0.1, 100.0, 1e-3, (0.2, 0.4, 0.6), 0, rgb, alpha, depth)
     g_rgb, g_alpha, _ = grads_for(fn, rng, rgb, alpha, depth)
-    ref_d, _ = fn.backward(g_rgb, g_alpha, None, accumulate_double=True)
+    ref_d, _, mags = fn.backward(g_rgb, g_alpha, None, accumulate_double=True, magnitudes=True)
     gf, _ = abi.backward(fw, g_rgb, g_alpha, None, k6_flags=K6_GLOBAL)
     assert H.rel_err(abi.host(gf), ref_d) <= K6_BOUND_EXACT
+    worst, bad = H.entrywise(abi.host(gf), ref_d, mags, k6_mode(K6_GLOBAL))
+    report('global_k6_entrywise', entrywise_worst=worst, above_1e4_elementwise=H.above_1e4(abi.host(gf), ref_d))
+    assert worst <= 1, [tuple(i) for i in bad[:5]]
 
 
 @pytest.mark.parametrize('S', [64, 256])
