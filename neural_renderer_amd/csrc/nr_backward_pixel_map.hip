@@ -998,11 +998,10 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
             // the fused `c * t + eps` below, 23 -> 17 per covered one; `diff <= 0` may then decide differently from :647 where
             // diff is within ~3 roundings of 0, about a term of the size of a rounding.  The exact mode keeps the products and
             // sums apart.)
-            constexpr bool FUSE = !EXACT && k6::FUSED_DIFF;
             auto bg_diff = [&](const float4 &g4, float ga) {
                 if (!RGB) return dba * ga;
                 float d;
-                if constexpr (FUSE) {
+                if constexpr (!EXACT) {
                     d = ALPHA ? __builtin_fmaf(dbr, g4.y, dba * g4.x) : dbr * g4.y;
                     d = __builtin_fmaf(dbg, g4.z, d);
                     d = __builtin_fmaf(dbb, g4.w, d);
@@ -1016,7 +1015,7 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
             auto own_diff = [&](const float4 &c4, float ca, const float4 &g4, float ga) {  // c4 / ca: the pixel's colour
                 if (!RGB) return (ca - ra) * ga;
                 float d;
-                if constexpr (FUSE) {
+                if constexpr (!EXACT) {
                     d = ALPHA ? __builtin_fmaf(c4.y - rr, g4.y, (c4.x - ra) * g4.x) : (c4.y - rr) * g4.y;
                     d = __builtin_fmaf(c4.z - rg, g4.z, d);
                     d = __builtin_fmaf(c4.w - rb, g4.w, d);
@@ -1027,15 +1026,8 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                 }
                 return d;
             };
-            // the reciprocal of the tolerance mode (nr_k6_tune.h: one Newton step brings v_rcp_f32's 1 ulp to ~0.5)
-            auto recip = [&](float y) {
-                float r = __builtin_amdgcn_rcpf(y);
-                if constexpr (k6::NEWTON) r = __builtin_fmaf(__builtin_fmaf(-y, r, 1.0f), r, r);
-                return r;
-            };
-            // the piece's two sums: double in the exact mode (and with NR_K6_BATCH_DOUBLE), float otherwise
-            constexpr bool DSUM = EXACT || k6::BATCH_DOUBLE;
-            typename std::conditional<DSUM, double, float>::type f0 = 0, f1 = 0;
+            // the piece's two sums: double in the exact mode, float otherwise
+            typename std::conditional<EXACT, double, float>::type f0 = 0, f1 = 0;
             if (cls < 2) {
                 // ---- U / M: FSEG pixels of an out sweep, unrolled; one address register per array, compile-time offsets
                 const int l0 = base + s_from;
@@ -1046,12 +1038,11 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                 // One visit without a branch: the visits of a batch are independent instruction chains that the scheduler
                 // interleaves.  Tolerance mode: y is never 0 (x and its eps have one sign), so the reciprocal is finite
                 // wherever the contribution is taken (:648 / :653) and 0 * it adds nothing.
-                // d1fb: t of the piece's first pixel (fused dist: pixel k has t_first + k, both of one sign: no
-                // cancellation) or its d1.  It is re-declared opaque per batch below: that keeps the compiler from computing
-                // all FSEG values of t ahead of the loop, which costs a register each and pushed the kernel into spilling.
-                constexpr bool T_INCR = !EXACT && k6::FUSED_DIST;
-                float d1fb = T_INCR ? t_first : d1f0;
-                float b0 = 0.0f, b1 = 0.0f;  // (NR_K6_BATCH_DOUBLE: float sums of one batch)
+                // d1fb: t of the piece's first pixel (tolerance mode, dist = fma(c, t, +-eps): pixel k has t_first + k, both
+                // of one sign: no cancellation) or its d1 (exact mode).  It is re-declared opaque per batch below: that keeps
+                // the compiler from computing all FSEG values of t ahead of the loop, which costs a register each and pushed
+                // the kernel into spilling.
+                float d1fb = EXACT ? d1f0 : t_first;
                 auto visit = [&](float diff, int k) {
                     if constexpr (EXACT) {
                         const float t = (d1fb + (float)k) - cross;
@@ -1061,25 +1052,11 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                         f1 -= (double)(skip ? 0.0f : q1);                          // :656
                     } else {
                         const float dm = (diff <= 0.0f) ? 0.0f : diff;
-                        float y0, y1;
-                        if constexpr (T_INCR) {
-                            const float t = d1fb + (float)k;
-                            y0 = __builtin_fmaf(c0k, t, e0); y1 = __builtin_fmaf(c1k, t, e1);  // :649-650 / :654-655
-                        } else {
-                            const float t = (d1fb + (float)k) - cross;
-                            y0 = c0k * t + e0; y1 = c1k * t + e1;
-                        }
-                        if constexpr (k6::BATCH_DOUBLE) {
-                            b0 = __builtin_fmaf(-dm, recip(y0), b0);
-                            b1 = __builtin_fmaf(-dm, recip(y1), b1);
-                        } else {
-                            f0 = __builtin_fmaf(-dm, recip(y0), f0);                   // :651
-                            f1 = __builtin_fmaf(-dm, recip(y1), f1);                   // :656
-                        }
+                        const float t = d1fb + (float)k;
+                        const float y0 = __builtin_fmaf(c0k, t, e0), y1 = __builtin_fmaf(c1k, t, e1);  // :649-650 / :654-655
+                        f0 = __builtin_fmaf(-dm, __builtin_amdgcn_rcpf(y0), f0);                      // :651
+                        f1 = __builtin_fmaf(-dm, __builtin_amdgcn_rcpf(y1), f1);                      // :656
                     }
-                };
-                auto end_batch = [&]() {
-                    if constexpr (!EXACT && k6::BATCH_DOUBLE) { f0 += (double)b0; f1 += (double)b1; b0 = b1 = 0.0f; }
                 };
                 if (cls == 0) {
                     // U: gradients only; the next batch's LDS reads are in flight while this one is evaluated.  The pieces of a
@@ -1109,7 +1086,6 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                         }
 #pragma unroll
                         for (int j = 0; j < FB; ++j) visit(bg_diff(gc[j], ac[j]), kb + j);
-                        end_batch();
 #pragma unroll
                         for (int j = 0; j < FB; ++j) { gc[j] = gn[j]; ac[j] = an[j]; }
                         __builtin_amdgcn_sched_barrier(0);  // (keeps the scheduler from hoisting every batch's reads to the top)
@@ -1141,7 +1117,6 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                         }
 #pragma unroll
                         for (int j = 0; j < FB; ++j) visit(own_diff(c4[j], ca[j], g4[j], ga[j]), kb + j);
-                        end_batch();
                         __builtin_amdgcn_sched_barrier(0);
                     }
                 }
@@ -1169,14 +1144,14 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
                         const float x0 = c0k * t, x1 = c1k * t;                               // :649 / :654 (2 / S folded into c)
                         const float y0 = x0 + ((0.0f < x0) ? eps_f : -eps_f);                 // :650 / :655
                         const float y1 = x1 + ((0.0f < x1) ? eps_f : -eps_f);
-                        b0 = __builtin_fmaf(-diff, recip(y0), b0);                            // :651
-                        b1 = __builtin_fmaf(-diff, recip(y1), b1);                            // :656
+                        b0 = __builtin_fmaf(-diff, __builtin_amdgcn_rcpf(y0), b0);            // :651
+                        b1 = __builtin_fmaf(-diff, __builtin_amdgcn_rcpf(y1), b1);            // :656
                     }
                 }
                 if constexpr (!EXACT) { f0 += b0; f1 += b1; }
             }
             // :648 / :653: a contribution whose vertex sits on the line is not taken (its coefficient was Inf / NaN)
-            using RunT = typename std::conditional<EXACT || k6::RUNSUM_DOUBLE, double, float>::type;
+            using RunT = typename std::conditional<EXACT, double, float>::type;
             RunT p0 = (valid && (flags & 2)) ? (RunT)f0 : RunT(0), p1 = (valid && (flags & 4)) ? (RunT)f1 : RunT(0);
             const int key = valid ? line : -1 - (tid & 63);  // (a padding lane: a run of its own)
             run_sums(key, p0, p1);
@@ -1427,26 +1402,14 @@ __device__ __forceinline__ void wave_lds_handover()
 // Flush: one lane per record adds in sweep + out sweep to the double scratch (global_atomic_add_f64), as k_bpm_fast does.
 // Images whose records exceed the line buffer (lines_ok == 0) are left to k_bpm_fast's scan path (launched behind this kernel
 // with overflow_only set).
-#ifndef NR_ROW_OFF  // (development, switch-off builds -- results wrong by construction: 1 no out sweeps, 2 no in sweeps, 4 no global atomics at the flush)
-#define NR_ROW_OFF 0
-#endif
-#ifndef NR_ROW_LDS_PAD  // (development: unused LDS per workgroup, to probe what a workgroup less per CU costs)
-#define NR_ROW_LDS_PAD 0
-#endif
 namespace rowk {
-#ifndef NR_ROW_NT  // (development: threads per workgroup of k_bpm_row -- 256, 128 or 64)
-#define NR_ROW_NT 256
-#endif
-constexpr int NT = NR_ROW_NT, NW = NT / 64;
+constexpr int NT = 256, NW = NT / 64;  // threads / waves per workgroup
 constexpr int WIN = 64;            // records per window (a lane each in phase A)
 constexpr int SEG = 16;            // pixels per step of a block
 constexpr int MAX_SEGS = 64;       // segments of a line, at most (raster <= 1024): the sort's keys
 constexpr int IN_SEG = 16;        // float terms per double addition of an in sweep (a piece of k_bpm_fast holds 15)
 constexpr int IN_BATCH = 4;       // pixels of an in sweep whose LDS reads are requested together
-#ifndef NR_ROW_MAX_PX  // (development)
-#define NR_ROW_MAX_PX 1024
-#endif
-constexpr int MAX_PX = NR_ROW_MAX_PX;       // pixels of a band, at most
+constexpr int MAX_PX = 1024;       // pixels of a band, at most
 // LDS of a workgroup, for the npx = W * SP pixels of its band: gradients [W][SP][NC] | sums P [W][SP] (the exact mode: colours
 // [W][SP][NC]) | face indices [W][SP] | K of the band's lines (not in the exact mode) | a window per wave
 constexpr int K_BYTES = 4 * 16, WAVE_BYTES = WIN * 16;
@@ -1454,7 +1417,7 @@ template <bool RGB> __host__ __device__ constexpr size_t g_bytes(size_t npx) { r
 template <bool RGB, bool EXACT> __host__ __device__ constexpr size_t c_bytes(size_t npx) { return EXACT ? g_bytes<RGB>(npx) : npx * 4; }
 template <bool RGB, bool EXACT> __host__ __device__ constexpr size_t lds_bytes(size_t npx)
 {
-    return g_bytes<RGB>(npx) + c_bytes<RGB, EXACT>(npx) + npx * 4 + (EXACT ? 0 : K_BYTES) + NW * WAVE_BYTES + NR_ROW_LDS_PAD;
+    return g_bytes<RGB>(npx) + c_bytes<RGB, EXACT>(npx) + npx * 4 + (EXACT ? 0 : K_BYTES) + NW * WAVE_BYTES;
 }
 }  // namespace rowk
 
@@ -1677,13 +1640,9 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
     // k_bpm_fast keeps the division everywhere; tests/test_hip_parity.py compares the two kernels' exact modes bit for bit.
     auto exact_scale = [&](float ct) {
         if constexpr (MODE == K6_EXACT_POW2) return ct * two_over_s_f;
-#ifdef NR_ROW_TRUE_DIV
-        return (float)((double)ct * 2.0 / s_d);
-#else
         float q = (float)((double)ct * two_over_s_d);
         if (__builtin_expect(!(fabsf(q) >= 1.17549435e-38f) && ct != 0.0f, 0)) q = (float)((double)ct * 2.0 / s_d);
         return q;
-#endif
     };
     auto exact_dist = [&](float ct) {
         const float dist = exact_scale(ct);
@@ -1827,7 +1786,7 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
             const int nseg = has_b ? (dpos ? nsl - (b_from >> 4) : (b_to >> 4) + 1) : 0;
             hist[lane] = 0;
             double in0 = 0.0, in1 = 0.0;
-            if (in_here && !(NR_ROW_OFF & 2) && sweeps_mine) {
+            if (in_here && sweeps_mine) {
                 const float cross = qq.x, c0k = qq.y, c1k = qq.z;
                 const int fnr = __float_as_int(qq.w);
                 const float d_first = (EXACT || d1_in < 0 || d1_in >= SL) ? 0.0f : direct_diff(c_in, c_out, base + d1_in);
@@ -1944,7 +1903,7 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
             if constexpr (EXACT) oref_b = c_in;
             const int g_first = 4 * member, g_step = 4 * team;  // (a shared window: every team-th group)
             int src_next = __builtin_amdgcn_ds_bpermute(((g_first + row) & 63) << 2, inv);
-            for (int g0 = g_first; g0 < ((NR_ROW_OFF & 1) ? 0 : n_out); g0 += g_step) {
+            for (int g0 = g_first; g0 < n_out; g0 += g_step) {
                 const bool act = g0 + row < n_out;
                 const int src = src_next;  // (of a block without a record: some lane; nothing of it is used)
                 src_next = __builtin_amdgcn_ds_bpermute(((g0 + g_step + row) & 63) << 2, inv);
@@ -2128,12 +2087,8 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
                 const double t1 = (flags & 4) ? in1 + (neg1 ? a.y : -a.y) : 0.0;
                 const int tgt = hh.w, lpos = tgt & 0x0fffffff;
                 double *dst = scratch + ((size_t)b * F + lpos) * 6 + (1 - axis);
-                if (NR_ROW_OFF & 4) {
-                    asm volatile("" : : "v"(t0), "v"(t1), "v"(dst));
-                } else {
-                    if (t0 != 0.0) atomicAdd(dst + 2 * ((tgt >> 28) & 3), t0);
-                    if (t1 != 0.0) atomicAdd(dst + 2 * ((tgt >> 30) & 3), t1);
-                }
+                if (t0 != 0.0) atomicAdd(dst + 2 * ((tgt >> 28) & 3), t0);
+                if (t1 != 0.0) atomicAdd(dst + 2 * ((tgt >> 30) & 3), t1);
             }
             wave_lds_handover();
         }
@@ -2321,41 +2276,73 @@ struct LdsLimit {
     }
 };
 
-template <bool RGB, bool ALPHA, int MODE, int NT, bool OVF = false>
-int launch_fast(const float *faces, const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb,
+// Which band kernel a call takes, and how it is shaped: decided once per call, on the host, from the call's shape alone (no
+// device).  run_backward_pixel_map executes the plan; nr_profile_k6_choice reports its kernel.
+enum K6Kernel { K6_KERNEL_FAST = 0, K6_KERNEL_ROW = 1, K6_KERNEL_GLOBAL = 2 };  // (0 / 1: nr_profile_band_kernel_which)
+struct K6Plan {
+    int kernel;           // K6Kernel
+    int mode;             // K6_FAST | K6_EXACT_POW2 | K6_EXACT
+    BandShape shape;      // k_bpm_fast: workgroup shape,
+    int W_fast;           // ... band width (lines; 0: no LDS band fits -- the global kernel),
+    size_t fast_lds;      // ... LDS bytes,
+    int win_lines, qcap;  // ... line records per window and piece-queue capacity
+    int W_row;            // k_bpm_row: band width (0: not taken)
+    size_t row_lds;       // ... LDS bytes
+    int W, n_bands;       // the band tables: lines per band, bands per image
+    bool use_records;     // line records from k_line_setup (false: every image takes k_bpm_fast's face scan)
+    bool overflow_pass;   // k_bpm_fast's overflow-only launch follows k_bpm_row
+    size_t fill_max;      // the largest zero fill (bytes) that the band kernel takes along
+};
+
+// The call's (rgb, alpha, mode) as template arguments of f(r, a, m): the three map combinations of the ABI (rgb and alpha, rgb,
+// alpha) times the three arithmetic modes.  Both band kernels are launched through it.
+template <class Fn> int with_k6_types(bool rgb, bool alpha, int mode, const Fn &f)
+{
+    using T = std::true_type;
+    using N = std::false_type;
+    auto by_mode = [&](auto r, auto a) {
+        if (mode == K6_FAST) return f(r, a, std::integral_constant<int, K6_FAST>());
+        if (mode == K6_EXACT_POW2) return f(r, a, std::integral_constant<int, K6_EXACT_POW2>());
+        return f(r, a, std::integral_constant<int, K6_EXACT>());
+    };
+    return (rgb && alpha) ? by_mode(T(), T()) : (rgb ? by_mode(T(), N()) : by_mode(N(), T()));
+}
+
+template <bool RGB, bool ALPHA, int MODE, bool OVF>
+int launch_fast(const K6Plan &p, const float *faces, const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb,
                 const float *g_alpha, const int *vis_list, const int *vis_count, const unsigned *rng, double *scratch,
                 const int *band_lines, const int *band_start, const int *lines_ok, const BandLine *line_buf, size_t cap,
-                int B, int F, int S, int W, size_t lds, double eps, float k2s, int win_lines, int qcap, hipStream_t st,
-                void *zero_ptr, size_t zero_bytes)
+                int B, int F, int S, double eps, float k2s, hipStream_t st, void *zero_ptr, size_t zero_bytes)
 {
-    static LdsLimit limit;  // one per instantiation
-    constexpr int overflow_only = OVF ? 1 : 0;
-    auto kern = k_bpm_fast<RGB, ALPHA, MODE, NT, OVF>;
-    if (int rc = limit.ensure((const void *)kern, lds)) return rc;
-    const unsigned total_wg = (unsigned)((S + W - 1) / W) * 2u * (unsigned)B;
+    const unsigned total_wg = (unsigned)((S + p.W_fast - 1) / p.W_fast) * 2u * (unsigned)B;
     // 1-D grid: the kernel maps ids to (image, axis, band) per XCD
     // (overflow-only launch behind k_bpm_row: a resident grid that strides over the bands, k6::OVF_GRID workgroups.  With nothing
     // to do it costs 4.6 us in a step whatever the grid -- a launch (1.3 us for up to 256 workgroups that leave at once,
     // scripts/dev/empty_launch_probe.hip) and one dependent load of the images' verdicts from memory the line setup wrote with
     // atomics; with every image over the line buffer -- 32 teapot views at 1024^2 -- 1024 workgroups took 5.0 ms against 7.3 at 256)
-    const unsigned grid = overflow_only ? (total_wg < k6::OVF_GRID ? total_wg : k6::OVF_GRID) : xcd_grid(total_wg);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), lds, st, faces, fi, rgb, alpha, g_rgb, g_alpha,
-                       vis_list, vis_count, rng, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, W, S + 4,
-                       eps, k2s, B, win_lines, qcap, (uint4 *)zero_ptr, zero_bytes / 16);
-    return 0;
+    const unsigned grid = OVF ? (total_wg < k6::OVF_GRID ? total_wg : k6::OVF_GRID) : xcd_grid(total_wg);
+    auto go = [&](auto nt) {
+        constexpr int NT = decltype(nt)::value;
+        static LdsLimit limit;  // one per instantiation
+        auto kern = k_bpm_fast<RGB, ALPHA, MODE, NT, OVF>;
+        if (int rc = limit.ensure((const void *)kern, p.fast_lds)) return rc;
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), p.fast_lds, st, faces, fi, rgb, alpha, g_rgb, g_alpha, vis_list, vis_count,
+                           rng, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, p.W_fast, S + 4, eps, k2s, B,
+                           p.win_lines, p.qcap, (uint4 *)zero_ptr, zero_bytes / 16);
+        return 0;
+    };
+    return p.shape.threads == 256 ? go(std::integral_constant<int, 256>()) : go(std::integral_constant<int, 512>());
 }
 
 // k_bpm_row's chunks: a line is cut into ceil(S / 512) pieces of equal length (a multiple of 32 pixels, the last one shorter):
 // the whole line up to raster 512, 2 x 320 at 640, 2 x 512 at 1024 (see the kernel) -- on meshes of fewer than 2^15 faces.  A
 // record is set up once per chunk, and on a dense mesh (hundreds of records per line) that costs more than the column bands'
 // staging gains: config 5 (655 360 faces at 1024^2) 1.34 ms per step with whole lines, 1.38 with half lines.
-#ifndef NR_ROW_CHUNK_PX  // (development: the longest chunk)
-#define NR_ROW_CHUNK_PX 512
-#endif
+constexpr int ROW_CHUNK_PX = 512;  // the longest chunk
 int row_chunk(int S, int F)
 {
     if (F >= (1 << 15)) return (S + 31) & ~31;
-    const int n_ch = (S + NR_ROW_CHUNK_PX - 1) / NR_ROW_CHUNK_PX, len = (S + n_ch - 1) / n_ch;
+    const int n_ch = (S + ROW_CHUNK_PX - 1) / ROW_CHUNK_PX, len = (S + n_ch - 1) / n_ch;
     return (len + 31) & ~31;
 }
 
@@ -2382,22 +2369,75 @@ int row_band_config(int S, int F, bool rgb, bool exact, int B, size_t *lds_bytes
 }
 
 template <bool RGB, bool ALPHA, int MODE>
-int launch_row(const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb, const float *g_alpha, double *scratch,
-               const int *band_lines, const int *band_start, const int *lines_ok, const BandLine *line_buf, size_t cap, int B,
-               int F, int S, int W, size_t lds, double eps, hipStream_t st, void *zero_ptr, size_t zero_bytes)
+int launch_row(const K6Plan &p, const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb, const float *g_alpha,
+               double *scratch, const int *band_lines, const int *band_start, const int *lines_ok, const BandLine *line_buf,
+               size_t cap, int B, int F, int S, double eps, hipStream_t st, void *zero_ptr, size_t zero_bytes)
 {
-    const int CH = row_chunk(S, F);
+    const int CH = row_chunk(S, F), W = p.W_row;
     const unsigned n_ch = (unsigned)((S + CH - 1) / CH), total_wg = (unsigned)((S + W - 1) / W) * 2u * (unsigned)B * n_ch;
     auto go = [&](auto chunked) {
         constexpr bool C = decltype(chunked)::value;
         static LdsLimit limit;  // one per instantiation (40 KB at most with the product's constants: never raised)
-        if (int rc = limit.ensure((const void *)k_bpm_row<RGB, ALPHA, MODE, C>, lds)) return rc;
-        hipLaunchKernelGGL((k_bpm_row<RGB, ALPHA, MODE, C>), dim3(xcd_grid(total_wg)), dim3(rowk::NT), lds, st, fi, rgb, alpha, g_rgb,
-                           g_alpha, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, W, CH, (float)eps, eps, B,
+        if (int rc = limit.ensure((const void *)k_bpm_row<RGB, ALPHA, MODE, C>, p.row_lds)) return rc;
+        hipLaunchKernelGGL((k_bpm_row<RGB, ALPHA, MODE, C>), dim3(xcd_grid(total_wg)), dim3(rowk::NT), p.row_lds, st, fi, rgb, alpha,
+                           g_rgb, g_alpha, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, W, CH, (float)eps, eps, B,
                            (uint4 *)zero_ptr, zero_bytes / 16);
         return 0;
     };
     return n_ch > 1 ? go(std::true_type()) : go(std::false_type());
+}
+
+// Whether k_bpm_row takes a call whose raster has a k_bpm_fast band: its band width (lines per workgroup) and LDS bytes, or 0.
+// Both arithmetic modes have ONE band kernel since round 6, k_bpm_row: it is ahead of k_bpm_fast on every shape measured
+// (profiles/r06_k6_kernels.md: 8 ... 128 teapot views at 256^2, 64 views at rasters 320 ... 768, 32 and 4 views at 1024^2, 256
+// views at 128^2, 1024 at 32^2, configs 4 and 5; the exact mode: 64 views at 256^2 and 512^2), so nothing about the call's size
+// enters the choice -- a batch and its shards take the same kernel.  k_bpm_fast keeps what k_bpm_row does not do: the in-kernel
+// face scan (NR_FLAG_K6_SCAN, and the images of a call whose records exceed the line buffer: an overflow-only launch behind
+// k_bpm_row), rasters beyond k_bpm_row's LDS band (> 1024), the default mode with eps = 0 (a lane outside a sweep multiplies 0
+// by 1 / (|c t| + eps), and t = 0 -- the crossing point on a pixel centre -- would make that 0 * Inf; the exact mode selects in
+// front of its division and takes any eps), and NR_FLAG_K6_LEGACY (tests, measurements).
+// With k_bpm_row the band tables and the line records are binned per LINE (band width 1).
+int k6_row_band(int B, int F, int S, bool rgb, double eps, int flags, size_t *row_lds)
+{
+    const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
+    const bool possible = !(flags & (NR_FLAG_K6_SCAN | NR_FLAG_K6_LEGACY)) && B <= 65535 && (exact || (float)eps >= 1e-30f);
+    return possible ? row_band_config(S, F, rgb, exact, B, row_lds) : 0;
+}
+
+K6Plan plan_k6(int B, int F, int S, bool rgb, double eps, int flags)
+{
+    K6Plan p = {};
+    const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
+    p.mode = !exact ? K6_FAST : ((S & (S - 1)) == 0 ? K6_EXACT_POW2 : K6_EXACT);
+    // Narrower bands when the launch would have few band workgroups (small batches): the chip holds 768 of them at a time and
+    // half of a teapot view's bands are empty; 16 views: stage 113 -> 104 us with W = 2, 4 views 70 -> 50, 1 view 66 -> 40 (W = 1).
+    p.shape = band_shape(S);
+    int w_max = p.shape.w_max, win = BAND_WIN;
+    while (w_max > 1 && (size_t)B * 2 * ((S + w_max - 1) / w_max) < 3072) w_max >>= 1;
+    p.W_fast = fast_band_config(S, rgb, p.shape, w_max, &p.fast_lds, &win, &p.qcap);
+    if (p.W_fast == 0 || (flags & NR_FLAG_K6_GLOBAL)) {  // raster too large for an LDS band (or the fallback asked for: tests)
+        p.kernel = K6_KERNEL_GLOBAL;
+        return p;
+    }
+    // lines per window: the packed piece scan keeps each class count in 16 bits (<= win * 2 * S / FSEG pieces)
+    p.win_lines = min(win, max(4, min(BAND_WIN, (int)(65535ll * FSEG / (2ll * S))) & ~3));
+    p.W_row = k6_row_band(B, F, S, rgb, eps, flags, &p.row_lds);
+    const bool row = p.W_row > 0;
+    p.kernel = row ? K6_KERNEL_ROW : K6_KERNEL_FAST;
+    p.overflow_pass = row;
+    p.W = row ? 1 : p.W_fast;
+    p.n_bands = (S + p.W - 1) / p.W;
+    // line records from k_line_setup, unless NR_FLAG_K6_SCAN asks for the in-kernel face scan (tests) or the launch is
+    // outside k_line_setup's shape (grid.y, 72 KB of LDS)
+    p.use_records = !(flags & NR_FLAG_K6_SCAN) && B <= 65535 && p.n_bands <= 3072;
+    // (a fill that rides in the band kernel: 16-byte words, and a slice per workgroup that is small next to the
+    // workgroup's own work -- k6::FOLD_KB per band workgroup: 4 KB at the headline size, 61 KB on config 4; config 5's
+    // 4 GB would be 2 MB for each of 2048 workgroups and go at 7 TB/s through a fill launch instead.  A 256-thread workgroup
+    // takes half of what a 512-thread one does.)
+    const int W_band = row ? p.W_row : p.W_fast;
+    const size_t band_wgs = (size_t)((S + W_band - 1) / W_band) * 2 * (size_t)B;
+    p.fill_max = band_wgs * ((size_t)k6::FOLD_KB << 10) * (size_t)(row ? rowk::NT : p.shape.threads) / 512;
+    return p;
 }
 
 }  // namespace
@@ -2408,24 +2448,6 @@ NR_API size_t nr_backward_workspace_bytes(int32_t B, int32_t F, int32_t S, int32
     // depth only (no K6): nothing but the per-image lists of the faces that own a pixel, for the K8 gather
     if (!return_rgb && !return_alpha) return lists_layout(B, F).total;
     return bpm_layout(B, F, S).total;
-}
-
-// Which band kernel a call takes: the band width (lines per workgroup) of k_bpm_row and its LDS bytes, or 0 for k_bpm_fast.
-// Both arithmetic modes have ONE band kernel since round 6, k_bpm_row: it is ahead of k_bpm_fast on every shape measured
-// (profiles/r06_k6_kernels.md: 8 ... 128 teapot views at 256^2, 64 views at rasters 320 ... 768, 32 and 4 views at 1024^2, 256
-// views at 128^2, 1024 at 32^2, configs 4 and 5; the exact mode: 64 views at 256^2 and 512^2), so nothing about the call's size
-// enters the choice -- a batch and its shards take the same kernel.  k_bpm_fast keeps what k_bpm_row does not do: the in-kernel
-// face scan (NR_FLAG_K6_SCAN, and the images of a call whose records exceed the line buffer: an overflow-only launch behind
-// k_bpm_row), rasters beyond k_bpm_row's LDS band (> 1024), the default mode with eps = 0 (a lane outside a sweep multiplies 0
-// by 1 / (|c t| + eps), and t = 0 -- the crossing point on a pixel centre -- would make that 0 * Inf; the exact mode selects in
-// front of its division and takes any eps), and NR_FLAG_K6_LEGACY (tests, measurements).
-// With k_bpm_row the band tables and the line records are binned per LINE (band width 1).
-int k6_row_band(int B, int F, int S, bool rgb, double eps, int flags, bool fast_fits, size_t *row_lds)
-{
-    const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
-    const bool possible = !(flags & (NR_FLAG_K6_SCAN | NR_FLAG_K6_LEGACY | NR_FLAG_K6_GLOBAL)) && B <= 65535 && fast_fits &&
-                          (exact || (float)eps >= 1e-30f);
-    return possible ? row_band_config(S, F, rgb, exact, B, row_lds) : 0;
 }
 
 // Measurement hook (include/nr_hip_profile.h, nr_profile_band_kernel): a pair of events around the band kernel's launch.  Only in the
@@ -2469,17 +2491,13 @@ NR_API int nr_profile_band_kernel_which(void) { return g_band_timer.recorded ? g
 // (pure host logic, no device needed: the per-launch rule as a function of the call's shape, for tests/test_abi.py)
 NR_API int nr_profile_k6_choice(int32_t B, int32_t F, int32_t S, int32_t return_rgb, int32_t return_alpha, double eps, int32_t flags)
 {
-    size_t lds = 0, fl = 0;
-    int win = 0, qcap = 0;
-    const BandShape shape = band_shape(S);
-    const bool fast_fits = fast_band_config(S, return_rgb != 0, shape, shape.w_max, &fl, &win, &qcap) != 0;
     (void)return_alpha;
-    return k6_row_band(B, F, S, return_rgb != 0, eps, flags, fast_fits, &lds) > 0 ? 1 : 0;
+    return plan_k6(B, F, S, return_rgb != 0, eps, flags).kernel == K6_KERNEL_ROW ? 1 : 0;
 }
-#define NR_BAND_TIMER_START(st) if (g_band_timer.on) { g_band_timer.which = use_row ? 1 : 0; g_band_timer.recorded = hipEventRecord(g_band_timer.start, st) == hipSuccess; }
+#define NR_BAND_TIMER_START(st, kernel) if (g_band_timer.on) { g_band_timer.which = (kernel); g_band_timer.recorded = hipEventRecord(g_band_timer.start, st) == hipSuccess; }
 #define NR_BAND_TIMER_STOP(st) if (g_band_timer.on && g_band_timer.recorded) g_band_timer.recorded = hipEventRecord(g_band_timer.stop, st) == hipSuccess
 #else
-#define NR_BAND_TIMER_START(st) ((void)0)
+#define NR_BAND_TIMER_START(st, kernel) ((void)0)
 #define NR_BAND_TIMER_STOP(st) ((void)0)
 #endif
 
@@ -2505,20 +2523,8 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
     const int n = B * F;
     const bool rgb = return_rgb != 0, alpha = return_alpha != 0;
     const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
-
-    size_t lds = 0;
-    int win = BAND_WIN, qcap = 0;
-    // Narrower bands when the launch would have few band workgroups (small batches): the chip holds 768 of them at a time and
-    // half of a teapot view's bands are empty; 16 views: stage 113 -> 104 us with W = 2, 4 views 70 -> 50, 1 view 66 -> 40 (W = 1).
-    const BandShape shape = band_shape(S);
-    int w_max = shape.w_max;
-    while (w_max > 1 && (size_t)B * 2 * ((S + w_max - 1) / w_max) < 3072) w_max >>= 1;
-    const int W_fast = fast_band_config(S, rgb, shape, w_max, &lds, &win, &qcap);
-    size_t row_lds = 0;
-    const int W_row = k6_row_band(B, F, S, rgb, eps, flags, W_fast != 0, &row_lds);  // (which launches take k_bpm_row: there)
-    const bool use_row = W_row > 0;
-    const int W = use_row ? 1 : W_fast;  // the band width of the tables
-    if (W_fast == 0 || (flags & NR_FLAG_K6_GLOBAL)) {  // raster too large for an LDS band (or the fallback asked for: tests)
+    const K6Plan plan = plan_k6(B, F, S, rgb, eps, flags);
+    if (plan.kernel == K6_KERNEL_GLOBAL) {
         const dim3 grid((unsigned)n), block(WAVE);
         if (rgb && alpha)
             hipLaunchKernelGGL((k_bpm_global<true, true>), grid, block, 0, st, faces, face_index_map, rgb_map,
@@ -2537,7 +2543,7 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
     const bool defer = defer_scratch && defer_slot_of;  // the caller's gather finishes the listed faces (see nr_device.h)
     unsigned char *ws = (unsigned char *)workspace;
     int *band_lines = (int *)(ws + L.band_off);
-    const int n_bands = (S + W - 1) / W;
+    const int W = plan.W, n_bands = plan.n_bands;
     double *scratch = (double *)(ws + L.scratch_off);
     int *vis_count = (int *)(ws + L.count_off);
     int *vis_list = (int *)(ws + L.list_off);
@@ -2557,9 +2563,7 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
     }
     int *band_start = (int *)(ws + L.start_off), *band_cursor = (int *)(ws + L.cursor_off), *lines_ok = (int *)(ws + L.ok_off);
     BandLine *line_buf = (BandLine *)(ws + L.lines_off);
-    // line records from k_line_setup, unless NR_FLAG_K6_SCAN asks for the in-kernel face scan (tests) or the launch is
-    // outside k_line_setup's shape (grid.y, 72 KB of LDS)
-    const bool use_records = !(flags & NR_FLAG_K6_SCAN) && B <= 65535 && n_bands <= 3072;
+    const bool use_records = plan.use_records;
     // the distance coefficients of a record: x 2 / S up front in the tolerance mode, as the reference has them in the exact one
     const float k2s = exact ? 1.0f : 2.0f / (float)S;
     const size_t cap = use_records ? L.cap : 0;  // capacity 0: every image is told to take the scan path
@@ -2599,64 +2603,32 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
             if (int rc = run_line_setup(la, st)) return rc;
         }
     }
-    // lines per window: the packed piece scan keeps each class count in 16 bits (<= win * 2 * S / FSEG pieces)
-    const int win_lines = min(win, max(4, min(BAND_WIN, (int)(65535ll * FSEG / (2ll * S))) & ~3));
-    int rc;
-    {
-        // (a fill that rides in the band kernel: 16-byte words, and a slice per workgroup that is small next to the
-        // workgroup's own work -- k6::FOLD_KB per band workgroup: 4 KB at the headline size, 61 KB on config 4; config 5's
-        // 4 GB would be 2 MB for each of 2048 workgroups and go at 7 TB/s through a fill launch instead)
-        const int W_band = use_row ? W_row : W_fast;  // lines per band workgroup of the kernel that carries the fill
-        const size_t band_wgs = (size_t)((S + W_band - 1) / W_band) * 2 * (size_t)B;
-        // (per workgroup: a 256-thread workgroup takes half of what a 512-thread one does)
-        const bool zero_ok = !hook && zero_ptr && zero_bytes > 0 && zero_bytes % 16 == 0 && ((size_t)zero_ptr & 15) == 0 &&
-                             zero_bytes <= band_wgs * ((size_t)k6::FOLD_KB << 10) * (size_t)(use_row ? rowk::NT : shape.threads) / 512;
-        const int mode = !exact ? K6_FAST : ((S & (S - 1)) == 0 ? K6_EXACT_POW2 : K6_EXACT);
-        auto launch = [&](auto r, auto a, auto m, auto nt) {
-            constexpr bool R = decltype(r)::value, A = decltype(a)::value;
-            constexpr int M = decltype(m)::value, NTH = decltype(nt)::value;
-            // (behind k_bpm_row: only the images whose records exceed the line buffer, by the scan path, no fill)
-            if (use_row)
-                return launch_fast<R, A, M, NTH, true>(
-                    faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, vis_list, vis_count, rng, scratch,
-                    band_lines, band_start, lines_ok, line_buf, L.cap, B, F, S, W_fast, lds, eps, k2s, win_lines, qcap, st, nullptr, 0);
-            return launch_fast<R, A, M, NTH>(
-                faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, vis_list, vis_count, rng, scratch,
-                band_lines, band_start, lines_ok, line_buf, L.cap, B, F, S, W_fast, lds, eps, k2s, win_lines, qcap, st,
-                zero_ok ? zero_ptr : nullptr, zero_ok ? zero_bytes : 0);
-        };
-        using T = std::true_type;
-        using N = std::false_type;
-        auto by_threads = [&](auto r, auto a, auto m) {
-            if (shape.threads == 256) return launch(r, a, m, std::integral_constant<int, 256>());
-            return launch(r, a, m, std::integral_constant<int, 512>());
-        };
-        auto by_mode = [&](auto r, auto a) {
-            if (mode == K6_FAST) return by_threads(r, a, std::integral_constant<int, K6_FAST>());
-            if (mode == K6_EXACT_POW2) return by_threads(r, a, std::integral_constant<int, K6_EXACT_POW2>());
-            return by_threads(r, a, std::integral_constant<int, K6_EXACT>());
-        };
-        NR_BAND_TIMER_START(st);
-        rc = 0;
-        if (use_row) {
-            auto lpm = [&](auto r, auto a, auto m) {
-                return launch_row<decltype(r)::value, decltype(a)::value, decltype(m)::value>(
-                    face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, scratch, band_lines, band_start, lines_ok,
-                    line_buf, L.cap, B, F, S, W_row, row_lds, eps, st, zero_ok ? zero_ptr : nullptr, zero_ok ? zero_bytes : 0);
-            };
-            auto lp = [&](auto r, auto a) {
-                if (mode == K6_FAST) return lpm(r, a, std::integral_constant<int, K6_FAST>());
-                if (mode == K6_EXACT_POW2) return lpm(r, a, std::integral_constant<int, K6_EXACT_POW2>());
-                return lpm(r, a, std::integral_constant<int, K6_EXACT>());
-            };
-            rc = (rgb && alpha) ? lp(T(), T()) : (rgb ? lp(T(), N()) : lp(N(), T()));
-            NR_BAND_TIMER_STOP(st);
-        }
-        if (rc == 0) rc = (rgb && alpha) ? by_mode(T(), T()) : (rgb ? by_mode(T(), N()) : by_mode(N(), T()));
-        if (!use_row) NR_BAND_TIMER_STOP(st);
-        if (rc == 0 && zero_ok && zeroed) *zeroed = 1;
-    }
+    // the band kernel (k_bpm_row or k_bpm_fast, with the caller's zero fill when it fits), then the overflow-only k_bpm_fast
+    // launch behind k_bpm_row: the images whose records exceed the line buffer, by the face scan, no fill
+    const bool zero_ok = !hook && zero_ptr && zero_bytes > 0 && zero_bytes % 16 == 0 && ((size_t)zero_ptr & 15) == 0 &&
+                         zero_bytes <= plan.fill_max;
+    void *const fill_ptr = zero_ok ? zero_ptr : nullptr;
+    const size_t fill_len = zero_ok ? zero_bytes : 0;
+    auto band_fast = [&](auto overflow_only, void *zp, size_t zb) {
+        return with_k6_types(rgb, alpha, plan.mode, [&](auto r, auto a, auto m) {
+            return launch_fast<decltype(r)::value, decltype(a)::value, decltype(m)::value, decltype(overflow_only)::value>(
+                plan, faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, vis_list, vis_count, rng, scratch,
+                band_lines, band_start, lines_ok, line_buf, L.cap, B, F, S, eps, k2s, st, zp, zb);
+        });
+    };
+    auto band_row = [&]() {
+        return with_k6_types(rgb, alpha, plan.mode, [&](auto r, auto a, auto m) {
+            return launch_row<decltype(r)::value, decltype(a)::value, decltype(m)::value>(
+                plan, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, scratch, band_lines, band_start, lines_ok,
+                line_buf, L.cap, B, F, S, eps, st, fill_ptr, fill_len);
+        });
+    };
+    NR_BAND_TIMER_START(st, plan.kernel);
+    int rc = plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill_ptr, fill_len);
+    NR_BAND_TIMER_STOP(st);
+    if (rc == 0 && plan.overflow_pass) rc = band_fast(std::true_type(), nullptr, 0);
     if (rc) return rc;
+    if (zero_ok && zeroed) *zeroed = 1;
     if (defer) {  // the caller finishes the listed faces (the fused gather, in the same launch as K7 / K8)
         *defer_scratch = scratch;
         *defer_slot_of = slot_of;
@@ -2756,7 +2728,6 @@ NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *face
     const double *k6_scratch = nullptr;
     const int *k6_slot_of = nullptr;
     int tex_zeroed = 0;
-    bool k6_done = false;
     // Small launches (up to 96 k faces in the call: 16 views of the 4928-face teapot) take the order
     //   compaction | line setup + gather + zeros of grad_textures in ONE grid | band kernel | the faces the gather left
     //   out + K6's sums onto grad_faces (one launch)
@@ -2789,13 +2760,9 @@ NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *face
             if (k6_scratch && !finalized) run_bpm_finalize(k6_scratch, k6_slot_of, grad_faces, B, F, st, true);
             return launch_status();
         }
-        // the band pipeline did not run (global-memory kernel: grad_faces complete, no lists): the gathers below, as they are
-        k6_scratch = nullptr;
-        k6_slot_of = nullptr;
-        k6_done = true;
-    }
-    if (k6_done) {
-    } else     if (use_rgb || use_alpha) {
+        // the band pipeline did not run (global-memory kernel: grad_faces complete, no lists, nothing deferred): the gathers
+        // below, as they are
+    } else if (use_rgb || use_alpha) {
         if (int rc = run_backward_pixel_map(faces, face_index_map, use_rgb ? rgb_map : nullptr,
                                             use_alpha ? alpha_map : nullptr, grad_rgb_map, grad_alpha_map, grad_faces,
                                             B, F, S, eps, use_rgb, use_alpha, flags, visible_faces, workspace,

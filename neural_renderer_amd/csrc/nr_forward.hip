@@ -38,10 +38,7 @@ namespace {
 // negative ones), so any `near` -- the reference accepts any, :331 -- orders correctly, faces behind the camera
 // (negative zp with near < 0) included.  The result does not depend on the order of the atomics:
 // face_index_map is bit-reproducible.
-#ifndef NR_FWD_SMALL_FACES  // (development knob)
-#define NR_FWD_SMALL_FACES (16384 * 32)
-#endif
-constexpr size_t SMALL_LAUNCH_FACES = (size_t)NR_FWD_SMALL_FACES;  // launches of fewer faces take 16 faces per raster wave (k_face_raster)
+constexpr size_t SMALL_LAUNCH_FACES = (size_t)16384 * 32;  // launches of fewer faces take 16 faces per raster wave (k_face_raster)
 constexpr int SMALL_AREA = 256;   // boxes up to this many pixels: rasterized by k_face_raster (measured with the round-2 form of
                                   // the kernel: 128 / 64 make config 4 15 % / 28 % slower, the headline +0 / +11 %)
 constexpr int WAVE_AREA = 4096;   // up to this: one wave per face (wave_raster); beyond, and strips: one workgroup (k_large_raster)
@@ -279,11 +276,7 @@ __global__ __launch_bounds__(256) void k_face_raster(const float *__restrict__ f
     const bool to_wave = queued && !cd.strip && cd.n <= WAVE_AREA;
     const bool to_large = queued && !to_wave;
     {
-#ifdef NR_FWD_NOQUEUE  // (development: queued faces are dropped -- what do the queues' counters cost?)
-        const unsigned long long mw = 0, ml = 0;
-#else
         const unsigned long long mw = __ballot(to_wave), ml = __ballot(to_large);
-#endif
         const int shard = (int)(blockIdx.x & (unsigned)(nshards - 1));  // (1 or QSHARDS)
         int *qc = n_large + shard * QSTRIDE;
         if (mw) {

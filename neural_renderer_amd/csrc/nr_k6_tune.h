@@ -1,25 +1,13 @@
-// nr_k6_tune.h -- the numerics / shape knobs of K6's default (tolerance-mode) kernel in one place.
+// nr_k6_tune.h -- the shape knobs of K6's band kernels in one place.
 //
 // The product build takes the defaults below.  Development builds (neural_renderer_amd._build.build_variant, timed side
-// by side through NR_HIP_LIB) override single knobs with -D...; nothing else in the library is conditional on macros.
-// What each knob costs and buys is measured in profiles/r04_k6_numerics.jsonl (LAB-NOTEBOOK, round 4).
+// by side through NR_HIP_LIB) override single numbers with -D...  Besides these, only the two measurement builds are
+// conditional on macros: NR_PROFILE_HOOK (the band kernel's timing hook) and NR_ROW_STATS (k_bpm_row's work counters).
+// k_bpm_fast's tolerance-mode arithmetic has no switches: fused multiply-adds for diff and dist, one v_rcp_f32 per term, float
+// piece and run sums.  Round 4 measured the alternatives (profiles/r04_k6_numerics.jsonl, LAB-NOTEBOOK): no accumulation knob
+// moved the default mode's error level.
 #pragma once
 
-#ifndef NR_K6_NEWTON       // one Newton step on each v_rcp_f32 of a visit (2 fma): the reciprocal to ~0.5 ulp instead of 1
-#define NR_K6_NEWTON 0
-#endif
-#ifndef NR_K6_FUSED_DIFF   // diff = sum (I - ref) * g accumulated with fused multiply-adds (0: the reference's roundings)
-#define NR_K6_FUSED_DIFF 1
-#endif
-#ifndef NR_K6_FUSED_DIST   // dist = fma(c, t, +-eps) (0: c * t rounded, then +- eps: the reference's two roundings)
-#define NR_K6_FUSED_DIST 1
-#endif
-#ifndef NR_K6_BATCH_DOUBLE // the float sums of a batch of NR_K6_FB visits are added to DOUBLE piece sums (0: float piece sums)
-#define NR_K6_BATCH_DOUBLE 0
-#endif
-#ifndef NR_K6_RUNSUM_DOUBLE  // the DPP run sums in front of the LDS atomics in double (0: float)
-#define NR_K6_RUNSUM_DOUBLE 0
-#endif
 #ifndef NR_K6_FB           // pixels of an unrolled piece whose LDS reads are requested together (FSEG is a multiple;
 #define NR_K6_FB 3         // 1 / 3 / 5 -> stage 229 / 230 / 252 us, 3 needs the fewest registers)
 #endif
@@ -64,11 +52,6 @@
 
 namespace nr {
 namespace k6 {
-constexpr bool NEWTON = NR_K6_NEWTON != 0;
-constexpr bool FUSED_DIFF = NR_K6_FUSED_DIFF != 0;
-constexpr bool FUSED_DIST = NR_K6_FUSED_DIST != 0;
-constexpr bool BATCH_DOUBLE = NR_K6_BATCH_DOUBLE != 0;
-constexpr bool RUNSUM_DOUBLE = NR_K6_RUNSUM_DOUBLE != 0;
 constexpr int FB = NR_K6_FB;
 constexpr int U_GROUP = NR_K6_U_GROUP;
 static_assert(U_GROUP >= 1 && U_GROUP <= 4, "a super-piece's count travels in two bits");

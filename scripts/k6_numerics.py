@@ -1,5 +1,6 @@
-"""K6 numerics study (development / profiles/r04_k6_numerics.jsonl): what each arithmetic knob of the default kernel
-(csrc/nr_k6_tune.h) costs in time and buys in accuracy, on the BASELINE configurations at full size.
+"""K6 numerics study (development / profiles/r04_k6_numerics.jsonl): what a variant build of the default kernel costs in time
+and buys in accuracy, on the BASELINE configurations at full size.  (Round 4 ran it on the arithmetic switches of
+csrc/nr_k6_tune.h; those have since been removed, the arm each study kept is the only code.)
 
 For every library given (variant builds of neural_renderer_amd._build.build_variant; '' = the product library) the stage
 call nr_backward_pixel_map runs on the same residual maps and upstream gradients; its grad_faces are compared with the

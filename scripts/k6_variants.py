@@ -1,5 +1,5 @@
-"""Development: time the K6 stage call (nr_backward_pixel_map) and the fused backward for several libraries (variant builds,
-NR_K6_* knobs of csrc/nr_k6_tune.h) on teapot batches of several sizes, one process.
+"""Development: time the K6 stage call (nr_backward_pixel_map) and the fused backward for several libraries (variant builds
+that set the numbers of csrc/nr_k6_tune.h, e.g. -DNR_K6_FB=5) on teapot batches of several sizes, one process.
     VARIANTS="t256b40 t128b20" SHAPES="8x256 16x256 64x256 64x512" python scripts/k6_variants.py"""
 import json
 import os

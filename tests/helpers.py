@@ -147,12 +147,12 @@ def entrywise(got, ref_d, mags, mode):
       'row' -- k_bpm_row, default mode.  Per term, against the oracle's float term (first order, S = sum_c (|I_c| + |ref_c| +
           2 kappa) |g_c| of the pixel, so that M = sum S / |dist|):
             diff: P formed in double and rounded once (u S), ref_c - K_c rounded (u S), four fused multiply-adds
-                (:2026-2031, 4 u S) -> 6 u S; the oracle's sum_c (I_c - ref_c) g_c (nr_oracle.c, K6): a subtraction, a
+                (:1984-1989, 4 u S) -> 6 u S; the oracle's sum_c (I_c - ref_c) g_c (nr_oracle.c, K6): a subtraction, a
                 product and an add per channel (the first add onto 0 exact) -> 5 u S;
             dist: t = fma(sdir, d1, -sdir cross) is the reference's subtraction (same bits); |c| 2/S (2 u: the product
                 and 2/S when S is no power of two), fma(|c| 2/S, |t|, eps) (u), eps in float (u) -> 4 u; the oracle's c t,
                 x 2/S, +- eps -> 3 u;
-            reciprocal: v_rcp_f32 <= 1 ulp = 2 u (:2038; phase A's recip_n with a Newton step, :1697-1699, less); the
+            reciprocal: v_rcp_f32 <= 1 ulp = 2 u (:1996; phase A's recip_n with a Newton step, :1655-1657, less); the
                 oracle's division u.
           |term - term_ref| <= (6 + 5) u S / |dist| + (4 + 3 + 2 + 1) u |term| <= 21 u S / |dist|: C1_ROW = 22 with the
           second-order products.  A visit that one side skips (diff <= 0) and the other keeps has |diff| within those
@@ -161,10 +161,10 @@ def entrywise(got, ref_d, mags, mode):
             ulp(ref_d) + 2 u_d N A + C1_ROW u M + gamma_M_ROW A.
       'fast' -- k_bpm_fast, default mode (NR_FLAG_K6_LEGACY, the scan path NR_FLAG_K6_SCAN, overflow images, rasters above
           k_bpm_row's): the colour difference from b - ref or c - ref, one product and three fused multiply-adds
-          (:1002-1022, 5 u S; the oracle 5 u S); t = (d1 - cross) + k, two roundings of one sign (:1043, :1066: 2 u against the
+          (:1001-1021, 5 u S; the oracle 5 u S); t = (d1 - cross) + k, two roundings of one sign (:1035, :1054: 2 u against the
           reference's one, 3 u apart), c 2/S (2 u), fma (u), eps (u); the oracle 3 u; v_rcp_f32 without a Newton step
-          (nr_k6_tune.h NR_K6_NEWTON = 0: 2 u), the oracle's division (u): (5 + 5) u S / |dist| + (3 + 4 + 3 + 2 + 1) u |term|
-          <= 23 u S / |dist|: C1_FAST = 24.  Float sums of <= M_FAST terms (:1073-1077 and the run sums), double above:
+          (:1056-1057: 2 u), the oracle's division (u): (5 + 5) u S / |dist| + (3 + 4 + 3 + 2 + 1) u |term|
+          <= 23 u S / |dist|: C1_FAST = 24.  Float sums of <= M_FAST terms (:1056-1057 and the run sums), double above:
             ulp(ref_d) + 2 u_d N A + C1_FAST u M + gamma_M_FAST A.
       'default' -- the default mode where either band kernel may serve an image (k_bpm_row hands overflow images to
           k_bpm_fast): the larger of the two.
