@@ -22,6 +22,8 @@
  *   nr_create_texture_image       <- create_texture_image kernels of save_obj(textures=...)   save_obj.py:32-146
  *   nr_frontend_forward/_backward <- fill_back + lighting + look_at/look + perspective + vertices_to_faces
  *                                    of Renderer.render*                                  renderer.py:35-107
+ *   nr_frontend_forward_projection / _backward_projection: the same front-end with a calibrated camera (K, R, t,
+ *                                    lens distortion) in place of look_at / look + perspective; not in the reference
  *   nr_forward_rasterize_lit / nr_backward_rasterize_lit / nr_frontend_forward_light / _backward_light: the fused
  *                                   rasterizer and front-end with per-face light colours instead of lit, duplicated
  *                                   textures (renderer.py:77-103 with lighting.py:50-51 moved into K4 / K7)
@@ -56,7 +58,9 @@
 extern "C" {
 #endif
 
-#define NR_VERSION 600 /* 0.6.0: K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
+#define NR_VERSION 600 /* 0.6.0 (additions without a version step: NR_CAMERA_PROJECTION, nr_projection and
+                          *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes);
+                          *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
                           *        measurement hook nr_profile_band_kernel left the product ABI (include/nr_hip_profile.h, libnr_hip_prof.so);
@@ -376,6 +380,63 @@ int nr_frontend_backward_light(const float *vertices, const int32_t *faces_idx, 
                                int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, int32_t eye_per_batch,
                                int32_t fill_back, const nr_camera *camera, const nr_light *light, void *workspace,
                                size_t workspace_bytes, void *stream);
+
+/*
+ * Projection camera (Renderer.camera_mode = 'projection', neural_renderer_amd/projection.py; not in the reference): the same
+ * front-end -- fill_back, lighting in world space, vertices_to_faces -- with a calibrated camera in place of look_at / look
+ * and perspective.  For world-space vertex w of image b, in float32 and in this order:
+ *
+ *   c   = R[b] w + t[b]                        camera space, OpenCV axes: x right, y down, z forward
+ *   x'  = c.x / c.z,  y' = c.y / c.z
+ *   r2  = x'^2 + y'^2
+ *   rad = 1 + k1 r2 + k2 r2^2 + k3 r2^3        dist_coeffs = (k1, k2, p1, p2, k3), OpenCV order
+ *   x'' = x' rad + 2 p1 x' y' + p2 (r2 + 2 x'^2)
+ *   y'' = y' rad + p1 (r2 + 2 y'^2) + 2 p2 x' y'
+ *   u   = K[0,0] x'' + K[0,1] y'' + K[0,2]     row 2 of K is ignored
+ *   v   = K[1,0] x'' + K[1,1] y'' + K[1,2]
+ *   out = ((2u - orig_size) / orig_size, (orig_size - 2v) / orig_size, c.z)    the rasterizer's NDC (y up) + depth
+ *
+ * u, v are continuous pixel coordinates of an orig_size^2 image, pixel i spanning [i, i+1): with orig_size == image_size a
+ * point at (u, v) = (i + 0.5, j + 0.5) lands on the centre of column i and row j counted from the TOP of the returned image
+ * (the photo's row).  OpenCV intrinsics put pixel centres at integers: add 0.5 to cx and cy.  dist_coeffs == NULL: no
+ * distortion (those terms are skipped).  Nothing is clamped: c.z <= near is culled by the rasterizer.
+ *
+ * K, R, t and dist_coeffs are DEVICE arrays, [B,3,3] / [B,3,3] / [B,3] / [B,5] when their *_per_batch != 0, else one
+ * [3,3] / [3,3] / [3] / [5] for the whole batch.  The library never reads them on the host, so the calls stay asynchronous
+ * and can be captured into a graph.  The nr_projection struct itself lives in HOST memory and is read during the call.
+ */
+#define NR_CAMERA_PROJECTION 3
+
+typedef struct nr_projection {
+    const float *K, *R, *t, *dist_coeffs; /* device pointers; dist_coeffs may be NULL */
+    int32_t K_per_batch, R_per_batch, t_per_batch, dist_per_batch;
+    float orig_size; /* > 0 */
+} nr_projection;
+
+/* Scratch for nr_frontend_backward_projection when grad_K, grad_R or grad_t is requested (per-image sums in double). */
+size_t nr_frontend_projection_workspace_bytes(int32_t batch_size);
+
+/*
+ * textures / textures_out as in nr_frontend_forward, or light_out [B,F,3] as in nr_frontend_forward_light; the two outputs
+ * are mutually exclusive, both NULL = silhouette / depth rendering.  `light` is needed with either.
+ */
+int nr_frontend_forward_projection(const float *vertices, const int32_t *faces_idx, const float *textures, float *faces_out,
+                                   float *textures_out, float *light_out, int32_t batch_size, int32_t num_vertices,
+                                   int32_t num_faces, int32_t texture_size, int32_t idx_per_batch, int32_t fill_back,
+                                   const nr_projection *projection, const nr_light *light, void *stream);
+
+/*
+ * Gradients as in nr_frontend_backward (grad_textures_out + grad_textures) or nr_frontend_backward_light (grad_light; then
+ * textures == NULL).  grad_K [B,3,3] or [3,3] (row 2 is 0), grad_R [B,3,3] or [3,3], grad_t [B,3] or [3], shaped like the
+ * parameter, are optional and need grad_vertices and the workspace; shared ones are zero-filled and accumulated with float
+ * atomics.  dist_coeffs receives no gradient.
+ */
+int nr_frontend_backward_projection(const float *vertices, const int32_t *faces_idx, const float *textures,
+                                    const float *grad_faces, const float *grad_textures_out, const float *grad_light,
+                                    float *grad_vertices, float *grad_textures, float *grad_K, float *grad_R, float *grad_t,
+                                    int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t texture_size,
+                                    int32_t idx_per_batch, int32_t fill_back, const nr_projection *projection,
+                                    const nr_light *light, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Texture baking of load_obj(load_texture=True) (K10, reference load_obj.py:87-144): for every texel (i0,i1,i2) of every

@@ -12,6 +12,7 @@ from .lighting import lighting
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
+from .projection import projection
 from .vertices_to_faces import vertices_to_faces
 # meshes, files, optimiser
 from .load_obj import load_obj
@@ -32,5 +33,6 @@ if _os.environ.get('NR_BACKWARD_ON_CALLER_THREAD', '0') not in ('', '0'):
 __version__ = '0.6.0'
 __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rasterize_silhouettes', 'use_unsafe_rasterizer', 'use_graph_replay',
            'clear_workspace_cache',
-           'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'vertices_to_faces',
+           'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'projection',
+           'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj']

@@ -27,7 +27,13 @@ class FaceLight(_c.Structure):
     _fields_ = [('light', _vp), ('texture_faces', _i32), ('textures', _vp), ('grad_light', _vp)]
 
 
-_cam_p, _light_p, _fl_p = _c.POINTER(Camera), _c.POINTER(Light), _c.POINTER(FaceLight)
+class Projection(_c.Structure):
+    """struct nr_projection (include/nr_hip.h): device pointers of K, R, t, dist_coeffs (or None) and their layouts."""
+    _fields_ = [('K', _vp), ('R', _vp), ('t', _vp), ('dist_coeffs', _vp), ('K_per_batch', _i32), ('R_per_batch', _i32),
+                ('t_per_batch', _i32), ('dist_per_batch', _i32), ('orig_size', _c.c_float)]
+
+
+_cam_p, _light_p, _fl_p, _proj_p = _c.POINTER(Camera), _c.POINTER(Light), _c.POINTER(FaceLight), _c.POINTER(Projection)
 
 # name -> (restype, argtypes); mirrors include/nr_hip.h one to one
 SIGNATURES = {
@@ -56,6 +62,9 @@ SIGNATURES = {
     'nr_backward_rasterize_lit': (_c.c_int, [_fl_p] + [_vp] * 12 + [_i32] * 4 + [_f64, _i32, _vp, _vp, _sz, _vp]),
     'nr_frontend_forward_light': (_c.c_int, [_vp] * 5 + [_i32] * 6 + [_cam_p, _light_p, _vp]),
     'nr_frontend_backward_light': (_c.c_int, [_vp] * 7 + [_i32] * 6 + [_cam_p, _light_p, _vp, _sz, _vp]),
+    'nr_frontend_projection_workspace_bytes': (_sz, [_i32]),
+    'nr_frontend_forward_projection': (_c.c_int, [_vp] * 6 + [_i32] * 6 + [_proj_p, _light_p, _vp]),
+    'nr_frontend_backward_projection': (_c.c_int, [_vp] * 11 + [_i32] * 6 + [_proj_p, _light_p, _vp, _sz, _vp]),
 }
 
 NR_VERSION = 600  # include/nr_hip.h; load() refuses a library of another version (a stale build)
@@ -71,6 +80,7 @@ NR_FLAG_K6_PX = 65536  # (accepted and ignored since 0.6.0; bits 8..15 of a forw
 NR_E_INDEX = -6
 NR_CAMERA_LOOK_AT = 1
 NR_CAMERA_LOOK = 2
+NR_CAMERA_PROJECTION = 3
 
 _lib = None
 

@@ -10,6 +10,10 @@
 // the lit textures back into the vertices through the face normals, the face->vertex scatter (hardware float atomics)
 // and the gradient of a learnable camera position (example4 optimises `eye`).
 //
+// Not in the reference: camera_mode 'projection' (NR_CAMERA_PROJECTION, nr_hip.h: nr_projection) -- intrinsics K, pose R | t
+// and OpenCV lens distortion read from device arrays -- replaces look_at / look + perspective in the same kernels
+// (template argument PROJ); its backward also yields per-image sums for grad_K / grad_R / grad_t (k_projection_backward).
+//
 // Why: in stock torch this chain is ~60 small launches forward and ~100 backward on [B,3]- to [B,Nv,3]-sized tensors,
 // i.e. ~1.1 ms of host launch latency around a 0.9 ms rasterizer step at the headline size (scripts/renderer_e2e.py),
 // plus three full passes over the [B, 2F, ts^3, 3] texture tensor (concat, multiply, and their backward).
@@ -31,7 +35,7 @@ constexpr int FE_THREADS = 256;
 constexpr float NORM_EPS = 1e-5f;  // chainer.functions.normalize default eps
 
 struct FrontendParams {
-    int camera_mode;  // NR_CAMERA_LOOK_AT / NR_CAMERA_LOOK
+    int camera_mode;  // NR_CAMERA_LOOK_AT / NR_CAMERA_LOOK / NR_CAMERA_PROJECTION
     int perspective;
     int eye_per_batch;
     int idx_per_batch;
@@ -117,6 +121,115 @@ __device__ __forceinline__ void project(const FrontendParams &P, const CameraBas
     out[2] = cam[2];
 }
 
+// ---- NR_CAMERA_PROJECTION: intrinsics K, pose R | t and OpenCV lens distortion (nr_hip.h: nr_projection) ----
+// The camera parameters are DEVICE arrays (the host never reads them); every lane that projects loads its image's copy.
+constexpr int PROJ_ACC = 18;  // per-image sums of the backward: [0..8] g_R, [9..11] g_t, [12..17] g_K rows 0-1
+
+struct ProjParams {
+    const float *K, *R, *t, *dist;  // [B,3,3] | [3,3], [B,3,3] | [3,3], [B,3] | [3], [B,5] | [5] | NULL
+    int K_per_batch, R_per_batch, t_per_batch, dist_per_batch;
+    float size;  // orig_size
+};
+
+struct ProjCamera {
+    float R[9], t[3], K[6], d[5];  // K: rows 0 and 1 only; d = (k1, k2, p1, p2, k3)
+};
+
+__device__ __forceinline__ void proj_camera(const ProjParams &Q, int b, ProjCamera &C)
+{
+    const float *K = Q.K + (Q.K_per_batch ? 9 * b : 0);
+    const float *R = Q.R + (Q.R_per_batch ? 9 * b : 0);
+    const float *t = Q.t + (Q.t_per_batch ? 3 * b : 0);
+#pragma unroll
+    for (int i = 0; i < 9; i++) C.R[i] = R[i];
+#pragma unroll
+    for (int i = 0; i < 6; i++) C.K[i] = K[i];
+#pragma unroll
+    for (int i = 0; i < 3; i++) C.t[i] = t[i];
+    if (Q.dist) {
+        const float *d = Q.dist + (Q.dist_per_batch ? 5 * b : 0);
+#pragma unroll
+        for (int i = 0; i < 5; i++) C.d[i] = d[i];
+    }
+}
+
+// The intermediate values of the camera model, kept for the backward
+struct ProjPoint {
+    float c[3];         // camera space: c = R w + t
+    float xp, yp;       // x' = c.x / c.z, y' = c.y / c.z
+    float r2, rad;      // (distortion only)
+    float xd, yd;       // x'', y''
+};
+
+// world vertex -> (NDC x, NDC y, depth): the contract of nr_hip.h, in its float32 operation order
+__device__ __forceinline__ void project_projection(const ProjParams &Q, const ProjCamera &C, const float *w, ProjPoint &p,
+                                                   float *out)
+{
+#pragma unroll
+    for (int i = 0; i < 3; i++) p.c[i] = ((C.R[3 * i] * w[0] + C.R[3 * i + 1] * w[1]) + C.R[3 * i + 2] * w[2]) + C.t[i];
+    p.xp = p.c[0] / p.c[2];
+    p.yp = p.c[1] / p.c[2];
+    if (Q.dist) {
+        const float k1 = C.d[0], k2 = C.d[1], p1 = C.d[2], p2 = C.d[3], k3 = C.d[4];
+        const float x = p.xp, y = p.yp;
+        p.r2 = x * x + y * y;
+        const float r4 = p.r2 * p.r2, r6 = r4 * p.r2;
+        p.rad = ((1.0f + k1 * p.r2) + k2 * r4) + k3 * r6;
+        p.xd = (x * p.rad + 2.0f * p1 * x * y) + p2 * (p.r2 + 2.0f * x * x);
+        p.yd = (y * p.rad + p1 * (p.r2 + 2.0f * y * y)) + 2.0f * p2 * x * y;
+    } else {
+        p.r2 = 0.0f;
+        p.rad = 1.0f;
+        p.xd = p.xp;
+        p.yd = p.yp;
+    }
+    const float u = (C.K[0] * p.xd + C.K[1] * p.yd) + C.K[2];
+    const float v = (C.K[3] * p.xd + C.K[4] * p.yd) + C.K[5];
+    out[0] = (2.0f * u - Q.size) / Q.size;
+    out[1] = (Q.size - 2.0f * v) / Q.size;
+    out[2] = p.c[2];
+}
+
+// backward of project_projection for one vertex: g = d loss / d out -> gw (world vertex, added), acc (PROJ_ACC sums, added)
+__device__ __forceinline__ void project_projection_bwd(const ProjParams &Q, const ProjCamera &C, const float *w, const float *g,
+                                                       float *gw, float *acc)
+{
+    ProjPoint p;
+    float o[3];
+    project_projection(Q, C, w, p, o);
+    const float gu = 2.0f * g[0] / Q.size;  // out.x = (2u - S) / S
+    const float gv = -2.0f * g[1] / Q.size; // out.y = (S - 2v) / S
+    acc[12] += gu * p.xd;
+    acc[13] += gu * p.yd;
+    acc[14] += gu;
+    acc[15] += gv * p.xd;
+    acc[16] += gv * p.yd;
+    acc[17] += gv;
+    const float gxd = gu * C.K[0] + gv * C.K[3];
+    const float gyd = gu * C.K[1] + gv * C.K[4];
+    float gxp = gxd, gyp = gyd;
+    if (Q.dist) {  // the Jacobian of (x'', y'') by (x', y'); it is symmetric
+        const float k1 = C.d[0], k2 = C.d[1], p1 = C.d[2], p2 = C.d[3], k3 = C.d[4];
+        const float x = p.xp, y = p.yp;
+        const float drad = (k1 + 2.0f * k2 * p.r2) + 3.0f * k3 * (p.r2 * p.r2);  // d rad / d r2
+        const float jxx = ((p.rad + 2.0f * x * x * drad) + 2.0f * p1 * y) + 6.0f * p2 * x;
+        const float jxy = ((2.0f * x * y * drad) + 2.0f * p1 * x) + 2.0f * p2 * y;
+        const float jyy = ((p.rad + 2.0f * y * y * drad) + 6.0f * p1 * y) + 2.0f * p2 * x;
+        gxp = gxd * jxx + gyd * jxy;
+        gyp = gxd * jxy + gyd * jyy;
+    }
+    const float gc[3] = {gxp / p.c[2], gyp / p.c[2], g[2] - (gxp * p.xp + gyp * p.yp) / p.c[2]};
+    // c = R w + t:  g_w = R^T g_c,  g_R[i][j] += g_c[i] w[j],  g_t += g_c
+#pragma unroll
+    for (int j = 0; j < 3; j++) gw[j] += (gc[0] * C.R[j] + gc[1] * C.R[3 + j]) + gc[2] * C.R[6 + j];
+#pragma unroll
+    for (int i = 0; i < 3; i++) {
+#pragma unroll
+        for (int j = 0; j < 3; j++) acc[3 * i + j] += gc[i] * w[j];
+        acc[9 + i] += gc[i];
+    }
+}
+
 // light colours of a face and of its reversed copy (lighting.py:31-47); n = unnormalised normal, dotn = n_hat . direction
 __device__ __forceinline__ void face_light(const FrontendParams &P, const float *w0, const float *w1, const float *w2, float *n,
                                            float &dotn, float *light_f, float *light_b)
@@ -141,12 +254,14 @@ __device__ __forceinline__ void face_light(const FrontendParams &P, const float 
     }
 }
 
+// PROJ: the NR_CAMERA_PROJECTION model of `Q` (eye unused) instead of look_at / look + perspective
+template <bool PROJ>
 __global__ __launch_bounds__(FE_THREADS) void k_frontend_forward(const float *__restrict__ vertices,
                                                                  const int32_t *__restrict__ faces_idx,
                                                                  const float *__restrict__ textures,
                                                                  const float *__restrict__ eye, float *__restrict__ faces_out,
                                                                  float *__restrict__ textures_out, int Nv, int Nf, int ts,
-                                                                 FrontendParams P, float *__restrict__ light_out)
+                                                                 FrontendParams P, float *__restrict__ light_out, ProjParams Q)
 {
     const int b = blockIdx.y;
     const int f = (blockIdx.x * FE_THREADS + threadIdx.x) / FE_LANES;
@@ -165,17 +280,28 @@ __global__ __launch_bounds__(FE_THREADS) void k_frontend_forward(const float *__
     }
 
     if (lane < 2 && (lane == 0 || P.fill_back)) {
-        CameraBasis C;
-        camera_basis(P, eye, b, C);
         float *dst = faces_out + ((size_t)b * Fout + (lane == 0 ? f : Nf + f)) * 9;
+        if constexpr (PROJ) {
+            ProjCamera C;
+            proj_camera(Q, b, C);
 #pragma unroll
-        for (int k = 0; k < 3; k++) {
-            float cam[3], o[3];
-            project(P, C, w[k], cam, o);
-            float *d = dst + 3 * (lane == 0 ? k : 2 - k);  // reversed vertex order for the back copy
-            d[0] = o[0];
-            d[1] = o[1];
-            d[2] = o[2];
+            for (int k = 0; k < 3; k++) {
+                ProjPoint p;
+                float *d = dst + 3 * (lane == 0 ? k : 2 - k);
+                project_projection(Q, C, w[k], p, d);
+            }
+        } else {
+            CameraBasis C;
+            camera_basis(P, eye, b, C);
+#pragma unroll
+            for (int k = 0; k < 3; k++) {
+                float cam[3], o[3];
+                project(P, C, w[k], cam, o);
+                float *d = dst + 3 * (lane == 0 ? k : 2 - k);  // reversed vertex order for the back copy
+                d[0] = o[0];
+                d[1] = o[1];
+                d[2] = o[2];
+            }
         }
     }
 
@@ -214,21 +340,24 @@ __global__ __launch_bounds__(FE_THREADS) void k_frontend_forward(const float *__
 
 // --------------------------------------------------------------------------------------------------------------------
 // backward
+// cam_acc: per-image camera sums, NACC doubles per image (12 for eye: sum of g_w, g_R; PROJ_ACC for PROJ)
+template <bool PROJ>
 __global__ __launch_bounds__(FE_THREADS) void k_frontend_backward(
     const float *__restrict__ vertices, const int32_t *__restrict__ faces_idx, const float *__restrict__ textures,
     const float *__restrict__ eye, const float *__restrict__ g_faces, const float *__restrict__ g_tex_out,
     float *__restrict__ grad_vertices, float *__restrict__ grad_textures, double *__restrict__ cam_acc, int Nv, int Nf, int ts,
-    FrontendParams P, const float *__restrict__ g_light)
+    FrontendParams P, const float *__restrict__ g_light, ProjParams Q)
 {
-    __shared__ double s_acc[FE_THREADS / 64][12];
+    constexpr int NACC = PROJ ? PROJ_ACC : 12;
+    __shared__ double s_acc[FE_THREADS / 64][NACC];
     const int b = blockIdx.y;
     const int f = (blockIdx.x * FE_THREADS + threadIdx.x) / FE_LANES;
     const int lane = threadIdx.x % FE_LANES;
     const bool live = f < Nf;
     const int Fout = P.fill_back ? 2 * Nf : Nf;
-    float acc[12];
+    float acc[NACC];
 #pragma unroll
-    for (int k = 0; k < 12; k++) acc[k] = 0.0f;
+    for (int k = 0; k < NACC; k++) acc[k] = 0.0f;
 
     if (live) {
         const int32_t *idx = faces_idx + ((size_t)(P.idx_per_batch ? b : 0) * Nf + f) * 3;
@@ -311,7 +440,24 @@ __global__ __launch_bounds__(FE_THREADS) void k_frontend_backward(
         }
 
         // ---- geometry: perspective, rotation, gather ----
-        if (lane == 0 && grad_vertices) {
+        if constexpr (PROJ) {
+            if (lane == 0 && grad_vertices) {
+                ProjCamera C;
+                proj_camera(Q, b, C);
+                const float *g0 = g_faces + ((size_t)b * Fout + f) * 9;
+                const float *g1 = g_faces + ((size_t)b * Fout + Nf + f) * 9;
+#pragma unroll
+                for (int k = 0; k < 3; k++) {
+                    float g[3] = {g0[3 * k], g0[3 * k + 1], g0[3 * k + 2]};
+                    if (P.fill_back) {
+                        g[0] += g1[3 * (2 - k)];
+                        g[1] += g1[3 * (2 - k) + 1];
+                        g[2] += g1[3 * (2 - k) + 2];
+                    }
+                    project_projection_bwd(Q, C, w[k], g, gw[k], acc);
+                }
+            }
+        } else if (lane == 0 && grad_vertices) {
             CameraBasis C;
             camera_basis(P, eye, b, C);
             const float *g0 = g_faces + ((size_t)b * Fout + f) * 9;
@@ -366,21 +512,21 @@ __global__ __launch_bounds__(FE_THREADS) void k_frontend_backward(
         }
     }
 
-    if (cam_acc) {  // per-image sums for the camera backward: [0..2] = sum of g_w, [3..11] = g_R
+    if (cam_acc) {  // per-image sums for the camera backward (eye: [0..2] = sum of g_w, [3..11] = g_R; PROJ: PROJ_ACC)
         const int wave = threadIdx.x / 64, wl = threadIdx.x % 64;
 #pragma unroll
-        for (int k = 0; k < 12; k++) {
+        for (int k = 0; k < NACC; k++) {
             double v = (double)acc[k];
 #pragma unroll
             for (int m = FE_LANES; m < 64; m <<= 1) v += __shfl_xor(v, m);
             if (wl == 0) s_acc[wave][k] = v;
         }
         __syncthreads();
-        if (threadIdx.x < 12) {
+        if (threadIdx.x < NACC) {
             double v = 0.0;
 #pragma unroll
             for (int q = 0; q < FE_THREADS / 64; q++) v += s_acc[q][threadIdx.x];
-            if (v != 0.0) atomicAdd(cam_acc + (size_t)b * 12 + threadIdx.x, v);
+            if (v != 0.0) atomicAdd(cam_acc + (size_t)b * NACC + threadIdx.x, v);
         }
     }
 }
@@ -432,6 +578,44 @@ __global__ void k_camera_backward(const float *__restrict__ eye, const double *_
         atomicAdd(grad_eye + 0, ge[0]);
         atomicAdd(grad_eye + 1, ge[1]);
         atomicAdd(grad_eye + 2, ge[2]);
+    }
+}
+
+// one thread per image: the per-image sums -> grad_K (rows 0-1; row 2 is 0), grad_R, grad_t.  A parameter shared by the
+// batch receives every image's sum through a float atomic (its output is zero-filled by the host call).
+__global__ void k_projection_backward(const double *__restrict__ cam_acc, float *__restrict__ grad_K, float *__restrict__ grad_R,
+                                      float *__restrict__ grad_t, int B, ProjParams Q)
+{
+    const int b = blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const double *a = cam_acc + (size_t)b * PROJ_ACC;
+    if (grad_R) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            if (Q.R_per_batch)
+                grad_R[9 * b + i] = (float)a[i];
+            else
+                atomicAdd(grad_R + i, (float)a[i]);
+        }
+    }
+    if (grad_t) {
+#pragma unroll
+        for (int i = 0; i < 3; i++) {
+            if (Q.t_per_batch)
+                grad_t[3 * b + i] = (float)a[9 + i];
+            else
+                atomicAdd(grad_t + i, (float)a[9 + i]);
+        }
+    }
+    if (grad_K) {
+#pragma unroll
+        for (int i = 0; i < 9; i++) {
+            const float v = i < 6 ? (float)a[12 + i] : 0.0f;
+            if (Q.K_per_batch)
+                grad_K[9 * b + i] = v;
+            else if (i < 6)
+                atomicAdd(grad_K + i, v);
+        }
     }
 }
 
@@ -492,8 +676,8 @@ NR_API int nr_frontend_forward(const float *vertices, const int32_t *faces_idx, 
     rc = fill_params(P, camera, light, idx_per_batch, eye_per_batch, fill_back, textures != nullptr);
     if (rc) return rc;
     const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_forward, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx, textures, eye,
-                       faces_out, textures_out, Nv, Nf, ts, P, (float *)nullptr);
+    hipLaunchKernelGGL(k_frontend_forward<false>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx, textures,
+                       eye, faces_out, textures_out, Nv, Nf, ts, P, (float *)nullptr, ProjParams{});
     return launch_status();
 }
 
@@ -509,8 +693,8 @@ NR_API int nr_frontend_forward_light(const float *vertices, const int32_t *faces
     rc = fill_params(P, camera, light, idx_per_batch, eye_per_batch, fill_back, true);
     if (rc) return rc;
     const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_forward, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx,
-                       (const float *)nullptr, eye, faces_out, (float *)nullptr, Nv, Nf, 0, P, light_out);
+    hipLaunchKernelGGL(k_frontend_forward<false>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx,
+                       (const float *)nullptr, eye, faces_out, (float *)nullptr, Nv, Nf, 0, P, light_out, ProjParams{});
     return launch_status();
 }
 
@@ -549,8 +733,8 @@ int frontend_backward(const float *vertices, const int32_t *faces_idx, const flo
         if (e != 0) return e;
     }
     const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_backward, grid, dim3(FE_THREADS), 0, st, vertices, faces_idx, textures, eye, grad_faces,
-                       grad_textures_out, grad_vertices, grad_textures, cam_acc, Nv, Nf, ts, P, grad_light);
+    hipLaunchKernelGGL(k_frontend_backward<false>, grid, dim3(FE_THREADS), 0, st, vertices, faces_idx, textures, eye, grad_faces,
+                       grad_textures_out, grad_vertices, grad_textures, cam_acc, Nv, Nf, ts, P, grad_light, ProjParams{});
     rc = launch_status();
     if (rc) return rc;
     if (grad_eye) {
@@ -582,4 +766,107 @@ NR_API int nr_frontend_backward_light(const float *vertices, const int32_t *face
     return frontend_backward(vertices, faces_idx, nullptr, eye, grad_faces, nullptr, grad_light, grad_vertices, nullptr,
                              grad_eye, B, Nv, Nf, 0, idx_per_batch, eye_per_batch, fill_back, camera, light, workspace,
                              workspace_bytes, stream);
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// NR_CAMERA_PROJECTION entry points
+namespace {
+int fill_projection(FrontendParams &P, ProjParams &Q, const nr_projection *proj, const nr_light *light, int idx_per_batch,
+                    int fill_back, bool lit)
+{
+    if (!proj || !proj->K || !proj->R || !proj->t) return NR_E_NULL;
+    if (!(proj->orig_size > 0.0f && proj->orig_size < __builtin_inff())) return NR_E_SIZE;
+    nr_camera cam = {};  // lighting, fill_back and the index layout as in the other modes; no look_at / perspective
+    cam.mode = NR_CAMERA_LOOK_AT;
+    const int rc = fill_params(P, &cam, light, idx_per_batch, 0, fill_back, lit);
+    if (rc) return rc;
+    P.camera_mode = NR_CAMERA_PROJECTION;
+    Q.K = proj->K;
+    Q.R = proj->R;
+    Q.t = proj->t;
+    Q.dist = proj->dist_coeffs;
+    Q.K_per_batch = proj->K_per_batch != 0;
+    Q.R_per_batch = proj->R_per_batch != 0;
+    Q.t_per_batch = proj->t_per_batch != 0;
+    Q.dist_per_batch = proj->dist_per_batch != 0;
+    Q.size = proj->orig_size;
+    return 0;
+}
+}  // namespace
+
+NR_API size_t nr_frontend_projection_workspace_bytes(int32_t B)
+{
+    return B < 1 ? 0 : (size_t)B * PROJ_ACC * sizeof(double);
+}
+
+NR_API int nr_frontend_forward_projection(const float *vertices, const int32_t *faces_idx, const float *textures,
+                                          float *faces_out, float *textures_out, float *light_out, int32_t B, int32_t Nv,
+                                          int32_t Nf, int32_t ts, int32_t idx_per_batch, int32_t fill_back,
+                                          const nr_projection *projection, const nr_light *light, void *stream)
+{
+    if (!vertices || !faces_idx || !faces_out) return NR_E_NULL;
+    if ((textures == nullptr) != (textures_out == nullptr)) return NR_E_MODE;
+    if (textures_out && light_out) return NR_E_MODE;
+    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
+    if (rc) return rc;
+    FrontendParams P;
+    ProjParams Q;
+    rc = fill_projection(P, Q, projection, light, idx_per_batch, fill_back, textures != nullptr || light_out != nullptr);
+    if (rc) return rc;
+    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
+    hipLaunchKernelGGL(k_frontend_forward<true>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx, textures,
+                       (const float *)nullptr, faces_out, textures_out, Nv, Nf, light_out ? 0 : ts, P, light_out, Q);
+    return launch_status();
+}
+
+NR_API int nr_frontend_backward_projection(const float *vertices, const int32_t *faces_idx, const float *textures,
+                                           const float *grad_faces, const float *grad_textures_out, const float *grad_light,
+                                           float *grad_vertices, float *grad_textures, float *grad_K, float *grad_R,
+                                           float *grad_t, int32_t B, int32_t Nv, int32_t Nf, int32_t ts,
+                                           int32_t idx_per_batch, int32_t fill_back, const nr_projection *projection,
+                                           const nr_light *light, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!vertices || !faces_idx || !grad_faces) return NR_E_NULL;
+    const bool want_cam = grad_K || grad_R || grad_t;
+    if (!grad_vertices && !grad_textures && !want_cam) return NR_E_MODE;
+    if (want_cam && !grad_vertices) return NR_E_MODE;  // the camera sums are produced by the vertex pass
+    if (grad_textures && !(textures && grad_textures_out)) return NR_E_MODE;
+    if (grad_textures_out && !textures) return NR_E_MODE;
+    if (grad_light && textures) return NR_E_MODE;
+    if (grad_light && !light) return NR_E_NULL;
+    const bool lit = textures != nullptr || grad_light != nullptr;
+    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
+    if (rc) return rc;
+    FrontendParams P;
+    ProjParams Q;
+    rc = fill_projection(P, Q, projection, light, idx_per_batch, fill_back, lit);
+    if (rc) return rc;
+    hipStream_t st = (hipStream_t)stream;
+    double *cam_acc = nullptr;
+    if (want_cam) {
+        const size_t ws = nr_frontend_projection_workspace_bytes(B);
+        if (!workspace || workspace_bytes < ws) return NR_E_WORKSPACE;
+        cam_acc = (double *)workspace;
+        int e = fill_bytes(cam_acc, 0, ws, st);
+        if (e == 0 && grad_K && !Q.K_per_batch) e = fill_bytes(grad_K, 0, 9 * sizeof(float), st);
+        if (e == 0 && grad_R && !Q.R_per_batch) e = fill_bytes(grad_R, 0, 9 * sizeof(float), st);
+        if (e == 0 && grad_t && !Q.t_per_batch) e = fill_bytes(grad_t, 0, 3 * sizeof(float), st);
+        if (e != 0) return e;
+    }
+    if (grad_vertices) {
+        const int e = fill_bytes(grad_vertices, 0, (size_t)B * Nv * 3 * sizeof(float), st);
+        if (e != 0) return e;
+    }
+    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
+    hipLaunchKernelGGL(k_frontend_backward<true>, grid, dim3(FE_THREADS), 0, st, vertices, faces_idx, textures,
+                       (const float *)nullptr, grad_faces, grad_textures_out, grad_vertices, grad_textures, cam_acc, Nv, Nf,
+                       grad_light ? 0 : ts, P, grad_light, Q);
+    rc = launch_status();
+    if (rc) return rc;
+    if (want_cam) {
+        hipLaunchKernelGGL(k_projection_backward, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, cam_acc, grad_K, grad_R,
+                           grad_t, B, Q);
+        rc = launch_status();
+    }
+    return rc;
 }

@@ -2,7 +2,8 @@
 
 On CUDA tensors with the usual parameter types the chain in front of the rasterizer (fill_back, lighting, look_at / look,
 perspective, vertices_to_faces) runs as one fused HIP kernel per direction (frontend.py); any other input keeps the
-module-by-module path below, which mirrors the reference line by line."""
+module-by-module path below, which mirrors the reference line by line.  camera_mode = 'projection' (a calibrated camera:
+K, R, t, dist_coeffs, orig_size; projection.py) is not in the reference."""
 import math
 import os
 import sys
@@ -14,11 +15,19 @@ from .lighting import lighting
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
+from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
 from .vertices_to_faces import vertices_to_faces
 
 # Renderer.face_light default (see the attribute): NR_FACE_LIGHT = 0 | 1 | auto
 FACE_LIGHT = {'0': False, '1': True}.get(os.environ.get('NR_FACE_LIGHT', 'auto'))
+
+
+def check_projection(renderer):
+    """camera_mode = 'projection' needs K, R, t and orig_size."""
+    missing = [n for n in ('K', 'R', 't', 'orig_size') if getattr(renderer, n) is None]
+    if missing:
+        raise ValueError("camera_mode 'projection' needs Renderer.%s" % ', '.join(missing))
 
 
 class Renderer(object):
@@ -37,6 +46,15 @@ class Renderer(object):
         self.camera_direction = [0, 0, 1]
         self.near = 0.1
         self.far = 100
+        # not in the reference: camera_mode = 'projection' -- a calibrated camera (projection.py): intrinsics K, pose R | t
+        # (world -> camera), OpenCV dist_coeffs (None = no distortion) and the size of the image K refers to.  Lists,
+        # arrays or (learnable) tensors, shared by the batch or one per image, like `eye`.  The mode ignores `perspective`
+        # and `viewing_angle`.
+        self.K = None
+        self.R = None
+        self.t = None
+        self.dist_coeffs = None
+        self.orig_size = None
 
         # light
         self.light_intensity_ambient = 0.5
@@ -69,6 +87,10 @@ class Renderer(object):
 
     def _project(self, vertices, faces):
         """camera + perspective + gather (renderer.py:40-51, :60-71, :92-103)."""
+        if self.camera_mode == 'projection':
+            check_projection(self)
+            vertices = projection(vertices, self.K, self.R, self.t, self.dist_coeffs, self.orig_size)
+            return vertices_to_faces(vertices, faces)
         if self.camera_mode == 'look_at':
             vertices = look_at(vertices, self.eye)
         elif self.camera_mode == 'look':
