@@ -890,172 +890,106 @@ inline dim3 big_grid(bool listed, int B, int F)
 }  // namespace
 
 // ====================================================================================================
-int nr::run_backward_textures(const int32_t *face_index_map, const float *sampling_weight_map,
-                              const int32_t *sampling_index_map, const float *faces, const float *faces_z_ref,
-                              const float *weight_map,
-                              const float *depth_map, const float *grad_rgb_map, float *grad_textures, int B, int F,
-                              int S, int ts, double eps, int flags, const int *vis_list, const int *vis_count,
-                              hipStream_t st, const float *g_depth, float *grad_faces, int *depth_done,
-                              const double *k6_scratch, const int *slot_of, int *k6_finalized, const FaceLight &lit,
-                              bool prefilled, int phase, const LineSetupArgs *ls, const int *zero_slot_of)
+// The gathers' steps: run_backward (nr_backward.hip) launches them in the order its plan says
+
+// K7's face gather (K8 riding along when the plan says so, K6's finish in its epilogue when the plan says so) -- or, with ls,
+// the line setup, that gather and the zeros of the unlisted faces' cubes in one launch (k_setup_gather)
+int nr::gather_faces(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l, const LineSetupArgs *ls)
 {
-    if (depth_done) *depth_done = 0;
-    if (k6_finalized) *k6_finalized = 0;
-    if (!face_index_map || !grad_rgb_map || !grad_textures || !faces) return NR_E_NULL;
-    if ((sampling_index_map == nullptr) != (sampling_weight_map == nullptr)) return NR_E_MODE;
-    if (!sampling_weight_map && (!weight_map || !depth_map)) return NR_E_NULL;
-    if (int e = check_sizes(B, F, S)) return e;
-    if (ts < 2 || ts > 1024) return NR_E_SIZE;
-    if (lit.light && sampling_weight_map) return NR_E_MODE;  // (the taps are recomputed in the original cube's layout)
-    const int fix = (flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0;
-    const float *zbase = faces_z_ref ? faces_z_ref : faces;  // :389 reads batch 0 of the GLOBAL batch (see nr_hip.h)
-    const int n = B * F;
+    const int B = c.B, F = c.F, n = B * F, ts = c.ts;
     const size_t n_tex = (size_t)ts * ts * ts * 3;
-    if (ts > 13) vis_list = nullptr;  // the atomic fallback walks pixels, not faces
-    if (ts > 8 || sampling_weight_map || !grad_faces) g_depth = nullptr;  // K8 is fused only into the one-wave-per-group gathers
-    // static taps (TS2 path): valid when the clamp of rasterize.py:402 keeps every index float below 1, i.e. when
-    // (ts - 1) - eps still rounds below ts - 1 in float32 (eps > 2^-25); otherwise a coordinate can be exactly 1.0
-    const bool ts2_static = ts == 2 && (float)(1.0 - eps) < 1.0f;
-    if (ts == 2 && !ts2_static) g_depth = nullptr;
-    if (g_depth && depth_done) *depth_done = 1;
-    // K6's finish folded into the gather (see the kernel): needs the lists, a face-per-group kernel and somewhere to store
-    // (phase 2: the finish rides in k_backward_big's launch instead, on top of what the gather of phase 1 left in grad_faces)
-    const double *finish_k6 = (phase == 2 && vis_list && k6_scratch && grad_faces && ts <= 8) ? k6_scratch : nullptr;
-    const bool fold = phase != 2 && vis_list && k6_scratch && slot_of && grad_faces && ts <= 13;
-    if (!fold) k6_scratch = nullptr, slot_of = nullptr;
-    if ((fold || finish_k6) && k6_finalized) *k6_finalized = 1;
-    // The line setup rides in the gather's launch (k_setup_gather) when there is a face-walking gather on the lists and the two
-    // fit one launch's dynamic LDS; the zeros of grad_textures ride along too (plain path; zero_slot_of: K6's face -> position
-    // table), else they are filled in front.
-    const bool face_kernel = ts <= 13;  // (above: the per-pixel scatter)
-    const size_t gather_lds = (ts2_static && !sampling_weight_map) ? 0 : (size_t)(256 / (ts <= 5 ? 16 : (ts <= 8 ? 64 : 256))) * n_tex * sizeof(double);
-    // (the shared launch's dynamic LDS is the larger of the two bodies' and its static arrays -- both bodies', ~6 KB -- come on top;
-    // without a hipFuncSetAttribute call a launch may use 64 KB in all, so the dynamic part is kept to 40 KB: texture_size 12
-    // (41.5 KB of gather accumulators) and rasters whose line setup needs more than 32 KB take the two launches)
-    const bool fuse = ls && vis_list && face_kernel && phase != 2 && ls->lds_bytes <= 32768 && gather_lds <= 40960;
-    const bool zero_in_launch = fuse && !lit.light && zero_slot_of && !prefilled && ((size_t)grad_textures & 15) == 0;
-    if (phase != 2) {
-    if (lit.light) {
-        // original cubes: a face and its reversed copy share one, so only the one that owns a pixel stores; the rest is zero
-        int e = prefilled ? 0 : fill_bytes(grad_textures, 0, (size_t)B * lit.tex_faces * n_tex * sizeof(float), st);
-        if (e == 0 && lit.grad_light) e = fill_bytes(lit.grad_light, 0, (size_t)n * 3 * sizeof(float), st);
-        if (e != 0) return e;
-    } else if (vis_list && !prefilled && !zero_in_launch) {
-        // only visible faces are visited: everything else is zero.  (Round 4 tried to spare the listed faces' cubes, which the
-        // gathers store completely -- config 5: a 4 GB fill, 565 us at 7.1 TB/s -- with a fill predicated on K6's face ->
-        // position table: 622-787 us in four forms, the division / table load / predicate cost more than the ~10 % of the
-        // bytes they save; as a launch of its own the plain fill stays.)
-        const int e = fill_bytes(grad_textures, 0, (size_t)n * n_tex * sizeof(float), st);
-        if (e != 0) return e;
-    }
-    }
-    bool setup_launched = false;
+    const int per = 256 / p.lanes;
+    const int *vis_list = p.listed ? l.vis_list : nullptr;
+    const dim3 grid = vis_list ? dim3((unsigned)((F + per - 1) / per), (unsigned)B) : dim3((unsigned)((n + per - 1) / per));
+    const bool fold = p.finish == FINISH_GATHER;
+    const FaceGatherArgs ga = {c.face_index_map, c.sampling_weight_map, c.sampling_index_map, c.faces,
+                               c.faces_z_ref ? c.faces_z_ref : c.faces,  // :389 reads batch 0 of the GLOBAL batch (see nr_hip.h)
+                               c.weight_map, c.depth_map, c.grad_rgb_map, c.grad_textures, n, F, c.S, ts, c.eps,
+                               (c.flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0, p.lanes, vis_list, l.vis_count,
+                               p.depth_in_gather ? c.grad_depth_map : nullptr,
+                               (p.depth_in_gather || fold) ? c.grad_faces : nullptr, fold ? l.scratch : nullptr,
+                               fold ? l.slot_of : nullptr, c.lit};
     // (the kernels take the per-face light mode as a template parameter: see k_backward_textures_face)
-    auto launch = [&](auto lit_mode) {
-    constexpr bool LITV = decltype(lit_mode)::value;
-    if (phase != 2 && ts <= 13) {
-        const bool st2 = ts2_static && !sampling_weight_map;
-        const int L = st2 ? 16 : (ts <= 5 ? 16 : (ts <= 8 ? 64 : 256));
-        const int per = 256 / L;
-        const size_t lds = st2 ? 0 : (size_t)per * n_tex * sizeof(double);
-        const dim3 grid = vis_list ? dim3((unsigned)((F + per - 1) / per), (unsigned)B) : dim3((unsigned)((n + per - 1) / per));
-        const bool depth = g_depth && L <= 64;  // K8 rides along in the one-wave-per-group gathers
-        const FaceGatherArgs ga = {face_index_map, sampling_weight_map, sampling_index_map, faces, zbase, weight_map, depth_map,
-                                   grad_rgb_map, grad_textures, n, F, S, ts, eps, fix, L, vis_list, vis_count,
-                                   depth ? g_depth : (const float *)nullptr,
-                                   depth ? grad_faces : (fold ? grad_faces : (float *)nullptr), k6_scratch, slot_of, lit};
-        auto go = [&](auto ts2, auto dep) {
-            constexpr bool T = decltype(ts2)::value, D = decltype(dep)::value;
-            if (fuse) {
-                ZeroArgs z = {grad_textures, zero_slot_of, F, (int)n_tex, 0, 0u};
-                if (zero_in_launch) {
-                    z.vec = n_tex % 4 == 0;
-                    z.epf = z.vec ? (int)(n_tex / 4) : (int)n_tex;
-                    z.wgs = (unsigned)(((size_t)F * z.epf + 2047) / 2048);
-                }
-                const size_t both = lds > ls->lds_bytes ? lds : ls->lds_bytes;
-                hipLaunchKernelGGL((k_setup_gather<T, D, LITV>), dim3(ls->grid_x + grid.x + z.wgs, (unsigned)B), dim3(256), both, st,
-                                   *ls, ga, z, grid.x);
-                setup_launched = true;
-            } else {
-                hipLaunchKernelGGL((k_backward_textures_face<T, D, LITV>), grid, dim3(256), lds, st, ga);
+    auto go = [&](auto ts2, auto dep, auto lit) {
+        constexpr bool T = decltype(ts2)::value, D = decltype(dep)::value, LIT = decltype(lit)::value;
+        if (ls) {
+            ZeroArgs z = {c.grad_textures, l.slot_of, F, (int)n_tex, 0, 0u};
+            if (p.tex_zeros == TEX_ZEROS_SETUP) {
+                z.vec = n_tex % 4 == 0;
+                z.epf = z.vec ? (int)(n_tex / 4) : (int)n_tex;
+                z.wgs = (unsigned)(((size_t)F * z.epf + 2047) / 2048);
             }
-        };
-        using T = std::true_type;
-        using N = std::false_type;
-        if (st2) { if (depth) go(T(), T()); else go(T(), N()); }
-        else { if (depth) go(N(), T()); else go(N(), N()); }
-    }
-    if (ts <= 8 && phase != 1) {
-        // faces the gathers above left out (more than BIG_PX candidates): a workgroup each
-        const dim3 grid = big_grid(vis_list != nullptr, B, F);
-        const bool st2 = ts2_static && !sampling_weight_map;
-        const size_t lds = st2 ? 0 : n_tex * sizeof(double);
-#define NR_BIG(T, D)                                                                                                    \
-    hipLaunchKernelGGL((k_backward_big<T, D, LITV>), grid, dim3(256), lds, st, face_index_map, sampling_weight_map,   \
-                       sampling_index_map, (const float *)nullptr, faces, zbase, weight_map, depth_map, grad_rgb_map, \
-                       grad_textures, n, F, S, ts, eps, fix, vis_list, vis_count, D ? g_depth : (const float *)nullptr, \
-                       (D || finish_k6) ? grad_faces : (float *)nullptr, (const unsigned char *)nullptr, lit, finish_k6)
-        if (st2) { if (g_depth) NR_BIG(2, true); else NR_BIG(2, false); }
+            const size_t both = p.gather_lds > ls->lds_bytes ? p.gather_lds : ls->lds_bytes;
+            hipLaunchKernelGGL((k_setup_gather<T, D, LIT>), dim3(ls->grid_x + grid.x + z.wgs, (unsigned)B), dim3(256), both, c.st,
+                               *ls, ga, z, grid.x);
+        } else {
+            hipLaunchKernelGGL((k_backward_textures_face<T, D, LIT>), grid, dim3(256), p.gather_lds, c.st, ga);
+        }
+    };
+    auto with_lit = [&](auto ts2, auto dep) {
+        if (c.lit.light) go(ts2, dep, std::true_type()); else go(ts2, dep, std::false_type());
+    };
+    using T = std::true_type;
+    using N = std::false_type;
+    if (p.static_taps) { if (p.depth_in_gather) with_lit(T(), T()); else with_lit(T(), N()); }
+    else { if (p.depth_in_gather) with_lit(N(), T()); else with_lit(N(), N()); }
+    return launch_status();
+}
+
+// the faces the face gather left out (more than BIG_PX candidates): a workgroup each.  FINISH_BIG: K6's sums of the listed
+// faces go on top of what the gather left in grad_faces, in this launch
+void nr::gather_big(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l)
+{
+    const int n = c.B * c.F, ts = c.ts;
+    const int *vis_list = p.listed ? l.vis_list : nullptr;
+    const dim3 grid = big_grid(vis_list != nullptr, c.B, c.F);
+    const size_t lds = p.static_taps ? 0 : (size_t)ts * ts * ts * 3 * sizeof(double);
+    const float *zbase = c.faces_z_ref ? c.faces_z_ref : c.faces;
+    const int fix = (c.flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0;
+    const double *finish_k6 = p.finish == FINISH_BIG ? l.scratch : nullptr;
+    const float *g_depth = p.depth_in_gather ? c.grad_depth_map : nullptr;
+    float *grad_faces = (p.depth_in_gather || finish_k6) ? c.grad_faces : nullptr;
+    auto go = [&](auto lit) {
+        constexpr bool LIT = decltype(lit)::value;
+#define NR_BIG(T, D)                                                                                                            \
+    hipLaunchKernelGGL((k_backward_big<T, D, LIT>), grid, dim3(256), lds, c.st, c.face_index_map, c.sampling_weight_map,        \
+                       c.sampling_index_map, (const float *)nullptr, c.faces, zbase, c.weight_map, c.depth_map, c.grad_rgb_map, \
+                       c.grad_textures, n, c.F, c.S, ts, c.eps, fix, vis_list, l.vis_count, g_depth, grad_faces,               \
+                       (const unsigned char *)nullptr, c.lit, finish_k6)
+        if (p.static_taps) { if (g_depth) NR_BIG(2, true); else NR_BIG(2, false); }
         else { if (g_depth) NR_BIG(1, true); else NR_BIG(1, false); }
 #undef NR_BIG
-    }
     };
-    if (lit.light) launch(std::true_type()); else launch(std::false_type());
-    if (phase == 2) return launch_status();
-    if (ls && !setup_launched)  // the line setup as a launch of its own (no face-walking gather to share one with)
-        if (int rc = run_line_setup(*ls, st)) return rc;
-    if (ts > 13 && lit.light) {
-        // (grad_textures and grad_light were zero-filled above)
-        const size_t np = (size_t)B * S * S;
-        hipLaunchKernelGGL(k_backward_textures_atomic_lit, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st, face_index_map,
-                           faces, zbase, weight_map, depth_map, grad_rgb_map, grad_textures, F, S, ts, eps, fix, np, lit);
-    } else if (ts > 13) {
-        // huge cubes: the reference's per-pixel scatter with hardware atomics
-        const int e = fill_bytes(grad_textures, 0, (size_t)n * n_tex * sizeof(float), st);
-        if (e != 0) return e;
-        const size_t np = (size_t)B * S * S;
-        hipLaunchKernelGGL(k_backward_textures_atomic, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, st,
-                           face_index_map, sampling_weight_map, sampling_index_map, faces, zbase, weight_map, depth_map,
-                           grad_rgb_map, grad_textures, F, S, ts, eps, fix, np);
-    }
-    return launch_status();
+    if (c.lit.light) go(std::true_type()); else go(std::false_type());
 }
 
-int nr::run_backward_depth_map(const float *faces, const float *depth_map, const int32_t *face_index_map,
-                               const float *face_inv_map, const float *weight_map, const float *grad_depth_map,
-                               float *grad_faces, int B, int F, int S, const int *vis_list, const int *vis_count,
-                               hipStream_t st, const unsigned char *visible)
+// texture_size > 13: the reference's per-pixel scatter with hardware atomics, onto the zeros filled in front
+void nr::gather_atomic(const BackwardCall &c)
 {
-    if (!faces || !depth_map || !face_index_map || !weight_map || !grad_depth_map || !grad_faces) return NR_E_NULL;
-    if (int e = check_sizes(B, F, S)) return e;
-    const int n = B * F;
-    const dim3 grid = vis_list ? dim3((unsigned)((F + 15) / 16), (unsigned)B) : dim3((unsigned)((n + 15) / 16));
-    hipLaunchKernelGGL(k_backward_depth_face, grid, dim3(256), 0, st, faces, depth_map, face_index_map, face_inv_map,
-                       weight_map, grad_depth_map, grad_faces, n, F, S, vis_list, vis_count, visible);
-    const dim3 grid_big = big_grid(vis_list != nullptr, B, F);
-    hipLaunchKernelGGL((k_backward_big<0, true, false>), grid_big, dim3(256), 0, st, face_index_map, (const float *)nullptr,
-                       (const int32_t *)nullptr, face_inv_map, faces, faces, weight_map, depth_map, (const float *)nullptr,
-                       (float *)nullptr, n, F, S, 2, 0.0, 0, vis_list, vis_count, grad_depth_map, grad_faces, visible, FaceLight(),
-                       (const double *)nullptr);
-    return launch_status();
+    const size_t np = (size_t)c.B * c.S * c.S;
+    const float *zbase = c.faces_z_ref ? c.faces_z_ref : c.faces;
+    const int fix = (c.flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0;
+    if (c.lit.light)
+        hipLaunchKernelGGL(k_backward_textures_atomic_lit, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c.st,
+                           c.face_index_map, c.faces, zbase, c.weight_map, c.depth_map, c.grad_rgb_map, c.grad_textures, c.F,
+                           c.S, c.ts, c.eps, fix, np, c.lit);
+    else
+        hipLaunchKernelGGL(k_backward_textures_atomic, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, c.st, c.face_index_map,
+                           c.sampling_weight_map, c.sampling_index_map, c.faces, zbase, c.weight_map, c.depth_map,
+                           c.grad_rgb_map, c.grad_textures, c.F, c.S, c.ts, c.eps, fix, np);
 }
 
-NR_API int nr_backward_textures(const int32_t *face_index_map, const float *sampling_weight_map,
-                                const int32_t *sampling_index_map, const float *faces, const float *faces_z_ref,
-                                const float *weight_map,
-                                const float *depth_map, const float *grad_rgb_map, float *grad_textures, int32_t B,
-                                int32_t F, int32_t S, int32_t ts, double eps, int32_t flags, void *stream)
+// K8 on its own: added onto grad_faces; the faces of K6's lists (or of the depth-only call's), else those the forward's
+// flags mark (the staged entry point has neither)
+void nr::gather_depth(const BackwardCall &c, const K6Lists &l)
 {
-    return run_backward_textures(face_index_map, sampling_weight_map, sampling_index_map, faces, faces_z_ref, weight_map,
-                                 depth_map, grad_rgb_map, grad_textures, B, F, S, ts, eps, flags, nullptr, nullptr,
-                                 (hipStream_t)stream, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr);
-}
-
-NR_API int nr_backward_depth_map(const float *faces, const float *depth_map, const int32_t *face_index_map,
-                                 const float *face_inv_map, const float *weight_map, const float *grad_depth_map,
-                                 float *grad_faces, int32_t B, int32_t F, int32_t S, void *stream)
-{
-    return run_backward_depth_map(faces, depth_map, face_index_map, face_inv_map, weight_map, grad_depth_map,
-                                  grad_faces, B, F, S, nullptr, nullptr, (hipStream_t)stream, nullptr);
+    const int B = c.B, F = c.F, n = B * F;
+    const dim3 grid = l.vis_list ? dim3((unsigned)((F + 15) / 16), (unsigned)B) : dim3((unsigned)((n + 15) / 16));
+    hipLaunchKernelGGL(k_backward_depth_face, grid, dim3(256), 0, c.st, c.faces, c.depth_map, c.face_index_map, c.face_inv_map,
+                       c.weight_map, c.grad_depth_map, c.grad_faces, n, F, c.S, l.vis_list, l.vis_count, c.visible_faces);
+    const dim3 grid_big = big_grid(l.vis_list != nullptr, B, F);
+    hipLaunchKernelGGL((k_backward_big<0, true, false>), grid_big, dim3(256), 0, c.st, c.face_index_map, (const float *)nullptr,
+                       (const int32_t *)nullptr, c.face_inv_map, c.faces, c.faces, c.weight_map, c.depth_map, (const float *)nullptr,
+                       (float *)nullptr, n, F, c.S, 2, 0.0, 0, l.vis_list, l.vis_count, c.grad_depth_map, c.grad_faces,
+                       c.visible_faces, FaceLight(), (const double *)nullptr);
 }

@@ -1,5 +1,6 @@
 // nr_backward_pixel_map.hip -- K6, the approximate gradient of rgb / alpha w.r.t. vertex x, y
-// (reference Rasterize.backward_pixel_map_gpu, rasterize.py:517-748) + its C-ABI entry point.
+// (reference Rasterize.backward_pixel_map_gpu, rasterize.py:517-748): its kernels and their host-side steps (the entry point and
+// the plan that orders the steps: nr_backward.hip).
 #include "nr_device.h"
 #include "nr_band_lines.h"
 #include "nr_k6_tune.h"
@@ -240,8 +241,7 @@ __global__ __launch_bounds__(WAVE) void k_bpm_global(
 //   k_line_setup   every line's record (crossing point, in / out pixels, sweep ranges, the two distance coefficients:
 //          rasterize.py:573-579, :606-609, :665-672), written band by band into one buffer.
 //          (The records and the kernel's body live in nr_band_lines.h: in the fused backward of a small call the K7 / K8
-//          gather shares this launch -- nr_backward_gather.hip, k_setup_gather, through the SetupHook of
-//          run_backward_pixel_map.)
+//          gather shares this launch -- nr_backward_gather.hip, k_setup_gather, when plan_backward says so.)
 //   k_bpm_fast<RGB, ALPHA, MODE>   one workgroup per (image, axis, band of W consecutive lines d0); workgroup ids are
 //          mapped so that all bands of an image run on one XCD (xcd_block).  It
 //          1. stages the band's W x S pixels in LDS, laid out [line][d1] so that a sweep is a contiguous LDS run
@@ -2200,11 +2200,6 @@ ListsLayout lists_layout(int B, int F)
 // i.e. while a two-line band leaves room for a window of >= 128 lines (raster <= 400 with colours) it wins, walked by four
 // waves: the same ~110 lines and ~1 200 pieces per window as four lines give eight waves, in workgroups half the size --
 // four per CU, a finer grain for the tail and for the mix of busy and empty bands.  Beyond that the wide shape stays.
-struct BandShape {
-    int threads;     // 256 | 512
-    int w_max;       // widest band (lines)
-    size_t budget;   // LDS per workgroup
-};
 BandShape band_shape(int S)
 {
     if (S <= k6::SMALL_RASTER_MAX) return {256, 2, (size_t)40 * 1024};  // four workgroups per 160 KB CU
@@ -2276,24 +2271,6 @@ struct LdsLimit {
     }
 };
 
-// Which band kernel a call takes, and how it is shaped: decided once per call, on the host, from the call's shape alone (no
-// device).  run_backward_pixel_map executes the plan; nr_profile_k6_choice reports its kernel.
-enum K6Kernel { K6_KERNEL_FAST = 0, K6_KERNEL_ROW = 1, K6_KERNEL_GLOBAL = 2 };  // (0 / 1: nr_profile_band_kernel_which)
-struct K6Plan {
-    int kernel;           // K6Kernel
-    int mode;             // K6_FAST | K6_EXACT_POW2 | K6_EXACT
-    BandShape shape;      // k_bpm_fast: workgroup shape,
-    int W_fast;           // ... band width (lines; 0: no LDS band fits -- the global kernel),
-    size_t fast_lds;      // ... LDS bytes,
-    int win_lines, qcap;  // ... line records per window and piece-queue capacity
-    int W_row;            // k_bpm_row: band width (0: not taken)
-    size_t row_lds;       // ... LDS bytes
-    int W, n_bands;       // the band tables: lines per band, bands per image
-    bool use_records;     // line records from k_line_setup (false: every image takes k_bpm_fast's face scan)
-    bool overflow_pass;   // k_bpm_fast's overflow-only launch follows k_bpm_row
-    size_t fill_max;      // the largest zero fill (bytes) that the band kernel takes along
-};
-
 // The call's (rgb, alpha, mode) as template arguments of f(r, a, m): the three map combinations of the ABI (rgb and alpha, rgb,
 // alpha) times the three arithmetic modes.  Both band kernels are launched through it.
 template <class Fn> int with_k6_types(bool rgb, bool alpha, int mode, const Fn &f)
@@ -2309,11 +2286,9 @@ template <class Fn> int with_k6_types(bool rgb, bool alpha, int mode, const Fn &
 }
 
 template <bool RGB, bool ALPHA, int MODE, bool OVF>
-int launch_fast(const K6Plan &p, const float *faces, const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb,
-                const float *g_alpha, const int *vis_list, const int *vis_count, const unsigned *rng, double *scratch,
-                const int *band_lines, const int *band_start, const int *lines_ok, const BandLine *line_buf, size_t cap,
-                int B, int F, int S, double eps, float k2s, hipStream_t st, void *zero_ptr, size_t zero_bytes)
+int launch_fast(const K6Plan &p, const BackwardCall &c, const K6Lists &l, const LineSetupArgs &ls, void *zero_ptr, size_t zero_bytes)
 {
+    const int B = c.B, S = c.S;
     const unsigned total_wg = (unsigned)((S + p.W_fast - 1) / p.W_fast) * 2u * (unsigned)B;
     // 1-D grid: the kernel maps ids to (image, axis, band) per XCD
     // (overflow-only launch behind k_bpm_row: a resident grid that strides over the bands, k6::OVF_GRID workgroups.  With nothing
@@ -2326,9 +2301,10 @@ int launch_fast(const K6Plan &p, const float *faces, const int32_t *fi, const fl
         static LdsLimit limit;  // one per instantiation
         auto kern = k_bpm_fast<RGB, ALPHA, MODE, NT, OVF>;
         if (int rc = limit.ensure((const void *)kern, p.fast_lds)) return rc;
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), p.fast_lds, st, faces, fi, rgb, alpha, g_rgb, g_alpha, vis_list, vis_count,
-                           rng, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, p.W_fast, S + 4, eps, k2s, B,
-                           p.win_lines, p.qcap, (uint4 *)zero_ptr, zero_bytes / 16);
+        hipLaunchKernelGGL(kern, dim3(grid), dim3(NT), p.fast_lds, c.st, c.faces, c.face_index_map, c.rgb_map, c.alpha_map,
+                           c.grad_rgb_map, c.grad_alpha_map, l.vis_list, l.vis_count, ls.rng, l.scratch, ls.band_lines, ls.band_start,
+                           ls.lines_ok, ls.line_buf, ls.cap, c.F, S, p.W_fast, S + 4, c.eps, ls.k2s, B, p.win_lines, p.qcap,
+                           (uint4 *)zero_ptr, zero_bytes / 16);
         return 0;
     };
     return p.shape.threads == 256 ? go(std::integral_constant<int, 256>()) : go(std::integral_constant<int, 512>());
@@ -2369,19 +2345,20 @@ int row_band_config(int S, int F, bool rgb, bool exact, int B, size_t *lds_bytes
 }
 
 template <bool RGB, bool ALPHA, int MODE>
-int launch_row(const K6Plan &p, const int32_t *fi, const float *rgb, const float *alpha, const float *g_rgb, const float *g_alpha,
-               double *scratch, const int *band_lines, const int *band_start, const int *lines_ok, const BandLine *line_buf,
-               size_t cap, int B, int F, int S, double eps, hipStream_t st, void *zero_ptr, size_t zero_bytes)
+int launch_row(const K6Plan &p, const BackwardCall &c, const K6Lists &l, const LineSetupArgs &ls, void *zero_ptr, size_t zero_bytes)
 {
+    const int B = c.B, F = c.F, S = c.S;
+    const double eps = c.eps;
     const int CH = row_chunk(S, F), W = p.W_row;
     const unsigned n_ch = (unsigned)((S + CH - 1) / CH), total_wg = (unsigned)((S + W - 1) / W) * 2u * (unsigned)B * n_ch;
     auto go = [&](auto chunked) {
         constexpr bool C = decltype(chunked)::value;
         static LdsLimit limit;  // one per instantiation (40 KB at most with the product's constants: never raised)
         if (int rc = limit.ensure((const void *)k_bpm_row<RGB, ALPHA, MODE, C>, p.row_lds)) return rc;
-        hipLaunchKernelGGL((k_bpm_row<RGB, ALPHA, MODE, C>), dim3(xcd_grid(total_wg)), dim3(rowk::NT), p.row_lds, st, fi, rgb, alpha,
-                           g_rgb, g_alpha, scratch, band_lines, band_start, lines_ok, line_buf, cap, F, S, W, CH, (float)eps, eps, B,
-                           (uint4 *)zero_ptr, zero_bytes / 16);
+        hipLaunchKernelGGL((k_bpm_row<RGB, ALPHA, MODE, C>), dim3(xcd_grid(total_wg)), dim3(rowk::NT), p.row_lds, c.st,
+                           c.face_index_map, c.rgb_map, c.alpha_map, c.grad_rgb_map, c.grad_alpha_map, l.scratch, ls.band_lines,
+                           ls.band_start, ls.lines_ok, ls.line_buf, ls.cap, F, S, W, CH, (float)eps, eps, B, (uint4 *)zero_ptr,
+                           zero_bytes / 16);
         return 0;
     };
     return n_ch > 1 ? go(std::true_type()) : go(std::false_type());
@@ -2404,7 +2381,11 @@ int k6_row_band(int B, int F, int S, bool rgb, double eps, int flags, size_t *ro
     return possible ? row_band_config(S, F, rgb, exact, B, row_lds) : 0;
 }
 
-K6Plan plan_k6(int B, int F, int S, bool rgb, double eps, int flags)
+}  // namespace
+
+// Which band kernel a call takes, and how it is shaped: decided once per call, on the host, from the call's shape alone (no
+// device).  plan_backward (nr_backward.hip) takes it into the call's plan; nr_profile_k6_choice reports its kernel.
+K6Plan nr::plan_k6(int B, int F, int S, bool rgb, double eps, int flags)
 {
     K6Plan p = {};
     const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
@@ -2439,8 +2420,6 @@ K6Plan plan_k6(int B, int F, int S, bool rgb, double eps, int flags)
     p.fill_max = band_wgs * ((size_t)k6::FOLD_KB << 10) * (size_t)(row ? rowk::NT : p.shape.threads) / 512;
     return p;
 }
-
-}  // namespace
 
 NR_API size_t nr_backward_workspace_bytes(int32_t B, int32_t F, int32_t S, int32_t return_rgb, int32_t return_alpha)
 {
@@ -2501,47 +2480,18 @@ NR_API int nr_profile_k6_choice(int32_t B, int32_t F, int32_t S, int32_t return_
 #define NR_BAND_TIMER_STOP(st) ((void)0)
 #endif
 
-int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map, const float *rgb_map,
-                               const float *alpha_map, const float *grad_rgb_map, const float *grad_alpha_map,
-                               float *grad_faces, int B, int F, int S, double eps, int return_rgb, int return_alpha,
-                               int flags, const unsigned char *visible_faces, void *workspace, size_t workspace_bytes,
-                               hipStream_t st, const int **vis_list_out, const int **vis_count_out,
-                               const double **defer_scratch, const int **defer_slot_of, void *zero_ptr, size_t zero_bytes,
-                               int *zeroed, const SetupHook *hook)
-{
-    if (zeroed) *zeroed = 0;
-    if (vis_list_out) *vis_list_out = nullptr;
-    if (vis_count_out) *vis_count_out = nullptr;
-    if (defer_scratch) *defer_scratch = nullptr;
-    if (defer_slot_of) *defer_slot_of = nullptr;
-    if (!faces || !face_index_map || !grad_faces) return NR_E_NULL;
-    if (!return_rgb && !return_alpha) return NR_E_MODE;  // rasterize.py:523-524 returns early; callers skip the call
-    if (return_rgb && (!rgb_map || !grad_rgb_map)) return NR_E_NULL;
-    if (return_alpha && (!alpha_map || !grad_alpha_map)) return NR_E_NULL;
-    if (int e = check_sizes(B, F, S)) return e;
-    if ((size_t)B * S * S > 0x7fffffffull / 3) return NR_E_SIZE;  // int32 pixel indexing inside the kernels
-    const int n = B * F;
-    const bool rgb = return_rgb != 0, alpha = return_alpha != 0;
-    const bool exact = (flags & NR_FLAG_EXACT_GRADIENT) != 0;
-    const K6Plan plan = plan_k6(B, F, S, rgb, eps, flags);
-    if (plan.kernel == K6_KERNEL_GLOBAL) {
-        const dim3 grid((unsigned)n), block(WAVE);
-        if (rgb && alpha)
-            hipLaunchKernelGGL((k_bpm_global<true, true>), grid, block, 0, st, faces, face_index_map, rgb_map,
-                               alpha_map, grad_rgb_map, grad_alpha_map, grad_faces, F, S, eps);
-        else if (rgb)
-            hipLaunchKernelGGL((k_bpm_global<true, false>), grid, block, 0, st, faces, face_index_map, rgb_map,
-                               alpha_map, grad_rgb_map, grad_alpha_map, grad_faces, F, S, eps);
-        else
-            hipLaunchKernelGGL((k_bpm_global<false, true>), grid, block, 0, st, faces, face_index_map, rgb_map,
-                               alpha_map, grad_rgb_map, grad_alpha_map, grad_faces, F, S, eps);
-        return launch_status();
-    }
+// --------------------------------------------------------------------------------------------------
+// K6's steps: run_backward (nr_backward.hip) launches them in the order its plan says
 
+// the compaction writes the chunk rows of k_compact_par (n_sum > 0: the consumer adds them up) while the two fit its LDS
+static bool compact_in_one_launch(const BpmLayout &L, int n_bands) { return L.n_chunks <= SMALL_CHUNKS && n_bands <= 4096; }
+
+int nr::k6_compact(const BackwardCall &c, const K6Plan &plan, int face_zeros, K6Lists &out)
+{
+    const int B = c.B, F = c.F, S = c.S, n = B * F;
     const BpmLayout L = bpm_layout(B, F, S);
-    if (!workspace || workspace_bytes < L.total) return NR_E_WORKSPACE;
-    const bool defer = defer_scratch && defer_slot_of;  // the caller's gather finishes the listed faces (see nr_device.h)
-    unsigned char *ws = (unsigned char *)workspace;
+    const hipStream_t st = c.st;
+    unsigned char *ws = (unsigned char *)c.workspace;
     int *band_lines = (int *)(ws + L.band_off);
     const int W = plan.W, n_bands = plan.n_bands;
     double *scratch = (double *)(ws + L.scratch_off);
@@ -2549,37 +2499,30 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
     int *vis_list = (int *)(ws + L.list_off);
     int *slot_of = (int *)(ws + L.slot_off);
     unsigned *rng = (unsigned *)(ws + L.rng_off);
-    if (vis_list_out) *vis_list_out = vis_list;
-    if (vis_count_out) *vis_count_out = vis_count;
-    const unsigned char *vflags = visible_faces;
+    out = {vis_list, vis_count, slot_of, scratch};
+    const unsigned char *vflags = c.visible_faces;
     if (!vflags) {  // the forward's flags were not kept: one pass over face_index_map rebuilds them
         unsigned char *f = ws + L.flags_off;
         const int he = fill_bytes(f, 0, (size_t)n, st);
         if (he != 0) return he;
         const size_t P = (size_t)B * S * S;
-        hipLaunchKernelGGL(k_mark_visible, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, face_index_map, f, F,
+        hipLaunchKernelGGL(k_mark_visible, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, c.face_index_map, f, F,
                            S * S, P);
         vflags = f;
     }
     int *band_start = (int *)(ws + L.start_off), *band_cursor = (int *)(ws + L.cursor_off), *lines_ok = (int *)(ws + L.ok_off);
-    BandLine *line_buf = (BandLine *)(ws + L.lines_off);
-    const bool use_records = plan.use_records;
-    // the distance coefficients of a record: x 2 / S up front in the tolerance mode, as the reference has them in the exact one
-    const float k2s = exact ? 1.0f : 2.0f / (float)S;
-    const size_t cap = use_records ? L.cap : 0;  // capacity 0: every image is told to take the scan path
-    int n_sum = 0;  // chunk rows per image that the consumer adds up (0: the band table is ready)
-    // (k_compact_par keeps its chunk's 2 * n_bands line counters in LDS: 32 KB at most)
-    if (L.n_chunks <= SMALL_CHUNKS && n_bands <= 4096) {
+    float *zero_faces = face_zeros != FACE_ZEROS_NONE ? c.grad_faces : nullptr;
+    const int zero_listed = face_zeros == FACE_ZEROS_ALL ? 1 : 0;
+    if (compact_in_one_launch(L, n_bands)) {
         int *chunk_band = (int *)(ws + L.cband_off);
-        n_sum = L.n_chunks;
         // (line-difference counting while the two line arrays fit beside the band counters: raster sides up to 3583)
         const int use_diff = (size_t)(2 * n_bands + 2 * (S + 1)) * sizeof(int) <= 40960 ? 1 : 0;
         hipLaunchKernelGGL(k_compact_par, dim3((unsigned)L.n_chunks, (unsigned)B), dim3(VIS_CHUNK),
                            (size_t)(2 * n_bands + (use_diff ? 2 * (S + 1) : 0)) * sizeof(int), st, vflags, vis_list, vis_count,
-                           slot_of, F, L.n_chunks, faces, rng, scratch, S, chunk_band, n_bands, W, band_cursor,
-                           defer ? grad_faces : (float *)nullptr, hook ? 1 : 0, use_diff);
-        if (!use_records)
-            hipLaunchKernelGGL(k_band_total, dim3((unsigned)B), dim3(256), 0, st, chunk_band, n_sum, band_lines, band_start,
+                           slot_of, F, L.n_chunks, c.faces, rng, scratch, S, chunk_band, n_bands, W, band_cursor, zero_faces,
+                           zero_listed, use_diff);
+        if (!plan.use_records)
+            hipLaunchKernelGGL(k_band_total, dim3((unsigned)B), dim3(256), 0, st, chunk_band, L.n_chunks, band_lines, band_start,
                                lines_ok, n_bands);
     } else {
         int *chunk_count = (int *)(ws + L.chunk_off);
@@ -2588,62 +2531,27 @@ int nr::run_backward_pixel_map(const float *faces, const int32_t *face_index_map
         const int lds_counters = n_bands <= 4096;  // 32 KB of LDS at most
         hipLaunchKernelGGL(k_compact_visible, dim3((unsigned)L.n_chunks, (unsigned)B), dim3(VIS_CHUNK),
                            lds_counters ? (size_t)2 * n_bands * sizeof(int) : 0, st, vflags, chunk_count, vis_list, vis_count,
-                           slot_of, F, L.n_chunks, faces, rng, scratch, S, band_lines, n_bands, W, lds_counters,
-                           defer ? grad_faces : (float *)nullptr, hook ? 1 : 0);
+                           slot_of, F, L.n_chunks, c.faces, rng, scratch, S, band_lines, n_bands, W, lds_counters, zero_faces,
+                           zero_listed);
+        // (capacity 0: every image is told to take the scan path)
         hipLaunchKernelGGL(k_band_scan, dim3((unsigned)B), dim3(256), 0, st, band_lines, band_start, band_cursor, lines_ok,
-                           n_bands, cap, 0);
+                           n_bands, plan.use_records ? L.cap : 0, 0);
     }
-    {
-        const LineSetupArgs la = {faces, face_index_map, vis_list, vis_count, rng, (const int *)(ws + L.cband_off), n_sum, band_lines,
-                                  band_start, band_cursor, lines_ok, line_buf, L.cap, F, S, W, n_bands, k2s,
-                                  (unsigned)((F + LS_FACES - 1) / LS_FACES), (unsigned)B, (size_t)6 * n_bands * sizeof(int)};
-        if (hook) {  // the caller launches the line setup, together with its gather (nr_band_lines.h)
-            if (int rc = hook->launch(hook->ctx, use_records ? &la : nullptr, vis_list, vis_count, slot_of, st)) return rc;
-        } else if (use_records) {
-            if (int rc = run_line_setup(la, st)) return rc;
-        }
-    }
-    // the band kernel (k_bpm_row or k_bpm_fast, with the caller's zero fill when it fits), then the overflow-only k_bpm_fast
-    // launch behind k_bpm_row: the images whose records exceed the line buffer, by the face scan, no fill
-    const bool zero_ok = !hook && zero_ptr && zero_bytes > 0 && zero_bytes % 16 == 0 && ((size_t)zero_ptr & 15) == 0 &&
-                         zero_bytes <= plan.fill_max;
-    void *const fill_ptr = zero_ok ? zero_ptr : nullptr;
-    const size_t fill_len = zero_ok ? zero_bytes : 0;
-    auto band_fast = [&](auto overflow_only, void *zp, size_t zb) {
-        return with_k6_types(rgb, alpha, plan.mode, [&](auto r, auto a, auto m) {
-            return launch_fast<decltype(r)::value, decltype(a)::value, decltype(m)::value, decltype(overflow_only)::value>(
-                plan, faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, vis_list, vis_count, rng, scratch,
-                band_lines, band_start, lines_ok, line_buf, L.cap, B, F, S, eps, k2s, st, zp, zb);
-        });
-    };
-    auto band_row = [&]() {
-        return with_k6_types(rgb, alpha, plan.mode, [&](auto r, auto a, auto m) {
-            return launch_row<decltype(r)::value, decltype(a)::value, decltype(m)::value>(
-                plan, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, scratch, band_lines, band_start, lines_ok,
-                line_buf, L.cap, B, F, S, eps, st, fill_ptr, fill_len);
-        });
-    };
-    NR_BAND_TIMER_START(st, plan.kernel);
-    int rc = plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill_ptr, fill_len);
-    NR_BAND_TIMER_STOP(st);
-    if (rc == 0 && plan.overflow_pass) rc = band_fast(std::true_type(), nullptr, 0);
-    if (rc) return rc;
-    if (zero_ok && zeroed) *zeroed = 1;
-    if (defer) {  // the caller finishes the listed faces (the fused gather, in the same launch as K7 / K8)
-        *defer_scratch = scratch;
-        *defer_slot_of = slot_of;
-        return launch_status();
-    }
-    hipLaunchKernelGGL(k_bpm_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scratch, slot_of, grad_faces,
-                       F, n, 0);
     return launch_status();
 }
 
-void nr::run_bpm_finalize(const double *scratch, const int *slot_of, float *grad_faces, int B, int F, hipStream_t st, bool add)
+LineSetupArgs nr::k6_line_setup_args(const BackwardCall &c, const K6Plan &plan)
 {
-    const int n = B * F;
-    hipLaunchKernelGGL(k_bpm_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, scratch, slot_of, grad_faces,
-                       F, n, add ? 1 : 0);
+    const BpmLayout L = bpm_layout(c.B, c.F, c.S);
+    unsigned char *ws = (unsigned char *)c.workspace;
+    const int n_bands = plan.n_bands;
+    // the distance coefficients of a record: x 2 / S up front in the tolerance mode, as the reference has them in the exact one
+    const float k2s = (c.flags & NR_FLAG_EXACT_GRADIENT) ? 1.0f : 2.0f / (float)c.S;
+    return {c.faces, c.face_index_map, (const int *)(ws + L.list_off), (const int *)(ws + L.count_off),
+            (const unsigned *)(ws + L.rng_off), (const int *)(ws + L.cband_off), compact_in_one_launch(L, n_bands) ? L.n_chunks : 0,
+            (int *)(ws + L.band_off), (int *)(ws + L.start_off), (int *)(ws + L.cursor_off), (int *)(ws + L.ok_off),
+            (BandLine *)(ws + L.lines_off), L.cap, c.F, c.S, plan.W, n_bands, k2s, (unsigned)((c.F + LS_FACES - 1) / LS_FACES),
+            (unsigned)c.B, (size_t)6 * n_bands * sizeof(int)};
 }
 
 int nr::run_line_setup(const LineSetupArgs &a, hipStream_t st)
@@ -2654,158 +2562,61 @@ int nr::run_line_setup(const LineSetupArgs &a, hipStream_t st)
     return launch_status();
 }
 
-NR_API int nr_backward_pixel_map(const float *faces, const int32_t *face_index_map, const float *rgb_map,
-                                 const float *alpha_map, const float *grad_rgb_map, const float *grad_alpha_map,
-                                 float *grad_faces, int32_t B, int32_t F, int32_t S, double eps, int32_t return_rgb,
-                                 int32_t return_alpha, int32_t flags, const uint8_t *visible_faces, void *workspace,
-                                 size_t workspace_bytes, void *stream)
+// The global-memory kernel, or the band kernel (k_bpm_row or k_bpm_fast, with the zero fill `fill` when the plan gave it one)
+// and then the overflow-only k_bpm_fast launch behind k_bpm_row: the images whose records exceed the line buffer, by the face
+// scan, no fill.  (l, ls: the compaction's lists and the band tables and line records of k6_line_setup_args.)
+int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes)
 {
-    return run_backward_pixel_map(faces, face_index_map, rgb_map, alpha_map, grad_rgb_map, grad_alpha_map, grad_faces, B,
-                                  F, S, eps, return_rgb, return_alpha, flags, visible_faces, workspace, workspace_bytes,
-                                  (hipStream_t)stream, nullptr, nullptr);
-}
-
-// The fused backward's hook into K6 (nr_band_lines.h SetupHook): where K6 would launch its line setup, the K7 / K8 gather goes
-// out with it in one grid (nr_backward_gather.hip, k_setup_gather).
-namespace {
-struct GatherCall {
-    const float *faces, *faces_z_ref, *weight_map, *depth_map, *grad_rgb_map, *grad_depth_map;
-    const int32_t *face_index_map;
-    float *grad_textures, *grad_faces;
-    int B, F, S, ts, flags;
-    double eps;
-    const FaceLight *lit;
-    bool called;
-    int depth_done;
-};
-
-int launch_setup_and_gather(void *ctx, const LineSetupArgs *ls, const int *vis_list, const int *vis_count, const int *slot_of,
-                            hipStream_t st)
-{
-    GatherCall &g = *static_cast<GatherCall *>(ctx);
-    g.called = true;
-    // (no K6 scratch to finish: the gather adds K8's sums onto the zeros of the compaction, K6's follow behind the band kernel)
-    return run_backward_textures(g.face_index_map, nullptr, nullptr, g.faces, g.faces_z_ref, g.weight_map, g.depth_map,
-                                 g.grad_rgb_map, g.grad_textures, g.B, g.F, g.S, g.ts, g.eps, g.flags, vis_list, vis_count, st,
-                                 g.grad_depth_map, g.grad_faces, &g.depth_done, nullptr, nullptr, nullptr, *g.lit, false, 1, ls,
-                                 slot_of);
-}
-}  // namespace
-
-// Fused backward: K6, K7 and K8 of one Rasterize.backward_gpu call (rasterize.py:849-889) behind one entry point.
-// Same results as calling the three stage functions in the reference's order; the visible-face lists built for
-// K6 are reused by the K7 / K8 gathers, which then visit ~1/5 of the faces.
-NR_API int nr_backward_rasterize(const float *faces, const float *faces_z_ref, const int32_t *face_index_map,
-                                 const float *weight_map, const float *depth_map, const float *rgb_map,
-                                 const float *alpha_map, const float *grad_rgb_map, const float *grad_alpha_map,
-                                 const float *grad_depth_map, float *grad_faces, float *grad_textures, int32_t B,
-                                 int32_t F, int32_t S, int32_t ts, double eps, int32_t flags,
-                                 const uint8_t *visible_faces, void *workspace, size_t workspace_bytes, void *stream)
-{
-    return nr_backward_rasterize_lit(nullptr, faces, faces_z_ref, face_index_map, weight_map, depth_map, rgb_map, alpha_map,
-                                     grad_rgb_map, grad_alpha_map, grad_depth_map, grad_faces, grad_textures, B, F, S, ts,
-                                     eps, flags, visible_faces, workspace, workspace_bytes, stream);
-}
-
-NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *faces, const float *faces_z_ref,
-                                     const int32_t *face_index_map, const float *weight_map, const float *depth_map,
-                                     const float *rgb_map, const float *alpha_map, const float *grad_rgb_map,
-                                     const float *grad_alpha_map, const float *grad_depth_map, float *grad_faces,
-                                     float *grad_textures, int32_t B, int32_t F, int32_t S, int32_t ts, double eps,
-                                     int32_t flags, const uint8_t *visible_faces, void *workspace, size_t workspace_bytes,
-                                     void *stream)
-{
-    if (!faces || !face_index_map || !grad_faces) return NR_E_NULL;
-    if (int e = check_sizes(B, F, S)) return e;
-    FaceLight fl;  // per-face light colours: only the texture gather sees them (the geometry gradients do not)
-    if (int e = face_light_args(grad_rgb_map && grad_textures ? lit : nullptr, F, true, fl)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    const bool use_rgb = grad_rgb_map != nullptr, use_alpha = grad_alpha_map != nullptr, use_depth = grad_depth_map != nullptr;
-    const int *vis_list = nullptr, *vis_count = nullptr;
-    // K6's last step (rounding the double sums into grad_faces, zeros for the unlisted faces) rides in the K7 / K8 gather's
-    // launch when there is one that walks faces (texture_size <= 13)
-    const bool fold = use_rgb && grad_textures && ts >= 2 && ts <= 13;
-    const double *k6_scratch = nullptr;
-    const int *k6_slot_of = nullptr;
-    int tex_zeroed = 0;
-    // Small launches (up to 96 k faces in the call: 16 views of the 4928-face teapot) take the order
-    //   compaction | line setup + gather + zeros of grad_textures in ONE grid | band kernel | the faces the gather left
-    //   out + K6's sums onto grad_faces (one launch)
-    // where the line setup and the gather -- two chains of dependent round trips that need nothing of each other -- run side
-    // by side (8 views: backward 82 -> 72 us, 16: 111 -> 104; 32: 156 -> 152, not taken).  Larger ones keep
-    //   compaction | line setup | band kernel with the fill on the side | gather with K6's finish:
-    // there both launches are bound by how many workgroups the chip holds, a shared grid takes the sum of their times (64
-    // views: 254.7 us either way), and the fill inside the band kernel and the finish inside the gather are worth more
-    // (config 4: 0.80 vs 0.87 ms, 1024 views of 32 x 32: 0.72 vs 0.85, config 5 with its 4 GB of zeros: 1.57 vs 1.97).
-    if (fold && (size_t)B * F <= k6::SHARED_LAUNCH_MAX_FACES && !(flags & NR_FLAG_SERIAL_BACKWARD)) {
-        GatherCall gc = {faces, faces_z_ref, weight_map, depth_map, grad_rgb_map, use_depth ? grad_depth_map : nullptr,
-                         face_index_map, grad_textures, grad_faces, B, F, S, ts, flags, eps, &fl, false, 0};
-        const SetupHook hook = {&launch_setup_and_gather, &gc};
-        if (int rc = run_backward_pixel_map(faces, face_index_map, rgb_map, use_alpha ? alpha_map : nullptr, grad_rgb_map,
-                                            grad_alpha_map, grad_faces, B, F, S, eps, 1, use_alpha, flags, visible_faces, workspace,
-                                            workspace_bytes, st, &vis_list, &vis_count, &k6_scratch, &k6_slot_of, nullptr, 0,
-                                            nullptr, &hook))
-            return rc;
-        if (gc.called) {
-            int dd = 0, finalized = 0;  // (K6's sums go onto grad_faces in k_backward_big's launch when there is one)
-            if (int rc = run_backward_textures(face_index_map, nullptr, nullptr, faces, faces_z_ref, weight_map, depth_map,
-                                               grad_rgb_map, grad_textures, B, F, S, ts, eps, flags, vis_list, vis_count, st,
-                                               use_depth ? grad_depth_map : nullptr, grad_faces, &dd, k6_scratch, k6_slot_of,
-                                               &finalized, fl, false, 2))
-                return rc;
-            if (use_depth && !gc.depth_done)
-                if (int rc = run_backward_depth_map(faces, depth_map, face_index_map, nullptr, weight_map, grad_depth_map,
-                                                    grad_faces, B, F, S, vis_list, vis_count, st, visible_faces))
-                    return rc;
-            if (k6_scratch && !finalized) run_bpm_finalize(k6_scratch, k6_slot_of, grad_faces, B, F, st, true);
+    if (plan.kernel == K6_KERNEL_GLOBAL) {
+        auto global = [&](auto r, auto a) {
+            hipLaunchKernelGGL((k_bpm_global<decltype(r)::value, decltype(a)::value>), dim3((unsigned)(c.B * c.F)), dim3(WAVE), 0,
+                               c.st, c.faces, c.face_index_map, c.rgb_map, c.alpha_map, c.grad_rgb_map, c.grad_alpha_map,
+                               c.grad_faces, c.F, c.S, c.eps);
             return launch_status();
-        }
-        // the band pipeline did not run (global-memory kernel: grad_faces complete, no lists, nothing deferred): the gathers
-        // below, as they are
-    } else if (use_rgb || use_alpha) {
-        if (int rc = run_backward_pixel_map(faces, face_index_map, use_rgb ? rgb_map : nullptr,
-                                            use_alpha ? alpha_map : nullptr, grad_rgb_map, grad_alpha_map, grad_faces,
-                                            B, F, S, eps, use_rgb, use_alpha, flags, visible_faces, workspace,
-                                            workspace_bytes, st, &vis_list, &vis_count, fold ? &k6_scratch : nullptr,
-                                            fold ? &k6_slot_of : nullptr,
-                                            // the zero fill of grad_textures inside the band kernel (with per-face light
-                                            // colours: the cubes of the original faces)
-                                            fold ? grad_textures : nullptr,
-                                            (size_t)B * (fl.light ? fl.tex_faces : F) * ts * ts * ts * 3 * sizeof(float),
-                                            &tex_zeroed))
-            return rc;
-    } else {
-        const int e = fill_bytes(grad_faces, 0, (size_t)B * F * 9 * sizeof(float), st);  // :851
-        if (e != 0) return e;
-        // depth only: no K6 and therefore no lists -- built from the forward's flags when there are any (one launch), so that
-        // the K8 gather visits the ~1/6 of the faces that own a pixel
-        const ListsLayout L = lists_layout(B, F);
-        const int n_chunks = (F + VIS_CHUNK - 1) / VIS_CHUNK;
-        if (use_depth && visible_faces && workspace && workspace_bytes >= L.total && n_chunks <= SMALL_CHUNKS) {
-            unsigned char *ws = (unsigned char *)workspace;
-            int *list = (int *)(ws + L.list_off), *count = (int *)(ws + L.count_off);
-            hipLaunchKernelGGL(k_list_visible, dim3((unsigned)n_chunks, (unsigned)B), dim3(VIS_CHUNK), 0, st, visible_faces,
-                               list, count, F, n_chunks);
-            vis_list = list;
-            vis_count = count;
-        }
+        };
+        using T = std::true_type;
+        using N = std::false_type;
+        return (c.rgb && c.alpha) ? global(T(), T()) : (c.rgb ? global(T(), N()) : global(N(), T()));
     }
-    int depth_done = 0;
-    if (use_rgb && grad_textures) {
-        // when both gradients are wanted, K8 rides along in the K7 gather (one walk of each face's screen box)
-        int finalized = 0;
-        if (int rc = run_backward_textures(face_index_map, nullptr, nullptr, faces, faces_z_ref, weight_map, depth_map,
-                                           grad_rgb_map, grad_textures, B, F, S, ts, eps, flags, vis_list, vis_count, st,
-                                           use_depth ? grad_depth_map : nullptr, grad_faces, &depth_done, k6_scratch,
-                                           k6_slot_of, &finalized, fl, tex_zeroed != 0))
-            return rc;
-        if (k6_scratch && !finalized) run_bpm_finalize(k6_scratch, k6_slot_of, grad_faces, B, F, st);  // (not expected)
-    }
-    if (use_depth && !depth_done) {
-        if (int rc = run_backward_depth_map(faces, depth_map, face_index_map, nullptr, weight_map, grad_depth_map,
-                                            grad_faces, B, F, S, vis_list, vis_count, st, visible_faces))
-            return rc;
-    }
-    return 0;
+    auto band_fast = [&](auto overflow_only, void *zp, size_t zb) {
+        return with_k6_types(c.rgb, c.alpha, plan.mode, [&](auto r, auto a, auto m) {
+            return launch_fast<decltype(r)::value, decltype(a)::value, decltype(m)::value, decltype(overflow_only)::value>(
+                plan, c, l, ls, zp, zb);
+        });
+    };
+    auto band_row = [&]() {
+        return with_k6_types(c.rgb, c.alpha, plan.mode, [&](auto r, auto a, auto m) {
+            return launch_row<decltype(r)::value, decltype(a)::value, decltype(m)::value>(plan, c, l, ls, fill, fill_bytes);
+        });
+    };
+    NR_BAND_TIMER_START(c.st, plan.kernel);
+    int rc = plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill, fill_bytes);
+    NR_BAND_TIMER_STOP(c.st);
+    if (rc == 0 && plan.overflow_pass) rc = band_fast(std::true_type(), nullptr, 0);
+    return rc ? rc : launch_status();
 }
 
+// add: on top of what grad_faces holds, listed faces only (see the kernel)
+void nr::k6_finalize(const BackwardCall &c, const K6Lists &l, bool add)
+{
+    const int n = c.B * c.F;
+    hipLaunchKernelGGL(k_bpm_finalize, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c.st, l.scratch, l.slot_of, c.grad_faces,
+                       c.F, n, add ? 1 : 0);
+}
+
+bool nr::k6_lists_fit(int B, int F, size_t workspace_bytes)
+{
+    return workspace_bytes >= lists_layout(B, F).total && (F + VIS_CHUNK - 1) / VIS_CHUNK <= SMALL_CHUNKS;
+}
+
+// the lists alone, from the forward's flags (a depth-only fused backward: no K6)
+K6Lists nr::k6_list_visible(const BackwardCall &c)
+{
+    const ListsLayout L = lists_layout(c.B, c.F);
+    const int n_chunks = (c.F + VIS_CHUNK - 1) / VIS_CHUNK;
+    unsigned char *ws = (unsigned char *)c.workspace;
+    int *list = (int *)(ws + L.list_off), *count = (int *)(ws + L.count_off);
+    hipLaunchKernelGGL(k_list_visible, dim3((unsigned)n_chunks, (unsigned)c.B), dim3(VIS_CHUNK), 0, c.st, c.visible_faces, list,
+                       count, c.F, n_chunks);
+    return {list, count, nullptr, nullptr};
+}

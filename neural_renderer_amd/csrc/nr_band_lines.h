@@ -17,8 +17,8 @@ struct __attribute__((aligned(16))) BandLine {
     int fn;
 };
 
-// (everything k_line_setup takes, as one block: the fused backward launches the body from a kernel of its own, beside the
-// gather -- nr_backward_gather.hip, k_setup_gather)
+// (everything k_line_setup takes, as one block: when the backward's plan says so the body runs inside the gather's launch --
+// nr_backward_gather.hip, k_setup_gather)
 struct LineSetupArgs {
     const float *faces;
     const int32_t *fi_map;
@@ -33,20 +33,6 @@ struct LineSetupArgs {
     float k2s;
     unsigned grid_x, grid_y;  // the launch: ceil(F / LS_FACES) x B workgroups of 256 threads, lds_bytes of dynamic LDS
     size_t lds_bytes;
-};
-
-// k_line_setup as a launch of its own (nr_backward_pixel_map.hip)
-int run_line_setup(const LineSetupArgs &a, hipStream_t st);
-
-// How the fused backward takes over the line-setup launch of run_backward_pixel_map: called where k_line_setup would be
-// launched -- the visible-face lists exist in stream order -- with the launch's arguments (NULL when the band kernel derives
-// its lines itself: NR_FLAG_K6_SCAN, shapes outside k_line_setup's).  With a hook the compaction zeroes grad_faces of EVERY
-// face (the gather adds K8's sums before K6's arrive: run_bpm_finalize(add = true) afterwards) and nothing is filled on the
-// side (zero_ptr is ignored).
-struct SetupHook {
-    int (*launch)(void *ctx, const LineSetupArgs *ls, const int *vis_list, const int *vis_count, const int *slot_of,
-                  hipStream_t st);  // slot_of: face -> list position or -1, [B][F]
-    void *ctx;
 };
 
 namespace {

@@ -281,46 +281,109 @@ inline int launch_status()
 
 
 // --------------------------------------------------------------------------------------------------
-// stage runners shared between the per-stage ABI entry points and the fused nr_backward_rasterize.
-// vis_list / vis_count (optional): per-image sorted lists of the faces that own at least one pixel, as built
-// by the K6 band pipeline ([B][F] ints, [B] counts); when given, the gather kernels visit only those faces.
-struct SetupHook;      // nr_band_lines.h
+// The backward of one ABI call (nr_backward.hip): K6 (grad_faces from the rgb / alpha maps), K7 (grad_textures) and K8
+// (grad_faces from the depth map).  The entry point describes the call (BackwardCall); plan_backward checks it and decides
+// every launch before the first one goes out (BackwardPlan); run_backward launches the plan's steps in order.  The steps are
+// the host sides of K6 (nr_backward_pixel_map.hip) and of the gathers (nr_backward_gather.hip).
+enum { STAGE_K6 = 1, STAGE_K7 = 2, STAGE_K8 = 4, STAGE_ALL = 7 };  // what the entry point computes (all: the fused backward)
+
+struct BackwardCall {
+    int stages;                        // STAGE_*
+    bool rgb, alpha;                   // K6 takes these maps
+    const float *faces, *faces_z_ref;
+    const int32_t *face_index_map;
+    const float *weight_map, *depth_map, *rgb_map, *alpha_map, *grad_rgb_map, *grad_alpha_map, *grad_depth_map;
+    const float *sampling_weight_map;  // nr_backward_textures: the forward's taps (or NULL)
+    const int32_t *sampling_index_map;
+    const float *face_inv_map;         // nr_backward_depth_map: the reference's per-pixel residual (or NULL)
+    float *grad_faces, *grad_textures;
+    int B, F, S, ts;
+    double eps;
+    int flags;
+    const unsigned char *visible_faces;  // the forward's per-face flags (or NULL)
+    void *workspace;
+    size_t workspace_bytes;
+    FaceLight lit;  // lit.light given: grad_textures is [B, lit.tex_faces, ts^3, 3], lit.grad_light receives [B, F, 3]
+    hipStream_t st;
+};
+
+// Which band kernel K6 takes, and how it is shaped: decided from the call's shape alone (plan_k6, nr_backward_pixel_map.hip).
+struct BandShape {
+    int threads;     // 256 | 512
+    int w_max;       // widest band (lines)
+    size_t budget;   // LDS per workgroup
+};
+enum K6Kernel { K6_KERNEL_FAST = 0, K6_KERNEL_ROW = 1, K6_KERNEL_GLOBAL = 2 };  // (0 / 1: nr_profile_band_kernel_which)
+struct K6Plan {
+    int kernel;           // K6Kernel
+    int mode;             // K6_FAST | K6_EXACT_POW2 | K6_EXACT
+    BandShape shape;      // k_bpm_fast: workgroup shape,
+    int W_fast;           // ... band width (lines; 0: no LDS band fits -- the global kernel),
+    size_t fast_lds;      // ... LDS bytes,
+    int win_lines, qcap;  // ... line records per window and piece-queue capacity
+    int W_row;            // k_bpm_row: band width (0: not taken)
+    size_t row_lds;       // ... LDS bytes
+    int W, n_bands;       // the band tables: lines per band, bands per image
+    bool use_records;     // line records from k_line_setup (false: every image takes k_bpm_fast's face scan)
+    bool overflow_pass;   // k_bpm_fast's overflow-only launch follows k_bpm_row
+    size_t fill_max;      // the largest zero fill (bytes) that the band kernel takes along
+};
+K6Plan plan_k6(int B, int F, int S, bool rgb, double eps, int flags);
+
+enum FaceZeros { FACE_ZEROS_NONE, FACE_ZEROS_UNLISTED, FACE_ZEROS_ALL };     // the compaction's stores of grad_faces
+enum TexZeros { TEX_ZEROS_NONE, TEX_ZEROS_BAND, TEX_ZEROS_SETUP, TEX_ZEROS_FILL };  // who zeroes grad_textures
+enum K6Finish { FINISH_NONE, FINISH_KERNEL, FINISH_GATHER, FINISH_BIG, FINISH_ADD };  // who rounds K6's sums into grad_faces
+enum Gather { GATHER_NONE, GATHER_FACE, GATHER_ATOMIC };                   // K7's gather
+
+struct BackwardPlan {
+    bool k6;               // K6 runs, as k6p says
+    K6Plan k6p;
+    bool bands;            // ... through the band pipeline (not k_bpm_global): K6's lists, scratch and face -> position table
+    int face_zeros;        // FaceZeros
+    bool gather_first;     // small calls: the K7 gather goes out between the compaction and the band kernel
+    bool setup_alone;      // k_line_setup as a launch of its own (behind the gather when gather_first)
+    bool setup_in_gather;  // k_line_setup's workgroups inside the gather's launch (k_setup_gather)
+    int tex_zeros;         // TexZeros (TEX_ZEROS_SETUP: the unlisted faces' cubes, in k_setup_gather)
+    size_t tex_bytes;      // grad_textures' bytes (the original cubes with per-face light colours)
+    bool light_fill;       // grad_light zero-filled in front of the gather
+    int gather;            // Gather
+    bool listed;           // the face gather and k_backward_big walk K6's lists
+    bool static_taps;      // texture_size 2 with static taps (TS2 kernels)
+    int lanes;             // face gather: lanes per face (16 / 64 / 256)
+    size_t gather_lds;     // ... its dynamic LDS
+    bool depth_in_gather;  // K8 rides in the K7 gather (and its k_backward_big)
+    bool big;              // k_backward_big behind the face gather (texture_size <= 8)
+    int finish;            // K6Finish
+    bool depth;            // K8 as launches of its own (k_backward_depth_face + k_backward_big)
+    bool fill_faces;       // depth-only fused call: grad_faces zero-filled
+    bool depth_lists;      // ... and K8's lists from the forward's flags (k_list_visible)
+};
+int plan_backward(const BackwardCall &c, BackwardPlan &p);  // 0 or an NR_E_* code; launches nothing
+int run_backward(const BackwardCall &c);  // plan_backward, then the plan's steps in order
+
+// K6's buffers in the workspace: per image the sorted list of the faces that own a pixel ([B][F] ints, [B] counts), face ->
+// list position or -1 ([B][F]), and the six double sums of each list position
+struct K6Lists {
+    const int *vis_list, *vis_count, *slot_of;
+    double *scratch;
+};
 struct LineSetupArgs;  // nr_band_lines.h
-int run_backward_pixel_map(const float *faces, const int32_t *face_index_map, const float *rgb_map,
-                           const float *alpha_map, const float *grad_rgb_map, const float *grad_alpha_map,
-                           float *grad_faces, int B, int F, int S, double eps, int return_rgb, int return_alpha,
-                           int flags, const unsigned char *visible_faces, void *workspace, size_t workspace_bytes,
-                           hipStream_t st, const int **vis_list_out, const int **vis_count_out,
-                           const double **defer_scratch = nullptr, const int **defer_slot_of = nullptr,
-                           void *zero_ptr = nullptr, size_t zero_bytes = 0, int *zeroed = nullptr,
-                           const SetupHook *hook = nullptr);
-// zero_ptr / zero_bytes: a buffer the caller wants zero-filled before its next kernel (the fused backward's grad_textures);
-// *zeroed = 1 when the band kernel did it on the side (default kernel, 16-byte aligned, <= 256 MB), else the caller fills
-// defer_scratch / defer_slot_of (both or none): the caller will finish K6 itself for the LISTED faces -- rounding the double
-// sums of their list positions into grad_faces (run_backward_textures does, or run_bpm_finalize for all faces) -- so
-// k_bpm_finalize is not launched and the compaction kernel stores the zeros of the unlisted faces; NULLs come back when
-// the band pipeline did not run (global-memory fallback: grad_faces are complete).
-void run_bpm_finalize(const double *scratch, const int *slot_of, float *grad_faces, int B, int F, hipStream_t st,
-                      bool add = false);  // add: on top of what grad_faces holds, listed faces only (see the kernel)
-int run_backward_textures(const int32_t *face_index_map, const float *sampling_weight_map,
-                          const int32_t *sampling_index_map, const float *faces, const float *faces_z_ref,
-                          const float *weight_map,
-                          const float *depth_map, const float *grad_rgb_map, float *grad_textures, int B, int F, int S,
-                          int ts, double eps, int flags, const int *vis_list, const int *vis_count, hipStream_t st,
-                          const float *g_depth_fused, float *grad_faces_fused, int *depth_done,
-                          const double *k6_scratch, const int *slot_of, int *k6_finalized, const FaceLight &lit = FaceLight(),
-                          bool prefilled = false, int phase = 0, const struct LineSetupArgs *ls = nullptr,
-                          const int *zero_slot_of = nullptr);
-// prefilled: grad_textures is already zero (no fill launch).  phase: 0 everything; 1 the fills and the gathers; 2 what they leave
-// out (k_backward_big) -- the fused backward runs K6's band kernel between the two.  ls: K6's line-setup launch, to go into
-// the gather's launch (phase 0 / 1; launched here in any case); zero_slot_of: K6's face -> list position table, with which
-// that launch also stores grad_textures' zeros (the cubes of unlisted faces) instead of a fill in front
-// lit.light given: grad_textures is [B, lit.tex_faces, ts^3, 3] (zero-filled here; a face stores only when it owns a
-// pixel -- of a face and its reversed copy at most one does), lit.grad_light receives [B, F, 3]
+
+// K6's steps (nr_backward_pixel_map.hip)
+int k6_compact(const BackwardCall &c, const K6Plan &p, int face_zeros, K6Lists &out);  // [k_mark_visible] + compaction
+LineSetupArgs k6_line_setup_args(const BackwardCall &c, const K6Plan &p);
+int run_line_setup(const LineSetupArgs &a, hipStream_t st);
+int k6_band(const BackwardCall &c, const K6Plan &p, const K6Lists &l, const LineSetupArgs &ls, void *fill,
+            size_t fill_bytes);  // k_bpm_global, or band kernel + overflow
+void k6_finalize(const BackwardCall &c, const K6Lists &l, bool add);
+bool k6_lists_fit(int B, int F, size_t workspace_bytes);  // k_list_visible's lists fit the workspace and one launch
+K6Lists k6_list_visible(const BackwardCall &c);
+// the gathers' steps (nr_backward_gather.hip)
+int gather_faces(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l, const LineSetupArgs *ls);
+void gather_big(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l);
+void gather_atomic(const BackwardCall &c);
+void gather_depth(const BackwardCall &c, const K6Lists &l);
+
 int face_light_args(const nr_face_light *lit, int F, bool backward, FaceLight &out);  // nr_forward.hip
-int run_backward_depth_map(const float *faces, const float *depth_map, const int32_t *face_index_map,
-                           const float *face_inv_map, const float *weight_map, const float *grad_depth_map,
-                           float *grad_faces, int B, int F, int S, const int *vis_list, const int *vis_count,
-                           hipStream_t st, const unsigned char *visible);  // visible: the forward's per-face flags or NULL
 
 }  // namespace nr

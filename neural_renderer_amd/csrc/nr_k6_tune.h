@@ -47,7 +47,7 @@
 #endif
 
 #ifndef NR_SHARED_LAUNCH_MAX_FACES  // fused backward: calls of up to this many faces (batch x faces) put the line setup and the
-#define NR_SHARED_LAUNCH_MAX_FACES 98304  // K7 / K8 gather into one launch (nr_backward_rasterize_lit; measured: LAB-NOTEBOOK, late round 4)
+#define NR_SHARED_LAUNCH_MAX_FACES 98304  // K7 / K8 gather into one launch (plan_backward; measured: LAB-NOTEBOOK, late round 4)
 #endif
 
 namespace nr {

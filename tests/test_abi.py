@@ -121,6 +121,11 @@ def test_argument_errors_do_not_need_a_gpu(lib_path):
     # NULL pointers / bad sizes are rejected before any launch
     assert lib.nr_forward_face_index_map(None, None, None, None, None, None, 1, 1, 8, 0.1, 100.0, None, 0, None) == -1
     assert lib.nr_backward_depth_map(None, None, None, None, None, None, None, 1, 1, 8, None) == -1
+    # the backward plans a call whole before its first launch: a fused call without its workspace, a texture gradient
+    # given one of the two sampling maps
+    assert lib.nr_backward_rasterize(1, None, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 64, 64, 2, 1e-3, 0, None, None, 0, None) == -3
+    assert lib.nr_backward_textures(1, 1, None, 1, None, 1, 1, 1, 1, 1, 4, 8, 2, 1e-3, 0, None) == -4
+    assert lib.nr_backward_textures(1, None, 1, 1, None, 1, 1, 1, 1, 1, 4, 8, 2, 1e-3, 0, None) == -4
     assert lib.nr_forward_texture_sampling(None, None, None, 1, None, None, None, None, None, None, 0, None,
                                            1, 1, 8, 2, 1e-3, 0, None) == -4
     # near <= 0 is accepted like in the reference (rasterize.py:331): the call gets as far as the workspace check
