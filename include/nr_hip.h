@@ -20,6 +20,8 @@
  *   nr_adam_update                <- AdamRule.update_core_gpu                                  optimizers.py:17-34
  *   nr_load_textures              <- load_textures kernel of load_obj(load_texture=True)      load_obj.py:87-144
  *   nr_create_texture_image       <- create_texture_image kernels of save_obj(textures=...)   save_obj.py:32-146
+ *   nr_bake_uv_textures[_backward], nr_uv_texture_map: the bake of nr_load_textures as a differentiable step on learnable
+ *                                   images (UVTextures); not in the reference
  *   nr_frontend_forward/_backward <- fill_back + lighting + look_at/look + perspective + vertices_to_faces
  *                                    of Renderer.render*                                  renderer.py:35-107
  *   nr_frontend_forward_projection / _backward_projection: the same front-end with a calibrated camera (K, R, t,
@@ -59,7 +61,8 @@ extern "C" {
 #endif
 
 #define NR_VERSION 600 /* 0.6.0 (additions without a version step: NR_CAMERA_PROJECTION, nr_projection and
-                          *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes);
+                          *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes;
+                          *        nr_bake_uv_textures[_backward], nr_uv_texture_map[_workspace_bytes]);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -447,6 +450,51 @@ int nr_frontend_backward_projection(const float *vertices, const int32_t *faces_
  */
 int nr_load_textures(const float *image, const float *faces_uv, const int32_t *is_update, float *textures,
                      int32_t num_faces, int32_t texture_size, int32_t image_height, int32_t image_width, void *stream);
+
+/*
+ * Learnable UV texture images (not in the reference; DESIGN K10, neural_renderer_amd/uv_textures.py): the bake of
+ * nr_load_textures as a differentiable step, for every image of a mesh at once.
+ *
+ * A UV layout of a mesh with F faces: faces_uv [F,3,2] (wrapped as load_obj does), face_image [F] (which of the M images a
+ * face samples; any value outside [0, M) = none), base [F,ts,ts,ts,3] (the texels of faces without an image) and the M image
+ * sizes.  The images are packed one after another, each [H_m,W_m,3] float32 with its TOP row first (file orientation; the
+ * kernels mirror the row index instead of flipping the image): images [Bi,P,3] with P = sum H_m*W_m, and image_table
+ * [M,3] int32 = (first pixel of image m in the packing, H_m, W_m) on the device.  The caller keeps the table consistent
+ * with P; the library reads it on the device only.
+ *
+ * nr_bake_uv_textures: textures [Bi,F,ts,ts,ts,3].  A face with image m takes, at every texel other than (0,0,0), the
+ * value nr_load_textures computes from image m flipped vertically, bit for bit (its clamped reads, yi1 = (int)(pos_y + 1)
+ * and double literals included).  DEPARTURE from nr_load_textures: texel (0,0,0), NaN there (0/0), is the same bilinear
+ * lookup at the uv centroid, with barycentric weights 1/3 in float.  Faces without an image copy `base`.  One launch;
+ * no host synchronisation; capturable in a graph.
+ */
+int nr_bake_uv_textures(const float *images, const int32_t *image_table, const float *faces_uv, const int32_t *face_image,
+                        const float *base, float *textures, int32_t batch_size, int32_t num_faces, int32_t texture_size,
+                        int32_t num_images, int32_t num_pixels, void *stream);
+
+/*
+ * The inverse of the bake, built once per layout: every bilinear read of every texel of a face with an image, grouped by
+ * the packed pixel it reads (CSR).  row_ptr [P+1]: the entries of pixel p are [row_ptr[p], row_ptr[p+1]), ordered by
+ * (face, texel, corner); entry_texel / entry_weight [4*F*ts^3]: the texel f*ts^3 + t and the weight of that read (the
+ * weights nr_bake_uv_textures uses).  Entries from row_ptr[P] on are unused.  Needs 4*F*ts^3 <= 2^31-1, P < 2^31-1 and
+ * the workspace of nr_uv_texture_map_workspace_bytes (a stable device radix sort; the query needs a visible device and
+ * returns 0 without one or for sizes out of range).  Not on the per-step path: it allocates nothing, but it is not
+ * meant for graph capture.
+ */
+size_t nr_uv_texture_map_workspace_bytes(int32_t num_faces, int32_t texture_size, int32_t num_images, int32_t num_pixels);
+int nr_uv_texture_map(const int32_t *image_table, const float *faces_uv, const int32_t *face_image, int32_t *row_ptr,
+                      int32_t *entry_texel, float *entry_weight, int32_t num_faces, int32_t texture_size, int32_t num_images,
+                      int32_t num_pixels, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Adjoint of nr_bake_uv_textures with respect to the images: grad_images [Bi,P,3] (every pixel written, 0 where no texel
+ * reads it) from grad_textures [Bi,F,ts,ts,ts,3] and the map of nr_uv_texture_map.  One thread per (b, pixel) walks the
+ * pixel's entries in map order and sums grad * weight in double, rounded once: no atomics, the same bits on every call, and
+ * a batch equals its elements one at a time.  No gradient to faces_uv or base.  No host synchronisation; capturable.
+ */
+int nr_bake_uv_textures_backward(const float *grad_textures, const int32_t *row_ptr, const int32_t *entry_texel,
+                                 const float *entry_weight, float *grad_images, int32_t batch_size, int32_t num_faces,
+                                 int32_t texture_size, int32_t num_pixels, void *stream);
 
 /*
  * Texture atlas of save_obj(..., textures) (K11, reference save_obj.py:10-146): image [tile_height*tso, tile_width*tso, 3]

@@ -34,12 +34,10 @@ def _read_image(path):
     return np.asarray(Image.open(path).convert('RGB'), dtype=np.float32) / np.float32(255.)
 
 
-def load_textures(filename_obj, filename_mtl, texture_size, device='cuda'):
-    """Texture cubes [Nf,ts,ts,ts,3] from the mesh's uv coordinates, materials and texture images -- load_obj.py:25-144."""
-    import torch
-
-    from . import _lib
-
+def parse_textures(filename_obj, filename_mtl, texture_size):
+    """The host half of load_textures (load_obj.py:25-77): -> (faces_uv [Nf,3,2] float32 with values above 1 wrapped,
+    material name per face [Nf], Kd colours by material, texture file names by material, textures [Nf,ts,ts,ts,3] filled
+    with the Kd colour or 0.5).  Shared by load_textures and UVLayout.from_obj."""
     # uv coordinates (`vt`), uv indices of the fan-triangulated faces and the material in force at each face (:26-62)
     uv = []
     corner_ids = []
@@ -73,6 +71,22 @@ def load_textures(filename_obj, filename_mtl, texture_size, device='cuda'):
     textures = np.zeros((num_faces, texture_size, texture_size, texture_size, 3), 'float32') + 0.5   # :69
     for name, color in colors.items():                             # :73-77
         textures[material_names == name] = color[None, None, None, None, :]
+    return faces_uv, material_names, colors, texture_filenames, textures
+
+
+def read_texture_image(filename_obj, filename_texture):
+    """A material's texture image, [H,W,3] float32 in [0,1], top row first (as in the file)."""
+    return _read_image(os.path.join(os.path.dirname(filename_obj), filename_texture))
+
+
+def load_textures(filename_obj, filename_mtl, texture_size, device='cuda'):
+    """Texture cubes [Nf,ts,ts,ts,3] from the mesh's uv coordinates, materials and texture images -- load_obj.py:25-144."""
+    import torch
+
+    from . import _lib
+
+    faces_uv, material_names, _, texture_filenames, textures = parse_textures(filename_obj, filename_mtl, texture_size)
+    num_faces = faces_uv.shape[0]
     if len(texture_filenames) == 0:
         return textures
 
@@ -83,7 +97,7 @@ def load_textures(filename_obj, filename_mtl, texture_size, device='cuda'):
         faces_uv_d = torch.from_numpy(np.ascontiguousarray(faces_uv)).to(dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         for name, filename_texture in texture_filenames.items():   # :80-143
-            image = _read_image(os.path.join(os.path.dirname(filename_obj), filename_texture))
+            image = read_texture_image(filename_obj, filename_texture)
             image_d = torch.from_numpy(np.ascontiguousarray(image[::-1])).to(dev)    # vertical flip, :85
             is_update = torch.from_numpy((material_names == name).astype('int32')).to(dev)
             _lib.check(lib.nr_load_textures(image_d.data_ptr(), faces_uv_d.data_ptr(), is_update.data_ptr(),
