@@ -18,6 +18,11 @@
 // i.e. ~1.1 ms of host launch latency around a 0.9 ms rasterizer step at the headline size (scripts/renderer_e2e.py),
 // plus three full passes over the [B, 2F, ts^3, 3] texture tensor (concat, multiply, and their backward).
 //
+// Host side: the six entry points (forward / backward, each with lit textures, with light colours `_light`, and for the
+// projection camera `_projection`) only fill one FrontendCall.  check_call applies every argument check and builds the
+// kernels' parameters; launch_forward / launch_backward then launch the PROJ instantiation the call names, and the
+// backward's zero fills and its camera kernel (k_camera_backward or k_projection_backward).
+//
 // Work decomposition: LANES = 8 consecutive lanes per (image, face).  Every lane recomputes the (cheap) camera basis and
 // the face's light colour; the lanes stride over the ts^3 texels, lanes 0/1 write the front/back copies of the face.
 //
@@ -619,66 +624,155 @@ __global__ void k_projection_backward(const double *__restrict__ cam_acc, float 
     }
 }
 
-int fill_params(FrontendParams &P, const nr_camera *cam, const nr_light *light, int idx_per_batch, int eye_per_batch,
-                int fill_back, bool with_textures)
+// ---- host: each entry point fills one FrontendCall; check_call and the two runners serve all six ----
+
+// One call of any entry point.  proj: the NR_CAMERA_PROJECTION model (`projection`), else look_at / look (`camera`, `eye`).
+// A forward call sets the forward outputs, a backward call the gradients; the rest stays NULL.
+struct FrontendCall {
+    bool proj;
+    const nr_camera *camera;
+    const nr_projection *projection;
+    const float *vertices, *textures, *eye;
+    const int32_t *faces_idx;
+    float *faces_out, *textures_out, *light_out;
+    const float *grad_faces, *grad_textures_out, *grad_light;
+    float *grad_vertices, *grad_textures, *grad_eye, *grad_K, *grad_R, *grad_t;
+    int32_t B, Nv, Nf, ts, idx_per_batch, eye_per_batch, fill_back;
+    const nr_light *light;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t st;
+};
+
+// the per-image camera sums of the backward: 12 doubles for eye, PROJ_ACC for the projection camera
+size_t cam_acc_bytes(int32_t B, bool proj) { return B < 1 ? 0 : (size_t)B * (proj ? PROJ_ACC : 12) * sizeof(double); }
+
+bool wants_camera(const FrontendCall &c) { return c.grad_eye || c.grad_K || c.grad_R || c.grad_t; }
+
+// Every argument check of a call, in the order the entry points apply them, then the kernels' parameters
+int check_call(const FrontendCall &c, bool backward, FrontendParams &P, ProjParams &Q)
 {
-    if (!cam) return NR_E_NULL;
-    if (cam->mode != NR_CAMERA_LOOK_AT && cam->mode != NR_CAMERA_LOOK) return NR_E_MODE;
-    if (with_textures && !light) return NR_E_NULL;
-    P.camera_mode = cam->mode;
-    P.perspective = cam->perspective != 0;
-    P.eye_per_batch = eye_per_batch != 0;
-    P.idx_per_batch = idx_per_batch != 0;
-    P.fill_back = fill_back != 0;
-    for (int k = 0; k < 3; k++) {
-        P.target[k] = cam->target[k];
-        P.up[k] = cam->up[k];
+    if (!c.vertices || !c.faces_idx || (!c.proj && !c.eye)) return NR_E_NULL;
+    const bool want_cam = wants_camera(c);
+    if (backward) {
+        if (!c.grad_faces) return NR_E_NULL;
+        if (!c.grad_vertices && !c.grad_textures && !want_cam) return NR_E_MODE;
+        if (want_cam && !c.grad_vertices) return NR_E_MODE;  // the camera sums are produced by the vertex pass
+        if (c.grad_textures && !(c.textures && c.grad_textures_out)) return NR_E_MODE;
+        if (c.grad_textures_out && !c.textures) return NR_E_MODE;
+        if (c.grad_light && c.textures) return NR_E_MODE;
+        if (c.grad_light && !c.light) return NR_E_NULL;
+    } else {
+        if (!c.faces_out) return NR_E_NULL;
+        if ((c.textures == nullptr) != (c.textures_out == nullptr)) return NR_E_MODE;
+        if (c.textures_out && c.light_out) return NR_E_MODE;
     }
-    P.width = cam->width;
-    P.ia = P.id = 0.0f;
-    P.has_directional = 0;
-    for (int k = 0; k < 3; k++) P.ca[k] = P.cd[k] = P.ldir[k] = 0.0f;
-    if (light) {
-        P.ia = light->intensity_ambient;
-        P.id = light->intensity_directional;
-        P.has_directional = light->intensity_directional != 0.0f;
+    if (c.B < 1 || c.Nv < 1 || c.Nf < 1 || c.B > 65535) return NR_E_SIZE;
+    if (c.textures && c.ts < 1) return NR_E_SIZE;
+    if ((size_t)c.B * (size_t)c.Nf > 0x7fffffffull / 18) return NR_E_SIZE;
+    P = {};
+    Q = {};
+    if (c.proj) {
+        const nr_projection *p = c.projection;
+        if (!p || !p->K || !p->R || !p->t) return NR_E_NULL;
+        if (!(p->orig_size > 0.0f && p->orig_size < __builtin_inff())) return NR_E_SIZE;
+        P.camera_mode = NR_CAMERA_PROJECTION;  // (no look_at / perspective parameters: they stay 0)
+        Q = {p->K, p->R, p->t, p->dist_coeffs, p->K_per_batch != 0, p->R_per_batch != 0, p->t_per_batch != 0,
+             p->dist_per_batch != 0, p->orig_size};
+    } else {
+        const nr_camera *cam = c.camera;
+        if (!cam) return NR_E_NULL;
+        if (cam->mode != NR_CAMERA_LOOK_AT && cam->mode != NR_CAMERA_LOOK) return NR_E_MODE;
+        P.camera_mode = cam->mode;
+        P.perspective = cam->perspective != 0;
         for (int k = 0; k < 3; k++) {
-            P.ca[k] = light->color_ambient[k];
-            P.cd[k] = light->color_directional[k];
-            P.ldir[k] = light->direction[k];
+            P.target[k] = cam->target[k];
+            P.up[k] = cam->up[k];
+        }
+        P.width = cam->width;
+    }
+    if ((c.textures || c.light_out || c.grad_light) && !c.light) return NR_E_NULL;
+    P.eye_per_batch = c.eye_per_batch != 0;
+    P.idx_per_batch = c.idx_per_batch != 0;
+    P.fill_back = c.fill_back != 0;
+    if (c.light) {
+        P.ia = c.light->intensity_ambient;
+        P.id = c.light->intensity_directional;
+        P.has_directional = c.light->intensity_directional != 0.0f;
+        for (int k = 0; k < 3; k++) {
+            P.ca[k] = c.light->color_ambient[k];
+            P.cd[k] = c.light->color_directional[k];
+            P.ldir[k] = c.light->direction[k];
         }
     }
+    if (want_cam && (!c.workspace || c.workspace_bytes < cam_acc_bytes(c.B, c.proj))) return NR_E_WORKSPACE;
     return 0;
 }
 
-inline int frontend_sizes(int B, int Nv, int Nf, int ts, bool with_textures)
+dim3 face_grid(const FrontendCall &c)
 {
-    if (B < 1 || Nv < 1 || Nf < 1 || B > 65535) return NR_E_SIZE;
-    if (with_textures && ts < 1) return NR_E_SIZE;
-    if ((size_t)B * (size_t)Nf > 0x7fffffffull / 18) return NR_E_SIZE;
-    return 0;
+    return dim3((unsigned)(((size_t)c.Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)c.B);
+}
+
+int launch_forward(const FrontendCall &c)
+{
+    FrontendParams P;
+    ProjParams Q;
+    if (int rc = check_call(c, false, P, Q)) return rc;
+    hipLaunchKernelGGL(c.proj ? k_frontend_forward<true> : k_frontend_forward<false>, face_grid(c), dim3(FE_THREADS), 0, c.st,
+                       c.vertices, c.faces_idx, c.textures, c.eye, c.faces_out, c.textures_out, c.Nv, c.Nf,
+                       c.light_out ? 0 : c.ts, P, c.light_out, Q);
+    return launch_status();
+}
+
+int launch_backward(const FrontendCall &c)
+{
+    FrontendParams P;
+    ProjParams Q;
+    if (int rc = check_call(c, true, P, Q)) return rc;
+    double *cam_acc = nullptr;
+    if (wants_camera(c)) {  // zeros for the camera sums and for the camera gradients the batch shares (float atomics)
+        cam_acc = (double *)c.workspace;
+        int e = fill_bytes(cam_acc, 0, cam_acc_bytes(c.B, c.proj), c.st);
+        if (e == 0 && c.grad_eye && !P.eye_per_batch) e = fill_bytes(c.grad_eye, 0, 3 * sizeof(float), c.st);
+        if (e == 0 && c.grad_K && !Q.K_per_batch) e = fill_bytes(c.grad_K, 0, 9 * sizeof(float), c.st);
+        if (e == 0 && c.grad_R && !Q.R_per_batch) e = fill_bytes(c.grad_R, 0, 9 * sizeof(float), c.st);
+        if (e == 0 && c.grad_t && !Q.t_per_batch) e = fill_bytes(c.grad_t, 0, 3 * sizeof(float), c.st);
+        if (e != 0) return e;
+    }
+    if (c.grad_vertices)
+        if (int e = fill_bytes(c.grad_vertices, 0, (size_t)c.B * c.Nv * 3 * sizeof(float), c.st)) return e;
+    hipLaunchKernelGGL(c.proj ? k_frontend_backward<true> : k_frontend_backward<false>, face_grid(c), dim3(FE_THREADS), 0, c.st,
+                       c.vertices, c.faces_idx, c.textures, c.eye, c.grad_faces, c.grad_textures_out, c.grad_vertices,
+                       c.grad_textures, cam_acc, c.Nv, c.Nf, c.grad_light ? 0 : c.ts, P, c.grad_light, Q);
+    if (int rc = launch_status()) return rc;
+    if (!cam_acc) return 0;
+    const dim3 grid((unsigned)((c.B + 63) / 64));
+    if (c.proj)
+        hipLaunchKernelGGL(k_projection_backward, grid, dim3(64), 0, c.st, cam_acc, c.grad_K, c.grad_R, c.grad_t, c.B, Q);
+    else
+        hipLaunchKernelGGL(k_camera_backward, grid, dim3(64), 0, c.st, c.eye, cam_acc, c.grad_eye, c.B, P);
+    return launch_status();
 }
 
 }  // namespace
 
-NR_API size_t nr_frontend_workspace_bytes(int32_t B) { return B < 1 ? 0 : (size_t)B * 12 * sizeof(double); }
+NR_API size_t nr_frontend_workspace_bytes(int32_t B) { return cam_acc_bytes(B, false); }
+
+NR_API size_t nr_frontend_projection_workspace_bytes(int32_t B) { return cam_acc_bytes(B, true); }
 
 NR_API int nr_frontend_forward(const float *vertices, const int32_t *faces_idx, const float *textures, const float *eye,
                                float *faces_out, float *textures_out, int32_t B, int32_t Nv, int32_t Nf, int32_t ts,
                                int32_t idx_per_batch, int32_t eye_per_batch, int32_t fill_back, const nr_camera *camera,
                                const nr_light *light, void *stream)
 {
-    if (!vertices || !faces_idx || !eye || !faces_out) return NR_E_NULL;
-    if ((textures == nullptr) != (textures_out == nullptr)) return NR_E_MODE;
-    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
-    if (rc) return rc;
-    FrontendParams P;
-    rc = fill_params(P, camera, light, idx_per_batch, eye_per_batch, fill_back, textures != nullptr);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_forward<false>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx, textures,
-                       eye, faces_out, textures_out, Nv, Nf, ts, P, (float *)nullptr, ProjParams{});
-    return launch_status();
+    FrontendCall c = {};
+    c.camera = camera, c.eye = eye, c.eye_per_batch = eye_per_batch;
+    c.vertices = vertices, c.faces_idx = faces_idx, c.textures = textures;
+    c.faces_out = faces_out, c.textures_out = textures_out;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.ts = ts, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.st = (hipStream_t)stream;
+    return launch_forward(c);
 }
 
 NR_API int nr_frontend_forward_light(const float *vertices, const int32_t *faces_idx, const float *eye, float *faces_out,
@@ -686,64 +780,14 @@ NR_API int nr_frontend_forward_light(const float *vertices, const int32_t *faces
                                      int32_t eye_per_batch, int32_t fill_back, const nr_camera *camera,
                                      const nr_light *light, void *stream)
 {
-    if (!vertices || !faces_idx || !eye || !faces_out || !light_out) return NR_E_NULL;
-    int rc = frontend_sizes(B, Nv, Nf, 0, false);
-    if (rc) return rc;
-    FrontendParams P;
-    rc = fill_params(P, camera, light, idx_per_batch, eye_per_batch, fill_back, true);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_forward<false>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx,
-                       (const float *)nullptr, eye, faces_out, (float *)nullptr, Nv, Nf, 0, P, light_out, ProjParams{});
-    return launch_status();
+    if (!light_out) return NR_E_NULL;
+    FrontendCall c = {};
+    c.camera = camera, c.eye = eye, c.eye_per_batch = eye_per_batch;
+    c.vertices = vertices, c.faces_idx = faces_idx, c.faces_out = faces_out, c.light_out = light_out;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.st = (hipStream_t)stream;
+    return launch_forward(c);
 }
-
-namespace {
-int frontend_backward(const float *vertices, const int32_t *faces_idx, const float *textures, const float *eye,
-                      const float *grad_faces, const float *grad_textures_out, const float *grad_light,
-                      float *grad_vertices, float *grad_textures, float *grad_eye, int32_t B, int32_t Nv, int32_t Nf,
-                      int32_t ts, int32_t idx_per_batch, int32_t eye_per_batch, int32_t fill_back,
-                      const nr_camera *camera, const nr_light *light, void *workspace, size_t workspace_bytes, void *stream)
-{
-    if (!vertices || !faces_idx || !eye || !grad_faces) return NR_E_NULL;
-    if (!grad_vertices && !grad_textures && !grad_eye) return NR_E_MODE;
-    if (grad_eye && !grad_vertices) return NR_E_MODE;  // the camera sums are produced by the vertex pass
-    if (grad_textures && !(textures && grad_textures_out)) return NR_E_MODE;
-    if (grad_textures_out && !textures) return NR_E_MODE;
-    const bool lit = textures != nullptr || grad_light != nullptr;
-    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
-    if (rc) return rc;
-    FrontendParams P;
-    rc = fill_params(P, camera, light, idx_per_batch, eye_per_batch, fill_back, lit);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    double *cam_acc = nullptr;
-    if (grad_eye) {
-        if (!workspace || workspace_bytes < nr_frontend_workspace_bytes(B)) return NR_E_WORKSPACE;
-        cam_acc = (double *)workspace;
-        int e = fill_bytes(cam_acc, 0, nr_frontend_workspace_bytes(B), st);
-        if (e != 0) return e;
-        if (!eye_per_batch) {
-            e = fill_bytes(grad_eye, 0, 3 * sizeof(float), st);
-            if (e != 0) return e;
-        }
-    }
-    if (grad_vertices) {
-        const int e = fill_bytes(grad_vertices, 0, (size_t)B * Nv * 3 * sizeof(float), st);
-        if (e != 0) return e;
-    }
-    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_backward<false>, grid, dim3(FE_THREADS), 0, st, vertices, faces_idx, textures, eye, grad_faces,
-                       grad_textures_out, grad_vertices, grad_textures, cam_acc, Nv, Nf, ts, P, grad_light, ProjParams{});
-    rc = launch_status();
-    if (rc) return rc;
-    if (grad_eye) {
-        hipLaunchKernelGGL(k_camera_backward, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, eye, cam_acc, grad_eye, B, P);
-        rc = launch_status();
-    }
-    return rc;
-}
-}  // namespace
 
 NR_API int nr_frontend_backward(const float *vertices, const int32_t *faces_idx, const float *textures, const float *eye,
                                 const float *grad_faces, const float *grad_textures_out, float *grad_vertices,
@@ -751,9 +795,14 @@ NR_API int nr_frontend_backward(const float *vertices, const int32_t *faces_idx,
                                 int32_t idx_per_batch, int32_t eye_per_batch, int32_t fill_back, const nr_camera *camera,
                                 const nr_light *light, void *workspace, size_t workspace_bytes, void *stream)
 {
-    return frontend_backward(vertices, faces_idx, textures, eye, grad_faces, grad_textures_out, nullptr, grad_vertices,
-                             grad_textures, grad_eye, B, Nv, Nf, ts, idx_per_batch, eye_per_batch, fill_back, camera, light,
-                             workspace, workspace_bytes, stream);
+    FrontendCall c = {};
+    c.camera = camera, c.eye = eye, c.eye_per_batch = eye_per_batch, c.grad_eye = grad_eye;
+    c.vertices = vertices, c.faces_idx = faces_idx, c.textures = textures;
+    c.grad_faces = grad_faces, c.grad_textures_out = grad_textures_out;
+    c.grad_vertices = grad_vertices, c.grad_textures = grad_textures;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.ts = ts, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+    return launch_backward(c);
 }
 
 NR_API int nr_frontend_backward_light(const float *vertices, const int32_t *faces_idx, const float *eye,
@@ -762,41 +811,14 @@ NR_API int nr_frontend_backward_light(const float *vertices, const int32_t *face
                                       int32_t eye_per_batch, int32_t fill_back, const nr_camera *camera,
                                       const nr_light *light, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (grad_light && !light) return NR_E_NULL;
-    return frontend_backward(vertices, faces_idx, nullptr, eye, grad_faces, nullptr, grad_light, grad_vertices, nullptr,
-                             grad_eye, B, Nv, Nf, 0, idx_per_batch, eye_per_batch, fill_back, camera, light, workspace,
-                             workspace_bytes, stream);
-}
-
-// --------------------------------------------------------------------------------------------------------------------
-// NR_CAMERA_PROJECTION entry points
-namespace {
-int fill_projection(FrontendParams &P, ProjParams &Q, const nr_projection *proj, const nr_light *light, int idx_per_batch,
-                    int fill_back, bool lit)
-{
-    if (!proj || !proj->K || !proj->R || !proj->t) return NR_E_NULL;
-    if (!(proj->orig_size > 0.0f && proj->orig_size < __builtin_inff())) return NR_E_SIZE;
-    nr_camera cam = {};  // lighting, fill_back and the index layout as in the other modes; no look_at / perspective
-    cam.mode = NR_CAMERA_LOOK_AT;
-    const int rc = fill_params(P, &cam, light, idx_per_batch, 0, fill_back, lit);
-    if (rc) return rc;
-    P.camera_mode = NR_CAMERA_PROJECTION;
-    Q.K = proj->K;
-    Q.R = proj->R;
-    Q.t = proj->t;
-    Q.dist = proj->dist_coeffs;
-    Q.K_per_batch = proj->K_per_batch != 0;
-    Q.R_per_batch = proj->R_per_batch != 0;
-    Q.t_per_batch = proj->t_per_batch != 0;
-    Q.dist_per_batch = proj->dist_per_batch != 0;
-    Q.size = proj->orig_size;
-    return 0;
-}
-}  // namespace
-
-NR_API size_t nr_frontend_projection_workspace_bytes(int32_t B)
-{
-    return B < 1 ? 0 : (size_t)B * PROJ_ACC * sizeof(double);
+    if (grad_light && !light) return NR_E_NULL;  // (ahead of every other check, as it always was here)
+    FrontendCall c = {};
+    c.camera = camera, c.eye = eye, c.eye_per_batch = eye_per_batch, c.grad_eye = grad_eye;
+    c.vertices = vertices, c.faces_idx = faces_idx;
+    c.grad_faces = grad_faces, c.grad_light = grad_light, c.grad_vertices = grad_vertices;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+    return launch_backward(c);
 }
 
 NR_API int nr_frontend_forward_projection(const float *vertices, const int32_t *faces_idx, const float *textures,
@@ -804,19 +826,13 @@ NR_API int nr_frontend_forward_projection(const float *vertices, const int32_t *
                                           int32_t Nf, int32_t ts, int32_t idx_per_batch, int32_t fill_back,
                                           const nr_projection *projection, const nr_light *light, void *stream)
 {
-    if (!vertices || !faces_idx || !faces_out) return NR_E_NULL;
-    if ((textures == nullptr) != (textures_out == nullptr)) return NR_E_MODE;
-    if (textures_out && light_out) return NR_E_MODE;
-    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
-    if (rc) return rc;
-    FrontendParams P;
-    ProjParams Q;
-    rc = fill_projection(P, Q, projection, light, idx_per_batch, fill_back, textures != nullptr || light_out != nullptr);
-    if (rc) return rc;
-    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_forward<true>, grid, dim3(FE_THREADS), 0, (hipStream_t)stream, vertices, faces_idx, textures,
-                       (const float *)nullptr, faces_out, textures_out, Nv, Nf, light_out ? 0 : ts, P, light_out, Q);
-    return launch_status();
+    FrontendCall c = {};
+    c.proj = true, c.projection = projection;
+    c.vertices = vertices, c.faces_idx = faces_idx, c.textures = textures;
+    c.faces_out = faces_out, c.textures_out = textures_out, c.light_out = light_out;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.ts = ts, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.st = (hipStream_t)stream;
+    return launch_forward(c);
 }
 
 NR_API int nr_frontend_backward_projection(const float *vertices, const int32_t *faces_idx, const float *textures,
@@ -826,47 +842,12 @@ NR_API int nr_frontend_backward_projection(const float *vertices, const int32_t 
                                            int32_t idx_per_batch, int32_t fill_back, const nr_projection *projection,
                                            const nr_light *light, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!vertices || !faces_idx || !grad_faces) return NR_E_NULL;
-    const bool want_cam = grad_K || grad_R || grad_t;
-    if (!grad_vertices && !grad_textures && !want_cam) return NR_E_MODE;
-    if (want_cam && !grad_vertices) return NR_E_MODE;  // the camera sums are produced by the vertex pass
-    if (grad_textures && !(textures && grad_textures_out)) return NR_E_MODE;
-    if (grad_textures_out && !textures) return NR_E_MODE;
-    if (grad_light && textures) return NR_E_MODE;
-    if (grad_light && !light) return NR_E_NULL;
-    const bool lit = textures != nullptr || grad_light != nullptr;
-    int rc = frontend_sizes(B, Nv, Nf, ts, textures != nullptr);
-    if (rc) return rc;
-    FrontendParams P;
-    ProjParams Q;
-    rc = fill_projection(P, Q, projection, light, idx_per_batch, fill_back, lit);
-    if (rc) return rc;
-    hipStream_t st = (hipStream_t)stream;
-    double *cam_acc = nullptr;
-    if (want_cam) {
-        const size_t ws = nr_frontend_projection_workspace_bytes(B);
-        if (!workspace || workspace_bytes < ws) return NR_E_WORKSPACE;
-        cam_acc = (double *)workspace;
-        int e = fill_bytes(cam_acc, 0, ws, st);
-        if (e == 0 && grad_K && !Q.K_per_batch) e = fill_bytes(grad_K, 0, 9 * sizeof(float), st);
-        if (e == 0 && grad_R && !Q.R_per_batch) e = fill_bytes(grad_R, 0, 9 * sizeof(float), st);
-        if (e == 0 && grad_t && !Q.t_per_batch) e = fill_bytes(grad_t, 0, 3 * sizeof(float), st);
-        if (e != 0) return e;
-    }
-    if (grad_vertices) {
-        const int e = fill_bytes(grad_vertices, 0, (size_t)B * Nv * 3 * sizeof(float), st);
-        if (e != 0) return e;
-    }
-    const dim3 grid((unsigned)(((size_t)Nf * FE_LANES + FE_THREADS - 1) / FE_THREADS), (unsigned)B);
-    hipLaunchKernelGGL(k_frontend_backward<true>, grid, dim3(FE_THREADS), 0, st, vertices, faces_idx, textures,
-                       (const float *)nullptr, grad_faces, grad_textures_out, grad_vertices, grad_textures, cam_acc, Nv, Nf,
-                       grad_light ? 0 : ts, P, grad_light, Q);
-    rc = launch_status();
-    if (rc) return rc;
-    if (want_cam) {
-        hipLaunchKernelGGL(k_projection_backward, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, st, cam_acc, grad_K, grad_R,
-                           grad_t, B, Q);
-        rc = launch_status();
-    }
-    return rc;
+    FrontendCall c = {};
+    c.proj = true, c.projection = projection, c.grad_K = grad_K, c.grad_R = grad_R, c.grad_t = grad_t;
+    c.vertices = vertices, c.faces_idx = faces_idx, c.textures = textures;
+    c.grad_faces = grad_faces, c.grad_textures_out = grad_textures_out, c.grad_light = grad_light;
+    c.grad_vertices = grad_vertices, c.grad_textures = grad_textures;
+    c.B = B, c.Nv = Nv, c.Nf = Nf, c.ts = ts, c.idx_per_batch = idx_per_batch, c.fill_back = fill_back;
+    c.light = light, c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+    return launch_backward(c);
 }

@@ -171,131 +171,24 @@ def _make_light_struct(renderer):
 
 
 class _FrontEnd(torch.autograd.Function):
-    """forward(ctx, vertices, textures | None, eye, faces_idx, camera, light | None, fill_back)
-    -> (faces [B,F,3,3], lit textures [B,F,ts,ts,ts,3] | None)."""
+    """forward(ctx, vertices, textures | None, faces_idx, setup, *camera)
+    -> (faces [B,F,3,3], lit textures [B,F,ts,ts,ts,3] | None), or with `colors` (the front-end for the rasterizer's
+    `face_light` mode, include/nr_hip.h: nr_frontend_forward_light; textures None, their gradient comes straight out of the
+    rasterizer) -> (faces, light colours [B,F,3]).
+    setup = (nr_camera struct | orig_size, dist | None, light | None, fill_back, colors).  camera = (eye [3] | [B,3],) with
+    the nr_camera struct (look_at / look), or the projection camera's (K, R [3,3] | [B,3,3], t [3] | [B,3]) with orig_size
+    and dist [5] | [B,5] | None; all float32 device tensors.  (The camera tensors come last so that a look_at call passes
+    autograd no unused arguments: a fixed-shape loop at B = 1 is bound by host time.)"""
 
     @staticmethod
-    def forward(ctx, vertices, textures, eye, faces_idx, camera, light, fill_back):
+    def forward(ctx, vertices, textures, faces_idx, setup, *camera):
         lib = _lib.load()
-        dev = vertices.device
-        v = vertices.detach().contiguous()
-        idx = faces_idx.detach().to(torch.int32).contiguous()
-        e = eye.detach().contiguous()
-        t = textures.detach().contiguous() if textures is not None else None
-        B, Nv = v.shape[:2]
-        Nf = idx.shape[1]
-        F = Nf * 2 if fill_back else Nf
-        ts = int(t.shape[2]) if t is not None else 0
-        faces_out = torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev)
-        textures_out = torch.empty((B, F, ts, ts, ts, 3), dtype=torch.float32, device=dev) if t is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_forward(
-                v.data_ptr(), idx.data_ptr(), _lib.ptr(t), e.data_ptr(), faces_out.data_ptr(), _lib.ptr(textures_out),
-                B, Nv, Nf, ts, 1, int(e.dim() == 2), int(fill_back), camera, light,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_frontend_forward')
-        ctx.save_for_backward(v, idx, e, t)
-        ctx.params = (camera, light, bool(fill_back), B, Nv, Nf, ts)
-        ctx.set_materialize_grads(False)
-        return faces_out, textures_out
-
-    @staticmethod
-    def backward(ctx, g_faces, g_textures_out):
-        lib = _lib.load()
-        v, idx, e, t = ctx.saved_tensors
-        camera, light, fill_back, B, Nv, Nf, ts = ctx.params
-        dev = v.device
-        need_v, need_t, need_e = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        F = Nf * 2 if fill_back else Nf
-        if g_faces is None:
-            g_faces = torch.zeros((B, F, 3, 3), dtype=torch.float32, device=dev)
-        g_faces = g_faces.contiguous()
-        if g_textures_out is not None:
-            g_textures_out = g_textures_out.contiguous()
-        need_t = need_t and t is not None and g_textures_out is not None
-        need_v = need_v or need_e  # the camera sums come out of the vertex pass
-        grad_v = torch.empty((B, Nv, 3), dtype=torch.float32, device=dev) if need_v else None
-        grad_t = torch.empty_like(t) if need_t else None
-        grad_e = torch.empty_like(e) if need_e else None
-        if not (need_v or need_t):
-            return None, None, None, None, None, None, None
-        ws_bytes = lib.nr_frontend_workspace_bytes(B) if need_e else 0
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_backward(
-                v.data_ptr(), idx.data_ptr(), _lib.ptr(t), e.data_ptr(), g_faces.data_ptr(),
-                _lib.ptr(g_textures_out) if t is not None else None, _lib.ptr(grad_v), _lib.ptr(grad_t), _lib.ptr(grad_e),
-                B, Nv, Nf, ts, 1, int(e.dim() == 2), int(fill_back), camera, light, ws.data_ptr(), ws_bytes,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_frontend_backward')
-        return (grad_v if ctx.needs_input_grad[0] else None), grad_t, grad_e, None, None, None, None
-
-
-class _FrontEndLight(torch.autograd.Function):
-    """forward(ctx, vertices, eye, faces_idx, camera, light, fill_back) -> (faces [B,F,3,3], light colours [B,F,3]):
-    the front-end for the rasterizer's `face_light` mode (include/nr_hip.h: nr_frontend_forward_light) -- no textures pass
-    through; their gradient comes straight out of the rasterizer."""
-
-    @staticmethod
-    def forward(ctx, vertices, eye, faces_idx, camera, light, fill_back):
-        lib = _lib.load()
-        dev = vertices.device
-        v = vertices.detach().contiguous()
-        idx = faces_idx.detach().to(torch.int32).contiguous()
-        e = eye.detach().contiguous()
-        B, Nv = v.shape[:2]
-        Nf = idx.shape[1]
-        F = Nf * 2 if fill_back else Nf
-        faces_out = torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev)
-        light_out = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_forward_light(
-                v.data_ptr(), idx.data_ptr(), e.data_ptr(), faces_out.data_ptr(), light_out.data_ptr(), B, Nv, Nf, 1,
-                int(e.dim() == 2), int(fill_back), camera, light, torch.cuda.current_stream(dev).cuda_stream),
-                'nr_frontend_forward_light')
-        ctx.save_for_backward(v, idx, e)
-        ctx.params = (camera, light, bool(fill_back), B, Nv, Nf)
-        ctx.set_materialize_grads(False)
-        return faces_out, light_out
-
-    @staticmethod
-    def backward(ctx, g_faces, g_light):
-        lib = _lib.load()
-        v, idx, e = ctx.saved_tensors
-        camera, light, fill_back, B, Nv, Nf = ctx.params
-        dev = v.device
-        need_v, need_e = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_v or need_e):
-            return None, None, None, None, None, None
-        F = Nf * 2 if fill_back else Nf
-        if g_faces is None:
-            g_faces = torch.zeros((B, F, 3, 3), dtype=torch.float32, device=dev)
-        g_faces = g_faces.contiguous()
-        if g_light is not None:
-            g_light = g_light.contiguous()
-        grad_v = torch.empty((B, Nv, 3), dtype=torch.float32, device=dev)  # the camera sums come out of the vertex pass
-        grad_e = torch.empty_like(e) if need_e else None
-        ws_bytes = lib.nr_frontend_workspace_bytes(B) if need_e else 0
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_backward_light(
-                v.data_ptr(), idx.data_ptr(), e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_light), grad_v.data_ptr(),
-                _lib.ptr(grad_e), B, Nv, Nf, 1, int(e.dim() == 2), int(fill_back), camera, light, ws.data_ptr(), ws_bytes,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_frontend_backward_light')
-        return (grad_v if need_v else None), grad_e, None, None, None, None
-
-
-class _FrontEndProjection(torch.autograd.Function):
-    """forward(ctx, vertices, textures | None, K, R, t, dist | None, faces_idx, orig_size, light | None, fill_back, colors)
-    -> (faces [B,F,3,3], lit textures [B,F,ts,ts,ts,3] | None), or with `colors` (the face_light front-end; textures None)
-    -> (faces, light colours [B,F,3]).  K, R [3,3] | [B,3,3], t [3] | [B,3], dist [5] | [B,5] are float32 device tensors."""
-
-    @staticmethod
-    def forward(ctx, vertices, textures, K, R, t, dist, faces_idx, orig_size, light, fill_back, colors):
-        lib = _lib.load()
+        cam, dist, light, fill_back, colors = setup
         dev = vertices.device
         v = vertices.detach().contiguous()
         idx = faces_idx.detach().to(torch.int32).contiguous()
         tex = textures.detach().contiguous() if textures is not None else None
-        K, R, t = (x.detach().contiguous() for x in (K, R, t))
+        camera = tuple(x.detach().contiguous() for x in camera)
         d = dist.detach().contiguous() if dist is not None else None
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
@@ -304,29 +197,38 @@ class _FrontEndProjection(torch.autograd.Function):
         faces_out = torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev)
         tex_out = torch.empty((B, F, ts, ts, ts, 3), dtype=torch.float32, device=dev) if tex is not None else None
         light_out = torch.empty((B, F, 3), dtype=torch.float32, device=dev) if colors else None
-        proj = _projection_struct(K, R, t, d, orig_size)
+        proj = _projection_struct(*camera, d, cam) if len(camera) == 3 else None
+        if proj is not None:
+            fn, args = lib.nr_frontend_forward_projection, (_lib.ptr(tex), faces_out.data_ptr(), _lib.ptr(tex_out),
+                                                            _lib.ptr(light_out), B, Nv, Nf, ts, 1, int(fill_back), proj)
+        else:
+            e = camera[0]
+            if colors:
+                fn, args = lib.nr_frontend_forward_light, (e.data_ptr(), faces_out.data_ptr(), light_out.data_ptr(), B, Nv,
+                                                           Nf, 1, int(e.dim() == 2), int(fill_back), cam)
+            else:
+                fn, args = lib.nr_frontend_forward, (_lib.ptr(tex), e.data_ptr(), faces_out.data_ptr(), _lib.ptr(tex_out),
+                                                     B, Nv, Nf, ts, 1, int(e.dim() == 2), int(fill_back), cam)
         with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_forward_projection(
-                v.data_ptr(), idx.data_ptr(), _lib.ptr(tex), faces_out.data_ptr(), _lib.ptr(tex_out), _lib.ptr(light_out),
-                B, Nv, Nf, ts, 1, int(fill_back), proj, light, torch.cuda.current_stream(dev).cuda_stream),
-                'nr_frontend_forward_projection')
-        ctx.save_for_backward(v, idx, tex, K, R, t, d)
-        ctx.params = (orig_size, light, bool(fill_back), bool(colors), B, Nv, Nf, ts)
+            _lib.check(fn(v.data_ptr(), idx.data_ptr(), *args, light, torch.cuda.current_stream(dev).cuda_stream),
+                       fn.__name__)
+        ctx.save_for_backward(v, idx, tex, d, *camera)
+        ctx.params = (cam, light, proj, bool(fill_back), bool(colors), B, Nv, Nf, ts)
         ctx.set_materialize_grads(False)
         return faces_out, (light_out if colors else tex_out)
 
     @staticmethod
     def backward(ctx, g_faces, g_second):
         lib = _lib.load()
-        v, idx, tex, K, R, t, d = ctx.saved_tensors
-        orig_size, light, fill_back, colors, B, Nv, Nf, ts = ctx.params
+        v, idx, tex, _, *camera = ctx.saved_tensors
+        cam, light, proj, fill_back, colors, B, Nv, Nf, ts = ctx.params
         dev = v.device
         need = ctx.needs_input_grad
-        need_cam = need[2] or need[3] or need[4]
+        need_cam = True in need[4:]
         need_tex = need[1] and tex is not None and g_second is not None
         need_v = need[0] or need_cam  # the camera sums come out of the vertex pass
         if not (need_v or need_tex):
-            return (None,) * 11
+            return (None,) * len(need)
         F = Nf * 2 if fill_back else Nf
         if g_faces is None:
             g_faces = torch.zeros((B, F, 3, 3), dtype=torch.float32, device=dev)
@@ -337,17 +239,29 @@ class _FrontEndProjection(torch.autograd.Function):
         g_light = g_second if colors else None
         grad_v = torch.empty((B, Nv, 3), dtype=torch.float32, device=dev) if need_v else None
         grad_tex = torch.empty_like(tex) if need_tex else None
-        grad_K, grad_R, grad_t = (torch.empty_like(x) if n else None for x, n in ((K, need[2]), (R, need[3]), (t, need[4])))
-        ws_bytes = lib.nr_frontend_projection_workspace_bytes(B) if need_cam else 0
+        grad_cam = tuple(torch.empty_like(x) if n else None for x, n in zip(camera, need[4:]))
+        ws_bytes = 0
+        if need_cam:
+            ws_bytes = (lib.nr_frontend_projection_workspace_bytes if proj is not None else lib.nr_frontend_workspace_bytes)(B)
         ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-        proj = _projection_struct(K, R, t, d, orig_size)
+        if proj is not None:
+            fn, args = lib.nr_frontend_backward_projection, (
+                _lib.ptr(tex), g_faces.data_ptr(), _lib.ptr(g_tex_out), _lib.ptr(g_light), _lib.ptr(grad_v), _lib.ptr(grad_tex),
+                *(_lib.ptr(g) for g in grad_cam), B, Nv, Nf, ts, 1, int(fill_back), proj)
+        else:
+            e = camera[0]
+            if colors:
+                fn, args = lib.nr_frontend_backward_light, (e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_light),
+                                                            grad_v.data_ptr(), _lib.ptr(grad_cam[0]), B, Nv, Nf, 1,
+                                                            int(e.dim() == 2), int(fill_back), cam)
+            else:
+                fn, args = lib.nr_frontend_backward, (_lib.ptr(tex), e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_tex_out),
+                                                      _lib.ptr(grad_v), _lib.ptr(grad_tex), _lib.ptr(grad_cam[0]), B, Nv, Nf,
+                                                      ts, 1, int(e.dim() == 2), int(fill_back), cam)
         with torch.cuda.device(dev):
-            _lib.check(lib.nr_frontend_backward_projection(
-                v.data_ptr(), idx.data_ptr(), _lib.ptr(tex), g_faces.data_ptr(), _lib.ptr(g_tex_out), _lib.ptr(g_light),
-                _lib.ptr(grad_v), _lib.ptr(grad_tex), _lib.ptr(grad_K), _lib.ptr(grad_R), _lib.ptr(grad_t), B, Nv, Nf, ts, 1,
-                int(fill_back), proj, light, ws.data_ptr(), ws_bytes, torch.cuda.current_stream(dev).cuda_stream),
-                'nr_frontend_backward_projection')
-        return ((grad_v if need[0] else None), grad_tex, grad_K, grad_R, grad_t) + (None,) * 6
+            _lib.check(fn(v.data_ptr(), idx.data_ptr(), *args, light, ws.data_ptr(), ws_bytes,
+                          torch.cuda.current_stream(dev).cuda_stream), fn.__name__)
+        return ((grad_v if need[0] else None), grad_tex, None, None) + grad_cam
 
 
 def _projection_struct(K, R, t, d, orig_size):
@@ -359,17 +273,6 @@ def _projection_struct(K, R, t, d, orig_size):
     p.dist_per_batch = int(d is not None and d.dim() == 2)
     p.orig_size = float(orig_size)
     return p
-
-
-def _project_projection(renderer, vertices, faces, textures, colors):
-    dev = vertices.device
-    K, R, t = (_eye_tensor(getattr(renderer, n), dev) for n in ('K', 'R', 't'))
-    if t.dim() == 3:  # [B, 1, 3]
-        t = t.reshape(t.shape[0], 3)
-    d = _eye_tensor(renderer.dist_coeffs, dev) if renderer.dist_coeffs is not None else None
-    light = _light_struct(renderer) if (textures is not None or colors) else None
-    return _FrontEndProjection.apply(vertices, textures, K, R, t, d, faces, float(renderer.orig_size), light,
-                                     bool(renderer.fill_back), bool(colors))
 
 
 _EYE_CACHE = {}
@@ -389,22 +292,26 @@ def _eye_tensor(eye, device):
     return t
 
 
+def _project(renderer, vertices, faces, textures, colors):
+    _util.check_face_indices(faces, vertices.shape[1], vertices.device)
+    dev = vertices.device
+    light = _light_struct(renderer) if (textures is not None or colors) else None
+    if renderer.camera_mode == 'projection':
+        K, R, t = (_eye_tensor(getattr(renderer, n), dev) for n in ('K', 'R', 't'))
+        if t.dim() == 3:  # [B, 1, 3]
+            t = t.reshape(t.shape[0], 3)
+        d = _eye_tensor(renderer.dist_coeffs, dev) if renderer.dist_coeffs is not None else None
+        setup = (float(renderer.orig_size), d, light, bool(renderer.fill_back), colors)
+        return _FrontEnd.apply(vertices, textures, faces, setup, K, R, t)
+    setup = (_camera_struct(renderer), None, light, bool(renderer.fill_back), colors)
+    return _FrontEnd.apply(vertices, textures, faces, setup, _eye_tensor(renderer.eye, dev))
+
+
 def project_and_light(renderer, vertices, faces, textures=None):
     """-> (faces [B,F,3,3], lit textures | None) for the rasterizer; call only when fusable(...)."""
-    _util.check_face_indices(faces, vertices.shape[1], vertices.device)
-    if renderer.camera_mode == 'projection':
-        return _project_projection(renderer, vertices, faces, textures, colors=False)
-    camera = _camera_struct(renderer)
-    light = _light_struct(renderer) if textures is not None else None
-    eye = _eye_tensor(renderer.eye, vertices.device)
-    return _FrontEnd.apply(vertices, textures, eye, faces, camera, light, bool(renderer.fill_back))
+    return _project(renderer, vertices, faces, textures, False)
 
 
 def project_and_light_colors(renderer, vertices, faces):
     """-> (faces [B,F,3,3], light colours [B,F,3]) for the rasterizer's face_light mode; call only when fusable(...)."""
-    _util.check_face_indices(faces, vertices.shape[1], vertices.device)
-    if renderer.camera_mode == 'projection':
-        return _project_projection(renderer, vertices, faces, None, colors=True)
-    eye = _eye_tensor(renderer.eye, vertices.device)
-    return _FrontEndLight.apply(vertices, eye, faces, _camera_struct(renderer), _light_struct(renderer),
-                                bool(renderer.fill_back))
+    return _project(renderer, vertices, faces, None, True)

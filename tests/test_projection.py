@@ -123,18 +123,23 @@ def test_other_camera_modes_unchanged(mode):
 
 
 def test_projection_entry_point_argument_errors():
-    """Host-side checks of nr_frontend_{forward,backward}_projection: they return before any launch."""
+    """Host-side checks of the six nr_frontend_* entry points: they return before any launch.  Every case is rejected; where
+    several arguments are wrong, the code that wins is pinned too (the entry points do not all check in the same order)."""
     from neural_renderer_amd import _build, _lib
     _build.build()
     lib = _lib.load()
     assert lib.nr_frontend_projection_workspace_bytes(4) == 4 * 18 * 8
     assert lib.nr_frontend_projection_workspace_bytes(0) == 0
+    assert lib.nr_frontend_workspace_bytes(4) == 4 * 12 * 8
+    assert lib.nr_frontend_workspace_bytes(0) == 0
     X = 4096  # stand-in device addresses: never dereferenced on the host
     proj = _lib.Projection(K=X, R=X, t=X, dist_coeffs=None, orig_size=64.0)
     light = _lib.Light()
+    E_NULL, E_SIZE, E_WORKSPACE, E_MODE = -1, -2, -3, -4
+    overflow = dict(B=65535, Nf=0x7fffffff // 18 // 65535 + 1)  # B * Nf above the kernels' int32 indexing
 
-    def fwd(p=proj, textures=None, textures_out=None, light_out=None, lt=None):
-        return lib.nr_frontend_forward_projection(X, X, textures, X, textures_out, light_out, 2, 10, 5, 2, 1, 1,
+    def fwd(p=proj, textures=None, textures_out=None, light_out=None, lt=None, B=2, Nf=5, ts=2):
+        return lib.nr_frontend_forward_projection(X, X, textures, X, textures_out, light_out, B, 10, Nf, ts, 1, 1,
                                                   p, lt, None)
 
     assert fwd(p=None) == -1
@@ -144,10 +149,16 @@ def test_projection_entry_point_argument_errors():
     assert fwd(textures=X) == -4                                          # textures without textures_out
     assert fwd(textures=X, textures_out=X, light_out=X, lt=light) == -4   # two colour outputs
     assert fwd(light_out=X) == -1                                         # colours without a light
+    assert fwd(textures=X, textures_out=X, lt=light, ts=0) == E_SIZE
+    assert fwd(light_out=X, lt=light, **overflow) == E_SIZE
+    assert fwd(textures=X, textures_out=X, light_out=X, lt=light, B=0) == E_MODE  # output checks before sizes
+    assert fwd(p=None, B=0) == E_SIZE                                     # sizes before the camera
+    assert fwd(p=_lib.Projection(K=X, R=X, t=X, orig_size=0.0), light_out=X) == E_SIZE  # the camera before the light
 
-    def bwd(grad_vertices=X, grad_K=None, ws=X, ws_bytes=1 << 20, textures=None, g_light=None, lt=None):
-        return lib.nr_frontend_backward_projection(X, X, textures, X, None, g_light, grad_vertices, None, grad_K, None, None,
-                                                   2, 10, 5, 2, 1, 1, proj, lt, ws, ws_bytes, None)
+    def bwd(grad_vertices=X, grad_K=None, ws=X, ws_bytes=1 << 20, textures=None, g_light=None, lt=None, p=proj, B=2,
+            grad_textures=None, g_tex_out=None):
+        return lib.nr_frontend_backward_projection(X, X, textures, X, g_tex_out, g_light, grad_vertices, grad_textures, grad_K,
+                                                   None, None, B, 10, 5, 2, 1, 1, p, lt, ws, ws_bytes, None)
 
     assert bwd(grad_vertices=None) == -4                  # nothing requested
     assert bwd(grad_vertices=None, grad_K=X) == -4        # camera sums need the vertex pass
@@ -155,6 +166,75 @@ def test_projection_entry_point_argument_errors():
     assert bwd(grad_K=X, ws=None) == -3
     assert bwd(textures=X, g_light=X, lt=light) == -4     # textures and colours are exclusive
     assert bwd(g_light=X) == -1                           # colours without a light
-    # the existing entry points do not take the projection mode
+    assert bwd(grad_textures=X, textures=X, lt=light) == E_MODE  # grad_textures without grad_textures_out
+    assert bwd(g_tex_out=X) == E_MODE                     # grad_textures_out without textures
+    assert bwd(textures=X, g_light=X) == E_MODE           # exclusive outputs before the missing light
+    assert bwd(g_light=X, grad_vertices=None) == E_MODE   # nothing requested before the missing light
+    assert bwd(g_light=X, B=0) == E_NULL                  # the missing light before sizes
+    assert bwd(textures=X, B=65536) == E_SIZE
+    assert bwd(p=None, grad_K=X, ws=None) == E_NULL       # the camera before the workspace
+    assert bwd(grad_K=X, ws=None, textures=X) == E_NULL   # the light before the workspace
+
+    # look_at / look: the camera struct's mode is checked after sizes; these entry points do not take the projection mode
     cam = _lib.Camera(mode=_lib.NR_CAMERA_PROJECTION)
     assert lib.nr_frontend_forward(X, X, None, X, X, None, 2, 10, 5, 2, 1, 0, 1, cam, None, None) == -4
+    look = _lib.Camera(mode=_lib.NR_CAMERA_LOOK_AT, perspective=1, width=0.5)
+
+    def fwd_look(camera=look, textures=None, eye=X, faces_out=X, textures_out=None, lt=None, B=2, Nv=10, Nf=5, ts=2):
+        return lib.nr_frontend_forward(X, X, textures, eye, faces_out, textures_out, B, Nv, Nf, ts, 1, 0, 1, camera, lt, None)
+
+    assert fwd_look(camera=None) == E_NULL
+    assert fwd_look(eye=None) == E_NULL
+    assert fwd_look(faces_out=None, textures=X) == E_NULL
+    assert fwd_look(textures_out=X) == E_MODE
+    assert fwd_look(textures=X, textures_out=X) == E_NULL              # textures without a light
+    assert fwd_look(camera=_lib.Camera(mode=7)) == E_MODE
+    for bad in (dict(B=0), dict(B=65536), dict(Nv=0), dict(Nf=0), overflow):
+        assert fwd_look(**bad) == E_SIZE
+    assert fwd_look(textures=X, textures_out=X, lt=light, ts=0) == E_SIZE
+    assert fwd_look(camera=cam, B=0) == E_SIZE                         # sizes before the camera's mode
+    assert fwd_look(textures=X, Nv=0) == E_MODE                        # the output pair before sizes
+    assert fwd_look(camera=cam, textures=X, textures_out=X) == E_MODE  # the camera's mode before the light
+
+    def fwd_light(camera=look, eye=X, light_out=X, lt=light, B=2):
+        return lib.nr_frontend_forward_light(X, X, eye, X, light_out, B, 10, 5, 1, 0, 1, camera, lt, None)
+
+    assert fwd_light(light_out=None) == E_NULL
+    assert fwd_light(light_out=None, B=0) == E_NULL
+    assert fwd_light(lt=None) == E_NULL
+    assert fwd_light(camera=cam, lt=None) == E_MODE
+    assert fwd_light(camera=None, B=0) == E_SIZE
+    assert fwd_light(B=65536) == E_SIZE
+
+    def bwd_look(camera=look, textures=None, eye=X, g_tex_out=None, grad_vertices=X, grad_textures=None, grad_eye=None,
+                 lt=None, ws=X, ws_bytes=1 << 20, B=2, ts=2):
+        return lib.nr_frontend_backward(X, X, textures, eye, X, g_tex_out, grad_vertices, grad_textures, grad_eye, B, 10, 5, ts,
+                                        1, 0, 1, camera, lt, ws, ws_bytes, None)
+
+    assert bwd_look(eye=None) == E_NULL
+    assert bwd_look(grad_vertices=None) == E_MODE                           # nothing requested
+    assert bwd_look(grad_vertices=None, grad_eye=X) == E_MODE               # camera sums need the vertex pass
+    assert bwd_look(grad_textures=X, textures=X, lt=light) == E_MODE        # grad_textures without grad_textures_out
+    assert bwd_look(g_tex_out=X) == E_MODE                                  # grad_textures_out without textures
+    assert bwd_look(textures=X) == E_NULL                                   # textures without a light
+    assert bwd_look(camera=cam) == E_MODE
+    assert bwd_look(grad_eye=X, ws=None) == E_WORKSPACE
+    assert bwd_look(grad_eye=X, ws_bytes=4 * 12 * 8 - 1, B=4) == E_WORKSPACE
+    assert bwd_look(textures=X, lt=light, ts=0) == E_SIZE
+    assert bwd_look(grad_vertices=None, B=0) == E_MODE                      # argument checks before sizes
+    assert bwd_look(grad_eye=X, ws=None, B=0) == E_SIZE                     # sizes before the workspace
+    assert bwd_look(grad_eye=X, ws=None, camera=cam) == E_MODE              # the camera before the workspace
+    assert bwd_look(grad_eye=X, ws=None, textures=X) == E_NULL              # the light before the workspace
+
+    def bwd_light(camera=look, g_light=X, grad_vertices=X, grad_eye=None, lt=light, ws=X, ws_bytes=1 << 20, B=2):
+        return lib.nr_frontend_backward_light(X, X, X, X, g_light, grad_vertices, grad_eye, B, 10, 5, 1, 0, 1, camera, lt, ws,
+                                              ws_bytes, None)
+
+    assert bwd_light(lt=None) == E_NULL
+    assert bwd_light(lt=None, grad_vertices=None) == E_NULL  # here the missing light wins over every other check
+    assert bwd_light(lt=None, B=0) == E_NULL
+    assert bwd_light(grad_vertices=None) == E_MODE
+    assert bwd_light(g_light=None, lt=None, grad_vertices=None) == E_MODE
+    assert bwd_light(camera=cam) == E_MODE
+    assert bwd_light(camera=None, B=65536) == E_SIZE
+    assert bwd_light(grad_eye=X, ws_bytes=8) == E_WORKSPACE
