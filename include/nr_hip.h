@@ -22,6 +22,8 @@
  *   nr_create_texture_image       <- create_texture_image kernels of save_obj(textures=...)   save_obj.py:32-146
  *   nr_bake_uv_textures[_backward], nr_uv_texture_map: the bake of nr_load_textures as a differentiable step on learnable
  *                                   images (UVTextures); not in the reference
+ *   nr_forward_rasterize_uv / nr_backward_uv_images: the same images sampled at every covered pixel instead of baked into
+ *                                   cubes (UVImages); not in the reference
  *   nr_frontend_forward/_backward <- fill_back + lighting + look_at/look + perspective + vertices_to_faces
  *                                    of Renderer.render*                                  renderer.py:35-107
  *   nr_frontend_forward_projection / _backward_projection: the same front-end with a calibrated camera (K, R, t,
@@ -62,7 +64,8 @@ extern "C" {
 
 #define NR_VERSION 600 /* 0.6.0 (additions without a version step: NR_CAMERA_PROJECTION, nr_projection and
                           *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes;
-                          *        nr_bake_uv_textures[_backward], nr_uv_texture_map[_workspace_bytes]);
+                          *        nr_bake_uv_textures[_backward], nr_uv_texture_map[_workspace_bytes]; nr_uv_images,
+                          *        nr_forward_rasterize_uv, nr_backward_uv_images[_workspace_bytes]);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -495,6 +498,67 @@ int nr_uv_texture_map(const int32_t *image_table, const float *faces_uv, const i
 int nr_bake_uv_textures_backward(const float *grad_textures, const int32_t *row_ptr, const int32_t *entry_texel,
                                  const float *entry_weight, float *grad_images, int32_t batch_size, int32_t num_faces,
                                  int32_t texture_size, int32_t num_pixels, void *stream);
+
+/*
+ * Per-pixel UV texture images (not in the reference; DESIGN K10 "Per-pixel UV images"): the rasterizer samples the images of
+ * a UV layout at every covered pixel instead of at the ts^3 texels of a baked cube.  The layout and the images are those of
+ * nr_bake_uv_textures (Nf = lit->texture_faces faces; images [image_batch, P, 3], top row first; image_batch = the batch B,
+ * or 1 for images shared by the batch: image batch stride 0, no expanded copy).  Per-face light colours are required
+ * (lit->light [B, F, 3], F == Nf or F == 2 * Nf as for nr_forward_rasterize_lit); baked lighting has no place in images that
+ * many faces share.
+ *
+ * Forward, at a pixel of batch element b covered by face f with weights w and depth zp (all float32, in this order):
+ *   f' = f for f < Nf; for a reversed copy f' = f - Nf, and the weights are taken in reversed corner order (w2, w1, w0);
+ *   z   = the three vertex depths of face f in batch element b ITSELF (NR_FLAG_FIX_TEXTURE_BATCH_Z is implied; faces_z_ref
+ *         does not apply);
+ *   d_k = fminf(fmaxf(w_k * (zp / z_k), 0), 1)            (the cube path's product without the ts - 1 factor);
+ *   face f' with image m: the four bilinear reads (q_r, omega_r) of image m at the barycentric point d of faces_uv[f'] that
+ *         nr_bake_uv_textures takes at a texel (rows mirrored, reads clamped into the image), c = ((0 + img[q_0] omega_0) +
+ *         img[q_1] omega_1) + ... in read order;  face f' without an image: c = the cube path's trilinear sample of base[f']
+ *         (with eps, and the transposed cube for a reversed copy);
+ *   rgb = (c * light[b, f]) * 1 + 0 * background.
+ * Uncovered pixels, alpha, depth, face_index_map, weight_map and visible_faces are exactly nr_forward_rasterize_lit's.
+ *
+ * Backward (nr_backward_uv_images), for the upstream g = grad_rgb_map, over the covered pixels:
+ *   grad_images[b or 0, q_r, :] += g * light[b, f] * omega_r     (faces with an image; shared images sum over the batch)
+ *   grad_light[b, f, :]         += g * c                          (every covered pixel; c as in the forward)
+ * Every element of grad_images [image_batch, P, 3] and grad_light [B, F, 3] is stored (0 where nothing reads).  No gradient
+ * to faces_uv or base.  grad_faces comes from nr_backward_rasterize_lit(NULL, ..., grad_textures = NULL, ...) on the rgb_map
+ * of this forward (K6 and K8 read only the maps and the geometry).  Both sums are accumulated in double and rounded once to
+ * float: within 1e-6 of the sum of |terms| of the exact adjoint, also where thousands of pixels read one image pixel.  The
+ * double additions arrive in no fixed order, so the last bits of a double sum may differ between calls; rounded to float
+ * they gave the same bits in every run measured (tests/test_uv_pixel_gpu.py).  rgb_map repeats bit for bit.
+ *
+ * Neither call synchronises the host or reads device values on the host: both can be captured into a graph.
+ */
+typedef struct nr_uv_images {
+    const float *images;         /* DEVICE [image_batch, num_pixels, 3] */
+    const int32_t *image_table;  /* DEVICE [num_images, 3]: first pixel, H, W (as nr_bake_uv_textures) */
+    const float *faces_uv;       /* DEVICE [Nf, 3, 2] */
+    const int32_t *face_image;   /* DEVICE [Nf]: the image of a face, any value outside [0, num_images) = none */
+    const float *base;           /* DEVICE [Nf, ts, ts, ts, 3]: the texels of faces without an image */
+    int32_t texture_size, num_images, num_pixels, image_batch;  /* ts in [2, 1024]; image_batch 1 or B */
+} nr_uv_images;
+
+/* rgb_map and background are required; lit->light is required; the other arguments as in nr_forward_rasterize_lit. */
+int nr_forward_rasterize_uv(const nr_face_light *lit, const nr_uv_images *uv, const float *faces, int32_t *face_index_map,
+                            float *weight_map, float *depth_map, float *rgb_map, float *alpha_map, uint8_t *visible_faces,
+                            const float *background, int32_t bg_per_batch, int32_t batch_size, int32_t num_faces,
+                            int32_t image_size, double near, double far, double eps, int32_t flags, void *workspace,
+                            size_t workspace_bytes, void *stream);
+
+/* Scratch of nr_backward_uv_images: the double sums of the images and of the light colours (0 for sizes out of range). */
+size_t nr_backward_uv_images_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t num_pixels, int32_t image_batch);
+
+/*
+ * grad_images [image_batch, P, 3] and lit->grad_light [B, F, 3] (either may be NULL, not both); face_index_map, weight_map and
+ * depth_map are the forward's (weight_map is read at covered pixels only); eps the forward's.  lit->light is required,
+ * lit->textures is not read.
+ */
+int nr_backward_uv_images(const nr_face_light *lit, const nr_uv_images *uv, const float *faces,
+                          const int32_t *face_index_map, const float *weight_map, const float *depth_map,
+                          const float *grad_rgb_map, float *grad_images, int32_t batch_size, int32_t num_faces,
+                          int32_t image_size, double eps, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Texture atlas of save_obj(..., textures) (K11, reference save_obj.py:10-146): image [tile_height*tso, tile_width*tso, 3]

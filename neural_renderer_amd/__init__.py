@@ -19,8 +19,8 @@ from .load_obj import load_obj
 from .mesh import Mesh
 from .optimizers import Adam
 from .save_obj import save_obj
-# not in the reference: learnable UV texture images (the load_obj bake as a differentiable step)
-from .uv_textures import UVLayout, UVTextures, bake_uv_textures
+# not in the reference: learnable UV texture images (the load_obj bake as a differentiable step, or sampled per pixel)
+from .uv_textures import UVImages, UVLayout, UVTextures, bake_uv_textures
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -37,4 +37,4 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'clear_workspace_cache',
            'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'projection',
            'vertices_to_faces',
-           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVLayout', 'UVTextures', 'bake_uv_textures']
+           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures']

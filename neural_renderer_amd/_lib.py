@@ -33,7 +33,14 @@ class Projection(_c.Structure):
                 ('t_per_batch', _i32), ('dist_per_batch', _i32), ('orig_size', _c.c_float)]
 
 
+class UVImagesStruct(_c.Structure):
+    """struct nr_uv_images (include/nr_hip.h): a UV layout's device tables and its packed images."""
+    _fields_ = [('images', _vp), ('image_table', _vp), ('faces_uv', _vp), ('face_image', _vp), ('base', _vp),
+                ('texture_size', _i32), ('num_images', _i32), ('num_pixels', _i32), ('image_batch', _i32)]
+
+
 _cam_p, _light_p, _fl_p, _proj_p = _c.POINTER(Camera), _c.POINTER(Light), _c.POINTER(FaceLight), _c.POINTER(Projection)
+_uv_p = _c.POINTER(UVImagesStruct)
 
 # name -> (restype, argtypes); mirrors include/nr_hip.h one to one
 SIGNATURES = {
@@ -58,6 +65,9 @@ SIGNATURES = {
     'nr_uv_texture_map_workspace_bytes': (_sz, [_i32] * 4),
     'nr_uv_texture_map': (_c.c_int, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
     'nr_bake_uv_textures_backward': (_c.c_int, [_vp] * 5 + [_i32] * 4 + [_vp]),
+    'nr_forward_rasterize_uv': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 8 + [_i32] * 4 + [_f64] * 3 + [_i32, _vp, _sz, _vp]),
+    'nr_backward_uv_images_workspace_bytes': (_sz, [_i32] * 4),
+    'nr_backward_uv_images': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 6 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),
     'nr_frontend_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_cam_p, _light_p, _vp]),

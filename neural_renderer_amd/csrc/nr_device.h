@@ -221,6 +221,122 @@ __device__ __forceinline__ void compute_taps(const float *__restrict__ z, const 
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// Bilinear reads of texture images (K10).  One definition for the load_obj bake, the learnable bake, its inverse map and
+// per-pixel UV shading (nr_texture_io.hip, nr_uv_pixel.hip, the UV branch of shade_pixel).
+
+__device__ __forceinline__ int f2i(float x) { return (int)x; }  // v_cvt_i32_f32: truncates, saturates, NaN -> 0 (as CUDA)
+
+// The four bilinear reads of an [H,W] image stored bottom row first at the barycentric point d of a face's uv triangle
+// (load_obj.py:112-128): the flat pixel indices in the order the sum takes them -- (yi,xi), (yi1,xi), (yi,xi+1), (yi1,xi+1),
+// with the reference's yi1 = (int)(pos_y + 1) -- clamped to [0, H*W-1], and their weights.
+__device__ __forceinline__ void texel_reads(const float *face, const float d[3], int H, int W, long long p[4], float w[4])
+{
+    const float pos_x = (face[0] * d[0] + face[2] * d[1] + face[4] * d[2]) * (float)(W - 1);  // :112-113
+    const float pos_y = (face[1] * d[0] + face[3] * d[1] + face[5] * d[2]) * (float)(H - 1);  // :114-115
+    const int xi = f2i(pos_x), yi = f2i(pos_y), yi1 = f2i(pos_y + 1.0f);
+    const float wx1 = pos_x - (float)xi, wx0 = 1.0f - wx1;  // :118-121
+    const float wy1 = pos_y - (float)yi, wy0 = 1.0f - wy1;
+    const long long last = (long long)H * W - 1;
+    auto clampi = [&](int row, int col) -> long long {
+        const long long q = (long long)row * W + col;
+        return q < 0 ? 0 : (q > last ? last : q);
+    };
+    p[0] = clampi(yi, xi);
+    p[1] = clampi(yi1, xi);
+    p[2] = clampi(yi, xi + 1);
+    p[3] = clampi(yi1, xi + 1);
+    w[0] = wx0 * wy0;
+    w[1] = wx0 * wy1;
+    w[2] = wx1 * wy0;
+    w[3] = wx1 * wy1;
+}
+
+// texel_reads' index (bottom row first) -> the same pixel in an image stored top row first (file orientation)
+__device__ __forceinline__ int mirror_row(long long p, int H, int W)
+{
+    const int row = (int)(p / W), col = (int)(p - (long long)row * W);
+    return (H - 1 - row) * W + col;
+}
+
+// Per-pixel sampling of UV texture images (nr_uv_images in include/nr_hip.h): the layout and images of
+// nr_bake_uv_textures, read at the pixel instead of at the texels of a cube.
+struct UVShade {
+    const float *images = nullptr;      // [Bi, P, 3], each image top row first
+    const int32_t *table = nullptr;     // [M, 3]: first pixel, H, W
+    const float *faces_uv = nullptr;    // [Nf, 3, 2]
+    const int32_t *face_image = nullptr;  // [Nf]; outside [0, M): the face samples `base`
+    const float *base = nullptr;        // [Nf, ts^3, 3]
+    int ts = 0, M = 0, P = 0;
+    int shared = 0;                     // 1: one set of images for the whole batch (image batch stride 0)
+};
+
+// Where the pixel of face fi (batch element b, weights w, depth zp) reads.  `face` = face fi of batch element b itself.  The
+// reversed copy fi >= tex_faces of face f0 = fi - tex_faces takes its weights in reversed corner order, as the cube path
+// transposes the cube.  m >= 0: four reads q (packed pixels) with weights w of image m; m < 0: the cube taps of `base`.
+struct UVSample {
+    int m, f0;
+    int q[4];
+    float w[4];
+    Taps t;
+};
+
+__device__ __forceinline__ void uv_locate(const UVShade &uv, int fi, int tex_faces, const float *face, float w0, float w1,
+                                          float w2, float zp, double eps, UVSample &s)
+{
+    const bool flip = fi >= tex_faces;
+    s.f0 = flip ? fi - tex_faces : fi;
+    const int m = uv.face_image[s.f0];
+    s.m = (m >= 0 && m < uv.M) ? m : -1;
+    const float fz[3] = {face[2], face[5], face[8]};
+    const float w[3] = {w0, w1, w2};
+    if (s.m < 0) {
+        compute_taps(fz, w, zp, uv.ts, eps, s.t, flip);
+        return;
+    }
+    float d[3];
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = fminf(fmaxf(w[k] * (zp / fz[k]), 0.0f), 1.0f);  // compute_taps' product, no ts - 1
+    if (flip) {
+        const float d0 = d[0];
+        d[0] = d[2];
+        d[2] = d0;
+    }
+    const int off = uv.table[3 * s.m], H = uv.table[3 * s.m + 1], W = uv.table[3 * s.m + 2];
+    long long p[4];
+    texel_reads(uv.faces_uv + (size_t)s.f0 * 6, d, H, W, p, s.w);
+#pragma unroll
+    for (int r = 0; r < 4; r++) s.q[r] = off + mirror_row(p[r], H, W);
+}
+
+// The sampled colour before the light factor: the reads summed in read order from 0 (as k_bake_uv sums a texel), or the
+// cube path's trilinear sum on `base` (as shade_pixel sums a cube).
+__device__ __forceinline__ void uv_color(const UVShade &uv, const UVSample &s, int b, float c[3])
+{
+    c[0] = c[1] = c[2] = 0.0f;
+    if (s.m >= 0) {
+        const float *img = uv.images + (uv.shared ? 0 : (size_t)b * uv.P * 3);
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const float *px = img + (size_t)s.q[r] * 3;
+            c[0] += px[0] * s.w[r];
+            c[1] += px[1] * s.w[r];
+            c[2] += px[2] * s.w[r];
+        }
+        return;
+    }
+    const int T = uv.ts * uv.ts * uv.ts;
+    const float *texture = uv.base + (size_t)s.f0 * T * 3;
+#pragma unroll
+    for (int pn = 0; pn < 8; pn++) {
+        if (s.t.isc[pn] >= T) continue;  // outside the cube: weight 0 (see compute_taps)
+        const float *tx = texture + s.t.isc[pn] * 3;
+        c[0] += s.t.w[pn] * tx[0];
+        c[1] += s.t.w[pn] * tx[1];
+        c[2] += s.t.w[pn] * tx[2];
+    }
+}
+
 
 // --------------------------------------------------------------------------------------------------
 // host side helpers
@@ -385,5 +501,7 @@ void gather_atomic(const BackwardCall &c);
 void gather_depth(const BackwardCall &c, const K6Lists &l);
 
 int face_light_args(const nr_face_light *lit, int F, bool backward, FaceLight &out);  // nr_forward.hip
+// nr_uv_images + its nr_face_light (lit->grad_light copied into fl) -> the kernels' arguments; nr_forward.hip
+int uv_images_args(const nr_face_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out);
 
 }  // namespace nr

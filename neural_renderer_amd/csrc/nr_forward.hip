@@ -497,7 +497,10 @@ __global__ __launch_bounds__(256) void k_large_raster(const float *__restrict__ 
 
 // --------------------------------------------------------------------------------------------------
 // F3: shading, one pixel per thread (linear pixel index: fully coalesced map traffic).
-// Shading of one pixel (K4 + K5, rasterize.py:361-465): shared by k_shade and the fused k_resolve.
+// Shading of one pixel (K4 + K5, rasterize.py:361-465): shared by k_shade and the fused k_resolve.  UV: the pixel samples UV
+// texture images (nr_forward_rasterize_uv; `uv` non-NULL, lit.light required) instead of the cubes in `textures`; the
+// instantiations without it are the cube path alone.
+template <bool UV>
 __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, float w1, float w2, float depth,
                                             const float *__restrict__ faces, const float *__restrict__ zbase,
                                             const float *__restrict__ textures, float *__restrict__ rgb_map,
@@ -505,13 +508,25 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
                                             float *__restrict__ sampling_weight_map,
                                             const float *__restrict__ background, int bg_per_batch,
                                             float *__restrict__ alpha_map, int F, int ts, double eps, int fix_batch_z,
-                                            const FaceLight &lit)
+                                            const FaceLight &lit, const UVShade *uv = nullptr)
 {
     if (alpha_map) alpha_map[i] = (fi >= 0) ? 1.0f : 0.0f;  // :449
     if (!rgb_map) return;
     float rgb[3];
     Taps t;
-    if (fi >= 0) {
+    if (UV && fi >= 0) {
+        // always the face's own batch element (NR_FLAG_FIX_TEXTURE_BATCH_Z implied), per-face light colours always
+        UVSample s;
+        uv_locate(*uv, fi, lit.tex_faces, faces + ((size_t)b * F + fi) * 9, w0, w1, w2, depth, eps, s);
+        uv_color(*uv, s, b, rgb);
+        const float *lc = lit.light + ((size_t)b * F + fi) * 3;
+        rgb[0] *= lc[0];
+        rgb[1] *= lc[1];
+        rgb[2] *= lc[2];
+        const float *bg = background + (bg_per_batch ? 3 * b : 0);
+#pragma unroll
+        for (int k = 0; k < 3; k++) rgb[k] = rgb[k] * 1.0f + 0.0f * bg[k];  // as below
+    } else if (fi >= 0) {
         // :389 (Q1): the reference reads batch element 0's geometry here; zbase = that element's faces (of the GLOBAL batch)
         const float *face = (fix_batch_z ? faces + (size_t)b * F * 9 : zbase) + (size_t)fi * 9;
         const float *texture = textures + ((size_t)b * F + fi) * ts * ts * ts * 3;   // :390
@@ -553,6 +568,7 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
     o[0] = rgb[0];
     o[1] = rgb[1];
     o[2] = rgb[2];
+    if (UV) return;  // (no sampling maps: the UV instantiations are the resolve pass's)
     if (sampling_index_map) {
         int4 *p = reinterpret_cast<int4 *>(sampling_index_map + 8 * i);
         p[0] = make_int4(t.isc[0], t.isc[1], t.isc[2], t.isc[3]);
@@ -582,8 +598,8 @@ __global__ __launch_bounds__(256) void k_shade(const float *__restrict__ faces, 
     const int b = (int)(i / ((size_t)S * S));
     float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, depth = 0.0f;
     if (rgb_map && fi >= 0) { w0 = weight_map[3 * i]; w1 = weight_map[3 * i + 1]; w2 = weight_map[3 * i + 2]; depth = depth_map[i]; }
-    shade_pixel(i, b, fi, w0, w1, w2, depth, faces, zbase, textures, rgb_map, sampling_index_map, sampling_weight_map,
-                background, bg_per_batch, alpha_map, F, ts, eps, fix_batch_z, lit);
+    shade_pixel<false>(i, b, fi, w0, w1, w2, depth, faces, zbase, textures, rgb_map, sampling_index_map, sampling_weight_map,
+                       background, bg_per_batch, alpha_map, F, ts, eps, fix_batch_z, lit);
 }
 
 // Everything the resolve pass needs (passed by value: one kernel argument block for its two launch shapes).
@@ -610,10 +626,16 @@ struct ResolveArgs {
     int sparse_weights;
     const unsigned char *touched;
 };
+// The argument block of the UV-images instantiations (nr_forward_rasterize_uv): the cube instantiations keep theirs as it was.
+struct ResolveArgsUV : ResolveArgs {
+    UVShade uv;
+};
+template <bool UV> using ResolveArgsOf = typename std::conditional<UV, ResolveArgsUV, ResolveArgs>::type;
 
 // One pixel of the resolve pass: decode the winner of z-buffer word i (`drawn` false: nobody drew near it, the word is not
 // read), re-evaluate it exactly as the candidate tests did, write the maps and shade.
-__device__ __forceinline__ void resolve_pixel(const ResolveArgs &a, size_t i, bool drawn)
+template <bool UV>
+__device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<UV> &a, size_t i, bool drawn)
 {
     const float *__restrict__ faces = a.faces;
     const int S = a.S, F = a.F, epoch = a.epoch;
@@ -650,9 +672,11 @@ __device__ __forceinline__ void resolve_pixel(const ResolveArgs &a, size_t i, bo
 #pragma unroll
         for (int k = 0; k < 9; k++) o[k] = inv[k];
     }
+    const UVShade *uv = nullptr;
+    if constexpr (UV) uv = &a.uv;
     if (a.rgb_map || a.alpha_map)
-        shade_pixel(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
-                    a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit);
+        shade_pixel<UV>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
+                        a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit, uv);
 }
 
 // epoch mode: nobody fills the workspace for the next call, so the queue counters go back to -1 in the resolve pass (the
@@ -665,7 +689,8 @@ __device__ __forceinline__ void reset_queue_counters(const ResolveArgs &a)
     }
 }
 
-__global__ __launch_bounds__(256) void k_resolve(ResolveArgs a)
+template <bool UV>
+__global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<UV> a)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     reset_queue_counters(a);
@@ -674,7 +699,7 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgs a)
     // sets to the call's epoch number: where it holds anything else nobody drew -- 7 of 8 segments of a teapot view -- and the
     // 512 bytes of z-buffer behind it are not read (round 4: 33.5 -> ~6 MB of z-buffer reads at the headline size).  Stale
     // bytes of earlier calls carry larger epoch numbers, the initial fill 0xff: no clearing.
-    resolve_pixel(a, i, !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch);
+    resolve_pixel<UV>(a, i, !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch);
 }
 
 // The same pass for epoch mode on rasters with an even side.  Most of what the pass writes is the constant of undrawn pixels
@@ -684,7 +709,8 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgs a)
 // pixel per lane as before, and the other waves of an undrawn stretch leave at once.  (Fused forward of the headline batch
 // 72.3 -> 66.2 us; workgroups of 512 / 1024 pixels with 2 / 4 passes per lane: 72.9 / 82.6, profiles/r04_fwd_variants.jsonl.)
 // (256 pixels per workgroup: 64 / 128 / 512 / 1024 were measured -- 74.7 / 73.7 / 76.5 / 84.5 us against 69-70)
-__global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgs a)
+template <bool UV>
+__global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<UV> a)
 {
     reset_queue_counters(a);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, i0 = (size_t)blockIdx.x * 256 + 4 * threadIdx.x;
@@ -718,7 +744,7 @@ __global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgs a)
             o[2] = make_float4(c[2], c[0], c[1], c[2]);
         }
     }
-    if (ti == ep) resolve_pixel(a, i, true);
+    if (ti == ep) resolve_pixel<UV>(a, i, true);
 }
 
 }  // namespace
@@ -776,7 +802,7 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
                 unsigned char *visible_faces, int B, int F, int S, double near, double far, void *workspace,
                 size_t workspace_bytes, hipStream_t st, const float *faces_z_ref, const float *textures, float *rgb_map,
                 const float *background, int bg_per_batch, float *alpha_map, int ts, double eps, int fix_batch_z,
-                int flags = 0, const FaceLight &lit = FaceLight())
+                int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr)
 {
     if (!faces || !face_index_map) return NR_E_NULL;
     if (int e = check_sizes(B, F, S)) return e;
@@ -829,10 +855,19 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
     ra.sparse_weights = (flags & NR_FLAG_SPARSE_WEIGHT_MAP) ? 1 : 0; ra.touched = touched;
     const uintptr_t align = (uintptr_t)face_index_map | (uintptr_t)weight_map | (uintptr_t)depth_map | (uintptr_t)face_inv_map |
                             (uintptr_t)rgb_map | (uintptr_t)alpha_map;
-    if (touched && S % 2 == 0 && (align & 15) == 0)  // (k_resolve_quads: 16-byte stores into every map)
-        hipLaunchKernelGGL(k_resolve_quads, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, ra);
-    else
-        hipLaunchKernelGGL(k_resolve, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, st, ra);
+    const bool quads = touched && S % 2 == 0 && (align & 15) == 0;  // (k_resolve_quads: 16-byte stores into every map)
+    const dim3 grid((unsigned)((P + 255) / 256));
+    if (uv) {  // per-pixel UV images (nr_forward_rasterize_uv)
+        ResolveArgsUV rau;
+        static_cast<ResolveArgs &>(rau) = ra;
+        rau.uv = *uv;
+        if (quads) hipLaunchKernelGGL(k_resolve_quads<true>, grid, dim3(256), 0, st, rau);
+        else hipLaunchKernelGGL(k_resolve<true>, grid, dim3(256), 0, st, rau);
+    } else if (quads) {
+        hipLaunchKernelGGL(k_resolve_quads<false>, grid, dim3(256), 0, st, ra);
+    } else {
+        hipLaunchKernelGGL(k_resolve<false>, grid, dim3(256), 0, st, ra);
+    }
     return launch_status();
 }
 }  // namespace
@@ -892,6 +927,45 @@ NR_API int nr_forward_rasterize_lit(const nr_face_light *lit, const float *faces
     return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
                        workspace, workspace_bytes, (hipStream_t)stream, faces_z_ref, textures, rgb_map, background,
                        bg_per_batch, alpha_map, ts, eps, (flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0, flags, fl);
+}
+
+// host-side check of an nr_uv_images with its nr_face_light (see include/nr_hip.h) -> the kernels' FaceLight / UVShade
+int nr::uv_images_args(const nr_face_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out)
+{
+    out = UVShade();
+    if (!lit || !uv) return NR_E_NULL;
+    if (int e = face_light_args(lit, F, false, fl)) return e;
+    fl.grad_light = lit->grad_light;
+    if (!uv->images || !uv->image_table || !uv->faces_uv || !uv->face_image || !uv->base) return NR_E_NULL;
+    if (uv->texture_size < 2 || uv->texture_size > 1024 || uv->num_images < 1 || uv->num_pixels < 1 ||
+        uv->num_pixels > 0x7ffffffe)
+        return NR_E_SIZE;
+    if (uv->image_batch != 1 && uv->image_batch != B) return NR_E_SIZE;
+    out.images = uv->images;
+    out.table = uv->image_table;
+    out.faces_uv = uv->faces_uv;
+    out.face_image = uv->face_image;
+    out.base = uv->base;
+    out.ts = uv->texture_size;
+    out.M = uv->num_images;
+    out.P = uv->num_pixels;
+    out.shared = uv->image_batch == 1 ? 1 : 0;
+    return 0;
+}
+
+NR_API int nr_forward_rasterize_uv(const nr_face_light *lit, const nr_uv_images *uv, const float *faces,
+                                   int32_t *face_index_map, float *weight_map, float *depth_map, float *rgb_map,
+                                   float *alpha_map, uint8_t *visible_faces, const float *background, int32_t bg_per_batch,
+                                   int32_t B, int32_t F, int32_t S, double near, double far, double eps, int32_t flags,
+                                   void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!rgb_map || !background) return NR_E_NULL;
+    FaceLight fl;
+    UVShade us;
+    if (int e = uv_images_args(lit, uv, B, F, fl, us)) return e;
+    return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
+                       workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr, rgb_map, background,
+                       bg_per_batch, alpha_map, us.ts, eps, 1, flags, fl, &us);
 }
 
 NR_API int nr_forward_texture_sampling(const float *faces, const float *faces_z_ref, const float *textures,

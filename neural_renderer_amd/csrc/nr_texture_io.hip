@@ -28,8 +28,6 @@ using namespace nr;
 
 namespace {
 
-__device__ __forceinline__ int f2i(float x) { return (int)x; }  // v_cvt_i32_f32: truncates, saturates, NaN -> 0 (as CUDA)
-
 // The barycentric point of texel t = (i0*ts + i1)*ts + i2 of a face (load_obj.py:98-106): (i0,i1,i2)/(ts-1) in double,
 // rounded to float, divided by its float sum.  At texel (0,0,0) the sum is 0 and the point NaN, as in the reference.
 __device__ __forceinline__ void texel_point(int t, int ts, float d[3])
@@ -54,38 +52,7 @@ __device__ __forceinline__ void uv_texel_point(int t, int ts, float d[3])
     texel_point(t, ts, d);
 }
 
-// One texel's four bilinear reads of an [H,W] image stored bottom row first (load_obj.py:112-128): the flat pixel indices
-// in the order the sum takes them -- (yi,xi), (yi1,xi), (yi,xi+1), (yi1,xi+1), with the reference's yi1 = (int)(pos_y + 1)
-// -- clamped to [0, H*W-1], and their weights.  The one place this arithmetic lives: the load_obj bake, the learnable bake
-// and its inverse map all call it.
-__device__ __forceinline__ void texel_reads(const float *face, const float d[3], int H, int W, long long p[4], float w[4])
-{
-    const float pos_x = (face[0] * d[0] + face[2] * d[1] + face[4] * d[2]) * (float)(W - 1);  // :112-113
-    const float pos_y = (face[1] * d[0] + face[3] * d[1] + face[5] * d[2]) * (float)(H - 1);  // :114-115
-    const int xi = f2i(pos_x), yi = f2i(pos_y), yi1 = f2i(pos_y + 1.0f);
-    const float wx1 = pos_x - (float)xi, wx0 = 1.0f - wx1;  // :118-121
-    const float wy1 = pos_y - (float)yi, wy0 = 1.0f - wy1;
-    const long long last = (long long)H * W - 1;
-    auto clampi = [&](int row, int col) -> long long {
-        const long long q = (long long)row * W + col;
-        return q < 0 ? 0 : (q > last ? last : q);
-    };
-    p[0] = clampi(yi, xi);
-    p[1] = clampi(yi1, xi);
-    p[2] = clampi(yi, xi + 1);
-    p[3] = clampi(yi1, xi + 1);
-    w[0] = wx0 * wy0;
-    w[1] = wx0 * wy1;
-    w[2] = wx1 * wy0;
-    w[3] = wx1 * wy1;
-}
-
-// texel_reads' index (bottom row first) -> the same pixel in an image stored top row first (file orientation)
-__device__ __forceinline__ int mirror_row(long long p, int H, int W)
-{
-    const int row = (int)(p / W), col = (int)(p - (long long)row * W);
-    return (H - 1 - row) * W + col;
-}
+// (texel_reads, mirror_row and f2i live in nr_device.h: one definition for the bakes, the inverse map and per-pixel UV shading)
 
 __global__ __launch_bounds__(256) void k_bake_textures(const float *__restrict__ image, const float *__restrict__ faces_uv,
                                                        const int32_t *__restrict__ is_update, float *__restrict__ textures,

@@ -67,6 +67,14 @@ def _projection_fusable(renderer, batch_size):
     return _number(size) and 0 < float(size) < float('inf')
 
 
+def light_fusable(renderer):
+    """The light parameters are host numbers / 3-vectors, as the fused kernels take them (nr_light)."""
+    if not (_number(renderer.light_intensity_ambient) and _number(renderer.light_intensity_directional)):
+        return False
+    return all(_vec3(v) is not None for v in (renderer.light_color_ambient, renderer.light_color_directional,
+                                              renderer.light_direction))
+
+
 def fusable(renderer, vertices, faces, textures):
     if not (torch.is_tensor(vertices) and vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 3
             and vertices.shape[2] == 3):
@@ -81,10 +89,7 @@ def fusable(renderer, vertices, faces, textures):
                 and tuple(textures.shape[:2]) == tuple(faces.shape[:2]) and textures.shape[5] == 3
                 and textures.shape[2] == textures.shape[3] == textures.shape[4]):
             return False
-        if not (_number(renderer.light_intensity_ambient) and _number(renderer.light_intensity_directional)):
-            return False
-        if any(_vec3(v) is None for v in (renderer.light_color_ambient, renderer.light_color_directional,
-                                          renderer.light_direction)):
+        if not light_fusable(renderer):
             return False
     if renderer.camera_mode == 'projection':
         return _projection_fusable(renderer, vertices.shape[0])

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .uv_textures import UVImages, pack_images
 
 DEFAULT_IMAGE_SIZE = 256
 DEFAULT_ANTI_ALIASING = True
@@ -185,7 +186,10 @@ class _Config(object):
 class _Residuals(object):
     """Everything one forward leaves behind for its backward (the reference keeps the same on `self`, rasterize.py:39-58)."""
     __slots__ = ('B', 'F', 'S', 'ts', 'Nf', 'flags', 'faces', 'textures', 'light', 'z_ref', 'face_index_map', 'weight_map',
-                 'depth_map', 'rgb_map', 'alpha_map', 'visible')
+                 'depth_map', 'rgb_map', 'alpha_map', 'visible', 'uv', 'packed')
+
+    def __init__(self):
+        self.uv = self.packed = None  # per-pixel UV images: the UVImages and their packing [Bi,P,3]
 
 
 def _check_inputs(cfg, faces, textures, light):
@@ -198,7 +202,22 @@ def _check_inputs(cfg, faces, textures, light):
                          % (faces.dtype, tuple(faces.shape)))
     B, F = int(faces.shape[0]), int(faces.shape[1])
     Nf, ts = F, 0
-    if cfg.return_rgb:
+    if cfg.return_rgb and isinstance(textures, UVImages):  # per-pixel UV images: per-face light colours required
+        Nf, ts = textures.layout.num_faces, textures.layout.texture_size
+        if light is None:
+            raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
+        if light.dtype != torch.float32 or tuple(light.shape) != (B, F, 3) or not light.is_cuda:
+            raise ValueError('face_light must be float32 [batch size, num of faces, 3] on the GPU, got %s %s'
+                             % (light.dtype, tuple(light.shape)))
+        if F not in (Nf, 2 * Nf):
+            raise ValueError('UVImages: the layout has %d faces, the call %d (the layout\'s, or twice that with fill_back)'
+                             % (Nf, F))
+        if textures.image_batch not in (1, B):
+            raise ValueError('UVImages: batched images must have the batch size of the faces (%d), got %d'
+                             % (B, textures.image_batch))
+        if textures.device != faces.device or light.device != faces.device:
+            raise ValueError('UVImages: images, face_light and faces must be on one device')
+    elif cfg.return_rgb:
         if textures is None:
             raise ValueError('textures are required when return_rgb is set')
         if light is not None:
@@ -216,8 +235,9 @@ def _check_inputs(cfg, faces, textures, light):
     return B, F, Nf, ts
 
 
-def _forward_impl(cfg, faces, textures, light):
-    """forward_gpu (rasterize.py:467-513): visibility + shading behind one C-ABI call.  Returns the residuals."""
+def _forward_impl(cfg, faces, textures, light, packed=None):
+    """forward_gpu (rasterize.py:467-513): visibility + shading behind one C-ABI call.  Returns the residuals.  `textures`
+    may be a UVImages (with `light` and the images' packing `packed`): the per-pixel UV forward (nr_forward_rasterize_uv)."""
     lib = _lib.load()
     B, F, Nf, ts = _check_inputs(cfg, faces, textures, light)
     return_rgb, return_alpha, return_depth = cfg.return_rgb, cfg.return_alpha, cfg.return_depth
@@ -226,7 +246,9 @@ def _forward_impl(cfg, faces, textures, light):
     r = _Residuals()
     r.B, r.F, r.S, r.ts, r.Nf = B, F, S, ts, Nf
     r.faces = faces.detach().contiguous()  # rasterize.py:470
-    r.textures = textures.detach().contiguous() if return_rgb else None  # :473
+    if return_rgb and isinstance(textures, UVImages):
+        r.uv, r.packed, textures = textures, packed.detach(), None
+    r.textures = textures.detach().contiguous() if (return_rgb and r.uv is None) else None  # :473
     r.light = light.detach().contiguous() if (return_rgb and light is not None) else None
     with _on_device(dev):
         stream = _stream_ptr(dev)
@@ -267,6 +289,13 @@ def _forward_impl(cfg, faces, textures, light):
         r.visible = torch.empty((B, F), dtype=torch.uint8, device=dev)
         ptr = _lib.ptr
         lit = _lib.FaceLight(r.light.data_ptr(), Nf, None, None) if r.light is not None else None
+        if r.uv is not None:  # per-pixel UV images: the same pass, with the images' lookup in the shading
+            _lib.check(lib.nr_forward_rasterize_uv(
+                lit, _uv_struct(r), r.faces.data_ptr(), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
+                r.rgb_map.data_ptr(), ptr(r.alpha_map), r.visible.data_ptr(), background.data_ptr(), bg_per_batch, B, F, S,
+                cfg.near, cfg.far, cfg.eps, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace.data_ptr(),
+                ws_bytes, stream), 'nr_forward_rasterize_uv')
+            return r
         # visibility + shading behind one call (rasterize.py:499-502).  weight_map is a residual only (the backward reads it at
         # covered pixels): the zeros of uncovered pixels are not stored (NR_FLAG_SPARSE_WEIGHT_MAP; `Rasterize.weight_map`
         # fills them in when somebody reads the attribute)
@@ -278,13 +307,23 @@ def _forward_impl(cfg, faces, textures, light):
     return r
 
 
+def _uv_struct(r):
+    """struct nr_uv_images of a call's UVImages (the layout's device tables, uploaded once per device) and packing."""
+    layout = r.uv.layout
+    st = layout._tensors(r.faces.device)
+    return _lib.UVImagesStruct(r.packed.data_ptr(), st['table'].data_ptr(), st['faces_uv'].data_ptr(),
+                               st['face_image'].data_ptr(), st['base'].data_ptr(), layout.texture_size, layout.num_images,
+                               layout.num_pixels, int(r.packed.shape[0]))
+
+
 _BWD_WS_BYTES = {}
 
 
 def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
     """backward_gpu (rasterize.py:849-889): K6 -> K7 -> K8 behind one C-ABI call.  `None` gradients are zeros (:858-878); a
     zero gradient adds exactly 0 to every `diff_grad`, so the corresponding term is skipped instead of being multiplied out.
-    Returns (grad_faces, grad_textures | None, grad_light | None)."""
+    Returns (grad_faces, grad_textures | None, grad_light | None); with per-pixel UV images (r.uv) grad_textures is the
+    gradient of the packed images [Bi,P,3] (nr_backward_uv_images)."""
     lib = _lib.load()
     B, F, S, ts = r.B, r.F, r.S, r.ts
     use_rgb = cfg.return_rgb and g_rgb is not None
@@ -302,7 +341,10 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
         grad_faces = torch.empty_like(r.faces)  # stored by the library (zeros when neither rgb nor alpha)
         lit = None
         f32 = torch.float32
-        if use_rgb and r.light is not None:
+        uv = getattr(r, 'uv', None)
+        if uv is not None:
+            pass  # grad_faces below with lit = NULL and no grad_textures (K6 + K8), the images' and colours' after it
+        elif use_rgb and r.light is not None:
             if want_textures or want_light:
                 # one gather produces both (the colours' gradient is a by-product of the texel sums)
                 grad_textures = torch.empty((B, r.Nf, ts, ts, ts, 3), dtype=f32, device=dev)
@@ -325,13 +367,23 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
             ptr(r.rgb_map) if use_rgb else None, ptr(r.alpha_map) if use_alpha else None, ptr(g_rgb), ptr(g_alpha),
             ptr(g_depth), grad_faces.data_ptr(), ptr(grad_textures), B, F, S, ts, cfg.eps, r.flags, ptr(r.visible),
             workspace.data_ptr(), ws_bytes, stream), 'nr_backward_rasterize')
+        if uv is not None and use_rgb and (want_textures or want_light):
+            Bi = int(r.packed.shape[0])
+            grad_textures = torch.empty((Bi, uv.layout.num_pixels, 3), dtype=f32, device=dev) if want_textures else None
+            grad_light = torch.empty((B, F, 3), dtype=f32, device=dev) if want_light else None
+            ws_uv = lib.nr_backward_uv_images_workspace_bytes(B, F, uv.layout.num_pixels, Bi)
+            ws2 = torch.empty((max(ws_uv, 1),), dtype=torch.uint8, device=dev)
+            _lib.check(lib.nr_backward_uv_images(
+                _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grad_light)), _uv_struct(r), r.faces.data_ptr(),
+                r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(), g_rgb.data_ptr(),
+                ptr(grad_textures), B, F, S, cfg.eps, ws2.data_ptr(), ws_uv, stream), 'nr_backward_uv_images')
     owner = cfg.owner()
     if owner is not None:  # rasterize.py:41-51: the gradient buffers stay readable on the instance
         owner.grad_rgb_map, owner.grad_alpha_map, owner.grad_depth_map = g_rgb, g_alpha, g_depth
         # (aliases, not the returned tensors themselves: a second reference to a returned gradient makes autograd's
         # AccumulateGrad clone it instead of adopting it -- two device copies, 41 MB per step at the headline size)
         owner.grad_faces = grad_faces.detach()
-        owner.grad_textures = grad_textures.detach() if grad_textures is not None else None
+        owner.grad_textures = grad_textures.detach() if (grad_textures is not None and uv is None) else None
     return grad_faces, grad_textures, grad_light
 
 
@@ -373,6 +425,52 @@ class _RasterizeFunction(torch.autograd.Function):
         need = ctx.needs_input_grad
         gf, gt, gl = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, need[1], need[3])
         return gf, (gt if need[1] else None), None, gl
+
+
+class _UVRasterizeFunction(torch.autograd.Function):
+    """Per-pixel UV images (include/nr_hip.h: nr_forward_rasterize_uv / nr_backward_uv_images).
+    forward(ctx, faces, light, cfg, uv, *images) -> (rgb_map, alpha_map | None, depth_map | None, face_index_map);
+    backward -> (grad_faces, grad_light, None, None, one gradient per image tensor).  grad_faces comes from the rasterizer's
+    own backward (K6 + K8, no texture stage), the images' and the colours' from nr_backward_uv_images.  Always eager: the
+    operator's graph-replay mode does not apply (a whole step can still be captured with neural_renderer_amd.graph)."""
+
+    @staticmethod
+    def forward(ctx, faces, light, cfg, uv, *images):
+        packed = pack_images(images, uv.batch)
+        r = _forward_impl(cfg, faces, uv, light, packed)
+        owner = cfg.owner()
+        if owner is not None:
+            owner._keep(r)
+        ctx.cfg, ctx.uv = cfg, uv
+        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
+        ctx.z_ref, ctx.visible = r.z_ref, r.visible
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.light,
+                              r.packed)
+        ctx.mark_non_differentiable(r.face_index_map)
+        return (r.rgb_map, r.alpha_map if cfg.return_alpha else None, r.depth_map if cfg.return_depth else None,
+                r.face_index_map)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
+        r = _Residuals()
+        r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
+        r.z_ref, r.visible, r.uv, r.textures = ctx.z_ref, ctx.visible, ctx.uv, None
+        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.light, r.packed = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        want_images = any(need[4:])
+        gf, gp, gl = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, want_images, need[1])
+        grads = [None] * len(ctx.uv.images)
+        if gp is not None:
+            layout, batch = ctx.uv.layout, ctx.uv.batch
+            for m, ((off, h, w), im) in enumerate(zip(layout.image_table.tolist(), ctx.uv.images)):
+                if not need[4 + m]:
+                    continue
+                g = gp[:, off:off + h * w].view(gp.shape[0], h, w, 3)
+                if im.dim() == 3:  # shared by the batch: one row when every image is shared, else the rows summed
+                    g = g[0] if batch is None else g.sum(0)
+                grads[m] = g
+        return (gf, gl if need[1] else None, None, None) + tuple(grads)
 
 
 def _capture(fn, dev):
@@ -713,6 +811,9 @@ class Rasterize(object):
         the maps on the instance for backward_gpu.  No autograd graph is recorded."""
         faces = inputs[0]
         textures = inputs[1] if len(inputs) > 1 and self.return_rgb else None
+        if isinstance(textures, UVImages):
+            raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
+                                      '(fn(faces, uv_images, face_light)), which records the autograd graph')
         r = _forward_impl(_Config(self), faces, textures, face_light if self.return_rgb else None)
         self._keep(r)
         return (r.rgb_map if self.return_rgb else None, r.alpha_map if self.return_alpha else None,
@@ -725,6 +826,9 @@ class Rasterize(object):
         (grad_faces,) or (grad_faces, grad_textures) like :886-889; with face_light also grad_light (third).  `inputs` is
         accepted for the protocol's sake: the residuals of the last forward_gpu are what is used."""
         r = self._res
+        if len(inputs) > 1 and isinstance(inputs[1], UVImages) or (r is not None and r.uv is not None):
+            raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
+                                      '(fn(faces, uv_images, face_light)), which records the autograd graph')
         if r is None:
             raise RuntimeError('backward_gpu before forward_gpu')
         g_rgb, g_alpha, g_depth = (tuple(grad_outputs) + (None, None, None))[:3]
@@ -742,10 +846,17 @@ class Rasterize(object):
     def __call__(self, faces, textures=None, face_light=None):
         """`face_light` (not in the reference; include/nr_hip.h nr_face_light): [B,F,3] colours that multiply the sampled
         colour of each face; `textures` are then the cubes of the original faces ([B,F,...], or [B,F/2,...] when the second
-        half of `faces` are fill_back's reversed copies)."""
+        half of `faces` are fill_back's reversed copies).  `textures` may be a UVImages (not in the reference): the images are
+        sampled at every covered pixel; `face_light` is then required, `faces` has the layout's faces (or twice as many with
+        fill_back), and the call runs eagerly whatever graph_replay says."""
         cfg = _Config(self)
         if not self.return_rgb:
             textures = face_light = None
+        if isinstance(textures, UVImages):
+            if face_light is None:
+                raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
+            rgb, alpha, depth, _ = _UVRasterizeFunction.apply(faces, face_light, cfg, textures, *textures.images)
+            return rgb, alpha, depth
         if self.graph_replay and face_light is None:
             entry = _graph_entry(faces, textures, cfg)
             if entry is not None:
@@ -785,7 +896,7 @@ def rasterize_rgbad(
 
     Returns a dict with 'rgb' [B, 3, image_size, image_size], 'alpha' and 'depth' [B, image_size, image_size]
     (None when not requested).  `faces_z_ref` (not in the reference): see Rasterize.faces_z_ref; `face_light` (not in the
-    reference): see Rasterize.__call__."""
+    reference): see Rasterize.__call__; `textures` may be a UVImages (not in the reference), with `face_light`."""
     inputs = [faces] if textures is None else [faces, textures, face_light]
     size = image_size * 2 if anti_aliasing else image_size  # 2x super-sampling, :945-951
     fn = Rasterize(size, near, far, eps, background_color, return_rgb, return_alpha, return_depth)

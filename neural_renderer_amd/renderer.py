@@ -17,6 +17,7 @@ from .look_at import look_at
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
+from .uv_textures import UVImages
 from .vertices_to_faces import vertices_to_faces
 
 # Renderer.face_light default (see the attribute): NR_FACE_LIGHT = 0 | 1 | auto
@@ -145,7 +146,32 @@ class Renderer(object):
         replay = self.graph_replay if self.graph_replay is not None else sys.modules[rasterize.__module__].GRAPH_REPLAY
         return not replay and frontend.fusable(self, vertices, faces, textures)
 
+    def _render_uv(self, vertices, faces, uv):
+        """render() with a UVImages: the images sampled at every covered pixel (not in the reference).  Per-face light colours
+        always (face_light is implied): from the fused front-end when it takes the call, else from lighting() on a ones
+        texture behind the module-by-module front-end.  Runs eagerly: graph_replay does not apply."""
+        if frontend.fusable(self, vertices, faces, None) and frontend.light_fusable(self):
+            self.last_frontend = 'fused'
+            faces, light = frontend.project_and_light_colors(self, vertices, faces)
+        else:
+            self.last_frontend = 'torch'
+            if self.fill_back:  # renderer.py:37-38
+                faces = torch.cat((faces, torch.flip(faces, dims=[2])), dim=1).detach()
+            B, F = faces.shape[:2]
+            ones = torch.ones((B, F, 1, 1, 1, 3), dtype=torch.float32, device=vertices.device)
+            light = lighting(vertices_to_faces(vertices, faces), ones, self.light_intensity_ambient,
+                             self.light_intensity_directional, self.light_color_ambient, self.light_color_directional,
+                             self.light_direction).reshape(B, F, 3)
+            faces = self._project(vertices, faces)
+        self.frontend_calls[self.last_frontend] += 1
+        return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                         self.background_color, face_light=light)
+
     def render(self, vertices, faces, textures):
+        """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference, or (not in the reference) a UVImages whose images are
+        sampled at every covered pixel (uv_textures.py)."""
+        if isinstance(textures, UVImages):
+            return self._render_uv(vertices, faces, textures)
         if self._use_face_light(vertices, faces, textures):
             self.last_frontend = 'fused'
             self.frontend_calls['fused'] += 1

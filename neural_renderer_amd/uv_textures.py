@@ -2,8 +2,9 @@
 
 `UVLayout.from_obj` reads a mesh's uv triangles, materials and texture images (the parsing of load_textures, no GPU);
 `bake_uv_textures(images, layout)` turns the images into the [Bi,F,ts,ts,ts,3] textures Renderer.render samples, and its
-backward hands the texture gradient back to the image pixels; `UVTextures` holds one learnable image per textured material
-and writes the result back out as OBJ / MTL / PNG in the mesh's own uv layout.
+backward hands the texture gradient back to the image pixels; `UVImages(layout, images)` hands Renderer.render the images
+themselves, sampled at every covered pixel (include/nr_hip.h: nr_forward_rasterize_uv); `UVTextures` holds one learnable
+image per textured material and writes the result back out as OBJ / MTL / PNG in the mesh's own uv layout.
 
 Both directions are HIP kernels (csrc/nr_texture_io.hip, include/nr_hip.h: nr_bake_uv_textures[_backward]); the inverse
 map the backward walks (nr_uv_texture_map) is built on the device on the first backward and cached on the layout.
@@ -121,13 +122,48 @@ class UVLayout(object):
         return state['row_ptr'], state['entry_texel'], state['entry_weight']
 
 
+def check_images(images, layout, who):
+    """The images of a layout as bake_uv_textures and UVImages take them: a list of float32 CUDA tensors on one device, top
+    row first, image m [H_m,W_m,3] (shared by the batch) or [Bi,H_m,W_m,3].  Returns (list, Bi or None when none is
+    batched); raises ValueError."""
+    if not isinstance(layout, UVLayout):
+        raise ValueError('%s: layout must be a UVLayout' % who)
+    if torch.is_tensor(images):
+        images = [images]
+    images = list(images)
+    if len(images) != layout.num_images or layout.num_images == 0:
+        raise ValueError('%s: the layout has %d images, %d given' % (who, layout.num_images, len(images)))
+    batch = None
+    for m, (im, (h, w)) in enumerate(zip(images, layout.image_sizes)):  # shapes first: checkable without a GPU
+        if not torch.is_tensor(im) or im.dim() not in (3, 4) or tuple(im.shape[-3:]) != (h, w, 3):
+            raise ValueError('%s: image %d must be a tensor [%d,%d,3] or [Bi,%d,%d,3], got %s'
+                             % (who, m, h, w, h, w, tuple(im.shape) if torch.is_tensor(im) else type(im).__name__))
+        if im.dim() == 4:
+            if im.shape[0] < 1 or (batch is not None and im.shape[0] != batch):
+                raise ValueError('%s: batched images must share one batch size' % who)
+            batch = im.shape[0]
+    for m, im in enumerate(images):
+        if not im.is_cuda or im.dtype != torch.float32:
+            raise ValueError('%s: image %d must be a float32 CUDA tensor' % (who, m))
+        if im.device != images[0].device:
+            raise ValueError('%s: all images must be on one device' % who)
+    return images, batch
+
+
+def pack_images(images, batch):
+    """[Bi,P,3] contiguous (Bi = batch or 1): the images one after another, the unbatched ones repeated for every element
+    when others are batched -- the packing the kernels read (include/nr_hip.h: images [Bi,P,3])."""
+    Bi = batch or 1
+    flat = [(im if im.dim() == 4 else im[None].expand(Bi, -1, -1, -1)).reshape(Bi, -1, 3) for im in images]
+    return (flat[0] if len(flat) == 1 else torch.cat(flat, 1)).contiguous()
+
+
 class _BakeUV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layout, *images):
         device = images[0].device
         Bi = images[0].shape[0]
-        flat = [im.reshape(Bi, -1, 3) for im in images]
-        packed = (flat[0] if len(flat) == 1 else torch.cat(flat, 1)).contiguous()
+        packed = pack_images(images, Bi)
         state = layout._tensors(device)
         F, ts = layout.num_faces, layout.texture_size
         textures = torch.empty((Bi, F, ts, ts, ts, 3), dtype=torch.float32, device=device)
@@ -167,29 +203,33 @@ def bake_uv_textures(images, layout):
     first, each [H_m,W_m,3] or [Bi,H_m,W_m,3]; unbatched ones are shared by the batch).  Differentiable in the images.
     Equal to load_obj(load_texture=True)'s bake of the same images bit for bit, except at texel (0,0,0) (the uv centroid
     here, NaN there).  For one image shared by a batch of B renders, use bake_uv_textures(...)[0:1].expand(B, ...)."""
-    if not isinstance(layout, UVLayout):
-        raise ValueError('bake_uv_textures: layout must be a UVLayout')
-    if torch.is_tensor(images):
-        images = [images]
-    images = list(images)
-    if len(images) != layout.num_images or layout.num_images == 0:
-        raise ValueError('bake_uv_textures: the layout has %d images, %d given' % (layout.num_images, len(images)))
-    batch = None
-    for m, (im, (h, w)) in enumerate(zip(images, layout.image_sizes)):
-        if not torch.is_tensor(im) or not im.is_cuda or im.dtype != torch.float32:
-            raise ValueError('bake_uv_textures: image %d must be a float32 CUDA tensor' % m)
-        if im.device != images[0].device:
-            raise ValueError('bake_uv_textures: all images must be on one device')
-        if im.dim() not in (3, 4) or tuple(im.shape[-3:]) != (h, w, 3):
-            raise ValueError('bake_uv_textures: image %d must be [%d,%d,3] or [Bi,%d,%d,3], got %s'
-                             % (m, h, w, h, w, tuple(im.shape)))
-        if im.dim() == 4:
-            if im.shape[0] < 1 or (batch is not None and im.shape[0] != batch):
-                raise ValueError('bake_uv_textures: batched images must share one batch size')
-            batch = im.shape[0]
+    images, batch = check_images(images, layout, 'bake_uv_textures')
     batch = batch or 1
     images = [im if im.dim() == 4 else im[None].expand(batch, -1, -1, -1) for im in images]
     return _BakeUV.apply(layout, *images)
+
+
+class UVImages(object):
+    """A UV layout's images for per-pixel sampling: Renderer.render(vertices, faces, UVImages(layout, images)) and
+    rasterize(faces, UVImages(...), ..., face_light=...) sample the images at every covered pixel with the bake's bilinear
+    lookup (include/nr_hip.h: nr_forward_rasterize_uv) instead of baking them into texture cubes first.  `images` as
+    bake_uv_textures takes them: a list of float32 CUDA tensors, top row first, [H_m,W_m,3] shared by the batch or
+    [B,H_m,W_m,3] per render.  Gradients reach every image tensor; faces_uv and base (the colour of faces without an
+    image, sampled as a cube) receive none.  Holds references, no copies: build one per step, or keep one whose tensors
+    are updated in place."""
+
+    def __init__(self, layout, images):
+        self.images, self.batch = check_images(images, layout, 'UVImages')
+        self.layout = layout
+
+    @property
+    def image_batch(self):
+        """1 when every image is shared by the batch, else the batch size of the batched images."""
+        return self.batch or 1
+
+    @property
+    def device(self):
+        return self.images[0].device
 
 
 class UVTextures(torch.nn.Module):
@@ -207,6 +247,10 @@ class UVTextures(torch.nn.Module):
         """textures [batch_size,F,ts,ts,ts,3]: the bake of the images, shared by the batch."""
         textures = bake_uv_textures(list(self.images), self.layout)
         return textures[0:1].expand(batch_size, -1, -1, -1, -1, -1)
+
+    def uv_images(self):
+        """The images as a UVImages (shared by the batch): Renderer.render samples them per pixel."""
+        return UVImages(self.layout, list(self.images))
 
     def save_obj(self, filename, vertices, faces):
         """Writes `filename` (one `vt` per face corner, `usemtl` runs), `<stem>.mtl` (Kd and map_Kd) and the learned images

@@ -9,6 +9,13 @@ that the rasterizer sees the 10 240 faces) with the bake in front (gradients to 
 [64,F,4,4,4,3] textures directly).  Also prints the algorithmic bytes of the two bake kernels (forward: texels x 12 written
 + each image read once; backward: grad_textures read once + the map read once + the image gradients written): divide by
 the kernel times of a `rocprofv3 --kernel-trace --stats` run of this script for their share of HBM bandwidth.
+
+Per-pixel sampling (UVImages, include/nr_hip.h nr_forward_rasterize_uv / nr_backward_uv_images) of the same images on the
+same views: Renderer.render forward + backward ('render_fwd_bwd_per_pixel_ms') and the algorithmic bytes of its backward's
+kernels -- k_uv_pixel_backward reads face_index_map everywhere, weights, depth and the upstream gradient at the covered
+pixels (each image pixel's double sum read-modify-written at least once is counted with k_uv_round); the zero fill writes
+the double sums once, k_uv_round reads them once and writes the float gradients.  The forward's image reads ride in the
+resolve pass (4 reads per covered pixel, mostly from L2).
 """
 import json
 import os
@@ -119,8 +126,21 @@ def main():
         def render_direct():
             direct.grad = None
             r.render(vertices, faces, direct).square().sum().backward()
+        shared = image[0] if Bi == 1 else image
+
+        def render_per_pixel():
+            image.grad = None
+            r.render(vertices, faces, nr.UVImages(layout, [shared])).square().sum().backward()
         out['render_fwd_bwd_with_bake_ms'] = round(timeit(render_with_bake), 3)
         out['render_fwd_bwd_without_bake_ms'] = round(timeit(render_direct), 3)
+        out['render_fwd_bwd_per_pixel_ms'] = round(timeit(render_per_pixel), 3)
+        with torch.no_grad():
+            covered = int((r.render_silhouettes(vertices, faces) > 0).sum())
+        S = r.image_size
+        out['covered_pixels'] = covered
+        out['bytes_uv_pixel_bwd'] = B * S * S * 4 + covered * (12 + 4 + 12)
+        out['bytes_uv_fill'] = (Bi * P * 3 + B * F * 3) * 8
+        out['bytes_uv_round'] = (Bi * P * 3 + B * F * 3) * (8 + 4)
         out['texels_per_step'] = texels
         print(json.dumps(out), flush=True)
         del image, textures, g, grad_images, direct
