@@ -24,6 +24,9 @@
  *                                   images (UVTextures); not in the reference
  *   nr_forward_rasterize_uv / nr_backward_uv_images: the same images sampled at every covered pixel instead of baked into
  *                                   cubes (UVImages); not in the reference
+ *   nr_forward_rasterize_corner / nr_backward_corner_colors: three colours per face, one per corner, interpolated at every
+ *                                   covered pixel; nr_vertex_shade_forward/_backward: those colours from per-vertex colours
+ *                                   and flat or smooth (vertex-normal) light (VertexColors); not in the reference
  *   nr_frontend_forward/_backward <- fill_back + lighting + look_at/look + perspective + vertices_to_faces
  *                                    of Renderer.render*                                  renderer.py:35-107
  *   nr_frontend_forward_projection / _backward_projection: the same front-end with a calibrated camera (K, R, t,
@@ -65,7 +68,9 @@ extern "C" {
 #define NR_VERSION 600 /* 0.6.0 (additions without a version step: NR_CAMERA_PROJECTION, nr_projection and
                           *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes;
                           *        nr_bake_uv_textures[_backward], nr_uv_texture_map[_workspace_bytes]; nr_uv_images,
-                          *        nr_forward_rasterize_uv, nr_backward_uv_images[_workspace_bytes]);
+                          *        nr_forward_rasterize_uv, nr_backward_uv_images[_workspace_bytes];
+                          *        nr_forward_rasterize_corner, nr_backward_corner_colors[_workspace_bytes],
+                          *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -559,6 +564,76 @@ int nr_backward_uv_images(const nr_face_light *lit, const nr_uv_images *uv, cons
                           const int32_t *face_index_map, const float *weight_map, const float *depth_map,
                           const float *grad_rgb_map, float *grad_images, int32_t batch_size, int32_t num_faces,
                           int32_t image_size, double eps, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Corner colours (not in the reference; DESIGN K10 "Vertex colours"): corner_colors [B, F, 3, 3] float32, indexed (batch, face,
+ * corner k, rgb), already lit.  F is the rasterizer's face count: with fill_back a reversed copy carries its own nine numbers in
+ * its own corner order.  Forward, at a pixel of batch element b covered by face f with weights w and depth zp (float32, in
+ * this order, no multiply-add contraction), z_k = faces[b, f, k, 2] (always the face's own batch element):
+ *   d_k   = fminf(fmaxf(w_k * (zp / z_k), 0), 1)
+ *   rgb_c = (C[b,f,0,c] * d_0 + C[b,f,1,c] * d_1) + C[b,f,2,c] * d_2
+ *   rgb_c = rgb_c * 1 + 0 * background_c
+ * Uncovered pixels, alpha, depth, face_index_map, weight_map and visible_faces are exactly nr_forward_rasterize's; the
+ * workspace is nr_forward_workspace_bytes'.  rgb_map, background and corner_colors are required.
+ *
+ * Backward (nr_backward_corner_colors): grad_corner[b,f,k,c] = sum over the pixels owned by (b, f) of grad_rgb_map[pixel, c] *
+ * d_k, every element stored (exact zeros for faces that own no pixel).  A face of up to 1024 candidate pixels (its box, as
+ * the forward scans it) gathers its own pixels: double sums in a fixed order, no atomics, the same bits in every run.  A
+ * larger face -- one may own the whole raster -- is summed per pixel: the lanes of a wave that share the face (runs of
+ * consecutive pixels) add up first, in float in a tree of depth 6, the runs' sums are accumulated with double atomics and
+ * rounded once to float: 8 float roundings at most, in no fixed order (see nr_backward_uv_images).  Either way the result is
+ * within 1e-6 of the sum of |terms|.  visible_faces: the forward's flags [B, F] (faces without a pixel skip their scan), or
+ * NULL.  grad_faces comes from
+ * nr_backward_rasterize(textures = NULL, grad_textures = NULL) on the rgb_map of this forward.
+ * Neither call synchronises the host: both can be captured into a graph.
+ */
+int nr_forward_rasterize_corner(const float *corner_colors, const float *faces, int32_t *face_index_map, float *weight_map,
+                                float *depth_map, float *rgb_map, float *alpha_map, uint8_t *visible_faces,
+                                const float *background, int32_t bg_per_batch, int32_t batch_size, int32_t num_faces,
+                                int32_t image_size, double near, double far, int32_t flags, void *workspace,
+                                size_t workspace_bytes, void *stream);
+
+/* Scratch of nr_backward_corner_colors: nine double sums and a flag per face (0 for sizes out of range). */
+size_t nr_backward_corner_colors_workspace_bytes(int32_t batch_size, int32_t num_faces);
+
+int nr_backward_corner_colors(const float *faces, const int32_t *face_index_map, const float *weight_map,
+                              const float *depth_map, const float *grad_rgb_map, const uint8_t *visible_faces,
+                              float *grad_corner, int32_t batch_size, int32_t num_faces, int32_t image_size, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+/*
+ * Vertex shading (not in the reference): corner_colors [B, F, 3, 3] (F = Nf * (fill_back ? 2 : 1)) from world-space vertices
+ * [B, Nv, 3], faces_idx [Nf, 3] (or [B, Nf, 3] with idx_per_batch), per-vertex colors [color_batch, Nv, 3] (color_batch 1 or B)
+ * and the light.  N_f = cross(v0 - v1, v2 - v1) is the unnormalised normal of face f (lighting.py:36-39).
+ *   smooth = 0: light[b, f] and light[b, Nf + f] are exactly nr_frontend_forward_light's colours of the face and of its
+ *     reversed copy; corner[b, f, k] = colors[v_k] * light[b, f], corner[b, Nf + f, k] = colors[v_(2-k)] * light[b, Nf + f].
+ *   smooth = 1: m_v = the sum of N_f over the (face, corner) pairs of vertex v in ascending (f, k) order in float32
+ *     (area-weighted), n_v = m_v / (|m_v| + 1e-5), light_front[v] = Ia Ca + Id (Cd max(n_v . dir, 0)), light_back[v] the same
+ *     with max(-n_v . dir, 0); the corners of f take colors * light_front, those of Nf + f colors * light_back in reversed
+ *     corner order.  A vertex without a face, or with a zero normal sum, gets the ambient light only.
+ * adj_offsets [T, Nv + 1] and adj_entries [T, 3 Nf] (T = B with idx_per_batch, else 1) are the vertex -> (face, corner) table
+ * of faces_idx: the entries adj_entries[adj_offsets[v] .. adj_offsets[v + 1]) of vertex v are its pairs 3 f + k in ascending
+ * order.  The forward needs them with smooth = 1, the backward always; every sum around a vertex is a gather through them,
+ * so there are no atomics and the results repeat bit for bit.  The workspace (nr_vertex_shade_workspace_bytes) is needed with
+ * smooth = 1, by the forward and by a backward with grad_vertices.
+ *
+ * Backward, from grad_corner [B, F, 3, 3]: grad_colors [color_batch, Nv, 3] (shared colours: the sum over the batch, in double
+ * in one fixed order) and grad_vertices [B, Nv, 3] through light -> normal -> normalize -> cross product (to be ADDED to the
+ * geometry front-end's).  Either may be NULL, not both; every element is stored.  The light is a constant of the call.
+ * nr_light lives in HOST memory; no call synchronises the host.
+ */
+size_t nr_vertex_shade_workspace_bytes(int32_t batch_size, int32_t num_vertices);
+
+int nr_vertex_shade_forward(const float *vertices, const int32_t *faces_idx, const float *colors, const int32_t *adj_offsets,
+                            const int32_t *adj_entries, float *corner_colors, int32_t batch_size, int32_t num_vertices,
+                            int32_t num_faces, int32_t color_batch, int32_t idx_per_batch, int32_t fill_back, int32_t smooth,
+                            const nr_light *light, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_vertex_shade_backward(const float *vertices, const int32_t *faces_idx, const float *colors, const int32_t *adj_offsets,
+                             const int32_t *adj_entries, const float *grad_corner, float *grad_colors, float *grad_vertices,
+                             int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t color_batch,
+                             int32_t idx_per_batch, int32_t fill_back, int32_t smooth, const nr_light *light, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /*
  * Texture atlas of save_obj(..., textures) (K11, reference save_obj.py:10-146): image [tile_height*tso, tile_width*tso, 3]

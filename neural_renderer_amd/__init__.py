@@ -21,6 +21,8 @@ from .optimizers import Adam
 from .save_obj import save_obj
 # not in the reference: learnable UV texture images (the load_obj bake as a differentiable step, or sampled per pixel)
 from .uv_textures import UVImages, UVLayout, UVTextures, bake_uv_textures
+# not in the reference: per-vertex colours and smooth (vertex-normal) shading, interpolated per pixel
+from .vertex_colors import CornerColors, VertexColors, vertex_shade
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -37,4 +39,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'clear_workspace_cache',
            'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'projection',
            'vertices_to_faces',
-           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures']
+           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
+           'CornerColors', 'VertexColors', 'vertex_shade']

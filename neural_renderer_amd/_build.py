@@ -10,10 +10,11 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = [os.path.join(HERE, 'csrc', n) for n in ('nr_forward.hip', 'nr_backward.hip', 'nr_backward_pixel_map.hip',
                                                       'nr_backward_gather.hip', 'nr_geometry.hip',
                                                       'nr_image.hip', 'nr_frontend.hip', 'nr_texture_io.hip', 'nr_optim.hip',
-                                                      'nr_uv_pixel.hip')]
+                                                      'nr_uv_pixel.hip', 'nr_vertex_colors.hip')]
 HEADERS = [os.path.join(os.path.dirname(HERE), 'include', 'nr_hip.h'), os.path.join(os.path.dirname(HERE), 'include', 'nr_hip_profile.h'),
            os.path.join(HERE, 'csrc', 'nr_device.h'),
-           os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h')]
+           os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h'),
+           os.path.join(HERE, 'csrc', 'nr_shade.h')]
 LIB_PATH = os.path.join(HERE, 'libnr_hip.so')
 # the measurement build: the same sources with -DNR_PROFILE_HOOK (include/nr_hip_profile.h); bench.py times the dominant kernel with it
 PROFILE_LIB_PATH = os.path.join(HERE, 'libnr_hip_prof.so')

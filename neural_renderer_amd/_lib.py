@@ -68,6 +68,12 @@ SIGNATURES = {
     'nr_forward_rasterize_uv': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 8 + [_i32] * 4 + [_f64] * 3 + [_i32, _vp, _sz, _vp]),
     'nr_backward_uv_images_workspace_bytes': (_sz, [_i32] * 4),
     'nr_backward_uv_images': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 6 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
+    'nr_forward_rasterize_corner': (_c.c_int, [_vp] * 9 + [_i32] * 4 + [_f64] * 2 + [_i32, _vp, _sz, _vp]),
+    'nr_backward_corner_colors_workspace_bytes': (_sz, [_i32] * 2),
+    'nr_backward_corner_colors': (_c.c_int, [_vp] * 7 + [_i32] * 3 + [_vp, _sz, _vp]),
+    'nr_vertex_shade_workspace_bytes': (_sz, [_i32] * 2),
+    'nr_vertex_shade_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
+    'nr_vertex_shade_backward': (_c.c_int, [_vp] * 8 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),
     'nr_frontend_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_cam_p, _light_p, _vp]),

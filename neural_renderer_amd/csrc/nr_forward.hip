@@ -499,8 +499,10 @@ __global__ __launch_bounds__(256) void k_large_raster(const float *__restrict__ 
 // F3: shading, one pixel per thread (linear pixel index: fully coalesced map traffic).
 // Shading of one pixel (K4 + K5, rasterize.py:361-465): shared by k_shade and the fused k_resolve.  UV: the pixel samples UV
 // texture images (nr_forward_rasterize_uv; `uv` non-NULL, lit.light required) instead of the cubes in `textures`; the
-// instantiations without it are the cube path alone.
-template <bool UV>
+// instantiations without it are the cube path alone.  CORNER: the pixel interpolates the three corner colours of its face
+// (nr_forward_rasterize_corner; `textures` = corner_colors [B, F, 3, 3], no light factor: the colours arrive lit).
+enum ShadeMode { SHADE_CUBE = 0, SHADE_UV = 1, SHADE_CORNER = 2 };
+template <int MODE>
 __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, float w1, float w2, float depth,
                                             const float *__restrict__ faces, const float *__restrict__ zbase,
                                             const float *__restrict__ textures, float *__restrict__ rgb_map,
@@ -514,7 +516,23 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
     if (!rgb_map) return;
     float rgb[3];
     Taps t;
-    if (UV && fi >= 0) {
+    constexpr bool UV = MODE == SHADE_UV;
+    if (MODE == SHADE_CORNER && fi >= 0) {
+        // always the face's own batch element; perspective-correct weights d_k as uv_locate takes them, then
+        // (C0 * d0 + C1 * d1) + C2 * d2 per channel
+        const float *face = faces + ((size_t)b * F + fi) * 9;
+        const float *cc = textures + ((size_t)b * F + fi) * 9;
+        const float w[3] = {w0, w1, w2};
+        float d[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) d[k] = fminf(fmaxf(w[k] * (depth / face[3 * k + 2]), 0.0f), 1.0f);
+        const float *bg = background + (bg_per_batch ? 3 * b : 0);
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            rgb[c] = (cc[c] * d[0] + cc[3 + c] * d[1]) + cc[6 + c] * d[2];
+            rgb[c] = rgb[c] * 1.0f + 0.0f * bg[c];  // as below
+        }
+    } else if (UV && fi >= 0) {
         // always the face's own batch element (NR_FLAG_FIX_TEXTURE_BATCH_Z implied), per-face light colours always
         UVSample s;
         uv_locate(*uv, fi, lit.tex_faces, faces + ((size_t)b * F + fi) * 9, w0, w1, w2, depth, eps, s);
@@ -568,7 +586,7 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
     o[0] = rgb[0];
     o[1] = rgb[1];
     o[2] = rgb[2];
-    if (UV) return;  // (no sampling maps: the UV instantiations are the resolve pass's)
+    if (MODE != SHADE_CUBE) return;  // (no sampling maps: the UV and corner instantiations are the resolve pass's)
     if (sampling_index_map) {
         int4 *p = reinterpret_cast<int4 *>(sampling_index_map + 8 * i);
         p[0] = make_int4(t.isc[0], t.isc[1], t.isc[2], t.isc[3]);
@@ -598,8 +616,8 @@ __global__ __launch_bounds__(256) void k_shade(const float *__restrict__ faces, 
     const int b = (int)(i / ((size_t)S * S));
     float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, depth = 0.0f;
     if (rgb_map && fi >= 0) { w0 = weight_map[3 * i]; w1 = weight_map[3 * i + 1]; w2 = weight_map[3 * i + 2]; depth = depth_map[i]; }
-    shade_pixel<false>(i, b, fi, w0, w1, w2, depth, faces, zbase, textures, rgb_map, sampling_index_map, sampling_weight_map,
-                       background, bg_per_batch, alpha_map, F, ts, eps, fix_batch_z, lit);
+    shade_pixel<SHADE_CUBE>(i, b, fi, w0, w1, w2, depth, faces, zbase, textures, rgb_map, sampling_index_map, sampling_weight_map,
+                            background, bg_per_batch, alpha_map, F, ts, eps, fix_batch_z, lit);
 }
 
 // Everything the resolve pass needs (passed by value: one kernel argument block for its two launch shapes).
@@ -630,12 +648,12 @@ struct ResolveArgs {
 struct ResolveArgsUV : ResolveArgs {
     UVShade uv;
 };
-template <bool UV> using ResolveArgsOf = typename std::conditional<UV, ResolveArgsUV, ResolveArgs>::type;
+template <int MODE> using ResolveArgsOf = typename std::conditional<MODE == SHADE_UV, ResolveArgsUV, ResolveArgs>::type;
 
 // One pixel of the resolve pass: decode the winner of z-buffer word i (`drawn` false: nobody drew near it, the word is not
 // read), re-evaluate it exactly as the candidate tests did, write the maps and shade.
-template <bool UV>
-__device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<UV> &a, size_t i, bool drawn)
+template <int MODE>
+__device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size_t i, bool drawn)
 {
     const float *__restrict__ faces = a.faces;
     const int S = a.S, F = a.F, epoch = a.epoch;
@@ -673,10 +691,10 @@ __device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<UV> &a, size_t
         for (int k = 0; k < 9; k++) o[k] = inv[k];
     }
     const UVShade *uv = nullptr;
-    if constexpr (UV) uv = &a.uv;
+    if constexpr (MODE == SHADE_UV) uv = &a.uv;
     if (a.rgb_map || a.alpha_map)
-        shade_pixel<UV>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
-                        a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit, uv);
+        shade_pixel<MODE>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
+                          a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit, uv);
 }
 
 // epoch mode: nobody fills the workspace for the next call, so the queue counters go back to -1 in the resolve pass (the
@@ -689,8 +707,8 @@ __device__ __forceinline__ void reset_queue_counters(const ResolveArgs &a)
     }
 }
 
-template <bool UV>
-__global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<UV> a)
+template <int MODE>
+__global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<MODE> a)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     reset_queue_counters(a);
@@ -699,7 +717,7 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<UV> a)
     // sets to the call's epoch number: where it holds anything else nobody drew -- 7 of 8 segments of a teapot view -- and the
     // 512 bytes of z-buffer behind it are not read (round 4: 33.5 -> ~6 MB of z-buffer reads at the headline size).  Stale
     // bytes of earlier calls carry larger epoch numbers, the initial fill 0xff: no clearing.
-    resolve_pixel<UV>(a, i, !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch);
+    resolve_pixel<MODE>(a, i, !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch);
 }
 
 // The same pass for epoch mode on rasters with an even side.  Most of what the pass writes is the constant of undrawn pixels
@@ -709,8 +727,8 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<UV> a)
 // pixel per lane as before, and the other waves of an undrawn stretch leave at once.  (Fused forward of the headline batch
 // 72.3 -> 66.2 us; workgroups of 512 / 1024 pixels with 2 / 4 passes per lane: 72.9 / 82.6, profiles/r04_fwd_variants.jsonl.)
 // (256 pixels per workgroup: 64 / 128 / 512 / 1024 were measured -- 74.7 / 73.7 / 76.5 / 84.5 us against 69-70)
-template <bool UV>
-__global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<UV> a)
+template <int MODE>
+__global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<MODE> a)
 {
     reset_queue_counters(a);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, i0 = (size_t)blockIdx.x * 256 + 4 * threadIdx.x;
@@ -744,7 +762,7 @@ __global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<UV> a)
             o[2] = make_float4(c[2], c[0], c[1], c[2]);
         }
     }
-    if (ti == ep) resolve_pixel<UV>(a, i, true);
+    if (ti == ep) resolve_pixel<MODE>(a, i, true);
 }
 
 }  // namespace
@@ -802,7 +820,7 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
                 unsigned char *visible_faces, int B, int F, int S, double near, double far, void *workspace,
                 size_t workspace_bytes, hipStream_t st, const float *faces_z_ref, const float *textures, float *rgb_map,
                 const float *background, int bg_per_batch, float *alpha_map, int ts, double eps, int fix_batch_z,
-                int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr)
+                int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr, bool corner = false)
 {
     if (!faces || !face_index_map) return NR_E_NULL;
     if (int e = check_sizes(B, F, S)) return e;
@@ -861,12 +879,15 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
         ResolveArgsUV rau;
         static_cast<ResolveArgs &>(rau) = ra;
         rau.uv = *uv;
-        if (quads) hipLaunchKernelGGL(k_resolve_quads<true>, grid, dim3(256), 0, st, rau);
-        else hipLaunchKernelGGL(k_resolve<true>, grid, dim3(256), 0, st, rau);
+        if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_UV>, grid, dim3(256), 0, st, rau);
+        else hipLaunchKernelGGL(k_resolve<SHADE_UV>, grid, dim3(256), 0, st, rau);
+    } else if (corner) {  // corner colours (nr_forward_rasterize_corner): ra.textures = corner_colors [B, F, 3, 3]
+        if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
+        else hipLaunchKernelGGL(k_resolve<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
     } else if (quads) {
-        hipLaunchKernelGGL(k_resolve_quads<false>, grid, dim3(256), 0, st, ra);
+        hipLaunchKernelGGL(k_resolve_quads<SHADE_CUBE>, grid, dim3(256), 0, st, ra);
     } else {
-        hipLaunchKernelGGL(k_resolve<false>, grid, dim3(256), 0, st, ra);
+        hipLaunchKernelGGL(k_resolve<SHADE_CUBE>, grid, dim3(256), 0, st, ra);
     }
     return launch_status();
 }
@@ -966,6 +987,19 @@ NR_API int nr_forward_rasterize_uv(const nr_face_light *lit, const nr_uv_images 
     return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
                        workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr, rgb_map, background,
                        bg_per_batch, alpha_map, us.ts, eps, 1, flags, fl, &us);
+}
+
+// Corner colours (include/nr_hip.h; DESIGN K10 "Vertex colours"): the resolve pass's third shading mode.
+NR_API int nr_forward_rasterize_corner(const float *corner_colors, const float *faces, int32_t *face_index_map,
+                                       float *weight_map, float *depth_map, float *rgb_map, float *alpha_map,
+                                       uint8_t *visible_faces, const float *background, int32_t bg_per_batch, int32_t B,
+                                       int32_t F, int32_t S, double near, double far, int32_t flags, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    if (!corner_colors || !rgb_map || !background) return NR_E_NULL;
+    return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
+                       workspace, workspace_bytes, (hipStream_t)stream, nullptr, corner_colors, rgb_map, background,
+                       bg_per_batch, alpha_map, 2, 0.0, 1, flags, FaceLight(), nullptr, true);
 }
 
 NR_API int nr_forward_texture_sampling(const float *faces, const float *faces_z_ref, const float *textures,

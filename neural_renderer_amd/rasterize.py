@@ -20,6 +20,7 @@ import torch
 
 from . import _lib
 from .uv_textures import UVImages, pack_images
+from .vertex_colors import CornerColors
 
 DEFAULT_IMAGE_SIZE = 256
 DEFAULT_ANTI_ALIASING = True
@@ -186,10 +187,11 @@ class _Config(object):
 class _Residuals(object):
     """Everything one forward leaves behind for its backward (the reference keeps the same on `self`, rasterize.py:39-58)."""
     __slots__ = ('B', 'F', 'S', 'ts', 'Nf', 'flags', 'faces', 'textures', 'light', 'z_ref', 'face_index_map', 'weight_map',
-                 'depth_map', 'rgb_map', 'alpha_map', 'visible', 'uv', 'packed')
+                 'depth_map', 'rgb_map', 'alpha_map', 'visible', 'uv', 'packed', 'corner')
 
     def __init__(self):
         self.uv = self.packed = None  # per-pixel UV images: the UVImages and their packing [Bi,P,3]
+        self.corner = None            # corner colours [B,F,3,3] (CornerColors)
 
 
 def _check_inputs(cfg, faces, textures, light):
@@ -217,6 +219,17 @@ def _check_inputs(cfg, faces, textures, light):
                              % (B, textures.image_batch))
         if textures.device != faces.device or light.device != faces.device:
             raise ValueError('UVImages: images, face_light and faces must be on one device')
+    elif cfg.return_rgb and isinstance(textures, CornerColors):  # three lit colours per face: no light, no cubes
+        cc = textures.colors
+        if light is not None:
+            raise ValueError('CornerColors are already lit: face_light does not apply')
+        if not cc.is_cuda or cc.device != faces.device:
+            raise ValueError('CornerColors: colors and faces must be on one GPU (%s, %s)' % (cc.device, faces.device))
+        if int(cc.shape[0]) != B:
+            raise ValueError('CornerColors: batch size %d, the faces have %d' % (cc.shape[0], B))
+        if int(cc.shape[1]) != F:
+            raise ValueError('CornerColors: %d faces, the call has %d (with fill_back the reversed copies carry their own '
+                             'colours: twice the mesh\'s faces)' % (cc.shape[1], F))
     elif cfg.return_rgb:
         if textures is None:
             raise ValueError('textures are required when return_rgb is set')
@@ -248,7 +261,9 @@ def _forward_impl(cfg, faces, textures, light, packed=None):
     r.faces = faces.detach().contiguous()  # rasterize.py:470
     if return_rgb and isinstance(textures, UVImages):
         r.uv, r.packed, textures = textures, packed.detach(), None
-    r.textures = textures.detach().contiguous() if (return_rgb and r.uv is None) else None  # :473
+    elif return_rgb and isinstance(textures, CornerColors):
+        r.corner, textures = textures.colors.detach().contiguous(), None
+    r.textures = textures.detach().contiguous() if (return_rgb and textures is not None) else None  # :473
     r.light = light.detach().contiguous() if (return_rgb and light is not None) else None
     with _on_device(dev):
         stream = _stream_ptr(dev)
@@ -296,6 +311,13 @@ def _forward_impl(cfg, faces, textures, light, packed=None):
                 cfg.near, cfg.far, cfg.eps, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace.data_ptr(),
                 ws_bytes, stream), 'nr_forward_rasterize_uv')
             return r
+        if r.corner is not None:  # corner colours: the same pass, interpolating the face's three colours
+            _lib.check(lib.nr_forward_rasterize_corner(
+                r.corner.data_ptr(), r.faces.data_ptr(), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
+                r.rgb_map.data_ptr(), ptr(r.alpha_map), r.visible.data_ptr(), background.data_ptr(), bg_per_batch, B, F, S,
+                cfg.near, cfg.far, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace.data_ptr(), ws_bytes,
+                stream), 'nr_forward_rasterize_corner')
+            return r
         # visibility + shading behind one call (rasterize.py:499-502).  weight_map is a residual only (the backward reads it at
         # covered pixels): the zeros of uncovered pixels are not stored (NR_FLAG_SPARSE_WEIGHT_MAP; `Rasterize.weight_map`
         # fills them in when somebody reads the attribute)
@@ -323,7 +345,8 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
     """backward_gpu (rasterize.py:849-889): K6 -> K7 -> K8 behind one C-ABI call.  `None` gradients are zeros (:858-878); a
     zero gradient adds exactly 0 to every `diff_grad`, so the corresponding term is skipped instead of being multiplied out.
     Returns (grad_faces, grad_textures | None, grad_light | None); with per-pixel UV images (r.uv) grad_textures is the
-    gradient of the packed images [Bi,P,3] (nr_backward_uv_images)."""
+    gradient of the packed images [Bi,P,3] (nr_backward_uv_images), with corner colours (r.corner) their gradient [B,F,3,3]
+    (nr_backward_corner_colors)."""
     lib = _lib.load()
     B, F, S, ts = r.B, r.F, r.S, r.ts
     use_rgb = cfg.return_rgb and g_rgb is not None
@@ -342,7 +365,8 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
         lit = None
         f32 = torch.float32
         uv = getattr(r, 'uv', None)
-        if uv is not None:
+        corner = getattr(r, 'corner', None)
+        if uv is not None or corner is not None:
             pass  # grad_faces below with lit = NULL and no grad_textures (K6 + K8), the images' and colours' after it
         elif use_rgb and r.light is not None:
             if want_textures or want_light:
@@ -377,13 +401,21 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
                 _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grad_light)), _uv_struct(r), r.faces.data_ptr(),
                 r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(), g_rgb.data_ptr(),
                 ptr(grad_textures), B, F, S, cfg.eps, ws2.data_ptr(), ws_uv, stream), 'nr_backward_uv_images')
+        if corner is not None and use_rgb and want_textures:
+            grad_textures = torch.empty_like(corner)
+            ws_cc = lib.nr_backward_corner_colors_workspace_bytes(B, F)
+            ws2 = torch.empty((max(ws_cc, 1),), dtype=torch.uint8, device=dev)
+            _lib.check(lib.nr_backward_corner_colors(
+                r.faces.data_ptr(), r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(),
+                g_rgb.data_ptr(), ptr(r.visible), grad_textures.data_ptr(), B, F, S, ws2.data_ptr(), ws_cc, stream),
+                'nr_backward_corner_colors')
     owner = cfg.owner()
     if owner is not None:  # rasterize.py:41-51: the gradient buffers stay readable on the instance
         owner.grad_rgb_map, owner.grad_alpha_map, owner.grad_depth_map = g_rgb, g_alpha, g_depth
         # (aliases, not the returned tensors themselves: a second reference to a returned gradient makes autograd's
         # AccumulateGrad clone it instead of adopting it -- two device copies, 41 MB per step at the headline size)
         owner.grad_faces = grad_faces.detach()
-        owner.grad_textures = grad_textures.detach() if (grad_textures is not None and uv is None) else None
+        owner.grad_textures = grad_textures.detach() if (grad_textures is not None and uv is None and corner is None) else None
     return grad_faces, grad_textures, grad_light
 
 
@@ -471,6 +503,40 @@ class _UVRasterizeFunction(torch.autograd.Function):
                     g = g[0] if batch is None else g.sum(0)
                 grads[m] = g
         return (gf, gl if need[1] else None, None, None) + tuple(grads)
+
+
+class _CornerRasterizeFunction(torch.autograd.Function):
+    """Corner colours (include/nr_hip.h: nr_forward_rasterize_corner / nr_backward_corner_colors).
+    forward(ctx, faces, colors [B,F,3,3], cfg) -> (rgb_map, alpha_map | None, depth_map | None, face_index_map);
+    backward -> (grad_faces, grad_colors, None).  grad_faces comes from the rasterizer's own backward (K6 + K8, no texture
+    stage).  Always eager, like _UVRasterizeFunction."""
+
+    @staticmethod
+    def forward(ctx, faces, colors, cfg):
+        r = _forward_impl(cfg, faces, CornerColors(colors), None)
+        owner = cfg.owner()
+        if owner is not None:
+            owner._keep(r)
+        ctx.cfg = cfg
+        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
+        ctx.z_ref, ctx.visible = r.z_ref, r.visible
+        ctx.set_materialize_grads(False)
+        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.corner)
+        ctx.mark_non_differentiable(r.face_index_map)
+        return (r.rgb_map, r.alpha_map if cfg.return_alpha else None, r.depth_map if cfg.return_depth else None,
+                r.face_index_map)
+
+    @staticmethod
+    def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
+        r = _Residuals()
+        r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
+        r.z_ref, r.visible, r.textures, r.light = ctx.z_ref, ctx.visible, None, None
+        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.corner = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        gf, gc, _ = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, need[1], False)
+        if need[1] and gc is None and g_rgb is not None:
+            gc = torch.zeros_like(r.corner)
+        return (gf if need[0] else None), (gc if need[1] else None), None
 
 
 def _capture(fn, dev):
@@ -814,6 +880,9 @@ class Rasterize(object):
         if isinstance(textures, UVImages):
             raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
                                       '(fn(faces, uv_images, face_light)), which records the autograd graph')
+        if isinstance(textures, CornerColors):
+            raise NotImplementedError('forward_gpu / backward_gpu do not take CornerColors: call the Rasterize instance '
+                                      'itself (fn(faces, corner_colors)), which records the autograd graph')
         r = _forward_impl(_Config(self), faces, textures, face_light if self.return_rgb else None)
         self._keep(r)
         return (r.rgb_map if self.return_rgb else None, r.alpha_map if self.return_alpha else None,
@@ -829,6 +898,9 @@ class Rasterize(object):
         if len(inputs) > 1 and isinstance(inputs[1], UVImages) or (r is not None and r.uv is not None):
             raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
                                       '(fn(faces, uv_images, face_light)), which records the autograd graph')
+        if len(inputs) > 1 and isinstance(inputs[1], CornerColors) or (r is not None and r.corner is not None):
+            raise NotImplementedError('forward_gpu / backward_gpu do not take CornerColors: call the Rasterize instance '
+                                      'itself (fn(faces, corner_colors)), which records the autograd graph')
         if r is None:
             raise RuntimeError('backward_gpu before forward_gpu')
         g_rgb, g_alpha, g_depth = (tuple(grad_outputs) + (None, None, None))[:3]
@@ -856,6 +928,11 @@ class Rasterize(object):
             if face_light is None:
                 raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
             rgb, alpha, depth, _ = _UVRasterizeFunction.apply(faces, face_light, cfg, textures, *textures.images)
+            return rgb, alpha, depth
+        if isinstance(textures, CornerColors):  # (not in the reference) three lit colours per face, eager like UVImages
+            if face_light is not None:
+                raise ValueError('CornerColors are already lit: face_light does not apply')
+            rgb, alpha, depth, _ = _CornerRasterizeFunction.apply(faces, textures.colors, cfg)
             return rgb, alpha, depth
         if self.graph_replay and face_light is None:
             entry = _graph_entry(faces, textures, cfg)
@@ -896,7 +973,8 @@ def rasterize_rgbad(
 
     Returns a dict with 'rgb' [B, 3, image_size, image_size], 'alpha' and 'depth' [B, image_size, image_size]
     (None when not requested).  `faces_z_ref` (not in the reference): see Rasterize.faces_z_ref; `face_light` (not in the
-    reference): see Rasterize.__call__; `textures` may be a UVImages (not in the reference), with `face_light`."""
+    reference): see Rasterize.__call__; `textures` may be a UVImages (not in the reference), with `face_light`, or a
+    CornerColors (not in the reference; vertex_colors.py), without."""
     inputs = [faces] if textures is None else [faces, textures, face_light]
     size = image_size * 2 if anti_aliasing else image_size  # 2x super-sampling, :945-951
     fn = Rasterize(size, near, far, eps, background_color, return_rgb, return_alpha, return_depth)

@@ -18,6 +18,7 @@ from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
 from .uv_textures import UVImages
+from .vertex_colors import VertexColors, vertex_shade
 from .vertices_to_faces import vertices_to_faces
 
 # Renderer.face_light default (see the attribute): NR_FACE_LIGHT = 0 | 1 | auto
@@ -85,6 +86,11 @@ class Renderer(object):
         # (texture_size >= 3).  Needs the fused front-end and no graph replay; otherwise, and with False,
         # the lit-texture path runs.  Default: NR_FACE_LIGHT (auto).
         self.face_light = FACE_LIGHT
+        # not in the reference: where render() computes the light -- 'flat': one colour per face (lighting.py), 'smooth': at
+        # the vertices, from the area-weighted normals of their faces, interpolated over the triangle (Gouraud shading).
+        # 'smooth' needs vertex colours (render(vertices, faces, VertexColors(c)), vertex_colors.py); render_silhouettes and
+        # render_depth ignore the attribute.
+        self.shading = 'flat'
 
     def _project(self, vertices, faces):
         """camera + perspective + gather (renderer.py:40-51, :60-71, :92-103)."""
@@ -167,9 +173,47 @@ class Renderer(object):
         return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                          self.background_color, face_light=light)
 
+    def _render_vertex_colors(self, vertices, faces, vc):
+        """render() with a VertexColors (not in the reference): vertex_shade lights the colours per corner, in world space,
+        the front-end projects the geometry, and the rasterizer interpolates the corner colours at every covered pixel.
+        Both pieces take their HIP kernels when the call fits them (`last_frontend` names the geometry's).  Runs eagerly:
+        graph_replay does not apply (a whole step can be captured with neural_renderer_amd.graph.capture once one eager
+        step has built the vertex adjacency table)."""
+        if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3):
+            raise ValueError('vertices must be a tensor [batch size, num of vertices, 3]')
+        if vc.num_vertices != vertices.shape[1]:
+            raise ValueError('VertexColors: %d colours for %d vertices' % (vc.num_vertices, vertices.shape[1]))
+        if vc.color_batch not in (1, vertices.shape[0]):
+            raise ValueError('VertexColors: batched colours must have the batch size of the vertices (%d), got %d'
+                             % (vertices.shape[0], vc.color_batch))
+        if vc.device != vertices.device:
+            raise ValueError('VertexColors: colours on %s, vertices on %s' % (vc.device, vertices.device))
+        fused = frontend.fusable(self, vertices, faces, None) and frontend.light_fusable(self)
+        corner = vertex_shade(vertices, faces, vc.colors, self.light_intensity_ambient, self.light_intensity_directional,
+                              self.light_color_ambient, self.light_color_directional, self.light_direction,
+                              fill_back=self.fill_back, smooth=self.shading == 'smooth',
+                              implementation=None if fused else 'torch')
+        self.last_frontend = 'fused' if fused else 'torch'
+        self.frontend_calls[self.last_frontend] += 1
+        if fused:
+            faces, _ = frontend.project_and_light(self, vertices, faces)
+        else:
+            if self.fill_back:  # renderer.py:37-38
+                faces = torch.cat((faces, torch.flip(faces, dims=[2])), dim=1).detach()
+            faces = self._project(vertices, faces)
+        return rasterize(faces, corner, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                         self.background_color)
+
     def render(self, vertices, faces, textures):
         """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference, or (not in the reference) a UVImages whose images are
-        sampled at every covered pixel (uv_textures.py)."""
+        sampled at every covered pixel (uv_textures.py), or a VertexColors (vertex_colors.py), lit as `shading` says."""
+        if self.shading not in ('flat', 'smooth'):
+            raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+        if isinstance(textures, VertexColors):
+            return self._render_vertex_colors(vertices, faces, textures)
+        if self.shading == 'smooth':
+            raise ValueError("Renderer.shading = 'smooth' needs vertex colours (VertexColors): texture cubes and UVImages are "
+                             "lit per face ('flat') only")
         if isinstance(textures, UVImages):
             return self._render_uv(vertices, faces, textures)
         if self._use_face_light(vertices, faces, textures):
