@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .uv_textures import UVImages, pack_images
+from .uv_textures import UVImages, pack_images, unpack_image_gradients
 from .vertex_colors import CornerColors
 
 DEFAULT_IMAGE_SIZE = 256
@@ -139,14 +139,14 @@ def clear_workspace_cache():
 
 
 def _forward_workspace(lib, dev, stream, B, F, S):
-    """(workspace tensor, bytes, flags) for one forward call.  A kept workspace is refilled with 0xff every 255 calls.  While
+    """(workspace tensor, flags) for one forward call.  A kept workspace is refilled with 0xff every 255 calls.  While
     a HIP graph is being captured the epoch would be frozen into the graph, so capture takes a throw-away workspace and the
     filling path."""
     ws_bytes = lib.nr_forward_workspace_bytes(B, F, S)
     if ws_bytes == 0:
         raise ValueError('unsupported sizes B=%d F=%d S=%d' % (B, F, S))
     if F >= (1 << 24) or 2 * ws_bytes > _ZBUF_CACHE_BYTES or torch.cuda.is_current_stream_capturing():
-        return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev), ws_bytes, 0
+        return torch.empty((ws_bytes,), dtype=torch.uint8, device=dev), 0
     # (the calling THREAD is part of the key: the epochs of a workspace must reach the stream in the order they were handed out
     # -- a call launched later with the larger epoch of an earlier hand-out would lose every atomic minimum against the words of
     # the call in front of it -- and within one host thread hand-out order is launch order; two threads rendering the same shapes
@@ -166,7 +166,7 @@ def _forward_workspace(lib, dev, stream, B, F, S):
             ent[1] = 254
         epoch = ent[1]
         ent[1] -= 1
-    return ent[0], ws_bytes, _lib.NR_FLAG_ZBUF_EPOCH | (epoch << 8)
+    return ent[0], _lib.NR_FLAG_ZBUF_EPOCH | (epoch << 8)
 
 
 class _Config(object):
@@ -185,52 +185,73 @@ class _Config(object):
 
 
 class _Residuals(object):
-    """Everything one forward leaves behind for its backward (the reference keeps the same on `self`, rasterize.py:39-58)."""
-    __slots__ = ('B', 'F', 'S', 'ts', 'Nf', 'flags', 'faces', 'textures', 'light', 'z_ref', 'face_index_map', 'weight_map',
-                 'depth_map', 'rgb_map', 'alpha_map', 'visible', 'uv', 'packed', 'corner')
+    """Everything one forward leaves behind for its backward (the reference keeps the same on `self`, rasterize.py:39-58).
+    `source` is the call's shading source; textures / light / packed / corner are what that source keeps (the rest None)."""
+    __slots__ = ('B', 'F', 'S', 'ts', 'Nf', 'flags', 'faces', 'z_ref', 'face_index_map', 'weight_map', 'depth_map',
+                 'rgb_map', 'alpha_map', 'visible', 'source', 'textures', 'light', 'packed', 'corner')
 
     def __init__(self):
-        self.uv = self.packed = None  # per-pixel UV images: the UVImages and their packing [Bi,P,3]
-        self.corner = None            # corner colours [B,F,3,3] (CornerColors)
+        self.textures = self.light = None  # cubes [B,Nf,ts,ts,ts,3]; per-face light colours [B,F,3]
+        self.packed = None                 # per-pixel UV images: their packing [Bi,P,3]
+        self.corner = None                 # corner colours [B,F,3,3]
 
 
-def _check_inputs(cfg, faces, textures, light):
-    """Type / shape checks of rasterize.py:66-90 (+ the face_light extension).  Returns (B, F, Nf, ts)."""
-    if not faces.is_cuda:
-        raise NotImplementedError('neural_renderer_amd has no CPU rasterizer (neither has the reference: '
-                                  'rasterize.py:893-897)')
-    if faces.dtype != torch.float32 or faces.dim() != 4 or tuple(faces.shape[2:]) != (3, 3):
-        raise ValueError('faces must be float32 [batch size, num of faces, 3, 3], got %s %s'
-                         % (faces.dtype, tuple(faces.shape)))
-    B, F = int(faces.shape[0]), int(faces.shape[1])
-    Nf, ts = F, 0
-    if cfg.return_rgb and isinstance(textures, UVImages):  # per-pixel UV images: per-face light colours required
-        Nf, ts = textures.layout.num_faces, textures.layout.texture_size
-        if light is None:
-            raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
-        if light.dtype != torch.float32 or tuple(light.shape) != (B, F, 3) or not light.is_cuda:
-            raise ValueError('face_light must be float32 [batch size, num of faces, 3] on the GPU, got %s %s'
-                             % (light.dtype, tuple(light.shape)))
-        if F not in (Nf, 2 * Nf):
-            raise ValueError('UVImages: the layout has %d faces, the call %d (the layout\'s, or twice that with fill_back)'
-                             % (Nf, F))
-        if textures.image_batch not in (1, B):
-            raise ValueError('UVImages: batched images must have the batch size of the faces (%d), got %d'
-                             % (B, textures.image_batch))
-        if textures.device != faces.device or light.device != faces.device:
-            raise ValueError('UVImages: images, face_light and faces must be on one device')
-    elif cfg.return_rgb and isinstance(textures, CornerColors):  # three lit colours per face: no light, no cubes
-        cc = textures.colors
-        if light is not None:
-            raise ValueError('CornerColors are already lit: face_light does not apply')
-        if not cc.is_cuda or cc.device != faces.device:
-            raise ValueError('CornerColors: colors and faces must be on one GPU (%s, %s)' % (cc.device, faces.device))
-        if int(cc.shape[0]) != B:
-            raise ValueError('CornerColors: batch size %d, the faces have %d' % (cc.shape[0], B))
-        if int(cc.shape[1]) != F:
-            raise ValueError('CornerColors: %d faces, the call has %d (with fill_back the reversed copies carry their own '
-                             'colours: twice the mesh\'s faces)' % (cc.shape[1], F))
-    elif cfg.return_rgb:
+def _base_flags(cfg):
+    """The flags both directions of a call share (the forward adds its workspace's and the sparse weight map's)."""
+    flags = (_lib.NR_FLAG_FIX_TEXTURE_BATCH_Z if cfg.fix_batch_z else 0) | _BACKWARD_ORDER_FLAG
+    if cfg.exact_gradient:
+        flags |= _lib.NR_FLAG_EXACT_GRADIENT
+    return flags
+
+
+def _alloc_maps(r, cfg, dev):
+    """The output and residual maps of a call of r's sizes."""
+    B, F, S = r.B, r.F, r.S
+    need_wd = cfg.return_rgb or cfg.return_depth
+    i32, f32 = torch.int32, torch.float32
+    r.face_index_map = torch.empty((B, S, S), dtype=i32, device=dev)
+    r.weight_map = torch.empty((B, S, S, 3), dtype=f32, device=dev) if need_wd else None
+    r.depth_map = torch.empty((B, S, S), dtype=f32, device=dev) if need_wd else None
+    r.rgb_map = torch.empty((B, S, S, 3), dtype=f32, device=dev) if cfg.return_rgb else None
+    r.alpha_map = torch.empty((B, S, S), dtype=f32, device=dev) if cfg.return_alpha else None
+    # per-face "owns a pixel" flags: a residual the backward starts from (K6's lists; the depth-only gather skips the
+    # faces without a pixel)
+    r.visible = torch.empty((B, F), dtype=torch.uint8, device=dev)
+
+
+def _launch_forward(lib, cfg, r, background, bg_per_batch, flags, workspace, stream):
+    """The forward's one C-ABI call (visibility + shading, rasterize.py:499-502) into r's maps: the source's entry point around
+    the arguments every source shares.  The eager operator and graph replay both launch through here."""
+    ptr = _lib.ptr
+    maps = (r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map), ptr(r.rgb_map), ptr(r.alpha_map),
+            r.visible.data_ptr(), ptr(background), bg_per_batch, r.B, r.F, r.S)
+    r.source.forward(lib, cfg, r, maps, (flags, workspace.data_ptr(), workspace.numel(), stream))
+
+
+def _launch_backward(lib, cfg, r, lit, grad_textures, g_rgb, g_alpha, g_depth, grad_faces, workspace, ws_bytes, stream):
+    """K6 -> K7 -> K8 (rasterize.py:881-883) behind one C-ABI call, from r's maps.  A gradient that is None is zeros: its terms
+    are skipped.  `lit` / `grad_textures`: the texture stage of the cubes (None: grad_faces alone, K6 + K8)."""
+    ptr = _lib.ptr
+    _lib.check(lib.nr_backward_rasterize_lit(
+        lit, r.faces.data_ptr(), ptr(r.z_ref), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
+        ptr(r.rgb_map) if g_rgb is not None else None, ptr(r.alpha_map) if g_alpha is not None else None, ptr(g_rgb),
+        ptr(g_alpha), ptr(g_depth), grad_faces.data_ptr(), ptr(grad_textures), r.B, r.F, r.S, r.ts, cfg.eps, r.flags,
+        ptr(r.visible), workspace.data_ptr(), ws_bytes, stream), 'nr_backward_rasterize')
+
+
+class _Cubes(object):
+    """Shading source: texture cubes [B,Nf,ts,ts,ts,3] as in the reference (None when no rgb is drawn), alone or with per-face
+    light colours [B,F,3] (F = Nf or 2 Nf; include/nr_hip.h: nr_face_light).  Inputs of the autograd node: (textures, light).
+
+    A shading source is everything the operator does differently for one kind of `textures`; _source_of picks it, and the
+    operator asks it for: `check` (the input checks -> Nf, ts), `keep` (the residuals of the inputs), `saved` / `restore`
+    (which of them go through save_for_backward), `forward` (the C call) and `backward` (the rasterizer's backward plus the
+    source's colour gradient -> one gradient per input)."""
+    def check(self, cfg, faces, B, F, inputs):
+        textures, light = inputs
+        Nf = F
+        if not cfg.return_rgb:
+            return Nf, 0
         if textures is None:
             raise ValueError('textures are required when return_rgb is set')
         if light is not None:
@@ -244,139 +265,257 @@ def _check_inputs(cfg, faces, textures, light):
                 sh[2] != sh[3] or sh[3] != sh[4] or sh[5] != 3):
             raise ValueError('textures must be float32 [batch size, num of faces, ts, ts, ts, 3] with ts >= 2, '
                              'got %s %s' % (textures.dtype, tuple(sh)))  # rasterize.py:78-90
-        ts = int(sh[2])
-    return B, F, Nf, ts
+        return Nf, int(sh[2])
+
+    def keep(self, r, inputs):
+        textures, light = inputs
+        r.textures = textures.detach().contiguous() if textures is not None else None  # rasterize.py:473
+        r.light = light.detach().contiguous() if light is not None else None
+
+    def saved(self, r):
+        return (r.textures if r.light is not None else None), r.light  # (the backward reads the cubes only with light)
+
+    def restore(self, r, saved):
+        r.textures, r.light = saved
+
+    def forward(self, lib, cfg, r, maps, tail):
+        # weight_map is a residual only (the backward reads it at covered pixels): the eager operator does not store the zeros
+        # of uncovered pixels (NR_FLAG_SPARSE_WEIGHT_MAP; `Rasterize.weight_map` fills them in when somebody reads the attribute)
+        lit = _lib.FaceLight(r.light.data_ptr(), r.Nf, None, None) if r.light is not None else None
+        _lib.check(lib.nr_forward_rasterize_lit(lit, r.faces.data_ptr(), _lib.ptr(r.z_ref), _lib.ptr(r.textures), *maps, r.ts,
+                                                cfg.near, cfg.far, cfg.eps, *tail), 'nr_forward_rasterize')
+
+    def backward(self, lib, cfg, r, want, call):
+        grad_textures = grad_light = lit = None
+        if call[0] is not None:  # a gradient of rgb_map: the texture stage (K7) runs inside the rasterizer's backward
+            B, F, ts = r.B, r.F, r.ts
+            f32, dev = torch.float32, r.faces.device
+            if r.light is not None:
+                if want[0] or want[1]:
+                    # one gather produces both (the colours' gradient is a by-product of the texel sums)
+                    grad_textures = torch.empty((B, r.Nf, ts, ts, ts, 3), dtype=f32, device=dev)
+                    if want[1]:
+                        grad_light = torch.empty((B, F, 3), dtype=f32, device=dev)
+                lit = _lib.FaceLight(r.light.data_ptr(), r.Nf, r.textures.data_ptr(), _lib.ptr(grad_light))
+            elif want[0]:
+                grad_textures = torch.empty((B, F, ts, ts, ts, 3), dtype=f32, device=dev)
+        _launch_backward(lib, cfg, r, lit, grad_textures, *call)
+        return grad_textures, grad_light
 
 
-def _forward_impl(cfg, faces, textures, light, packed=None):
-    """forward_gpu (rasterize.py:467-513): visibility + shading behind one C-ABI call.  Returns the residuals.  `textures`
-    may be a UVImages (with `light` and the images' packing `packed`): the per-pixel UV forward (nr_forward_rasterize_uv)."""
+class _UVSource(object):
+    """Shading source: a UVImages with per-face light colours [B,F,3] -- the images sampled at every covered pixel
+    (include/nr_hip.h: nr_forward_rasterize_uv / nr_backward_uv_images).  Inputs of the autograd node: (light, *images).
+    grad_faces comes from the rasterizer's own backward (K6 + K8, no texture stage), the images' and the colours' gradients
+    from nr_backward_uv_images.  Always eager: the operator's graph-replay mode does not apply (a whole step can still be
+    captured with neural_renderer_amd.graph)."""
+    name = 'UVImages'
+
+    def __init__(self, uv):
+        self.uv = uv
+
+    def check(self, cfg, faces, B, F, inputs):
+        uv, light = self.uv, inputs[0]
+        Nf = uv.layout.num_faces
+        if light.dtype != torch.float32 or tuple(light.shape) != (B, F, 3) or not light.is_cuda:
+            raise ValueError('face_light must be float32 [batch size, num of faces, 3] on the GPU, got %s %s'
+                             % (light.dtype, tuple(light.shape)))
+        if F not in (Nf, 2 * Nf):
+            raise ValueError('UVImages: the layout has %d faces, the call %d (the layout\'s, or twice that with fill_back)'
+                             % (Nf, F))
+        if uv.image_batch not in (1, B):
+            raise ValueError('UVImages: batched images must have the batch size of the faces (%d), got %d'
+                             % (B, uv.image_batch))
+        if uv.device != faces.device or light.device != faces.device:
+            raise ValueError('UVImages: images, face_light and faces must be on one device')
+        return Nf, uv.layout.texture_size
+
+    def keep(self, r, inputs):
+        r.light = inputs[0].detach().contiguous()
+        r.packed = pack_images(inputs[1:], self.uv.batch).detach()
+
+    def saved(self, r):
+        return r.light, r.packed
+
+    def restore(self, r, saved):
+        r.light, r.packed = saved
+
+    def _struct(self, r):
+        """struct nr_uv_images of the layout's device tables (uploaded once per device) and the call's packing."""
+        layout = self.uv.layout
+        st = layout._tensors(r.faces.device)
+        return _lib.UVImagesStruct(r.packed.data_ptr(), st['table'].data_ptr(), st['faces_uv'].data_ptr(),
+                                   st['face_image'].data_ptr(), st['base'].data_ptr(), layout.texture_size, layout.num_images,
+                                   layout.num_pixels, int(r.packed.shape[0]))
+
+    def forward(self, lib, cfg, r, maps, tail):
+        _lib.check(lib.nr_forward_rasterize_uv(_lib.FaceLight(r.light.data_ptr(), r.Nf, None, None), self._struct(r),
+                                               r.faces.data_ptr(), *maps, cfg.near, cfg.far, cfg.eps, *tail),
+                   'nr_forward_rasterize_uv')
+
+    def backward(self, lib, cfg, r, want, call):
+        _launch_backward(lib, cfg, r, None, None, *call)
+        g_rgb, stream = call[0], call[-1]
+        grads = [None] * len(want)
+        want_images = True in want[1:]
+        if g_rgb is None or not (want[0] or want_images):
+            return tuple(grads)
+        uv, B, F = self.uv, r.B, r.F
+        f32, dev, ptr = torch.float32, r.faces.device, _lib.ptr
+        Bi, P = int(r.packed.shape[0]), uv.layout.num_pixels
+        grad_packed = torch.empty((Bi, P, 3), dtype=f32, device=dev) if want_images else None
+        grads[0] = torch.empty((B, F, 3), dtype=f32, device=dev) if want[0] else None
+        ws_bytes = lib.nr_backward_uv_images_workspace_bytes(B, F, P, Bi)
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.nr_backward_uv_images(
+            _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grads[0])), self._struct(r), r.faces.data_ptr(),
+            r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(), g_rgb.data_ptr(),
+            ptr(grad_packed), B, F, r.S, cfg.eps, ws.data_ptr(), ws_bytes, stream), 'nr_backward_uv_images')
+        if want_images:
+            for m, (g, im) in enumerate(zip(unpack_image_gradients(uv.layout, grad_packed), uv.images), 1):
+                if want[m]:  # an image shared by the batch: one row when every image is shared, else the rows summed
+                    grads[m] = g if im.dim() == 4 else (g[0] if uv.batch is None else g.sum(0))
+        return tuple(grads)
+
+
+class _CornerSource(object):
+    """Shading source: corner colours [B,F,3,3], three lit colours per face interpolated at every covered pixel
+    (include/nr_hip.h: nr_forward_rasterize_corner / nr_backward_corner_colors).  Input of the autograd node: (colors,).
+    grad_faces comes from the rasterizer's own backward (K6 + K8, no texture stage).  Always eager, like _UVSource."""
+    name = 'CornerColors'
+
+    def check(self, cfg, faces, B, F, inputs):
+        cc = inputs[0]
+        if not cc.is_cuda or cc.device != faces.device:
+            raise ValueError('CornerColors: colors and faces must be on one GPU (%s, %s)' % (cc.device, faces.device))
+        if int(cc.shape[0]) != B:
+            raise ValueError('CornerColors: batch size %d, the faces have %d' % (cc.shape[0], B))
+        if int(cc.shape[1]) != F:
+            raise ValueError('CornerColors: %d faces, the call has %d (with fill_back the reversed copies carry their own '
+                             'colours: twice the mesh\'s faces)' % (cc.shape[1], F))
+        return F, 0
+
+    def keep(self, r, inputs):
+        r.corner = inputs[0].detach().contiguous()
+
+    def saved(self, r):
+        return r.corner,
+
+    def restore(self, r, saved):
+        r.corner, = saved
+
+    def forward(self, lib, cfg, r, maps, tail):
+        _lib.check(lib.nr_forward_rasterize_corner(r.corner.data_ptr(), r.faces.data_ptr(), *maps, cfg.near, cfg.far, *tail),
+                   'nr_forward_rasterize_corner')
+
+    def backward(self, lib, cfg, r, want, call):
+        _launch_backward(lib, cfg, r, None, None, *call)
+        g_rgb, stream = call[0], call[-1]
+        if g_rgb is None or not want[0]:
+            return None,
+        grad_colors = torch.empty_like(r.corner)
+        ws_bytes = lib.nr_backward_corner_colors_workspace_bytes(r.B, r.F)
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=r.faces.device)
+        _lib.check(lib.nr_backward_corner_colors(
+            r.faces.data_ptr(), r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(),
+            g_rgb.data_ptr(), _lib.ptr(r.visible), grad_colors.data_ptr(), r.B, r.F, r.S, ws.data_ptr(), ws_bytes, stream),
+            'nr_backward_corner_colors')
+        return grad_colors,
+
+
+_CUBES, _CORNER = _Cubes(), _CornerSource()
+
+
+def _no_protocol(name):
+    raise NotImplementedError('forward_gpu / backward_gpu do not take %s: call the Rasterize instance itself, which records '
+                              'the autograd graph' % name)
+
+
+def _source_of(textures, face_light, protocol=False):
+    """(shading source, the differentiable inputs it takes after `faces`) of a call -- the one place that looks at what
+    `textures` is.  `protocol`: the call comes through forward_gpu / backward_gpu, which take cubes only."""
+    if not isinstance(textures, (UVImages, CornerColors)):
+        return _CUBES, (textures, face_light)
+    if protocol:
+        _no_protocol(type(textures).__name__)
+    if isinstance(textures, UVImages):  # (not in the reference) images sampled per pixel: per-face light colours required
+        if face_light is None:
+            raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
+        return _UVSource(textures), (face_light,) + tuple(textures.images)
+    if face_light is not None:  # (not in the reference) three lit colours per face: no light, no cubes
+        raise ValueError('CornerColors are already lit: face_light does not apply')
+    return _CORNER, (textures.colors,)
+
+
+def _forward_impl(cfg, faces, src, inputs):
+    """forward_gpu (rasterize.py:467-513): visibility + shading behind one C-ABI call, for the shading source `src` and its
+    `inputs` (_source_of).  Returns the residuals."""
     lib = _lib.load()
-    B, F, Nf, ts = _check_inputs(cfg, faces, textures, light)
-    return_rgb, return_alpha, return_depth = cfg.return_rgb, cfg.return_alpha, cfg.return_depth
+    # type / shape checks of rasterize.py:66-90 (the source's: + the face_light, UVImages and CornerColors extensions)
+    if not faces.is_cuda:
+        raise NotImplementedError('neural_renderer_amd has no CPU rasterizer (neither has the reference: '
+                                  'rasterize.py:893-897)')
+    if faces.dtype != torch.float32 or faces.dim() != 4 or tuple(faces.shape[2:]) != (3, 3):
+        raise ValueError('faces must be float32 [batch size, num of faces, 3, 3], got %s %s'
+                         % (faces.dtype, tuple(faces.shape)))
+    B, F = int(faces.shape[0]), int(faces.shape[1])
+    Nf, ts = src.check(cfg, faces, B, F, inputs)
     dev = faces.device
     S = cfg.image_size
     r = _Residuals()
-    r.B, r.F, r.S, r.ts, r.Nf = B, F, S, ts, Nf
+    r.B, r.F, r.S, r.ts, r.Nf, r.source = B, F, S, ts, Nf, src
     r.faces = faces.detach().contiguous()  # rasterize.py:470
-    if return_rgb and isinstance(textures, UVImages):
-        r.uv, r.packed, textures = textures, packed.detach(), None
-    elif return_rgb and isinstance(textures, CornerColors):
-        r.corner, textures = textures.colors.detach().contiguous(), None
-    r.textures = textures.detach().contiguous() if (return_rgb and textures is not None) else None  # :473
-    r.light = light.detach().contiguous() if (return_rgb and light is not None) else None
+    src.keep(r, inputs)
     with _on_device(dev):
         stream = _stream_ptr(dev)
-        need_wd = return_rgb or return_depth
-        i32, f32 = torch.int32, torch.float32
-        r.face_index_map = torch.empty((B, S, S), dtype=i32, device=dev)
-        r.weight_map = torch.empty((B, S, S, 3), dtype=f32, device=dev) if need_wd else None
-        r.depth_map = torch.empty((B, S, S), dtype=f32, device=dev) if need_wd else None
-        workspace, ws_bytes, ws_flags = _forward_workspace(lib, dev, stream, B, F, S)
-        r.rgb_map = r.alpha_map = background = None
+        _alloc_maps(r, cfg, dev)
+        workspace, ws_flags = _forward_workspace(lib, dev, stream, B, F, S)
+        background = None
         bg_per_batch = 0
-        if return_rgb:
-            r.rgb_map = torch.empty((B, S, S, 3), dtype=f32, device=dev)
+        if cfg.return_rgb:
             bg = cfg.background_color
             if torch.is_tensor(bg):
-                background = bg.detach().to(device=dev, dtype=f32).contiguous()
+                background = bg.detach().to(device=dev, dtype=torch.float32).contiguous()
             else:
                 background = _background_tensor(bg, dev)
             if tuple(background.shape) == (B, 3):
                 bg_per_batch = 1  # rasterize.py:464-465
             elif tuple(background.shape) != (3,):
                 raise ValueError('background_color must have shape (3,) or (batch size, 3)')
-        if return_alpha:
-            r.alpha_map = torch.empty((B, S, S), dtype=f32, device=dev)
-        flags = (_lib.NR_FLAG_FIX_TEXTURE_BATCH_Z if cfg.fix_batch_z else 0) | _BACKWARD_ORDER_FLAG
-        if cfg.exact_gradient:
-            flags |= _lib.NR_FLAG_EXACT_GRADIENT
-        r.flags = flags
+        r.flags = _base_flags(cfg)
         # batch element 0 of the GLOBAL batch when this call holds a shard of it (SURVEY Q1, include/nr_hip.h)
         z_ref = cfg.faces_z_ref
         if z_ref is not None:
-            z_ref = z_ref.detach().to(device=dev, dtype=f32).contiguous()
+            z_ref = z_ref.detach().to(device=dev, dtype=torch.float32).contiguous()
             if tuple(z_ref.shape) != (F, 3, 3):
                 raise ValueError('faces_z_ref must have shape (num of faces, 3, 3), got %s' % (tuple(z_ref.shape),))
         r.z_ref = z_ref
-        # per-face "owns a pixel" flags: a residual the backward starts from (K6's lists; the depth-only gather skips the
-        # faces without a pixel)
-        r.visible = torch.empty((B, F), dtype=torch.uint8, device=dev)
-        ptr = _lib.ptr
-        lit = _lib.FaceLight(r.light.data_ptr(), Nf, None, None) if r.light is not None else None
-        if r.uv is not None:  # per-pixel UV images: the same pass, with the images' lookup in the shading
-            _lib.check(lib.nr_forward_rasterize_uv(
-                lit, _uv_struct(r), r.faces.data_ptr(), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
-                r.rgb_map.data_ptr(), ptr(r.alpha_map), r.visible.data_ptr(), background.data_ptr(), bg_per_batch, B, F, S,
-                cfg.near, cfg.far, cfg.eps, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace.data_ptr(),
-                ws_bytes, stream), 'nr_forward_rasterize_uv')
-            return r
-        if r.corner is not None:  # corner colours: the same pass, interpolating the face's three colours
-            _lib.check(lib.nr_forward_rasterize_corner(
-                r.corner.data_ptr(), r.faces.data_ptr(), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
-                r.rgb_map.data_ptr(), ptr(r.alpha_map), r.visible.data_ptr(), background.data_ptr(), bg_per_batch, B, F, S,
-                cfg.near, cfg.far, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace.data_ptr(), ws_bytes,
-                stream), 'nr_forward_rasterize_corner')
-            return r
-        # visibility + shading behind one call (rasterize.py:499-502).  weight_map is a residual only (the backward reads it at
-        # covered pixels): the zeros of uncovered pixels are not stored (NR_FLAG_SPARSE_WEIGHT_MAP; `Rasterize.weight_map`
-        # fills them in when somebody reads the attribute)
-        _lib.check(lib.nr_forward_rasterize_lit(
-            lit, r.faces.data_ptr(), ptr(z_ref), ptr(r.textures), r.face_index_map.data_ptr(), ptr(r.weight_map),
-            ptr(r.depth_map), ptr(r.rgb_map), ptr(r.alpha_map), r.visible.data_ptr(), ptr(background), bg_per_batch,
-            B, F, S, ts, cfg.near, cfg.far, cfg.eps, flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP,
-            workspace.data_ptr(), ws_bytes, stream), 'nr_forward_rasterize')
+        _launch_forward(lib, cfg, r, background, bg_per_batch, r.flags | ws_flags | _lib.NR_FLAG_SPARSE_WEIGHT_MAP, workspace,
+                        stream)
     return r
-
-
-def _uv_struct(r):
-    """struct nr_uv_images of a call's UVImages (the layout's device tables, uploaded once per device) and packing."""
-    layout = r.uv.layout
-    st = layout._tensors(r.faces.device)
-    return _lib.UVImagesStruct(r.packed.data_ptr(), st['table'].data_ptr(), st['faces_uv'].data_ptr(),
-                               st['face_image'].data_ptr(), st['base'].data_ptr(), layout.texture_size, layout.num_images,
-                               layout.num_pixels, int(r.packed.shape[0]))
 
 
 _BWD_WS_BYTES = {}
 
 
-def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
-    """backward_gpu (rasterize.py:849-889): K6 -> K7 -> K8 behind one C-ABI call.  `None` gradients are zeros (:858-878); a
-    zero gradient adds exactly 0 to every `diff_grad`, so the corresponding term is skipped instead of being multiplied out.
-    Returns (grad_faces, grad_textures | None, grad_light | None); with per-pixel UV images (r.uv) grad_textures is the
-    gradient of the packed images [Bi,P,3] (nr_backward_uv_images), with corner colours (r.corner) their gradient [B,F,3,3]
-    (nr_backward_corner_colors)."""
+def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want):
+    """backward_gpu (rasterize.py:849-889).  `None` gradients are zeros (:858-878); a zero gradient adds exactly 0 to every
+    `diff_grad`, so the corresponding term is skipped instead of being multiplied out.  Returns (grad_faces, one gradient or
+    None per input of the call's shading source); `want` says which of those inputs ask for one."""
     lib = _lib.load()
-    B, F, S, ts = r.B, r.F, r.S, r.ts
+    B, F, S = r.B, r.F, r.S
     use_rgb = cfg.return_rgb and g_rgb is not None
     use_alpha = cfg.return_alpha and g_alpha is not None
     use_depth = cfg.return_depth and g_depth is not None
     if not (use_rgb or use_alpha or use_depth):
-        return None, None, None
+        return None, (None,) * len(want)
     dev = r.faces.device
-    grad_textures = grad_light = None
     with _on_device(dev):
         stream = _stream_ptr(dev)
         g_rgb = g_rgb.contiguous() if use_rgb else None
         g_alpha = g_alpha.contiguous() if use_alpha else None
         g_depth = g_depth.contiguous() if use_depth else None
         grad_faces = torch.empty_like(r.faces)  # stored by the library (zeros when neither rgb nor alpha)
-        lit = None
-        f32 = torch.float32
-        uv = getattr(r, 'uv', None)
-        corner = getattr(r, 'corner', None)
-        if uv is not None or corner is not None:
-            pass  # grad_faces below with lit = NULL and no grad_textures (K6 + K8), the images' and colours' after it
-        elif use_rgb and r.light is not None:
-            if want_textures or want_light:
-                # one gather produces both (the colours' gradient is a by-product of the texel sums)
-                grad_textures = torch.empty((B, r.Nf, ts, ts, ts, 3), dtype=f32, device=dev)
-                if want_light:
-                    grad_light = torch.empty((B, F, 3), dtype=f32, device=dev)
-            lit = _lib.FaceLight(r.light.data_ptr(), r.Nf, r.textures.data_ptr(), _lib.ptr(grad_light))
-        elif use_rgb and want_textures:
-            grad_textures = torch.empty((B, F, ts, ts, ts, 3), dtype=f32, device=dev)
         key = (B, F, S, use_rgb, use_alpha)
         ws_bytes = _BWD_WS_BYTES.get(key)
         if ws_bytes is None:
@@ -384,56 +523,29 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want_textures, want_light):
                 _BWD_WS_BYTES.clear()
             ws_bytes = _BWD_WS_BYTES[key] = lib.nr_backward_workspace_bytes(B, F, S, int(use_rgb), int(use_alpha))
         workspace = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-        ptr = _lib.ptr
-        # K6 -> K7 -> K8 (rasterize.py:881-883) behind one call
-        _lib.check(lib.nr_backward_rasterize_lit(
-            lit, r.faces.data_ptr(), ptr(r.z_ref), r.face_index_map.data_ptr(), ptr(r.weight_map), ptr(r.depth_map),
-            ptr(r.rgb_map) if use_rgb else None, ptr(r.alpha_map) if use_alpha else None, ptr(g_rgb), ptr(g_alpha),
-            ptr(g_depth), grad_faces.data_ptr(), ptr(grad_textures), B, F, S, ts, cfg.eps, r.flags, ptr(r.visible),
-            workspace.data_ptr(), ws_bytes, stream), 'nr_backward_rasterize')
-        if uv is not None and use_rgb and (want_textures or want_light):
-            Bi = int(r.packed.shape[0])
-            grad_textures = torch.empty((Bi, uv.layout.num_pixels, 3), dtype=f32, device=dev) if want_textures else None
-            grad_light = torch.empty((B, F, 3), dtype=f32, device=dev) if want_light else None
-            ws_uv = lib.nr_backward_uv_images_workspace_bytes(B, F, uv.layout.num_pixels, Bi)
-            ws2 = torch.empty((max(ws_uv, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_backward_uv_images(
-                _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grad_light)), _uv_struct(r), r.faces.data_ptr(),
-                r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(), g_rgb.data_ptr(),
-                ptr(grad_textures), B, F, S, cfg.eps, ws2.data_ptr(), ws_uv, stream), 'nr_backward_uv_images')
-        if corner is not None and use_rgb and want_textures:
-            grad_textures = torch.empty_like(corner)
-            ws_cc = lib.nr_backward_corner_colors_workspace_bytes(B, F)
-            ws2 = torch.empty((max(ws_cc, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_backward_corner_colors(
-                r.faces.data_ptr(), r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(),
-                g_rgb.data_ptr(), ptr(r.visible), grad_textures.data_ptr(), B, F, S, ws2.data_ptr(), ws_cc, stream),
-                'nr_backward_corner_colors')
+        grads = r.source.backward(lib, cfg, r, want, (g_rgb, g_alpha, g_depth, grad_faces, workspace, ws_bytes, stream))
     owner = cfg.owner()
     if owner is not None:  # rasterize.py:41-51: the gradient buffers stay readable on the instance
         owner.grad_rgb_map, owner.grad_alpha_map, owner.grad_depth_map = g_rgb, g_alpha, g_depth
         # (aliases, not the returned tensors themselves: a second reference to a returned gradient makes autograd's
         # AccumulateGrad clone it instead of adopting it -- two device copies, 41 MB per step at the headline size)
         owner.grad_faces = grad_faces.detach()
-        owner.grad_textures = grad_textures.detach() if (grad_textures is not None and uv is None and corner is None) else None
-    return grad_faces, grad_textures, grad_light
+        owner.grad_textures = grads[0].detach() if (r.source is _CUBES and grads[0] is not None) else None
+    return grad_faces, grads
 
 
 class _RasterizeFunction(torch.autograd.Function):
-    """forward(ctx, faces, textures, cfg, light) -> (rgb_map [B,S,S,3] | None, alpha_map [B,S,S] | None,
-    depth_map [B,S,S] | None, face_index_map); backward(ctx, g_rgb, g_alpha, g_depth, _) -> (grad_faces, grad_textures, None,
-    grad_light).  `light` [B,F,3] (or None): per-face light colours, textures are then the original cubes [B,Nf,...] with
-    F = Nf or 2 Nf (include/nr_hip.h: nr_face_light)."""
+    """forward(ctx, faces, cfg, source, *inputs) -> (rgb_map [B,S,S,3] | None, alpha_map [B,S,S] | None,
+    depth_map [B,S,S] | None, face_index_map); backward(ctx, g_rgb, g_alpha, g_depth, _) -> (grad_faces, None, None, one
+    gradient per input).  `source`, `inputs`: the call's shading source and its differentiable inputs (_source_of)."""
 
     @staticmethod
-    def forward(ctx, faces, textures, cfg, light=None):
-        if not cfg.return_rgb:
-            textures = light = None
-        r = _forward_impl(cfg, faces, textures, light)
+    def forward(ctx, faces, cfg, src, *inputs):
+        r = _forward_impl(cfg, faces, src, inputs)
         owner = cfg.owner()
         if owner is not None:
             owner._keep(r)
-        ctx.cfg = cfg
+        ctx.cfg, ctx.source = cfg, src
         # (the node must not hold its own OUTPUTS except through save_for_backward: output -> grad_fn -> node -> output is a
         # cycle through C++ that nothing collects -- every step's maps would stay allocated)
         ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
@@ -441,8 +553,7 @@ class _RasterizeFunction(torch.autograd.Function):
         ctx.set_materialize_grads(False)  # an unused output arrives as `None` in backward and its terms are skipped
         # residuals (the reference keeps them on `self`, rasterize.py:39-58); outputs and inputs among them go through
         # save_for_backward so that in-place edits by the caller are detected
-        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.textures if
-                              r.light is not None else None, r.light)
+        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, *src.saved(r))
         ctx.mark_non_differentiable(r.face_index_map)
         return (r.rgb_map if cfg.return_rgb else None, r.alpha_map if cfg.return_alpha else None,
                 r.depth_map if cfg.return_depth else None, r.face_index_map)
@@ -451,92 +562,13 @@ class _RasterizeFunction(torch.autograd.Function):
     def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
         r = _Residuals()
         r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
-        r.z_ref, r.visible = ctx.z_ref, ctx.visible
+        r.z_ref, r.visible, r.source = ctx.z_ref, ctx.visible, ctx.source
         # (unpacking checks the version counters of the saved tensors: an in-place edit since the forward raises)
-        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.textures, r.light = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        gf, gt, gl = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, need[1], need[3])
-        return gf, (gt if need[1] else None), None, gl
-
-
-class _UVRasterizeFunction(torch.autograd.Function):
-    """Per-pixel UV images (include/nr_hip.h: nr_forward_rasterize_uv / nr_backward_uv_images).
-    forward(ctx, faces, light, cfg, uv, *images) -> (rgb_map, alpha_map | None, depth_map | None, face_index_map);
-    backward -> (grad_faces, grad_light, None, None, one gradient per image tensor).  grad_faces comes from the rasterizer's
-    own backward (K6 + K8, no texture stage), the images' and the colours' from nr_backward_uv_images.  Always eager: the
-    operator's graph-replay mode does not apply (a whole step can still be captured with neural_renderer_amd.graph)."""
-
-    @staticmethod
-    def forward(ctx, faces, light, cfg, uv, *images):
-        packed = pack_images(images, uv.batch)
-        r = _forward_impl(cfg, faces, uv, light, packed)
-        owner = cfg.owner()
-        if owner is not None:
-            owner._keep(r)
-        ctx.cfg, ctx.uv = cfg, uv
-        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
-        ctx.z_ref, ctx.visible = r.z_ref, r.visible
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.light,
-                              r.packed)
-        ctx.mark_non_differentiable(r.face_index_map)
-        return (r.rgb_map, r.alpha_map if cfg.return_alpha else None, r.depth_map if cfg.return_depth else None,
-                r.face_index_map)
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
-        r = _Residuals()
-        r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
-        r.z_ref, r.visible, r.uv, r.textures = ctx.z_ref, ctx.visible, ctx.uv, None
-        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.light, r.packed = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        want_images = any(need[4:])
-        gf, gp, gl = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, want_images, need[1])
-        grads = [None] * len(ctx.uv.images)
-        if gp is not None:
-            layout, batch = ctx.uv.layout, ctx.uv.batch
-            for m, ((off, h, w), im) in enumerate(zip(layout.image_table.tolist(), ctx.uv.images)):
-                if not need[4 + m]:
-                    continue
-                g = gp[:, off:off + h * w].view(gp.shape[0], h, w, 3)
-                if im.dim() == 3:  # shared by the batch: one row when every image is shared, else the rows summed
-                    g = g[0] if batch is None else g.sum(0)
-                grads[m] = g
-        return (gf, gl if need[1] else None, None, None) + tuple(grads)
-
-
-class _CornerRasterizeFunction(torch.autograd.Function):
-    """Corner colours (include/nr_hip.h: nr_forward_rasterize_corner / nr_backward_corner_colors).
-    forward(ctx, faces, colors [B,F,3,3], cfg) -> (rgb_map, alpha_map | None, depth_map | None, face_index_map);
-    backward -> (grad_faces, grad_colors, None).  grad_faces comes from the rasterizer's own backward (K6 + K8, no texture
-    stage).  Always eager, like _UVRasterizeFunction."""
-
-    @staticmethod
-    def forward(ctx, faces, colors, cfg):
-        r = _forward_impl(cfg, faces, CornerColors(colors), None)
-        owner = cfg.owner()
-        if owner is not None:
-            owner._keep(r)
-        ctx.cfg = cfg
-        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
-        ctx.z_ref, ctx.visible = r.z_ref, r.visible
-        ctx.set_materialize_grads(False)
-        ctx.save_for_backward(r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.corner)
-        ctx.mark_non_differentiable(r.face_index_map)
-        return (r.rgb_map, r.alpha_map if cfg.return_alpha else None, r.depth_map if cfg.return_depth else None,
-                r.face_index_map)
-
-    @staticmethod
-    def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
-        r = _Residuals()
-        r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
-        r.z_ref, r.visible, r.textures, r.light = ctx.z_ref, ctx.visible, None, None
-        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map, r.corner = ctx.saved_tensors
-        need = ctx.needs_input_grad
-        gf, gc, _ = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, need[1], False)
-        if need[1] and gc is None and g_rgb is not None:
-            gc = torch.zeros_like(r.corner)
-        return (gf if need[0] else None), (gc if need[1] else None), None
+        saved = ctx.saved_tensors
+        r.faces, r.face_index_map, r.weight_map, r.depth_map, r.rgb_map, r.alpha_map = saved[:6]
+        r.source.restore(r, saved[6:])
+        gf, grads = _backward_impl(ctx.cfg, r, g_rgb, g_alpha, g_depth, ctx.needs_input_grad[3:])
+        return (gf, None, None) + grads
 
 
 def _capture(fn, dev):
@@ -548,29 +580,24 @@ def _capture(fn, dev):
 class _GraphEntry(object):
     """Fixed buffers + captured graphs of one (device, sizes, configuration) of the operator."""
 
-    def __init__(self, lib, dev, cfg, B, F, S, ts, bg, bg_per_batch, has_z_ref):
+    def __init__(self, lib, dev, cfg, B, F, S, ts, bg, bg_per_batch):
         self.lib, self.dev, self.cfg = lib, dev, cfg
-        self.dims = (B, F, S, ts)
         f32 = dict(dtype=torch.float32, device=dev)
-        rgb, alpha, depth = cfg.return_rgb, cfg.return_alpha, cfg.return_depth
-        need_wd = rgb or depth
-        self.faces = torch.zeros((B, F, 3, 3), **f32)
-        self.textures = torch.zeros((B, F, ts, ts, ts, 3), **f32) if rgb else None
-        self.z_ref = torch.zeros((F, 3, 3), **f32) if has_z_ref else None
+        # the residuals every replay writes and every backward reads: the eager operator's, in buffers that stay.  The
+        # z-buffer is filled by every call (a replayed epoch number would stand still) and weight_map is written densely:
+        # `Rasterize.weight_map` hands it out as it is
+        r = self.r = _Residuals()
+        r.B, r.F, r.S, r.ts, r.Nf, r.source, r.z_ref = B, F, S, ts, F, _CUBES, None
+        r.faces = torch.zeros((B, F, 3, 3), **f32)
+        r.textures = torch.zeros((B, F, ts, ts, ts, 3), **f32) if cfg.return_rgb else None
+        _alloc_maps(r, cfg, dev)
+        r.flags = _base_flags(cfg)
         self.background = bg.clone() if bg is not None else None
         self.bg_per_batch = bg_per_batch
-        self.face_index_map = torch.empty((B, S, S), dtype=torch.int32, device=dev)
-        self.weight_map = torch.empty((B, S, S, 3), **f32) if need_wd else None
-        self.depth_map = torch.empty((B, S, S), **f32) if need_wd else None
-        self.rgb_map = torch.empty((B, S, S, 3), **f32) if rgb else None
-        self.alpha_map = torch.empty((B, S, S), **f32) if alpha else None
-        self.visible = torch.empty((B, F), dtype=torch.uint8, device=dev)
         ws_bytes = lib.nr_forward_workspace_bytes(B, F, S)
         if ws_bytes == 0:
             raise ValueError('unsupported sizes B=%d F=%d S=%d' % (B, F, S))
         self.fwd_ws = torch.empty((ws_bytes,), dtype=torch.uint8, device=dev)
-        self.flags = (_lib.NR_FLAG_FIX_TEXTURE_BATCH_Z if cfg.fix_batch_z else 0) | _BACKWARD_ORDER_FLAG | \
-                     (_lib.NR_FLAG_EXACT_GRADIENT if cfg.exact_gradient else 0)
         self.generation = 0
         self.pending = None  # generation of the forward whose residuals the buffers hold and whose backward may still come
         self.bwd = {}        # (use_rgb, use_alpha, use_depth, want grad_textures) -> (graph, buffers)
@@ -579,17 +606,11 @@ class _GraphEntry(object):
             self.fwd = _capture(self._forward, dev)
 
     def _forward(self):
-        B, F, S, ts = self.dims
-        cfg = self.cfg
-        _lib.check(self.lib.nr_forward_rasterize(
-            self.faces.data_ptr(), _lib.ptr(self.z_ref), _lib.ptr(self.textures), self.face_index_map.data_ptr(),
-            _lib.ptr(self.weight_map), _lib.ptr(self.depth_map), _lib.ptr(self.rgb_map), _lib.ptr(self.alpha_map),
-            self.visible.data_ptr(), _lib.ptr(self.background), self.bg_per_batch, B, F, S, ts, cfg.near,
-            cfg.far, cfg.eps, self.flags, self.fwd_ws.data_ptr(), self.fwd_ws.numel(),
-            _stream_ptr(self.dev)), 'nr_forward_rasterize')
+        _launch_forward(self.lib, self.cfg, self.r, self.background, self.bg_per_batch, self.r.flags, self.fwd_ws,
+                        _stream_ptr(self.dev))
 
     def _backward_buffers(self, use_rgb, use_alpha, use_depth, want_gt):
-        B, F, S, ts = self.dims
+        B, F, S, ts = self.r.B, self.r.F, self.r.S, self.r.ts
         f32 = dict(dtype=torch.float32, device=self.dev)
         buf = {'g_rgb': torch.zeros((B, S, S, 3), **f32) if use_rgb else None,
                'g_alpha': torch.zeros((B, S, S), **f32) if use_alpha else None,
@@ -600,13 +621,8 @@ class _GraphEntry(object):
         buf['ws'] = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=self.dev)
 
         def run():
-            _lib.check(self.lib.nr_backward_rasterize(
-                self.faces.data_ptr(), _lib.ptr(self.z_ref), self.face_index_map.data_ptr(), _lib.ptr(self.weight_map),
-                _lib.ptr(self.depth_map), _lib.ptr(self.rgb_map) if use_rgb else None,
-                _lib.ptr(self.alpha_map) if use_alpha else None, _lib.ptr(buf['g_rgb']), _lib.ptr(buf['g_alpha']),
-                _lib.ptr(buf['g_depth']), buf['grad_faces'].data_ptr(), _lib.ptr(buf['grad_textures']), B, F, S, ts,
-                self.cfg.eps, self.flags, self.visible.data_ptr(), buf['ws'].data_ptr(), ws_bytes,
-                _stream_ptr(self.dev)), 'nr_backward_rasterize')
+            _launch_backward(self.lib, self.cfg, self.r, None, buf['grad_textures'], buf['g_rgb'], buf['g_alpha'],
+                             buf['g_depth'], buf['grad_faces'], buf['ws'], ws_bytes, _stream_ptr(self.dev))
         return run, buf
 
     def prepare_backward(self, key):
@@ -641,19 +657,19 @@ class _GraphedRasterizeFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, faces, textures, entry):
-        cfg = entry.cfg
-        entry.faces.copy_(faces.detach())
-        if entry.textures is not None:
-            entry.textures.copy_(textures.detach())
+        cfg, r = entry.cfg, entry.r
+        r.faces.copy_(faces.detach())
+        if r.textures is not None:
+            r.textures.copy_(textures.detach())
         entry.fwd()
         entry.generation += 1
         entry.pending = entry.generation
         ctx.entry, ctx.generation = entry, entry.generation
         ctx.set_materialize_grads(False)
-        fi = entry.face_index_map.clone()
+        fi = r.face_index_map.clone()
         ctx.mark_non_differentiable(fi)
-        return (entry.rgb_map.clone() if cfg.return_rgb else None, entry.alpha_map.clone() if cfg.return_alpha else None,
-                entry.depth_map.clone() if cfg.return_depth else None, fi)
+        return (r.rgb_map.clone() if cfg.return_rgb else None, r.alpha_map.clone() if cfg.return_alpha else None,
+                r.depth_map.clone() if cfg.return_depth else None, fi)
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
@@ -676,9 +692,13 @@ class _GraphedRasterizeFunction(torch.autograd.Function):
         return buf['grad_faces'].clone(), (buf['grad_textures'].clone() if want_gt else None), None
 
 
-def _graph_entry(faces, textures, cfg):
-    """The cached graphs for this call's device / sizes / configuration, or None when the call is not eligible (CPU tensors
-    raise in the eager operator; tensor-valued backgrounds or z references that change between calls are handled by value)."""
+def _graph_entry(faces, src, inputs, cfg):
+    """The cached graphs for this call's device / sizes / configuration, or None when the call is not eligible (replay knows
+    cubes without face_light only; CPU tensors raise in the eager operator; tensor-valued backgrounds or z references that
+    change between calls are handled by value)."""
+    if src is not _CUBES or inputs[1] is not None:
+        return None
+    textures = inputs[0]
     if not faces.is_cuda or faces.dtype != torch.float32 or faces.dim() != 4 or torch.cuda.is_current_stream_capturing():
         return None
     dev = faces.device
@@ -707,7 +727,7 @@ def _graph_entry(faces, textures, cfg):
     if entry is None:
         if len(_GRAPH_CACHE) >= 8:
             _GRAPH_CACHE.pop(next(iter(_GRAPH_CACHE)))
-        entry = _GRAPH_CACHE[key] = _GraphEntry(_lib.load(), dev, cfg, B, F, S, ts, bg, bg_per_batch, False)
+        entry = _GRAPH_CACHE[key] = _GraphEntry(_lib.load(), dev, cfg, B, F, S, ts, bg, bg_per_batch)
     return entry
 
 
@@ -877,13 +897,7 @@ class Rasterize(object):
         the maps on the instance for backward_gpu.  No autograd graph is recorded."""
         faces = inputs[0]
         textures = inputs[1] if len(inputs) > 1 and self.return_rgb else None
-        if isinstance(textures, UVImages):
-            raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
-                                      '(fn(faces, uv_images, face_light)), which records the autograd graph')
-        if isinstance(textures, CornerColors):
-            raise NotImplementedError('forward_gpu / backward_gpu do not take CornerColors: call the Rasterize instance '
-                                      'itself (fn(faces, corner_colors)), which records the autograd graph')
-        r = _forward_impl(_Config(self), faces, textures, face_light if self.return_rgb else None)
+        r = _forward_impl(_Config(self), faces, *_source_of(textures, face_light if self.return_rgb else None, protocol=True))
         self._keep(r)
         return (r.rgb_map if self.return_rgb else None, r.alpha_map if self.return_alpha else None,
                 r.depth_map if self.return_depth else None)
@@ -895,16 +909,13 @@ class Rasterize(object):
         (grad_faces,) or (grad_faces, grad_textures) like :886-889; with face_light also grad_light (third).  `inputs` is
         accepted for the protocol's sake: the residuals of the last forward_gpu are what is used."""
         r = self._res
-        if len(inputs) > 1 and isinstance(inputs[1], UVImages) or (r is not None and r.uv is not None):
-            raise NotImplementedError('forward_gpu / backward_gpu do not take UVImages: call the Rasterize instance itself '
-                                      '(fn(faces, uv_images, face_light)), which records the autograd graph')
-        if len(inputs) > 1 and isinstance(inputs[1], CornerColors) or (r is not None and r.corner is not None):
-            raise NotImplementedError('forward_gpu / backward_gpu do not take CornerColors: call the Rasterize instance '
-                                      'itself (fn(faces, corner_colors)), which records the autograd graph')
+        _source_of(inputs[1] if len(inputs) > 1 else None, None, protocol=True)
         if r is None:
             raise RuntimeError('backward_gpu before forward_gpu')
+        if r.source is not _CUBES:  # (the last forward was the instance's own call)
+            _no_protocol(r.source.name)
         g_rgb, g_alpha, g_depth = (tuple(grad_outputs) + (None, None, None))[:3]
-        gf, gt, gl = _backward_impl(_Config(self), r, g_rgb, g_alpha, g_depth, self.return_rgb, r.light is not None)
+        gf, (gt, gl) = _backward_impl(_Config(self), r, g_rgb, g_alpha, g_depth, (self.return_rgb, r.light is not None))
         if gf is None:  # no gradient at all: zeros (:851-853)
             gf = torch.zeros_like(r.faces)
         if not self.return_rgb or len(inputs) < 2:
@@ -924,18 +935,9 @@ class Rasterize(object):
         cfg = _Config(self)
         if not self.return_rgb:
             textures = face_light = None
-        if isinstance(textures, UVImages):
-            if face_light is None:
-                raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
-            rgb, alpha, depth, _ = _UVRasterizeFunction.apply(faces, face_light, cfg, textures, *textures.images)
-            return rgb, alpha, depth
-        if isinstance(textures, CornerColors):  # (not in the reference) three lit colours per face, eager like UVImages
-            if face_light is not None:
-                raise ValueError('CornerColors are already lit: face_light does not apply')
-            rgb, alpha, depth, _ = _CornerRasterizeFunction.apply(faces, textures.colors, cfg)
-            return rgb, alpha, depth
-        if self.graph_replay and face_light is None:
-            entry = _graph_entry(faces, textures, cfg)
+        src, inputs = _source_of(textures, face_light)
+        if self.graph_replay:
+            entry = _graph_entry(faces, src, inputs, cfg)
             if entry is not None:
                 if torch.is_grad_enabled() and (faces.requires_grad or (textures is not None and textures.requires_grad)):
                     # the usual case: every requested output receives a gradient
@@ -943,13 +945,14 @@ class Rasterize(object):
                                             bool(self.return_rgb and textures is not None and textures.requires_grad)))
                 rgb, alpha, depth, fi = _GraphedRasterizeFunction.apply(faces, textures, entry)
                 self._res, self._lazy = None, {}
-                self.faces, self.textures, self.weight_map = entry.faces, entry.textures, entry.weight_map  # (dense there)
-                self.depth_map = depth if depth is not None else entry.depth_map
+                r = entry.r
+                self.faces, self.textures, self.weight_map = r.faces, r.textures, r.weight_map  # (dense there)
+                self.depth_map = depth if depth is not None else r.depth_map
                 self.rgb_map, self.alpha_map, self.face_index_map = rgb, alpha, fi
-                self.batch_size, self.num_faces = entry.dims[0], entry.dims[1]
-                self.texture_size = entry.dims[3] if self.return_rgb else None
+                self.batch_size, self.num_faces = r.B, r.F
+                self.texture_size = r.ts if self.return_rgb else None
                 return rgb, alpha, depth
-        rgb, alpha, depth, _ = _RasterizeFunction.apply(faces, textures, cfg, face_light)
+        rgb, alpha, depth, _ = _RasterizeFunction.apply(faces, cfg, src, *inputs)
         return rgb, alpha, depth
 
 

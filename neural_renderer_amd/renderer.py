@@ -106,12 +106,15 @@ class Renderer(object):
             vertices = perspective(vertices, angle=self.viewing_angle)
         return vertices_to_faces(vertices, faces)
 
-    def _frontend_torch(self, vertices, faces, textures=None):
-        """Everything in front of the rasterizer, module by module as in the reference (renderer.py:37-51, :77-103)."""
+    def _frontend_torch(self, vertices, faces, textures=None, light_colors=False):
+        """Everything in front of the rasterizer, module by module as in the reference (renderer.py:37-51, :77-103).  With
+        `light_colors` (not in the reference) the second result is lighting()'s colour of every face, [B,F,3]."""
         if self.fill_back:  # renderer.py:37-38, :77-79
             faces = torch.cat((faces, torch.flip(faces, dims=[2])), dim=1).detach()
             if textures is not None:
                 textures = torch.cat((textures, textures.permute(0, 1, 4, 3, 2, 5)), dim=1)
+        if light_colors:  # the light of a white texel
+            textures = torch.ones(tuple(faces.shape[:2]) + (1, 1, 1, 3), dtype=torch.float32, device=vertices.device)
         if textures is not None:  # lighting in world space (renderer.py:82-90)
             faces_lighting = vertices_to_faces(vertices, faces)
             textures = lighting(
@@ -122,16 +125,24 @@ class Renderer(object):
                 self.light_color_ambient,
                 self.light_color_directional,
                 self.light_direction)
+        if light_colors:
+            textures = textures.reshape(textures.shape[0], -1, 3)
         return self._project(vertices, faces), textures
 
-    def _frontend(self, vertices, faces, textures=None):
-        """-> (faces [B,F,3,3], lit textures | None): the fused HIP front-end when the call fits it, else torch."""
-        fused = frontend.fusable(self, vertices, faces, textures)
+    def _frontend(self, vertices, faces, textures=None, light_colors=False, fused=None):
+        """-> (faces [B,F,3,3], what the rasterizer takes second: lit textures, with `light_colors` the per-face light colours
+        [B,F,3] for its face_light, else None): the fused HIP front-end when the call fits it (`fused`: the caller's answer
+        where it had to ask already), else torch.  Every render* comes through here, once, and only here are `last_frontend`
+        and `frontend_calls` written."""
+        if fused is None:
+            fused = frontend.fusable(self, vertices, faces, textures) and (not light_colors or frontend.light_fusable(self))
         self.last_frontend = 'fused' if fused else 'torch'
         self.frontend_calls[self.last_frontend] += 1
-        if fused:
-            return frontend.project_and_light(self, vertices, faces, textures)
-        return self._frontend_torch(vertices, faces, textures)
+        if not fused:
+            return self._frontend_torch(vertices, faces, textures, light_colors)
+        if light_colors:
+            return frontend.project_and_light_colors(self, vertices, faces)
+        return frontend.project_and_light(self, vertices, faces, textures)
 
     def render_silhouettes(self, vertices, faces):
         faces, _ = self._frontend(vertices, faces)
@@ -156,20 +167,7 @@ class Renderer(object):
         """render() with a UVImages: the images sampled at every covered pixel (not in the reference).  Per-face light colours
         always (face_light is implied): from the fused front-end when it takes the call, else from lighting() on a ones
         texture behind the module-by-module front-end.  Runs eagerly: graph_replay does not apply."""
-        if frontend.fusable(self, vertices, faces, None) and frontend.light_fusable(self):
-            self.last_frontend = 'fused'
-            faces, light = frontend.project_and_light_colors(self, vertices, faces)
-        else:
-            self.last_frontend = 'torch'
-            if self.fill_back:  # renderer.py:37-38
-                faces = torch.cat((faces, torch.flip(faces, dims=[2])), dim=1).detach()
-            B, F = faces.shape[:2]
-            ones = torch.ones((B, F, 1, 1, 1, 3), dtype=torch.float32, device=vertices.device)
-            light = lighting(vertices_to_faces(vertices, faces), ones, self.light_intensity_ambient,
-                             self.light_intensity_directional, self.light_color_ambient, self.light_color_directional,
-                             self.light_direction).reshape(B, F, 3)
-            faces = self._project(vertices, faces)
-        self.frontend_calls[self.last_frontend] += 1
+        faces, light = self._frontend(vertices, faces, light_colors=True)
         return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                          self.background_color, face_light=light)
 
@@ -193,14 +191,7 @@ class Renderer(object):
                               self.light_color_ambient, self.light_color_directional, self.light_direction,
                               fill_back=self.fill_back, smooth=self.shading == 'smooth',
                               implementation=None if fused else 'torch')
-        self.last_frontend = 'fused' if fused else 'torch'
-        self.frontend_calls[self.last_frontend] += 1
-        if fused:
-            faces, _ = frontend.project_and_light(self, vertices, faces)
-        else:
-            if self.fill_back:  # renderer.py:37-38
-                faces = torch.cat((faces, torch.flip(faces, dims=[2])), dim=1).detach()
-            faces = self._project(vertices, faces)
+        faces, _ = self._frontend(vertices, faces, fused=fused)
         return rasterize(faces, corner, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                          self.background_color)
 
@@ -217,9 +208,7 @@ class Renderer(object):
         if isinstance(textures, UVImages):
             return self._render_uv(vertices, faces, textures)
         if self._use_face_light(vertices, faces, textures):
-            self.last_frontend = 'fused'
-            self.frontend_calls['fused'] += 1
-            faces, light = frontend.project_and_light_colors(self, vertices, faces)
+            faces, light = self._frontend(vertices, faces, light_colors=True, fused=True)
             return rasterize(
                 faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                 self.background_color, faces_z_ref=self.faces_z_ref, face_light=light)

@@ -158,6 +158,12 @@ def pack_images(images, batch):
     return (flat[0] if len(flat) == 1 else torch.cat(flat, 1)).contiguous()
 
 
+def unpack_image_gradients(layout, grad_packed):
+    """A gradient of pack_images' packing [Bi,P,3] as one view [Bi,H_m,W_m,3] per image of the layout."""
+    Bi = grad_packed.shape[0]
+    return [grad_packed[:, off:off + h * w].view(Bi, h, w, 3) for off, h, w in layout.image_table.tolist()]
+
+
 class _BakeUV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layout, *images):
@@ -192,10 +198,7 @@ class _BakeUV(torch.autograd.Function):
                                                         layout.texture_size, P,
                                                         torch.cuda.current_stream(device).cuda_stream),
                        'nr_bake_uv_textures_backward')
-        grads = []
-        for off, h, w in layout.image_table.tolist():
-            grads.append(grad_packed[:, off:off + h * w].view(Bi, h, w, 3))
-        return (None,) + tuple(grads)
+        return (None,) + tuple(unpack_image_gradients(layout, grad_packed))
 
 
 def bake_uv_textures(images, layout):
