@@ -19,7 +19,11 @@ extern "C" {
  * nr_backward_rasterize[_lit] is bracketed by a pair of HIP events recorded on the call's stream (events of the library's own,
  * created on the first enable); nr_profile_band_kernel_ms() waits for the last pair and returns the time between them in
  * milliseconds (< 0: no launch was bracketed, or an event call failed).  That is the duration of the path's dominant kernel
- * alone, without the helper launches of its stage call, as `rocprofv3 --kernel-trace --stats` reports it.  Process-wide, not
+ * alone, without the helper launches of its stage call, as `rocprofv3 --kernel-trace --stats` reports it.  (A fused backward
+ * whose plan puts the K7 / K8 gather's workgroups behind the band kernel's in one grid -- k_band_gather, calls of more than
+ * 96 k faces with texture_size 2 -- has that MERGED launch bracketed: band kernel and gather together.  bench.py's
+ * `in_fused_backward_us` is then the merged launch's time; `avg_launch_us`, from nr_backward_pixel_map, stays k_bpm_row's.)
+ * Process-wide, not
  * thread-safe, and the two event packets cost the stream a few microseconds per call: off outside measurements. */
 int nr_profile_band_kernel(int32_t enable);
 float nr_profile_band_kernel_ms(void);

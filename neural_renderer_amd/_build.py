@@ -13,7 +13,7 @@ SOURCES = [os.path.join(HERE, 'csrc', n) for n in ('nr_forward.hip', 'nr_backwar
                                                       'nr_uv_pixel.hip', 'nr_vertex_colors.hip')]
 HEADERS = [os.path.join(os.path.dirname(HERE), 'include', 'nr_hip.h'), os.path.join(os.path.dirname(HERE), 'include', 'nr_hip_profile.h'),
            os.path.join(HERE, 'csrc', 'nr_device.h'),
-           os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h'),
+           os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h'), os.path.join(HERE, 'csrc', 'nr_face_gather.h'),
            os.path.join(HERE, 'csrc', 'nr_shade.h')]
 LIB_PATH = os.path.join(HERE, 'libnr_hip.so')
 # the measurement build: the same sources with -DNR_PROFILE_HOOK (include/nr_hip_profile.h); bench.py times the dominant kernel with it

@@ -54,16 +54,27 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
     // views: 254.7 us either way), and the fill inside the band kernel and the finish inside the gather are worth more
     // (config 4: 0.80 vs 0.87 ms, 1024 views of 32 x 32: 0.72 vs 0.85, config 5 with its 4 GB of zeros: 1.57 vs 1.97).
     p.gather_first = fold && (size_t)B * F <= k6::SHARED_LAUNCH_MAX_FACES && !(c.flags & NR_FLAG_SERIAL_BACKWARD);
+    // Above that, up to TAIL_GATHER_MAX_FACES, where the gather is the static-tap face gather (texture_size 2, the Renderer's
+    // default) and K6 takes k_bpm_row in the default arithmetic on whole lines:
+    //   compaction | line setup | band kernel + gather in ONE grid, the gather's workgroups behind the band's | overflow | the
+    //   faces the gather left out + K6's sums onto grad_faces (one launch)
+    // The gather starts in the slots that the band kernel's last round frees instead of behind a launch boundary on an empty
+    // chip (k_band_gather, nr_backward_pixel_map.hip; measured: nr_k6_tune.h).  The band workgroups zero the unlisted faces'
+    // cubes of grad_textures only: the gather of the same launch stores the listed ones.
+    // static taps (TS2 path): valid when the clamp of rasterize.py:402 keeps every index float below 1, i.e. when
+    // (ts - 1) - eps still rounds below ts - 1 in float32 (eps > 2^-25); otherwise a coordinate can be exactly 1.0
+    const bool ts2_static = ts == 2 && (float)(1.0 - c.eps) < 1.0f;
+    p.gather_in_tail = k6::TAIL_GATHER_MAX_FACES > 0 && fold && !p.gather_first && !(c.flags & NR_FLAG_SERIAL_BACKWARD) &&
+                       ts2_static && !sampled && !c.lit.light && p.k6p.kernel == K6_KERNEL_ROW && !(c.flags & NR_FLAG_EXACT_GRADIENT) &&
+                       !p.k6p.row_chunked && c.S <= 512 && (size_t)B * F <= k6::TAIL_GATHER_MAX_FACES;
     // the compaction stores the zeros of grad_faces that no later launch stores: of the unlisted faces when the gather's
     // epilogue stores the listed ones, of every face when the gather runs first and adds K8's sums before K6's arrive
-    p.face_zeros = p.gather_first ? FACE_ZEROS_ALL : (fold ? FACE_ZEROS_UNLISTED : FACE_ZEROS_NONE);
-    p.finish = !p.bands ? FINISH_NONE : p.gather_first ? (ts <= 8 ? FINISH_BIG : FINISH_ADD) : (fold ? FINISH_GATHER : FINISH_KERNEL);
+    const bool gather_early = p.gather_first || p.gather_in_tail;  // the gather does not wait for K6's sums
+    p.face_zeros = gather_early ? FACE_ZEROS_ALL : (fold ? FACE_ZEROS_UNLISTED : FACE_ZEROS_NONE);
+    p.finish = !p.bands ? FINISH_NONE : gather_early ? (ts <= 8 ? FINISH_BIG : FINISH_ADD) : (fold ? FINISH_GATHER : FINISH_KERNEL);
 
     if (k7) {
         const size_t n_tex = (size_t)ts * ts * ts * 3;
-        // static taps (TS2 path): valid when the clamp of rasterize.py:402 keeps every index float below 1, i.e. when
-        // (ts - 1) - eps still rounds below ts - 1 in float32 (eps > 2^-25); otherwise a coordinate can be exactly 1.0
-        const bool ts2_static = ts == 2 && (float)(1.0 - c.eps) < 1.0f;
         p.static_taps = ts2_static && !sampled;
         p.gather = ts <= 13 ? GATHER_FACE : GATHER_ATOMIC;  // (above: the per-pixel scatter)
         p.listed = p.bands && ts <= 13;                      // (the atomic fallback walks pixels, not faces)
@@ -82,7 +93,8 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
             p.setup_in_gather = p.k6p.use_records && k6_line_setup_args(c, p.k6p).lds_bytes <= 32768 && p.gather_lds <= 40960;
             if (p.setup_in_gather && !c.lit.light && ((size_t)c.grad_textures & 15) == 0) p.tex_zeros = TEX_ZEROS_SETUP;
         } else if (fold && p.tex_bytes % 16 == 0 && ((size_t)c.grad_textures & 15) == 0 && p.tex_bytes <= p.k6p.fill_max) {
-            p.tex_zeros = TEX_ZEROS_BAND;  // the band kernel's slices (with per-face light colours: the original cubes)
+            // the band kernel's slices (with per-face light colours: the original cubes); beside the gather: the unlisted faces'
+            p.tex_zeros = p.gather_in_tail ? TEX_ZEROS_BAND_UNLISTED : TEX_ZEROS_BAND;
         }
         // Only visible faces are visited, and the per-pixel scatter adds: everything else is zero.  With per-face light
         // colours a face and its reversed copy share one cube, and only the one that owns a pixel stores.  (Round 4 tried to
@@ -129,11 +141,15 @@ int nr::run_backward(const BackwardCall &c)
         }
         if (p.setup_alone)
             if (int rc = run_line_setup(ls, c.st)) return rc;
-        const bool band_fill = p.tex_zeros == TEX_ZEROS_BAND;
-        if (int rc = k6_band(c, p.k6p, l, ls, band_fill ? c.grad_textures : nullptr, band_fill ? p.tex_bytes : 0)) return rc;
+        if (p.gather_in_tail)  // (a fill too large for the band workgroups goes out in front of the launch whose gather stores)
+            if (int rc = fill_texture_zeros(c, p)) return rc;
+        const bool band_fill = p.tex_zeros == TEX_ZEROS_BAND || p.tex_zeros == TEX_ZEROS_BAND_UNLISTED;
+        if (int rc = k6_band(c, p.k6p, l, ls, band_fill ? c.grad_textures : nullptr, band_fill ? p.tex_bytes : 0,
+                             p.gather_in_tail ? &p : nullptr))
+            return rc;
         if (p.finish == FINISH_KERNEL) k6_finalize(c, l, false);
     }
-    if (p.gather != GATHER_NONE && !p.gather_first) {
+    if (p.gather != GATHER_NONE && !p.gather_first && !p.gather_in_tail) {
         if (int rc = fill_texture_zeros(c, p)) return rc;
         if (p.gather == GATHER_FACE)
             if (int rc = gather_faces(c, p, l, nullptr)) return rc;

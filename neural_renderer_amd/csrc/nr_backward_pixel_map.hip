@@ -3,6 +3,7 @@
 // the plan that orders the steps: nr_backward.hip).
 #include "nr_device.h"
 #include "nr_band_lines.h"
+#include "nr_face_gather.h"
 #include "nr_k6_tune.h"
 
 #include <atomic>
@@ -1451,13 +1452,17 @@ NR_API int nr_dev_row_dump(unsigned *out, unsigned *n_windows)
 // (the colours, not the centred sums, are staged: 36 bytes per pixel, four workgroups per CU), `x * 2. / is` and `dist +- eps` in
 // double, IEEE division, every sum in double -- a lane adds its terms to double accumulators, the matrix pipe adds the lanes.
 // A masked lane divides 0 by 1 (the select sits in front of the division: no 0 / 0, no Inf * 0).
-template <bool RGB, bool ALPHA, int MODE, bool CHUNKED>
-__global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
+// The kernel's body is a device function: k_bpm_row below runs it alone, k_band_gather runs it in front of the K7 / K8 gather's
+// workgroups in one grid.  It takes its workgroup from xcd_block, i.e. from blockIdx.x: the band workgroups are the first ids
+// of either grid.  UNLISTED: the zero fill that rides along spares the cubes of the listed faces (zero_slot: K6's face -> list
+// position table, n_zero16 / zero_epf entries), which the gather of the same launch stores.
+template <bool RGB, bool ALPHA, int MODE, bool CHUNKED, bool UNLISTED>
+__device__ __forceinline__ void bpm_row_body(
     const int32_t *__restrict__ fi_map, const float *__restrict__ rgb_map, const float *__restrict__ alpha_map,
     const float *__restrict__ g_rgb, const float *__restrict__ g_alpha, double *__restrict__ scratch,
     const int *__restrict__ band_lines, const int *__restrict__ band_start, const int *__restrict__ lines_ok,
     const BandLine *__restrict__ line_buf, size_t cap, int F, int S, int W, int CH, float eps_f, double eps_d, int B,
-    uint4 *__restrict__ zero16, size_t n_zero16)
+    uint4 *__restrict__ zero16, size_t n_zero16, const int *__restrict__ zero_slot, unsigned zero_epf)
 {
     using namespace rowk;
     constexpr bool EXACT = MODE != K6_FAST;
@@ -1481,7 +1486,10 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
     if (logical >= total_wg) return;
     if (n_zero16) {  // the fused backward's zero fill of grad_textures rides along (see k_bpm_fast)
         const size_t per = (n_zero16 + total_wg - 1) / total_wg, z_lo = (size_t)logical * per, z_hi = min(n_zero16, z_lo + per);
-        for (size_t k = z_lo + tid; k < z_hi; k += NT) zero16[k] = make_uint4(0u, 0u, 0u, 0u);
+        for (size_t k = z_lo + tid; k < z_hi; k += NT) {
+            if constexpr (UNLISTED) { if (zero_slot[k / zero_epf] >= 0) continue; }
+            zero16[k] = make_uint4(0u, 0u, 0u, 0u);
+        }
     }
     const unsigned bandidx = logical / n_ch;  // (the chunks of a band next to each other: they read the same records)
     const int c0 = CHUNKED ? (int)(logical - bandidx * n_ch) * CH : 0, SL = CHUNKED ? min(CH, S - c0) : S;  // the chunk: pixels [c0, c0 + SL) of the band's lines
@@ -2095,6 +2103,60 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
     }
 }
 
+template <bool RGB, bool ALPHA, int MODE, bool CHUNKED>
+__global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
+    const int32_t *__restrict__ fi_map, const float *__restrict__ rgb_map, const float *__restrict__ alpha_map,
+    const float *__restrict__ g_rgb, const float *__restrict__ g_alpha, double *__restrict__ scratch,
+    const int *__restrict__ band_lines, const int *__restrict__ band_start, const int *__restrict__ lines_ok,
+    const BandLine *__restrict__ line_buf, size_t cap, int F, int S, int W, int CH, float eps_f, double eps_d, int B,
+    uint4 *__restrict__ zero16, size_t n_zero16)
+{
+    bpm_row_body<RGB, ALPHA, MODE, CHUNKED, false>(fi_map, rgb_map, alpha_map, g_rgb, g_alpha, scratch, band_lines, band_start, lines_ok,
+                                                   line_buf, cap, F, S, W, CH, eps_f, eps_d, B, zero16, n_zero16, nullptr, 1u);
+}
+
+// --------------------------------------------------------------------------------------------------
+// The fused backward's merged launch (plan_backward: gather_in_tail): k_bpm_row's workgroups and, BEHIND them in grid order, the
+// K7 / K8 face gather's (nr_face_gather.h; static taps, texture_size 2).  Both kernels are bound by the workgroups the chip
+// holds -- five per CU either way -- times a workgroup's life, and a kernel that runs in rounds ends with a tail: once the last
+// band workgroup is handed out the chip empties over one workgroup life while a launch of its own could start nothing.  Here
+// the dispatcher, which hands out workgroups in grid order, goes on with the gather's: they fill the slots the band kernel's
+// last round frees and take no slot a band workgroup was waiting for, and one launch boundary goes.  (Round 5's "side job"
+// interleaved the two in runs of 8 ids and paid k_bpm_fast's 40 KB of LDS per gather workgroup: it lost.)
+// Nothing in the launch waits for anything: the gather reads nothing the band part writes.  K6's sums are rounded onto
+// grad_faces by k_backward_big behind this launch (FINISH_BIG), the compaction stored grad_faces' zeros (FACE_ZEROS_ALL), and
+// of grad_textures the band workgroups zero the unlisted faces' cubes only -- the gather stores every listed face's cube.
+//   grid = [xcd_grid(band workgroups) | gather_x * B], gather id -> (bx, by) = (id % gather_x, id / gather_x): the order of
+//   the gather's own 2-D grid.
+struct BandRowArgs {
+    const int32_t *fi_map;
+    const float *rgb_map, *alpha_map, *g_rgb, *g_alpha;
+    double *scratch;
+    const int *band_lines, *band_start, *lines_ok;
+    const BandLine *line_buf;
+    size_t cap;
+    int F, S, W, B;
+    float eps_f;
+    double eps_d;
+    uint4 *zero16;
+    size_t n_zero16;
+    const int *zero_slot;
+    unsigned zero_epf;
+};
+
+template <bool RGB, bool ALPHA, bool DEPTH>
+__global__ __launch_bounds__(rowk::NT, 5) void k_band_gather(BandRowArgs r, FaceGatherArgs g, unsigned band_grid, unsigned gather_x)
+{
+    if (blockIdx.x < band_grid) {
+        bpm_row_body<RGB, ALPHA, K6_FAST, false, true>(r.fi_map, r.rgb_map, r.alpha_map, r.g_rgb, r.g_alpha, r.scratch, r.band_lines,
+                                                       r.band_start, r.lines_ok, r.line_buf, r.cap, r.F, r.S, r.W, r.S, r.eps_f, r.eps_d,
+                                                       r.B, r.zero16, r.n_zero16, r.zero_slot, r.zero_epf);
+    } else {
+        const unsigned id = blockIdx.x - band_grid;
+        face_gather_body<true, DEPTH, false>(g, (int)(id % gather_x), (int)(id / gather_x));
+    }
+}
+
 // add: grad_faces holds what K8 left for the face (zeros from the compaction, then the gather's sums: the fused backward whose
 // gather runs beside the line setup) and K6's rounded sums go on top -- the one float addition per element that the in-gather
 // finish makes, operands exchanged
@@ -2364,6 +2426,30 @@ int launch_row(const K6Plan &p, const BackwardCall &c, const K6Lists &l, const L
     return n_ch > 1 ? go(std::true_type()) : go(std::false_type());
 }
 
+// The merged launch: k_bpm_row's grid with the K7 / K8 face gather's workgroups behind it (k_band_gather).  fill: grad_textures
+// when the band workgroups zero the unlisted faces' cubes (texture_size 2: six 16-byte words per cube), else NULL.
+template <bool RGB, bool ALPHA>
+int launch_band_gather(const K6Plan &p, const BackwardCall &c, const BackwardPlan &bp, const K6Lists &l, const LineSetupArgs &ls,
+                       void *fill, size_t fill_bytes)
+{
+    const int B = c.B, F = c.F, S = c.S, W = p.W_row;
+    const unsigned total_wg = (unsigned)((S + W - 1) / W) * 2u * (unsigned)B, band_grid = xcd_grid(total_wg);
+    const unsigned gather_x = (unsigned)((F + 15) / 16);
+    const BandRowArgs ra = {c.face_index_map, c.rgb_map, c.alpha_map, c.grad_rgb_map, c.grad_alpha_map, l.scratch, ls.band_lines,
+                            ls.band_start, ls.lines_ok, ls.line_buf, ls.cap, F, S, W, B, (float)c.eps, c.eps, (uint4 *)fill,
+                            fill_bytes / 16, l.slot_of, 6u};
+    const FaceGatherArgs ga = face_gather_args(c, bp, l);
+    auto go = [&](auto depth) {
+        constexpr bool D = decltype(depth)::value;
+        static LdsLimit limit;  // one per instantiation
+        if (int rc = limit.ensure((const void *)k_band_gather<RGB, ALPHA, D>, p.row_lds)) return rc;
+        hipLaunchKernelGGL((k_band_gather<RGB, ALPHA, D>), dim3(band_grid + gather_x * (unsigned)B), dim3(rowk::NT), p.row_lds, c.st,
+                           ra, ga, band_grid, gather_x);
+        return 0;
+    };
+    return bp.depth_in_gather ? go(std::true_type()) : go(std::false_type());
+}
+
 // Whether k_bpm_row takes a call whose raster has a k_bpm_fast band: its band width (lines per workgroup) and LDS bytes, or 0.
 // Both arithmetic modes have ONE band kernel since round 6, k_bpm_row: it is ahead of k_bpm_fast on every shape measured
 // (profiles/r06_k6_kernels.md: 8 ... 128 teapot views at 256^2, 64 views at rasters 320 ... 768, 32 and 4 views at 1024^2, 256
@@ -2406,6 +2492,7 @@ K6Plan nr::plan_k6(int B, int F, int S, bool rgb, double eps, int flags)
     const bool row = p.W_row > 0;
     p.kernel = row ? K6_KERNEL_ROW : K6_KERNEL_FAST;
     p.overflow_pass = row;
+    p.row_chunked = row && row_chunk(S, F) < S;
     p.W = row ? 1 : p.W_fast;
     p.n_bands = (S + p.W - 1) / p.W;
     // line records from k_line_setup, unless NR_FLAG_K6_SCAN asks for the in-kernel face scan (tests) or the launch is
@@ -2565,7 +2652,10 @@ int nr::run_line_setup(const LineSetupArgs &a, hipStream_t st)
 // The global-memory kernel, or the band kernel (k_bpm_row or k_bpm_fast, with the zero fill `fill` when the plan gave it one)
 // and then the overflow-only k_bpm_fast launch behind k_bpm_row: the images whose records exceed the line buffer, by the face
 // scan, no fill.  (l, ls: the compaction's lists and the band tables and line records of k6_line_setup_args.)
-int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes)
+// tail: the plan of a fused backward whose K7 / K8 gather shares k_bpm_row's launch (gather_in_tail; the fill then spares the
+// listed faces' cubes), else NULL.
+int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes,
+                const BackwardPlan *tail)
 {
     if (plan.kernel == K6_KERNEL_GLOBAL) {
         auto global = [&](auto r, auto a) {
@@ -2589,8 +2679,16 @@ int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, con
             return launch_row<decltype(r)::value, decltype(a)::value, decltype(m)::value>(plan, c, l, ls, fill, fill_bytes);
         });
     };
+    auto band_gather = [&]() {
+        auto go = [&](auto r, auto a) {
+            return launch_band_gather<decltype(r)::value, decltype(a)::value>(plan, c, *tail, l, ls, fill, fill_bytes);
+        };
+        using T = std::true_type;
+        using N = std::false_type;
+        return (c.rgb && c.alpha) ? go(T(), T()) : (c.rgb ? go(T(), N()) : go(N(), T()));
+    };
     NR_BAND_TIMER_START(c.st, plan.kernel);
-    int rc = plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill, fill_bytes);
+    int rc = tail ? band_gather() : (plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill, fill_bytes));
     NR_BAND_TIMER_STOP(c.st);
     if (rc == 0 && plan.overflow_pass) rc = band_fast(std::true_type(), nullptr, 0);
     return rc ? rc : launch_status();

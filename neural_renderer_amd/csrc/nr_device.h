@@ -442,12 +442,14 @@ struct K6Plan {
     int W, n_bands;       // the band tables: lines per band, bands per image
     bool use_records;     // line records from k_line_setup (false: every image takes k_bpm_fast's face scan)
     bool overflow_pass;   // k_bpm_fast's overflow-only launch follows k_bpm_row
+    bool row_chunked;     // k_bpm_row cuts its lines into chunks (rasters above 512 on meshes below 2^15 faces)
     size_t fill_max;      // the largest zero fill (bytes) that the band kernel takes along
 };
 K6Plan plan_k6(int B, int F, int S, bool rgb, double eps, int flags);
 
 enum FaceZeros { FACE_ZEROS_NONE, FACE_ZEROS_UNLISTED, FACE_ZEROS_ALL };     // the compaction's stores of grad_faces
-enum TexZeros { TEX_ZEROS_NONE, TEX_ZEROS_BAND, TEX_ZEROS_SETUP, TEX_ZEROS_FILL };  // who zeroes grad_textures
+// who zeroes grad_textures (TEX_ZEROS_BAND_UNLISTED: the band workgroups of the merged launch, the unlisted faces' cubes only)
+enum TexZeros { TEX_ZEROS_NONE, TEX_ZEROS_BAND, TEX_ZEROS_SETUP, TEX_ZEROS_FILL, TEX_ZEROS_BAND_UNLISTED };
 enum K6Finish { FINISH_NONE, FINISH_KERNEL, FINISH_GATHER, FINISH_BIG, FINISH_ADD };  // who rounds K6's sums into grad_faces
 enum Gather { GATHER_NONE, GATHER_FACE, GATHER_ATOMIC };                   // K7's gather
 
@@ -457,6 +459,7 @@ struct BackwardPlan {
     bool bands;            // ... through the band pipeline (not k_bpm_global): K6's lists, scratch and face -> position table
     int face_zeros;        // FaceZeros
     bool gather_first;     // small calls: the K7 gather goes out between the compaction and the band kernel
+    bool gather_in_tail;   // large calls: the K7 / K8 gather's workgroups behind k_bpm_row's in one grid (k_band_gather)
     bool setup_alone;      // k_line_setup as a launch of its own (behind the gather when gather_first)
     bool setup_in_gather;  // k_line_setup's workgroups inside the gather's launch (k_setup_gather)
     int tex_zeros;         // TexZeros (TEX_ZEROS_SETUP: the unlisted faces' cubes, in k_setup_gather)
@@ -489,8 +492,8 @@ struct LineSetupArgs;  // nr_band_lines.h
 int k6_compact(const BackwardCall &c, const K6Plan &p, int face_zeros, K6Lists &out);  // [k_mark_visible] + compaction
 LineSetupArgs k6_line_setup_args(const BackwardCall &c, const K6Plan &p);
 int run_line_setup(const LineSetupArgs &a, hipStream_t st);
-int k6_band(const BackwardCall &c, const K6Plan &p, const K6Lists &l, const LineSetupArgs &ls, void *fill,
-            size_t fill_bytes);  // k_bpm_global, or band kernel + overflow
+int k6_band(const BackwardCall &c, const K6Plan &p, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes,
+            const BackwardPlan *tail);  // k_bpm_global, or band kernel (tail: with the gather behind it) + overflow
 void k6_finalize(const BackwardCall &c, const K6Lists &l, bool add);
 bool k6_lists_fit(int B, int F, size_t workspace_bytes);  // k_list_visible's lists fit the workspace and one launch
 K6Lists k6_list_visible(const BackwardCall &c);

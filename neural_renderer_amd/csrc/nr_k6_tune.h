@@ -49,6 +49,16 @@
 #ifndef NR_SHARED_LAUNCH_MAX_FACES  // fused backward: calls of up to this many faces (batch x faces) put the line setup and the
 #define NR_SHARED_LAUNCH_MAX_FACES 98304  // K7 / K8 gather into one launch (plan_backward; measured: LAB-NOTEBOOK, late round 4)
 #endif
+#ifndef NR_TAIL_GATHER_MAX_FACES  // fused backward: calls above NR_SHARED_LAUNCH_MAX_FACES and up to this many faces run the K7 / K8
+#define NR_TAIL_GATHER_MAX_FACES 655360  // gather's workgroups behind k_bpm_row's in one grid (k_band_gather, plan_backward; 0: never).
+#endif                                   // Fused backward, us, merged launch / serial order (teapot views, texture_size 2, all three
+                                         // outputs; medians of 7 x 30 calls): 32 views at 256^2 117.3 / 138.9, 64 views 197.2 / 215.0,
+                                         // 80 views 245.9 / 260.4, 96 views 285.5 / 300.8, 128 views (630 784 faces) 374.3 / 386.0,
+                                         // 64 views at 512^2 606.9 / 620.0 -- and beyond the bound 256 views at 128^2 (1.26 M faces)
+                                         // 333.0 / 324.7, 1024 views at 32^2 (5 M) 545.3 / 452.6: there the band kernel is short, the
+                                         // gather's grid of F / 16 workgroups per image (most of which only read their list's length)
+                                         // is long, and the fill inside the band kernel and the finish inside the gather are worth more.
+                                         // Configs 4 and 5 (texture sizes 4 and 8) have no static-tap gather: serial order as before.
 
 namespace nr {
 namespace k6 {
@@ -64,5 +74,6 @@ constexpr unsigned long ROW_MIN_WGS = NR_ROW_MIN_WGS, ROW_MIN_WGS_1 = NR_ROW_MIN
 constexpr unsigned OVF_GRID = NR_K6_OVF_GRID;
 constexpr int WIDE_BUDGET_FROM = NR_K6_WIDE_BUDGET_FROM, WIDE_BUDGET_TO = NR_K6_WIDE_BUDGET_TO;
 constexpr unsigned long SHARED_LAUNCH_MAX_FACES = NR_SHARED_LAUNCH_MAX_FACES;
+constexpr unsigned long TAIL_GATHER_MAX_FACES = NR_TAIL_GATHER_MAX_FACES;
 }  // namespace k6
 }  // namespace nr

@@ -14,7 +14,8 @@ nr_backward_pixel_map and the fused nr_backward_rasterize) is therefore split by
 dealt to the stages that launch it, in call order, in equal shares.  If the occurrence count does not fit that protocol
 the kernel's overall average is used for each of its stages and the record says so (`attribution: "name"`).
 The library's own fills are `nr::k_fill_bytes` launches (the z-buffer in both forward stage calls) and are attributed like every
-other kernel; the fused backward's zero fill of grad_textures is part of k_bpm_fast (30 MB of its writes there).
+other kernel; the fused backward's zero fill of grad_textures is part of the band kernel (30 MB of its writes there; in the merged launch
+k_band_gather: the unlisted faces' cubes, the gather stores the rest).
 """
 import json
 import sqlite3
@@ -36,6 +37,9 @@ KERNEL_STAGES = [
     # fused backward's fill rides in k_bpm_fast)
     ('k_fill_bytes', ['forward_face_index_map']),
     ('k_shade', ['forward_texture_sampling']),
+    # (the fused backward's merged launch: k_bpm_row's workgroups with the K7 / K8 gather's behind them in one grid -- band and
+    # gather traffic under a name of its own; while it is there, k_bpm_row itself is the staged call's alone: attribute())
+    ('k_band_gather', ['fused_backward_rasterize']),
 ] + [(k, ['backward_pixel_map', 'fused_backward_rasterize']) for k in K6] + [
     # (template argument lists are matched as prefixes: the gathers carry a third argument, the per-face light mode)
     ('k_backward_textures_face<true, false', ['backward_textures']),
@@ -67,10 +71,11 @@ def dispatches(db, counter):
     return list(c.execute(q, (counter,)))
 
 
-def stages_of(name):
+def stages_of(name, merged=False):
+    """merged: the trace holds k_band_gather launches, i.e. the fused backward did not launch k_bpm_row"""
     for pat, st in KERNEL_STAGES:
         if pat in name:
-            return pat, st
+            return pat, (['backward_pixel_map'] if merged and pat == 'k_bpm_row' else st)
     return None, None
 
 
@@ -82,8 +87,9 @@ def attribute(rows, scale):
         by_name.setdefault(name, []).append(v * scale)
     kernels = {n: (len(v), sum(v) / len(v)) for n, v in by_name.items()}
     stages, how = {}, {}
+    merged = any('k_band_gather' in n for n in by_name)
     for name, vals in by_name.items():
-        pat, sts = stages_of(name)
+        pat, sts = stages_of(name, merged)
         if pat is None:
             continue
         vals = list(vals)
