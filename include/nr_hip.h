@@ -24,6 +24,8 @@
  *                                   images (UVTextures); not in the reference
  *   nr_forward_rasterize_uv / nr_backward_uv_images: the same images sampled at every covered pixel instead of baked into
  *                                   cubes (UVImages); not in the reference
+ *   nr_forward_rasterize_uv_smooth / nr_backward_uv_images_smooth: the same with a light colour per CORNER of every face,
+ *                                   interpolated at the pixel (smooth light on UV images); not in the reference
  *   nr_forward_rasterize_corner / nr_backward_corner_colors: three colours per face, one per corner, interpolated at every
  *                                   covered pixel; nr_vertex_shade_forward/_backward: those colours from per-vertex colours
  *                                   and flat or smooth (vertex-normal) light (VertexColors); not in the reference
@@ -69,6 +71,7 @@ extern "C" {
                           *        nr_frontend_{forward,backward}_projection, nr_frontend_projection_workspace_bytes;
                           *        nr_bake_uv_textures[_backward], nr_uv_texture_map[_workspace_bytes]; nr_uv_images,
                           *        nr_forward_rasterize_uv, nr_backward_uv_images[_workspace_bytes];
+                          *        nr_corner_light, nr_forward_rasterize_uv_smooth, nr_backward_uv_images_smooth[_workspace_bytes];
                           *        nr_forward_rasterize_corner, nr_backward_corner_colors[_workspace_bytes],
                           *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
@@ -564,6 +567,58 @@ int nr_backward_uv_images(const nr_face_light *lit, const nr_uv_images *uv, cons
                           const int32_t *face_index_map, const float *weight_map, const float *depth_map,
                           const float *grad_rgb_map, float *grad_images, int32_t batch_size, int32_t num_faces,
                           int32_t image_size, double eps, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Smooth light on per-pixel UV images (not in the reference; DESIGN K10 "Smooth light on UV images"): the calls above with
+ * one light colour per CORNER of every face, lit->light [B, F, 3(corner), 3(rgb)], interpolated perspective-correctly at the
+ * pixel -- the light nr_vertex_shade_forward(smooth = 1) gives a white mesh.  nr_uv_images, F == Nf or 2 Nf, the workspace
+ * of the forward and every other argument are nr_forward_rasterize_uv's / nr_backward_uv_images'.
+ *
+ * Forward, at a pixel of batch element b covered by face f with weights w and depth zp (all float32, in this order, no
+ * multiply-add contraction), z_k = faces[b, f, k, 2]:
+ *   c     = exactly nr_forward_rasterize_uv's sample (for a reversed copy: f' = f - Nf, the weights reversed for the lookup,
+ *           the transposed base cube);
+ *   e_k   = fminf(fmaxf(w_k * (zp / z_k), 0), 1)    in the face's OWN corner order, also for a reversed copy (its light
+ *           corners arrive flipped, as nr_vertex_shade_forward flips the corner colours of a reversed copy);
+ *   L_c   = (light[b,f,0,c] * e_0 + light[b,f,1,c] * e_1) + light[b,f,2,c] * e_2
+ *   rgb_c = (c_c * L_c) * 1 + 0 * background_c.
+ * Uncovered pixels, alpha, depth, face_index_map, weight_map and visible_faces are bit for bit nr_forward_rasterize_uv's.
+ *
+ * Backward (nr_backward_uv_images_smooth), for the upstream g = grad_rgb_map, over the covered pixels:
+ *   grad_images[b or 0, q_r, c] += g_c * L_c * omega_r    (faces with an image; L_c the forward's float32 value)
+ *   grad_light[b, f, k, c]      += g_c * c_c * e_k         (every covered pixel)
+ * Every element of grad_images [image_batch, P, 3] and lit->grad_light [B, F, 3, 3] is stored (0 where nothing reads; either
+ * may be NULL, not both).  One pass over the pixels produces both.  The terms are formed and summed in double -- the nine
+ * light sums of a face first over the runs of consecutive pixels of a wave that share the face, then with double atomics --
+ * and rounded once to float: within 1e-6 of the sum of |terms| of the exact adjoint, also where thousands of pixels feed one
+ * image pixel or one face.  The double additions arrive in no fixed order (see nr_backward_uv_images); rgb_map repeats bit
+ * for bit.  No gradient to faces_uv or base.  grad_faces comes from nr_backward_rasterize_lit(NULL, ..., grad_textures =
+ * NULL, ...) on the rgb_map of this forward.
+ *
+ * Argument errors (a NULL pointer, F not in {Nf, 2 Nf}, image_batch not in {1, B}, a workspace that is too small) return
+ * NR_E_* before any launch.  Neither call synchronises the host or reads device values on the host: both can be captured
+ * into a graph.
+ */
+typedef struct nr_corner_light {
+    const float *light;     /* DEVICE [B, F, 3(corner), 3(rgb)] */
+    int32_t texture_faces;  /* Nf; F == Nf or 2 Nf */
+    float *grad_light;      /* backward: DEVICE [B, F, 3, 3] or NULL; every element stored */
+} nr_corner_light;
+
+int nr_forward_rasterize_uv_smooth(const nr_corner_light *lit, const nr_uv_images *uv, const float *faces,
+                                   int32_t *face_index_map, float *weight_map, float *depth_map, float *rgb_map,
+                                   float *alpha_map, uint8_t *visible_faces, const float *background, int32_t bg_per_batch,
+                                   int32_t batch_size, int32_t num_faces, int32_t image_size, double near, double far,
+                                   double eps, int32_t flags, void *workspace, size_t workspace_bytes, void *stream);
+
+/* Scratch of nr_backward_uv_images_smooth: the double sums of the images and nine per face (0 for sizes out of range). */
+size_t nr_backward_uv_images_smooth_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t num_pixels,
+                                                    int32_t image_batch);
+
+int nr_backward_uv_images_smooth(const nr_corner_light *lit, const nr_uv_images *uv, const float *faces,
+                                 const int32_t *face_index_map, const float *weight_map, const float *depth_map,
+                                 const float *grad_rgb_map, float *grad_images, int32_t batch_size, int32_t num_faces,
+                                 int32_t image_size, double eps, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Corner colours (not in the reference; DESIGN K10 "Vertex colours"): corner_colors [B, F, 3, 3] float32, indexed (batch, face,

@@ -27,6 +27,11 @@ class FaceLight(_c.Structure):
     _fields_ = [('light', _vp), ('texture_faces', _i32), ('textures', _vp), ('grad_light', _vp)]
 
 
+class CornerLight(_c.Structure):
+    """struct nr_corner_light (include/nr_hip.h): a light colour per corner for the _uv_smooth entry points."""
+    _fields_ = [('light', _vp), ('texture_faces', _i32), ('grad_light', _vp)]
+
+
 class Projection(_c.Structure):
     """struct nr_projection (include/nr_hip.h): device pointers of K, R, t, dist_coeffs (or None) and their layouts."""
     _fields_ = [('K', _vp), ('R', _vp), ('t', _vp), ('dist_coeffs', _vp), ('K_per_batch', _i32), ('R_per_batch', _i32),
@@ -40,7 +45,7 @@ class UVImagesStruct(_c.Structure):
 
 
 _cam_p, _light_p, _fl_p, _proj_p = _c.POINTER(Camera), _c.POINTER(Light), _c.POINTER(FaceLight), _c.POINTER(Projection)
-_uv_p = _c.POINTER(UVImagesStruct)
+_uv_p, _cl_p = _c.POINTER(UVImagesStruct), _c.POINTER(CornerLight)
 
 # name -> (restype, argtypes); mirrors include/nr_hip.h one to one
 SIGNATURES = {
@@ -68,6 +73,9 @@ SIGNATURES = {
     'nr_forward_rasterize_uv': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 8 + [_i32] * 4 + [_f64] * 3 + [_i32, _vp, _sz, _vp]),
     'nr_backward_uv_images_workspace_bytes': (_sz, [_i32] * 4),
     'nr_backward_uv_images': (_c.c_int, [_fl_p, _uv_p] + [_vp] * 6 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
+    'nr_forward_rasterize_uv_smooth': (_c.c_int, [_cl_p, _uv_p] + [_vp] * 8 + [_i32] * 4 + [_f64] * 3 + [_i32, _vp, _sz, _vp]),
+    'nr_backward_uv_images_smooth_workspace_bytes': (_sz, [_i32] * 4),
+    'nr_backward_uv_images_smooth': (_c.c_int, [_cl_p, _uv_p] + [_vp] * 6 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
     'nr_forward_rasterize_corner': (_c.c_int, [_vp] * 9 + [_i32] * 4 + [_f64] * 2 + [_i32, _vp, _sz, _vp]),
     'nr_backward_corner_colors_workspace_bytes': (_sz, [_i32] * 2),
     'nr_backward_corner_colors': (_c.c_int, [_vp] * 7 + [_i32] * 3 + [_vp, _sz, _vp]),

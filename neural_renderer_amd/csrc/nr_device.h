@@ -281,6 +281,18 @@ struct UVSample {
     Taps t;
 };
 
+// The perspective-correct corner weights of a pixel (weights w, depth zp) of a face with vertex depths z, in the face's own
+// corner order: d_k = fminf(fmaxf(w_k * (zp / z_k), 0), 1) -- compute_taps' product without the ts - 1 factor.  Used by
+// the resolve pass's corner mode (shade_pixel<SHADE_CORNER>) and by smooth UV shading in both directions.  NOT the only place
+// that states the product: uv_locate below and nr_vertex_colors.hip's backward (its own corner_weights) keep their own line
+// of it, because routing them through here changed the code generated for those existing kernels (DESIGN K10 "Smooth light
+// on UV images").  A change to the formula has to be made in all three.
+__device__ __forceinline__ void corner_weights(const float (&z)[3], const float (&w)[3], float zp, float (&d)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; k++) d[k] = fminf(fmaxf(w[k] * (zp / z[k]), 0.0f), 1.0f);
+}
+
 __device__ __forceinline__ void uv_locate(const UVShade &uv, int fi, int tex_faces, const float *face, float w0, float w1,
                                           float w2, float zp, double eps, UVSample &s)
 {
@@ -506,5 +518,7 @@ void gather_depth(const BackwardCall &c, const K6Lists &l);
 int face_light_args(const nr_face_light *lit, int F, bool backward, FaceLight &out);  // nr_forward.hip
 // nr_uv_images + its nr_face_light (lit->grad_light copied into fl) -> the kernels' arguments; nr_forward.hip
 int uv_images_args(const nr_face_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out);
+// the same for an nr_corner_light (smooth UV shading): fl.light is then [B, F, 3, 3] and fl.grad_light likewise
+int uv_smooth_args(const nr_corner_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out);
 
 }  // namespace nr

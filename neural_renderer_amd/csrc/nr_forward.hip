@@ -500,8 +500,10 @@ __global__ __launch_bounds__(256) void k_large_raster(const float *__restrict__ 
 // Shading of one pixel (K4 + K5, rasterize.py:361-465): shared by k_shade and the fused k_resolve.  UV: the pixel samples UV
 // texture images (nr_forward_rasterize_uv; `uv` non-NULL, lit.light required) instead of the cubes in `textures`; the
 // instantiations without it are the cube path alone.  CORNER: the pixel interpolates the three corner colours of its face
-// (nr_forward_rasterize_corner; `textures` = corner_colors [B, F, 3, 3], no light factor: the colours arrive lit).
-enum ShadeMode { SHADE_CUBE = 0, SHADE_UV = 1, SHADE_CORNER = 2 };
+// (nr_forward_rasterize_corner; `textures` = corner_colors [B, F, 3, 3], no light factor: the colours arrive lit).  UV_SMOOTH:
+// UV with one light colour per CORNER (nr_forward_rasterize_uv_smooth; lit.light is [B, F, 3, 3]), interpolated with the
+// corner path's weights.
+enum ShadeMode { SHADE_CUBE = 0, SHADE_UV = 1, SHADE_CORNER = 2, SHADE_UV_SMOOTH = 3 };
 template <int MODE>
 __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, float w1, float w2, float depth,
                                             const float *__restrict__ faces, const float *__restrict__ zbase,
@@ -516,16 +518,15 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
     if (!rgb_map) return;
     float rgb[3];
     Taps t;
-    constexpr bool UV = MODE == SHADE_UV;
+    constexpr bool UV = MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH;
     if (MODE == SHADE_CORNER && fi >= 0) {
         // always the face's own batch element; perspective-correct weights d_k as uv_locate takes them, then
         // (C0 * d0 + C1 * d1) + C2 * d2 per channel
         const float *face = faces + ((size_t)b * F + fi) * 9;
         const float *cc = textures + ((size_t)b * F + fi) * 9;
-        const float w[3] = {w0, w1, w2};
+        const float w[3] = {w0, w1, w2}, fz[3] = {face[2], face[5], face[8]};
         float d[3];
-#pragma unroll
-        for (int k = 0; k < 3; k++) d[k] = fminf(fmaxf(w[k] * (depth / face[3 * k + 2]), 0.0f), 1.0f);
+        corner_weights(fz, w, depth, d);
         const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
@@ -537,10 +538,22 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
         UVSample s;
         uv_locate(*uv, fi, lit.tex_faces, faces + ((size_t)b * F + fi) * 9, w0, w1, w2, depth, eps, s);
         uv_color(*uv, s, b, rgb);
-        const float *lc = lit.light + ((size_t)b * F + fi) * 3;
-        rgb[0] *= lc[0];
-        rgb[1] *= lc[1];
-        rgb[2] *= lc[2];
+        if (MODE == SHADE_UV_SMOOTH) {
+            // the light of the face's three corners at the corner path's weights, in the face's OWN corner order (a reversed
+            // copy's light arrives flipped, as corner colours do): L = (L0 * e0 + L1 * e1) + L2 * e2 per channel
+            const float *face = faces + ((size_t)b * F + fi) * 9;
+            const float w[3] = {w0, w1, w2}, fz[3] = {face[2], face[5], face[8]};
+            float e[3];
+            corner_weights(fz, w, depth, e);
+            const float *lc = lit.light + ((size_t)b * F + fi) * 9;
+#pragma unroll
+            for (int c = 0; c < 3; c++) rgb[c] *= (lc[c] * e[0] + lc[3 + c] * e[1]) + lc[6 + c] * e[2];
+        } else {
+            const float *lc = lit.light + ((size_t)b * F + fi) * 3;
+            rgb[0] *= lc[0];
+            rgb[1] *= lc[1];
+            rgb[2] *= lc[2];
+        }
         const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int k = 0; k < 3; k++) rgb[k] = rgb[k] * 1.0f + 0.0f * bg[k];  // as below
@@ -648,7 +661,8 @@ struct ResolveArgs {
 struct ResolveArgsUV : ResolveArgs {
     UVShade uv;
 };
-template <int MODE> using ResolveArgsOf = typename std::conditional<MODE == SHADE_UV, ResolveArgsUV, ResolveArgs>::type;
+template <int MODE> using ResolveArgsOf =
+    typename std::conditional<MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH, ResolveArgsUV, ResolveArgs>::type;
 
 // One pixel of the resolve pass: decode the winner of z-buffer word i (`drawn` false: nobody drew near it, the word is not
 // read), re-evaluate it exactly as the candidate tests did, write the maps and shade.
@@ -691,7 +705,7 @@ __device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size
         for (int k = 0; k < 9; k++) o[k] = inv[k];
     }
     const UVShade *uv = nullptr;
-    if constexpr (MODE == SHADE_UV) uv = &a.uv;
+    if constexpr (MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH) uv = &a.uv;
     if (a.rgb_map || a.alpha_map)
         shade_pixel<MODE>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
                           a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit, uv);
@@ -820,7 +834,8 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
                 unsigned char *visible_faces, int B, int F, int S, double near, double far, void *workspace,
                 size_t workspace_bytes, hipStream_t st, const float *faces_z_ref, const float *textures, float *rgb_map,
                 const float *background, int bg_per_batch, float *alpha_map, int ts, double eps, int fix_batch_z,
-                int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr, bool corner = false)
+                int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr, bool corner = false,
+                bool corner_light = false)
 {
     if (!faces || !face_index_map) return NR_E_NULL;
     if (int e = check_sizes(B, F, S)) return e;
@@ -879,8 +894,14 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
         ResolveArgsUV rau;
         static_cast<ResolveArgs &>(rau) = ra;
         rau.uv = *uv;
-        if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_UV>, grid, dim3(256), 0, st, rau);
-        else hipLaunchKernelGGL(k_resolve<SHADE_UV>, grid, dim3(256), 0, st, rau);
+        if (corner_light) {  // (nr_forward_rasterize_uv_smooth: rau.lit.light is [B, F, 3, 3])
+            if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_UV_SMOOTH>, grid, dim3(256), 0, st, rau);
+            else hipLaunchKernelGGL(k_resolve<SHADE_UV_SMOOTH>, grid, dim3(256), 0, st, rau);
+        } else if (quads) {
+            hipLaunchKernelGGL(k_resolve_quads<SHADE_UV>, grid, dim3(256), 0, st, rau);
+        } else {
+            hipLaunchKernelGGL(k_resolve<SHADE_UV>, grid, dim3(256), 0, st, rau);
+        }
     } else if (corner) {  // corner colours (nr_forward_rasterize_corner): ra.textures = corner_colors [B, F, 3, 3]
         if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
         else hipLaunchKernelGGL(k_resolve<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
@@ -987,6 +1008,31 @@ NR_API int nr_forward_rasterize_uv(const nr_face_light *lit, const nr_uv_images 
     return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
                        workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr, rgb_map, background,
                        bg_per_batch, alpha_map, us.ts, eps, 1, flags, fl, &us);
+}
+
+// host-side check of an nr_uv_images with its nr_corner_light: uv_images_args' checks on the same fields
+int nr::uv_smooth_args(const nr_corner_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out)
+{
+    if (!lit) return NR_E_NULL;
+    const nr_face_light as_face = {lit->light, lit->texture_faces, nullptr, lit->grad_light};
+    return uv_images_args(&as_face, uv, B, F, fl, out);
+}
+
+// Smooth light on per-pixel UV images (include/nr_hip.h; DESIGN K10 "Smooth light on UV images"): the UV instantiation with
+// a light colour per corner.
+NR_API int nr_forward_rasterize_uv_smooth(const nr_corner_light *lit, const nr_uv_images *uv, const float *faces,
+                                          int32_t *face_index_map, float *weight_map, float *depth_map, float *rgb_map,
+                                          float *alpha_map, uint8_t *visible_faces, const float *background,
+                                          int32_t bg_per_batch, int32_t B, int32_t F, int32_t S, double near, double far,
+                                          double eps, int32_t flags, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!rgb_map || !background) return NR_E_NULL;
+    FaceLight fl;
+    UVShade us;
+    if (int e = uv_smooth_args(lit, uv, B, F, fl, us)) return e;
+    return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
+                       workspace, workspace_bytes, (hipStream_t)stream, nullptr, nullptr, rgb_map, background,
+                       bg_per_batch, alpha_map, us.ts, eps, 1, flags, fl, &us, false, true);
 }
 
 // Corner colours (include/nr_hip.h; DESIGN K10 "Vertex colours"): the resolve pass's third shading mode.

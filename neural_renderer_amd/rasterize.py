@@ -255,6 +255,9 @@ class _Cubes(object):
         if textures is None:
             raise ValueError('textures are required when return_rgb is set')
         if light is not None:
+            if light.dim() == 4 and tuple(light.shape) == (B, F, 3, 3):
+                raise ValueError('face_light [batch size, num of faces, 3, 3] (a light colour per corner) goes with UVImages '
+                                 'only: texture cubes take one colour per face, [batch size, num of faces, 3]')
             if light.dtype != torch.float32 or tuple(light.shape) != (B, F, 3):
                 raise ValueError('face_light must be float32 [batch size, num of faces, 3], got %s %s'
                                  % (light.dtype, tuple(light.shape)))
@@ -305,7 +308,9 @@ class _Cubes(object):
 
 class _UVSource(object):
     """Shading source: a UVImages with per-face light colours [B,F,3] -- the images sampled at every covered pixel
-    (include/nr_hip.h: nr_forward_rasterize_uv / nr_backward_uv_images).  Inputs of the autograd node: (light, *images).
+    (include/nr_hip.h: nr_forward_rasterize_uv / nr_backward_uv_images) -- or with a light colour per corner [B,F,3,3],
+    interpolated at the pixel (nr_forward_rasterize_uv_smooth / nr_backward_uv_images_smooth): light.dim() picks the entry
+    points, and the light's gradient has the light's shape.  Inputs of the autograd node: (light, *images).
     grad_faces comes from the rasterizer's own backward (K6 + K8, no texture stage), the images' and the colours' gradients
     from nr_backward_uv_images.  Always eager: the operator's graph-replay mode does not apply (a whole step can still be
     captured with neural_renderer_amd.graph)."""
@@ -317,8 +322,9 @@ class _UVSource(object):
     def check(self, cfg, faces, B, F, inputs):
         uv, light = self.uv, inputs[0]
         Nf = uv.layout.num_faces
-        if light.dtype != torch.float32 or tuple(light.shape) != (B, F, 3) or not light.is_cuda:
-            raise ValueError('face_light must be float32 [batch size, num of faces, 3] on the GPU, got %s %s'
+        if (light.dtype != torch.float32 or tuple(light.shape) not in ((B, F, 3), (B, F, 3, 3)) or not light.is_cuda):
+            raise ValueError('face_light must be float32 [batch size, num of faces, 3] (a colour per face) or [batch size, '
+                             'num of faces, 3, 3] (a colour per corner) on the GPU, got %s %s'
                              % (light.dtype, tuple(light.shape)))
         if F not in (Nf, 2 * Nf):
             raise ValueError('UVImages: the layout has %d faces, the call %d (the layout\'s, or twice that with fill_back)'
@@ -349,6 +355,11 @@ class _UVSource(object):
                                    layout.num_pixels, int(r.packed.shape[0]))
 
     def forward(self, lib, cfg, r, maps, tail):
+        if r.light.dim() == 4:
+            _lib.check(lib.nr_forward_rasterize_uv_smooth(_lib.CornerLight(r.light.data_ptr(), r.Nf, None), self._struct(r),
+                                                          r.faces.data_ptr(), *maps, cfg.near, cfg.far, cfg.eps, *tail),
+                       'nr_forward_rasterize_uv_smooth')
+            return
         _lib.check(lib.nr_forward_rasterize_uv(_lib.FaceLight(r.light.data_ptr(), r.Nf, None, None), self._struct(r),
                                                r.faces.data_ptr(), *maps, cfg.near, cfg.far, cfg.eps, *tail),
                    'nr_forward_rasterize_uv')
@@ -364,13 +375,17 @@ class _UVSource(object):
         f32, dev, ptr = torch.float32, r.faces.device, _lib.ptr
         Bi, P = int(r.packed.shape[0]), uv.layout.num_pixels
         grad_packed = torch.empty((Bi, P, 3), dtype=f32, device=dev) if want_images else None
-        grads[0] = torch.empty((B, F, 3), dtype=f32, device=dev) if want[0] else None
-        ws_bytes = lib.nr_backward_uv_images_workspace_bytes(B, F, P, Bi)
+        grads[0] = torch.empty_like(r.light) if want[0] else None
+        if r.light.dim() == 4:
+            name, lit = 'nr_backward_uv_images_smooth', _lib.CornerLight(r.light.data_ptr(), r.Nf, ptr(grads[0]))
+        else:
+            name, lit = 'nr_backward_uv_images', _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grads[0]))
+        ws_bytes = getattr(lib, name + '_workspace_bytes')(B, F, P, Bi)
         ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
-        _lib.check(lib.nr_backward_uv_images(
-            _lib.FaceLight(r.light.data_ptr(), r.Nf, None, ptr(grads[0])), self._struct(r), r.faces.data_ptr(),
-            r.face_index_map.data_ptr(), r.weight_map.data_ptr(), r.depth_map.data_ptr(), g_rgb.data_ptr(),
-            ptr(grad_packed), B, F, r.S, cfg.eps, ws.data_ptr(), ws_bytes, stream), 'nr_backward_uv_images')
+        _lib.check(getattr(lib, name)(
+            lit, self._struct(r), r.faces.data_ptr(), r.face_index_map.data_ptr(), r.weight_map.data_ptr(),
+            r.depth_map.data_ptr(), g_rgb.data_ptr(), ptr(grad_packed), B, F, r.S, cfg.eps, ws.data_ptr(), ws_bytes, stream),
+            name)
         if want_images:
             for m, (g, im) in enumerate(zip(unpack_image_gradients(uv.layout, grad_packed), uv.images), 1):
                 if want[m]:  # an image shared by the batch: one row when every image is shared, else the rows summed
@@ -440,7 +455,8 @@ def _source_of(textures, face_light, protocol=False):
         _no_protocol(type(textures).__name__)
     if isinstance(textures, UVImages):  # (not in the reference) images sampled per pixel: per-face light colours required
         if face_light is None:
-            raise ValueError('UVImages need face_light: per-face light colours [batch size, num of faces, 3]')
+            raise ValueError('UVImages need face_light: light colours per face [batch size, num of faces, 3] or per corner '
+                             '[batch size, num of faces, 3, 3]')
         return _UVSource(textures), (face_light,) + tuple(textures.images)
     if face_light is not None:  # (not in the reference) three lit colours per face: no light, no cubes
         raise ValueError('CornerColors are already lit: face_light does not apply')

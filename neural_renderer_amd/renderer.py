@@ -18,7 +18,7 @@ from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
 from .uv_textures import UVImages
-from .vertex_colors import VertexColors, vertex_shade
+from .vertex_colors import VertexColors, vertex_light, vertex_shade
 from .vertices_to_faces import vertices_to_faces
 
 # Renderer.face_light default (see the attribute): NR_FACE_LIGHT = 0 | 1 | auto
@@ -88,8 +88,8 @@ class Renderer(object):
         self.face_light = FACE_LIGHT
         # not in the reference: where render() computes the light -- 'flat': one colour per face (lighting.py), 'smooth': at
         # the vertices, from the area-weighted normals of their faces, interpolated over the triangle (Gouraud shading).
-        # 'smooth' needs vertex colours (render(vertices, faces, VertexColors(c)), vertex_colors.py); render_silhouettes and
-        # render_depth ignore the attribute.
+        # 'smooth' takes vertex colours (render(vertices, faces, VertexColors(c)), vertex_colors.py) or UV images (UVImages,
+        # uv_textures.py); texture cubes are lit per face only.  render_silhouettes and render_depth ignore the attribute.
         self.shading = 'flat'
 
     def _project(self, vertices, faces):
@@ -167,7 +167,24 @@ class Renderer(object):
         """render() with a UVImages: the images sampled at every covered pixel (not in the reference).  Per-face light colours
         always (face_light is implied): from the fused front-end when it takes the call, else from lighting() on a ones
         texture behind the module-by-module front-end.  Runs eagerly: graph_replay does not apply."""
+        if self.shading == 'smooth':
+            return self._render_uv_smooth(vertices, faces, uv)
         faces, light = self._frontend(vertices, faces, light_colors=True)
+        return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                         self.background_color, face_light=light)
+
+    def _render_uv_smooth(self, vertices, faces, uv):
+        """render() with a UVImages and shading = 'smooth' (not in the reference): vertex_light computes the light at the
+        vertices in world space (area-weighted normals, a colour per face corner), the front-end projects the geometry, and
+        the rasterizer multiplies its image sample by the light interpolated at the pixel.  HIP or torch by the rule of
+        _render_vertex_colors; runs eagerly, and a capture needs one eager step first (the vertex adjacency table)."""
+        if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3):
+            raise ValueError('vertices must be a tensor [batch size, num of vertices, 3]')
+        fused = frontend.fusable(self, vertices, faces, None) and frontend.light_fusable(self)
+        light = vertex_light(vertices, faces, self.light_intensity_ambient, self.light_intensity_directional,
+                             self.light_color_ambient, self.light_color_directional, self.light_direction,
+                             fill_back=self.fill_back, smooth=True, implementation=None if fused else 'torch')
+        faces, _ = self._frontend(vertices, faces, fused=fused)
         return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                          self.background_color, face_light=light)
 
@@ -202,11 +219,11 @@ class Renderer(object):
             raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
         if isinstance(textures, VertexColors):
             return self._render_vertex_colors(vertices, faces, textures)
-        if self.shading == 'smooth':
-            raise ValueError("Renderer.shading = 'smooth' needs vertex colours (VertexColors): texture cubes and UVImages are "
-                             "lit per face ('flat') only")
         if isinstance(textures, UVImages):
             return self._render_uv(vertices, faces, textures)
+        if self.shading == 'smooth':
+            raise ValueError("Renderer.shading = 'smooth' takes UVImages or VertexColors: texture cubes are lit per face "
+                             "('flat') only")
         if self._use_face_light(vertices, faces, textures):
             faces, light = self._frontend(vertices, faces, light_colors=True, fused=True)
             return rasterize(

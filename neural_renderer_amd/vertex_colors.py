@@ -300,3 +300,17 @@ def vertex_shade(vertices, faces, colors, intensity_ambient=0.5, intensity_direc
     idx, off, ent, per_batch = _adjacency(faces, Nv)
     setup = (idx, off, ent, per_batch, light, bool(fill_back), bool(smooth))
     return CornerColors(_VertexShade.apply(vertices, colors, setup))
+
+
+def vertex_light(vertices, faces, intensity_ambient=0.5, intensity_directional=0.5, color_ambient=(1, 1, 1),
+                 color_directional=(1, 1, 1), direction=(0, 1, 0), fill_back=True, smooth=True, implementation=None):
+    """The light of every face corner, a float32 tensor [B,F,3,3] (F = Nf, or 2 Nf with fill_back; the corners of a reversed
+    copy in its own, flipped order): the corner colours vertex_shade gives a white mesh.  It is what the rasterizer takes as
+    `face_light` next to a UVImages for smooth light (Renderer.shading = 'smooth').  Differentiable in vertices.  The HIP
+    path runs nr_vertex_shade_* with one row of ones shared by the batch and asks for no colour gradient; `implementation`
+    as in vertex_shade."""
+    if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3 and vertices.is_floating_point()):
+        raise ValueError('vertex_light: vertices must be a float tensor [batch size, num of vertices, 3]')
+    ones = torch.ones((int(vertices.shape[1]), 3), dtype=vertices.dtype, device=vertices.device)
+    return vertex_shade(vertices, faces, ones, intensity_ambient, intensity_directional, color_ambient, color_directional,
+                        direction, fill_back, smooth, implementation).colors
