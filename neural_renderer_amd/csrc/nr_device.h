@@ -221,6 +221,35 @@ __device__ __forceinline__ void compute_taps(const float *__restrict__ z, const 
     }
 }
 
+// The trilinear sum of a cube of T texels at taps t, from 0 in tap order.  The eight texels are requested together -- a tap
+// outside the cube (compute_taps) at the cube's last texel, for the address alone -- and summed once they are all there: a
+// load under its own condition is a basic block of its own that waits for its data before the next one is issued, eight
+// round trips one behind the other.  A tap outside the cube is skipped by keeping the sums as they are (not by its zero
+// weight: a NaN or Inf texel must not come in).
+__device__ __forceinline__ void sum_taps(const float *__restrict__ texture, const Taps &t, int T, float c[3])
+{
+    float tx[8][3];
+    unsigned inside = 0;  // bit pn: tap pn lies inside the cube
+#pragma unroll
+    for (int pn = 0; pn < 8; pn++) {
+        inside |= (unsigned)(t.isc[pn] < T) << pn;
+        const float *p = texture + min(t.isc[pn], T - 1) * 3;
+        tx[pn][0] = p[0];
+        tx[pn][1] = p[1];
+        tx[pn][2] = p[2];
+    }
+    c[0] = c[1] = c[2] = 0.0f;
+#pragma unroll
+    for (int pn = 0; pn < 8; pn++) {
+        const bool in = (inside >> pn) & 1u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float s = c[k] + t.w[pn] * tx[pn][k];
+            c[k] = in ? s : c[k];
+        }
+    }
+}
+
 // --------------------------------------------------------------------------------------------------
 // Bilinear reads of texture images (K10).  One definition for the load_obj bake, the learnable bake, its inverse map and
 // per-pixel UV shading (nr_texture_io.hip, nr_uv_pixel.hip, the UV branch of shade_pixel).

@@ -128,7 +128,7 @@ __device__ __forceinline__ float pixel_center_p(int i, int S, float inv_s, bool 
 }
 
 // vertices -> FaceGeo with the inverse barycentric matrix of K1 (rasterize.py:240-277); zeros for back faces (:240, :253)
-__device__ __forceinline__ void load_face_geo(const float *__restrict__ f, int S, FaceGeo &g, float inv[9])
+__device__ __forceinline__ void face_geo(const float (&f)[9], int S, FaceGeo &g, float inv[9])
 {
     g.x0 = f[0]; g.y0 = f[1]; g.z0 = f[2]; g.x1 = f[3]; g.y1 = f[4]; g.z1 = f[5]; g.x2 = f[6]; g.y2 = f[7]; g.z2 = f[8];
     if (is_backside(g.x0, g.y0, g.x1, g.y1, g.x2, g.y2)) {
@@ -142,6 +142,11 @@ __device__ __forceinline__ void load_face_geo(const float *__restrict__ f, int S
     }
     g.i0 = inv[0]; g.i1 = inv[1]; g.i2 = inv[2]; g.i3 = inv[3]; g.i4 = inv[4]; g.i5 = inv[5];
     g.i6 = inv[6]; g.i7 = inv[7]; g.i8 = inv[8];
+}
+__device__ __forceinline__ void load_face_geo(const float *__restrict__ f, int S, FaceGeo &g, float inv[9])
+{
+    const float v[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]};
+    face_geo(v, S, g, inv);
 }
 
 // --------------------------------------------------------------------------------------------------
@@ -504,13 +509,109 @@ __global__ __launch_bounds__(256) void k_large_raster(const float *__restrict__ 
 // UV with one light colour per CORNER (nr_forward_rasterize_uv_smooth; lit.light is [B, F, 3, 3]), interpolated with the
 // corner path's weights.
 enum ShadeMode { SHADE_CUBE = 0, SHADE_UV = 1, SHADE_CORNER = 2, SHADE_UV_SMOOTH = 3 };
+// The background colour of batch element b (the caller's once, up front: uniform, or uniform per image with bg_per_batch).
+__device__ __forceinline__ void load_background(const float *__restrict__ background, int bg_per_batch, int b, float (&bg)[3])
+{
+    const float *p = background + (bg_per_batch ? 3 * b : 0);
+    bg[0] = p[0];
+    bg[1] = p[1];
+    bg[2] = p[2];
+}
+
+// What the cube path of a covered pixel reads that (b, fi) alone addresses -- the vertex depths the taps are computed with
+// (quirk Q1), the light colour of the lit path -- requested as one group of loads behind the word that names fi, and, TS2,
+// the face's whole 2 x 2 x 2 cube as six 16-byte loads (load_cube).  The taps of other texture sizes need the pixel's
+// weights: sum_taps.
+template <bool TS2>
+struct CubeFace {
+    float fz[3], lc[3];
+    const float *texture;
+    bool flip;
+    float4 cube[TS2 ? 6 : 1];
+};
+
+template <bool TS2>
+__device__ __forceinline__ void load_cube_face(CubeFace<TS2> &c, int b, int fi, const float *__restrict__ faces,
+                                               const float *__restrict__ zbase, const float *__restrict__ textures, int F,
+                                               int ts, int fix_batch_z, const FaceLight &lit)
+{
+    // :389 (Q1): the reference reads batch element 0's geometry here; zbase = that element's faces (of the GLOBAL batch)
+    const float *face = (fix_batch_z ? faces + (size_t)b * F * 9 : zbase) + (size_t)fi * 9;
+    c.fz[0] = face[2]; c.fz[1] = face[5]; c.fz[2] = face[8];
+    if constexpr (TS2) {  // (never with a light)
+        c.flip = false;
+        c.texture = textures + ((size_t)b * F + fi) * 24;  // :390
+    } else {
+        // :390; with a light, the cube of the original face: its reversed copy reads it transposed (nr_device.h: FaceLight)
+        c.flip = lit.light && fi >= lit.tex_faces;
+        c.texture = textures + ((size_t)b * (lit.light ? lit.tex_faces : F) + (c.flip ? fi - lit.tex_faces : fi)) * ts * ts * ts * 3;
+        const float *lc = lit.light ? lit.light + ((size_t)b * F + fi) * 3 : face;  // (no light: a readable address, values unused)
+        c.lc[0] = lc[0]; c.lc[1] = lc[1]; c.lc[2] = lc[2];
+    }
+}
+
+__device__ __forceinline__ void load_cube(CubeFace<true> &c)
+{
+#pragma unroll
+    for (int k = 0; k < 6; k++) c.cube[k] = reinterpret_cast<const float4 *>(c.texture)[k];
+}
+__device__ __forceinline__ void load_cube(CubeFace<false> &) {}
+
+__device__ __forceinline__ float quad_elem(const float4 &q, int k) { return k == 0 ? q.x : (k == 1 ? q.y : (k == 2 ? q.z : q.w)); }
+
+// the staged pass's two sampling maps of pixel i (either may be NULL)
+__device__ __forceinline__ void store_taps(const Taps &t, int32_t *__restrict__ sampling_index_map,
+                                           float *__restrict__ sampling_weight_map, size_t i)
+{
+    if (sampling_index_map) {
+        int4 *p = reinterpret_cast<int4 *>(sampling_index_map + 8 * i);
+        p[0] = make_int4(t.isc[0], t.isc[1], t.isc[2], t.isc[3]);
+        p[1] = make_int4(t.isc[4], t.isc[5], t.isc[6], t.isc[7]);
+    }
+    if (sampling_weight_map) {
+        float4 *p = reinterpret_cast<float4 *>(sampling_weight_map + 8 * i);
+        p[0] = make_float4(t.w[0], t.w[1], t.w[2], t.w[3]);
+        p[1] = make_float4(t.w[4], t.w[5], t.w[6], t.w[7]);
+    }
+}
+
+// The lit trilinear sample of a covered pixel (:398-425 and lighting.py:50-51 applied to the sample instead of to every
+// texel).  TS2 (texture size 2 with eps above 2^-25 and no light, decided on the host: nr_backward.hip, "static taps"): every
+// index float stays below 1, so tap pn reads texel (pn & 1, pn >> 1 & 1, pn >> 2) -- all eight inside the cube -- and the sum
+// takes its texels out of the registers of `c.cube` at compile-time positions.
+// (the sampling maps, k_shade only, leave in front of the texel loads: sixteen registers that the loads need)
+template <bool TS2>
+__device__ __forceinline__ void shade_cube(const CubeFace<TS2> &c, const float (&w)[3], float depth, int ts, double eps,
+                                           bool lit, Taps &t, float (&rgb)[3], int32_t *__restrict__ sampling_index_map = nullptr,
+                                           float *__restrict__ sampling_weight_map = nullptr, size_t i = 0)
+{
+    compute_taps(c.fz, w, depth, ts, eps, t, c.flip);
+    store_taps(t, sampling_index_map, sampling_weight_map, i);
+    if constexpr (TS2) {
+        rgb[0] = rgb[1] = rgb[2] = 0.0f;
+#pragma unroll
+        for (int pn = 0; pn < 8; pn++) {
+            const int b0 = pn & 1, b1 = (pn >> 1) & 1, b2 = pn >> 2;
+            const int e = (b0 * 4 + b1 * 2 + b2) * 3;
+#pragma unroll
+            for (int k = 0; k < 3; k++) rgb[k] += t.w[pn] * quad_elem(c.cube[(e + k) >> 2], (e + k) & 3);
+        }
+    } else {
+        sum_taps(c.texture, t, ts * ts * ts, rgb);
+    }
+    if (!TS2 && lit) {
+        rgb[0] *= c.lc[0];
+        rgb[1] *= c.lc[1];
+        rgb[2] *= c.lc[2];
+    }
+}
+
 template <int MODE>
 __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, float w1, float w2, float depth,
                                             const float *__restrict__ faces, const float *__restrict__ zbase,
                                             const float *__restrict__ textures, float *__restrict__ rgb_map,
                                             int32_t *__restrict__ sampling_index_map,
-                                            float *__restrict__ sampling_weight_map,
-                                            const float *__restrict__ background, int bg_per_batch,
+                                            float *__restrict__ sampling_weight_map, const float (&bg)[3],
                                             float *__restrict__ alpha_map, int F, int ts, double eps, int fix_batch_z,
                                             const FaceLight &lit, const UVShade *uv = nullptr)
 {
@@ -527,7 +628,6 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
         const float w[3] = {w0, w1, w2}, fz[3] = {face[2], face[5], face[8]};
         float d[3];
         corner_weights(fz, w, depth, d);
-        const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             rgb[c] = (cc[c] * d[0] + cc[3 + c] * d[1]) + cc[6 + c] * d[2];
@@ -554,42 +654,17 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
             rgb[1] *= lc[1];
             rgb[2] *= lc[2];
         }
-        const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int k = 0; k < 3; k++) rgb[k] = rgb[k] * 1.0f + 0.0f * bg[k];  // as below
     } else if (fi >= 0) {
-        // :389 (Q1): the reference reads batch element 0's geometry here; zbase = that element's faces (of the GLOBAL batch)
-        const float *face = (fix_batch_z ? faces + (size_t)b * F * 9 : zbase) + (size_t)fi * 9;
-        const float *texture = textures + ((size_t)b * F + fi) * ts * ts * ts * 3;   // :390
-        bool flip = false;
-        if (lit.light) {  // the cube of the original face; its reversed copy reads it transposed (nr_device.h: FaceLight)
-            flip = fi >= lit.tex_faces;
-            texture = textures + ((size_t)b * lit.tex_faces + (flip ? fi - lit.tex_faces : fi)) * ts * ts * ts * 3;
-        }
+        CubeFace<false> c;
+        load_cube_face(c, b, fi, faces, zbase, textures, F, ts, fix_batch_z, lit);
         const float w[3] = {w0, w1, w2};
-        const float fz[3] = {face[2], face[5], face[8]};
-        compute_taps(fz, w, depth, ts, eps, t, flip);
-        rgb[0] = rgb[1] = rgb[2] = 0.0f;
-#pragma unroll
-        for (int pn = 0; pn < 8; pn++) {
-            if (t.isc[pn] >= ts * ts * ts) continue;  // outside the cube: weight 0 (see compute_taps), never dereferenced
-            const float *tx = texture + t.isc[pn] * 3;
-            rgb[0] += t.w[pn] * tx[0];
-            rgb[1] += t.w[pn] * tx[1];
-            rgb[2] += t.w[pn] * tx[2];
-        }
-        if (lit.light) {  // lighting.py:50-51 applied to the sample instead of to every texel
-            const float *lc = lit.light + ((size_t)b * F + fi) * 3;
-            rgb[0] *= lc[0];
-            rgb[1] *= lc[1];
-            rgb[2] *= lc[2];
-        }
+        shade_cube(c, w, depth, ts, eps, lit.light != nullptr, t, rgb, sampling_index_map, sampling_weight_map, i);
         // :463 with mask = 1: rgb * 1 + 0 * bg (kept literal: it maps -0 to +0 and NaN backgrounds to NaN)
-        const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int k = 0; k < 3; k++) rgb[k] = rgb[k] * 1.0f + 0.0f * bg[k];
     } else {
-        const float *bg = background + (bg_per_batch ? 3 * b : 0);
 #pragma unroll
         for (int k = 0; k < 3; k++) rgb[k] = 0.0f * 0.0f + 1.0f * bg[k];
 #pragma unroll
@@ -599,17 +674,8 @@ __device__ __forceinline__ void shade_pixel(size_t i, int b, int fi, float w0, f
     o[0] = rgb[0];
     o[1] = rgb[1];
     o[2] = rgb[2];
-    if (MODE != SHADE_CUBE) return;  // (no sampling maps: the UV and corner instantiations are the resolve pass's)
-    if (sampling_index_map) {
-        int4 *p = reinterpret_cast<int4 *>(sampling_index_map + 8 * i);
-        p[0] = make_int4(t.isc[0], t.isc[1], t.isc[2], t.isc[3]);
-        p[1] = make_int4(t.isc[4], t.isc[5], t.isc[6], t.isc[7]);
-    }
-    if (sampling_weight_map) {
-        float4 *p = reinterpret_cast<float4 *>(sampling_weight_map + 8 * i);
-        p[0] = make_float4(t.w[0], t.w[1], t.w[2], t.w[3]);
-        p[1] = make_float4(t.w[4], t.w[5], t.w[6], t.w[7]);
-    }
+    // (the sampling maps of a covered pixel: shade_cube; none in the UV and corner instantiations, the resolve pass's)
+    if (MODE == SHADE_CUBE && fi < 0) store_taps(t, sampling_index_map, sampling_weight_map, i);
 }
 
 __global__ __launch_bounds__(256) void k_shade(const float *__restrict__ faces, const float *__restrict__ zbase,
@@ -625,12 +691,14 @@ __global__ __launch_bounds__(256) void k_shade(const float *__restrict__ faces, 
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n_pixels) return;
-    const int fi = face_index_map[i];
     const int b = (int)(i / ((size_t)S * S));
+    float bg[3] = {0.0f, 0.0f, 0.0f};
+    if (rgb_map) load_background(background, bg_per_batch, b, bg);  // (up front: its address needs nothing that is loaded)
+    const int fi = face_index_map[i];
     float w0 = 0.0f, w1 = 0.0f, w2 = 0.0f, depth = 0.0f;
     if (rgb_map && fi >= 0) { w0 = weight_map[3 * i]; w1 = weight_map[3 * i + 1]; w2 = weight_map[3 * i + 2]; depth = depth_map[i]; }
     shade_pixel<SHADE_CUBE>(i, b, fi, w0, w1, w2, depth, faces, zbase, textures, rgb_map, sampling_index_map, sampling_weight_map,
-                            background, bg_per_batch, alpha_map, F, ts, eps, fix_batch_z, lit);
+                            bg, alpha_map, F, ts, eps, fix_batch_z, lit);
 }
 
 // Everything the resolve pass needs (passed by value: one kernel argument block for its two launch shapes).
@@ -664,30 +732,58 @@ struct ResolveArgsUV : ResolveArgs {
 template <int MODE> using ResolveArgsOf =
     typename std::conditional<MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH, ResolveArgsUV, ResolveArgs>::type;
 
-// One pixel of the resolve pass: decode the winner of z-buffer word i (`drawn` false: nobody drew near it, the word is not
-// read), re-evaluate it exactly as the candidate tests did, write the maps and shade.
-template <int MODE>
-__device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size_t i, bool drawn)
+// One pixel of the resolve pass: decode the winner in z-buffer word pk (ZEMPTY where nobody drew near the pixel: the word was
+// not read), re-evaluate it exactly as the candidate tests did, shade, write the maps.  bg: the background of the pixel's
+// image, loaded by the caller up front.  The loads of a covered pixel come in groups, one per level of what depends on what
+// -- [the `touched` byte,] the z-buffer word, everything that (b, fn) addresses, the taps whose addresses need the weights
+// (none with TS2) -- and all of them in front of the pixel's stores: the pass is bound by the round trips of the workgroups
+// that hold a drawn segment, and this ISA's vmcnt counts stores too, so a load behind stores waits for them.
+template <int MODE, bool TS2>
+__device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size_t i, unsigned long long pk, const float (&bg)[3])
 {
+    constexpr bool CUBE = MODE == SHADE_CUBE;
     const float *__restrict__ faces = a.faces;
     const int S = a.S, F = a.F, epoch = a.epoch;
-    const unsigned long long pk = drawn ? a.zbuf[i] : ZEMPTY;
     int fn = -1;
     float zp = (float)a.far_d, w0 = 0.0f, w1 = 0.0f, w2 = 0.0f;  // rasterize.py:296, :478-480
-    float inv[9] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
     int b = 0;
-    if (a.rgb_map || a.alpha_map) b = (int)(i / ((size_t)S * S));
-    const bool hit = drawn && (epoch < 0 ? pk != ZEMPTY : (int)(pk >> 56) == epoch);
+    float rgb[3];
+    const bool hit = epoch < 0 ? pk != ZEMPTY : (int)(pk >> 56) == epoch;
     if (hit) {
         fn = epoch < 0 ? (int)(unsigned)(pk & 0xffffffffu) : (int)(unsigned)(pk & 0xffffffu);
         const size_t SS = (size_t)S * S;
         b = (int)(i / SS);
         const int pn = (int)(i - (size_t)b * SS);
         const int py = pn / S, px = pn - py * S;
+        const float *f = faces + ((size_t)b * F + fn) * 9;
+        const float fv[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]};
+        CubeFace<TS2> c;
+        if (CUBE && a.rgb_map) load_cube_face(c, b, fn, faces, a.zbase, a.textures, F, a.ts, a.fix_batch_z, a.lit);
         FaceGeo g;
-        load_face_geo(faces + ((size_t)b * F + fn) * 9, S, g, inv);
+        float inv[9];
+        face_geo(fv, S, g, inv);
+        // (the cube's 24 registers do not fit beside the inverse matrix in the making -- 64 registers keep eight waves on a
+        // SIMD -- so its loads leave here: their round trip runs beside the seven divisions of the weights and the depth)
+        if (CUBE && a.rgb_map) load_cube(c);
         eval_pixel(g, pixel_center_f(px, S), pixel_center_f(py, S), (float)px, (float)py, a.near_d, a.far_d, zp, w0, w1, w2);
-        if (a.visible_faces) a.visible_faces[(size_t)b * F + fn] = 1;  // same value from every pixel of the face: no atomic
+        // (the inverse matrix leaves here, not with the other maps below: nine registers that the shading needs; the entry
+        // point that asks for this map does not shade)
+        if (a.face_inv_map) {
+            float *o = a.face_inv_map + 9 * i;
+#pragma unroll
+            for (int k = 0; k < 9; k++) o[k] = inv[k];
+        }
+        if (CUBE && a.rgb_map) {
+            Taps t;
+            const float w[3] = {w0, w1, w2};
+            shade_cube(c, w, zp, a.ts, a.eps, a.lit.light != nullptr, t, rgb);
+            // :463 with mask = 1: rgb * 1 + 0 * bg (kept literal: it maps -0 to +0 and NaN backgrounds to NaN)
+#pragma unroll
+            for (int k = 0; k < 3; k++) rgb[k] = rgb[k] * 1.0f + 0.0f * bg[k];
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < 3; k++) rgb[k] = 0.0f * 0.0f + 1.0f * bg[k];  // :463 with mask = 0
     }
     a.face_index_map[i] = fn;
     if (a.depth_map) a.depth_map[i] = zp;
@@ -699,16 +795,26 @@ __device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size
         w[1] = w1;
         w[2] = w2;
     }
-    if (a.face_inv_map) {
+    if (a.face_inv_map && !hit) {
         float *o = a.face_inv_map + 9 * i;
 #pragma unroll
-        for (int k = 0; k < 9; k++) o[k] = inv[k];
+        for (int k = 0; k < 9; k++) o[k] = 0.0f;
     }
-    const UVShade *uv = nullptr;
-    if constexpr (MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH) uv = &a.uv;
-    if (a.rgb_map || a.alpha_map)
-        shade_pixel<MODE>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, a.background,
-                          a.bg_per_batch, a.alpha_map, F, a.ts, a.eps, a.fix_batch_z, a.lit, uv);
+    if (hit && a.visible_faces) a.visible_faces[(size_t)b * F + fn] = 1;  // same value from every pixel of the face: no atomic
+    if constexpr (CUBE) {
+        if (a.alpha_map) a.alpha_map[i] = hit ? 1.0f : 0.0f;  // :449
+        if (a.rgb_map) {
+            float *o = a.rgb_map + 3 * i;
+            o[0] = rgb[0];
+            o[1] = rgb[1];
+            o[2] = rgb[2];
+        }
+    } else if (a.rgb_map || a.alpha_map) {
+        const UVShade *uv = nullptr;
+        if constexpr (MODE == SHADE_UV || MODE == SHADE_UV_SMOOTH) uv = &a.uv;
+        shade_pixel<MODE>(i, b, fn, w0, w1, w2, zp, faces, a.zbase, a.textures, a.rgb_map, nullptr, nullptr, bg, a.alpha_map, F,
+                          a.ts, a.eps, a.fix_batch_z, a.lit, uv);
+    }
 }
 
 // epoch mode: nobody fills the workspace for the next call, so the queue counters go back to -1 in the resolve pass (the
@@ -722,16 +828,19 @@ __device__ __forceinline__ void reset_queue_counters(const ResolveArgs &a)
 }
 
 template <int MODE>
-__global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<MODE> a)
+__global__ __launch_bounds__(256, 8) void k_resolve(ResolveArgsOf<MODE> a)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     reset_queue_counters(a);
     if (i >= a.n_pixels) return;
+    float bg[3] = {0.0f, 0.0f, 0.0f};
+    if (a.rgb_map) load_background(a.background, a.bg_per_batch, a.bg_per_batch ? (int)(i / ((size_t)a.S * a.S)) : 0, bg);
     // Epoch mode keeps a byte per 64 consecutive pixels (= the pixels of one wave here) that every z-buffer update of this call
     // sets to the call's epoch number: where it holds anything else nobody drew -- 7 of 8 segments of a teapot view -- and the
     // 512 bytes of z-buffer behind it are not read (round 4: 33.5 -> ~6 MB of z-buffer reads at the headline size).  Stale
     // bytes of earlier calls carry larger epoch numbers, the initial fill 0xff: no clearing.
-    resolve_pixel<MODE>(a, i, !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch);
+    const bool drawn = !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch;
+    resolve_pixel<MODE, false>(a, i, drawn ? a.zbuf[i] : ZEMPTY, bg);
 }
 
 // The same pass for epoch mode on rasters with an even side.  Most of what the pass writes is the constant of undrawn pixels
@@ -741,15 +850,27 @@ __global__ __launch_bounds__(256) void k_resolve(ResolveArgsOf<MODE> a)
 // pixel per lane as before, and the other waves of an undrawn stretch leave at once.  (Fused forward of the headline batch
 // 72.3 -> 66.2 us; workgroups of 512 / 1024 pixels with 2 / 4 passes per lane: 72.9 / 82.6, profiles/r04_fwd_variants.jsonl.)
 // (256 pixels per workgroup: 64 / 128 / 512 / 1024 were measured -- 74.7 / 73.7 / 76.5 / 84.5 us against 69-70)
-template <int MODE>
-__global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<MODE> a)
+// A lane's two `touched` bytes (of the quad it fills, first wave only, and of the pixel it resolves) are requested together
+// at the top, with the workgroup's background colour, and the z-buffer word in front of the fills' stores.
+// TS2: the cube instantiation's static taps (shade_cube)
+template <int MODE, bool TS2 = false>
+__global__ __launch_bounds__(256, 8) void k_resolve_quads(ResolveArgsOf<MODE> a)
 {
     reset_queue_counters(a);
     const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x, i0 = (size_t)blockIdx.x * 256 + 4 * threadIdx.x;
+    const size_t last = a.n_pixels - 1;
     const unsigned char ep = (unsigned char)a.epoch;
-    unsigned char tq = ep, ti = (unsigned char)(ep + 1);
-    if (threadIdx.x < 64 && i0 < a.n_pixels) tq = a.touched[i0 >> 6];
-    if (i < a.n_pixels) ti = a.touched[i >> 6];
+    const bool filler = threadIdx.x < 64 && i0 < a.n_pixels;
+    // (addresses clamped into the maps, so that neither read stands under a condition of its own)
+    const unsigned char tq_read = a.touched[(filler ? i0 : min(i, last)) >> 6], ti_read = a.touched[min(i, last) >> 6];
+    // the background: one colour for the workgroup (uniform, or uniform per image and the workgroup inside one image -- the
+    // host sends other shapes to k_resolve), so it arrives in scalar registers
+    float bg[3] = {0.0f, 0.0f, 0.0f};
+    if (a.rgb_map)
+        load_background(a.background, a.bg_per_batch, a.bg_per_batch ? (int)(((size_t)blockIdx.x * 256) / ((size_t)a.S * a.S)) : 0, bg);
+    const unsigned char tq = filler ? tq_read : ep, ti = i < a.n_pixels ? ti_read : (unsigned char)(ep + 1);
+    unsigned long long pk = ZEMPTY;
+    if (ti == ep) pk = a.zbuf[i];
     if (tq != ep) {
         reinterpret_cast<int4 *>(a.face_index_map)[i0 >> 2] = make_int4(-1, -1, -1, -1);
         const float zf = (float)a.far_d;  // rasterize.py:296
@@ -766,17 +887,16 @@ __global__ __launch_bounds__(256) void k_resolve_quads(ResolveArgsOf<MODE> a)
         }
         if (a.alpha_map) reinterpret_cast<float4 *>(a.alpha_map)[i0 >> 2] = zero;  // :449
         if (a.rgb_map) {
-            const float *bg = a.background + (a.bg_per_batch ? 3 * (int)(i0 / ((size_t)a.S * a.S)) : 0);
             float c[3];
 #pragma unroll
-            for (int k = 0; k < 3; k++) c[k] = 0.0f * 0.0f + 1.0f * bg[k];  // :463 with mask = 0 (shade_pixel)
+            for (int k = 0; k < 3; k++) c[k] = 0.0f * 0.0f + 1.0f * bg[k];  // :463 with mask = 0 (resolve_pixel)
             float4 *o = reinterpret_cast<float4 *>(a.rgb_map + 3 * i0);
             o[0] = make_float4(c[0], c[1], c[2], c[0]);
             o[1] = make_float4(c[1], c[2], c[0], c[1]);
             o[2] = make_float4(c[2], c[0], c[1], c[2]);
         }
     }
-    if (ti == ep) resolve_pixel<MODE>(a, i, true);
+    if (ti == ep) resolve_pixel<MODE, TS2>(a, i, pk, bg);
 }
 
 }  // namespace
@@ -888,7 +1008,8 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
     ra.sparse_weights = (flags & NR_FLAG_SPARSE_WEIGHT_MAP) ? 1 : 0; ra.touched = touched;
     const uintptr_t align = (uintptr_t)face_index_map | (uintptr_t)weight_map | (uintptr_t)depth_map | (uintptr_t)face_inv_map |
                             (uintptr_t)rgb_map | (uintptr_t)alpha_map;
-    const bool quads = touched && S % 2 == 0 && (align & 15) == 0;  // (k_resolve_quads: 16-byte stores into every map)
+    // (k_resolve_quads: 16-byte stores into every map; one background colour per workgroup of 256 pixels)
+    const bool quads = touched && S % 2 == 0 && (align & 15) == 0 && (!(rgb_map && bg_per_batch) || ((size_t)S * S) % 256 == 0);
     const dim3 grid((unsigned)((P + 255) / 256));
     if (uv) {  // per-pixel UV images (nr_forward_rasterize_uv)
         ResolveArgsUV rau;
@@ -905,6 +1026,9 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
     } else if (corner) {  // corner colours (nr_forward_rasterize_corner): ra.textures = corner_colors [B, F, 3, 3]
         if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
         else hipLaunchKernelGGL(k_resolve<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
+    } else if (quads && rgb_map && !lit.light && ts == 2 && (float)(1.0 - eps) < 1.0f && ((uintptr_t)textures & 15) == 0) {
+        // static taps (the backward's rule, nr_backward.hip: no index float reaches 1) on cubes that 16-byte loads can read
+        hipLaunchKernelGGL((k_resolve_quads<SHADE_CUBE, true>), grid, dim3(256), 0, st, ra);
     } else if (quads) {
         hipLaunchKernelGGL(k_resolve_quads<SHADE_CUBE>, grid, dim3(256), 0, st, ra);
     } else {
