@@ -73,7 +73,8 @@ extern "C" {
                           *        nr_forward_rasterize_uv, nr_backward_uv_images[_workspace_bytes];
                           *        nr_corner_light, nr_forward_rasterize_uv_smooth, nr_backward_uv_images_smooth[_workspace_bytes];
                           *        nr_forward_rasterize_corner, nr_backward_corner_colors[_workspace_bytes],
-                          *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes);
+                          *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes;
+                          *        NR_FLAG_SHARED_TEXTURES, nr_backward_textures_shared[_workspace_bytes]);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -146,6 +147,13 @@ extern "C" {
                                          (raster <= 1024; the default mode: eps > 0); the scan path, larger rasters and the default
                                          mode with eps = 0 run on k_bpm_fast).  Which kernel a call takes does not depend on its
                                          batch size. */
+#define NR_FLAG_SHARED_TEXTURES 131072   /* nr_forward_rasterize[_lit]: `textures` is ONE set of cubes, [Nf, ts,ts,ts, 3], for all B images
+                                         (texture batch stride 0; Nf as the call says: F, or lit->texture_faces).  Same arithmetic
+                                         as on B copies of it: bit-identical maps.  Its texture gradient, summed over the images,
+                                         is nr_backward_textures_shared's; nr_backward_rasterize[_lit] gives grad_faces for such a
+                                         call with grad_textures == NULL.  Every entry point that strides cubes by the batch and is
+                                         handed the flag -- nr_forward_texture_sampling, nr_backward_textures, nr_backward_rasterize[_lit]
+                                         with grad_textures -- returns NR_E_MODE. */
 
 /*
  * faces_z_ref (nr_forward_texture_sampling, nr_forward_rasterize, nr_backward_textures, nr_backward_rasterize):
@@ -300,6 +308,28 @@ int nr_backward_rasterize_lit(const nr_face_light *lit, const float *faces, cons
                               float *grad_textures, int32_t batch_size, int32_t num_faces, int32_t image_size,
                               int32_t texture_size, double eps, int32_t flags, const uint8_t *visible_faces,
                               void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Texture cubes shared by the batch (not in the reference; DESIGN K7 "Shared cubes"): the texture gradient of a forward that ran
+ * with NR_FLAG_SHARED_TEXTURES.  grad_textures [Nf, ts,ts,ts, 3] = the sum over the B images of what nr_backward_rasterize[_lit]
+ * stores per image -- the reference's per-pixel terms (rasterize.py:780), with lit times light[b, f, :], the reversed copies
+ * Nf + f folded into cube f -- and every element is stored (zeros for cubes that own no pixel in any image).  lit == NULL:
+ * F cubes, sampled as they are; with lit, lit->texture_faces cubes, and lit->grad_light [B, F, 3] (optional, needs
+ * lit->textures = the ONE set of cubes) receives each image's own colour gradient, every element stored.
+ * A group of lanes owns one (image, face) pair whose visible_faces flag is set (NULL: every pair), sums the pair's pixels
+ * privately (float registers at texture_size 2 with static taps, doubles in LDS otherwise) and adds each texel's sum ONCE, in
+ * double, onto the workspace's [Nf, ts^3 * 3] doubles; a second launch rounds them to float.  Nothing grows with B * Nf * ts^3.
+ * The double additions of the images arrive in no fixed order, so the last bit of a sum may differ between calls.
+ * texture_size in [2, 13] (NR_E_SIZE above: no shared counterpart of the per-pixel scatter); weight_map and depth_map are the
+ * forward's; flags: NR_FLAG_FIX_TEXTURE_BATCH_Z as the forward had it.  The size query runs on the host alone and does not
+ * depend on batch_size (0 for sizes out of range).  No host synchronisation; capturable.
+ */
+size_t nr_backward_textures_shared_workspace_bytes(int32_t batch_size, int32_t texture_faces, int32_t texture_size);
+int nr_backward_textures_shared(const nr_face_light *lit, const float *faces, const float *faces_z_ref,
+                                const int32_t *face_index_map, const float *weight_map, const float *depth_map,
+                                const float *grad_rgb_map, const uint8_t *visible_faces, float *grad_textures,
+                                int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t texture_size, double eps,
+                                int32_t flags, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * vertices_to_faces (reference neural_renderer/vertices_to_faces.py:4-21): faces_out[b,f,k,:] = vertices[b, faces_idx[.,f,k], :]

@@ -88,6 +88,8 @@ SIGNATURES = {
     'nr_frontend_backward': (_c.c_int, [_vp] * 9 + [_i32] * 7 + [_cam_p, _light_p, _vp, _sz, _vp]),
     'nr_forward_rasterize_lit': (_c.c_int, [_fl_p] + [_vp] * 10 + [_i32] * 5 + [_f64] * 3 + [_i32, _vp, _sz, _vp]),
     'nr_backward_rasterize_lit': (_c.c_int, [_fl_p] + [_vp] * 12 + [_i32] * 4 + [_f64, _i32, _vp, _vp, _sz, _vp]),
+    'nr_backward_textures_shared_workspace_bytes': (_sz, [_i32] * 3),
+    'nr_backward_textures_shared': (_c.c_int, [_fl_p] + [_vp] * 8 + [_i32] * 4 + [_f64, _i32, _vp, _sz, _vp]),
     'nr_frontend_forward_light': (_c.c_int, [_vp] * 5 + [_i32] * 6 + [_cam_p, _light_p, _vp]),
     'nr_frontend_backward_light': (_c.c_int, [_vp] * 7 + [_i32] * 6 + [_cam_p, _light_p, _vp, _sz, _vp]),
     'nr_frontend_projection_workspace_bytes': (_sz, [_i32]),
@@ -104,6 +106,7 @@ NR_FLAG_ZBUF_EPOCH = 16  # + epoch number << 8 (include/nr_hip.h)
 NR_FLAG_SPARSE_WEIGHT_MAP = 32
 NR_FLAG_SERIAL_BACKWARD = 64
 NR_FLAG_K6_LEGACY = 128
+NR_FLAG_SHARED_TEXTURES = 131072  # one set of cubes for the batch (forward; nr_backward_textures_shared)
 NR_FLAG_K6_PX = 65536  # (accepted and ignored since 0.6.0; bits 8..15 of a forward's flags carry the epoch number)
 NR_E_INDEX = -6
 NR_CAMERA_LOOK_AT = 1

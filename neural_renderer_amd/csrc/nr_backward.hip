@@ -33,6 +33,7 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
     if (k6 && (size_t)c.B * c.S * c.S > 0x7fffffffull / 3) return NR_E_SIZE;  // int32 pixel indexing inside the kernels
     if (k7 && (c.ts < 2 || c.ts > 1024)) return NR_E_SIZE;
     if (k7 && c.lit.light && sampled) return NR_E_MODE;  // (the taps are recomputed in the original cube's layout)
+    if (k7 && (c.flags & NR_FLAG_SHARED_TEXTURES)) return NR_E_MODE;  // (K7 strides the cubes by the batch: nr_backward_textures_shared)
 
     const int B = c.B, F = c.F, ts = c.ts;
     p.k6 = k6;

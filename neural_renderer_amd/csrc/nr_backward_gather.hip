@@ -448,6 +448,258 @@ __global__ __launch_bounds__(256) void k_backward_depth_face(
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// Shared cubes (nr_backward_textures_shared, DESIGN K7 "Shared cubes"): ONE set of cubes [Nf, ts^3, 3] sampled by all B images,
+// its gradient the sum over the images.  The batched gathers above store a cube per (image, face); here the pairs of all
+// images meet in one cube, so a pair's group sums its pixels privately as before -- the same walk, the same taps, float
+// registers with static taps, LDS doubles otherwise -- and then adds every texel's sum ONCE, in double, onto sums [Nf][ts^3 * 3]
+// (zero-filled in front; k_round_sums stores the floats, all of them).  Atomics per (pair, texel that received something),
+// never per pixel; nothing of size B * Nf * ts^3 exists.
+//   grid = (ranges of 256 faces, image).  A workgroup reads the forward's `visible` flags of its range, one face per thread,
+//   and compacts the pairs that own a pixel into two LDS lists: `small` (candidate sets up to BIG_PX; a group of L = 16 | 64
+//   lanes each, 256 / L at a time, until the list is done) and `wide` (above BIG_PX -- a ground plane --, and every pair at
+//   texture_size 9 .. 13, where one cube of doubles is all the LDS holds: the whole workgroup walks each in turn, as
+//   k_backward_big does).  So the ~5/6 of a mesh's pairs that own nothing cost one byte load, and a workgroup's groups stay
+//   busy while its list lasts.  LIT: the contribution carries light[b, f], a reversed copy Nf + f lands in cube f (its taps
+//   are flattened in the original layout: compute_taps' flip), and grad_light[b, f] -- the pair's own -- is stored by whoever
+//   handles the pair, zeros by the scan for pairs that own nothing.
+struct SharedGatherArgs {
+    const int32_t *face_index_map;
+    const float *faces, *zbase, *weight_map, *depth_map, *g_rgb;
+    const unsigned char *visible;  // [B, F] or NULL (every pair is scanned)
+    double *sums;                  // [Nf][ts^3 * 3]
+    int F, S, ts;
+    double eps;
+    int fix_batch_z, L, wide_all, n_lds;  // n_lds: doubles of dynamic LDS
+    FaceLight lit;
+};
+
+template <bool TS2, bool LIT>
+__global__ __launch_bounds__(256) void k_shared_gather(SharedGatherArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) double s_acc[];  // [256 / L][ts^3 * 3]; a wide pair: the first cube
+    __shared__ int s_queue[512];                                    // walk_owned_pixels
+    __shared__ int s_small[256], s_wide[256];
+    __shared__ int s_wave_n[4][2];
+    __shared__ int s_own;
+    __shared__ float s_gl[3];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int b = blockIdx.y, F = a.F, S = a.S, ts = a.ts, L = a.L;
+    const int n_tex = ts * ts * ts * 3;
+    const FaceLight &lit = a.lit;
+    const int Nf = LIT ? lit.tex_faces : F;
+    const size_t img = (size_t)b * S * S;
+    const float *__restrict__ faces_b = a.faces + (size_t)b * F * 9;
+    const float *__restrict__ zfaces = a.fix_batch_z ? faces_b : a.zbase;  // :389, Q1
+    float *__restrict__ grad_light = LIT ? lit.grad_light : nullptr;
+
+    int n_small, n_wide;
+    {   // the range's pairs, one per thread; both lists in thread order
+        const int f = (int)blockIdx.x * 256 + tid;
+        const bool vis = f < F && (!a.visible || a.visible[(size_t)b * F + f] != 0);
+        bool small = false, wide = false;
+        if (vis) {
+            const float *fp = faces_b + (size_t)f * 9;
+            const Cand cd = face_candidates(fp[0], fp[1], fp[3], fp[4], fp[6], fp[7], S);
+            wide = cd.n > BIG_PX || (a.wide_all && cd.n > 0);
+            small = cd.n > 0 && !wide;
+        }
+        if (grad_light && f < F && !small && !wide) {
+            float *gl = grad_light + ((size_t)b * F + f) * 3;
+            gl[0] = 0.0f; gl[1] = 0.0f; gl[2] = 0.0f;
+        }
+        const unsigned long long ms = __ballot(small), mw = __ballot(wide);
+        if (lane == 0) { s_wave_n[wave][0] = __popcll(ms); s_wave_n[wave][1] = __popcll(mw); }
+        for (int k = tid; k < a.n_lds; k += 256) s_acc[k] = 0.0;
+        __syncthreads();
+        int bs = 0, bw = 0;
+        for (int w = 0; w < wave; w++) { bs += s_wave_n[w][0]; bw += s_wave_n[w][1]; }
+        const unsigned long long below = (1ull << lane) - 1ull;
+        if (small) s_small[bs + __popcll(ms & below)] = f;
+        if (wide) s_wide[bw + __popcll(mw & below)] = f;
+        n_small = s_wave_n[0][0] + s_wave_n[1][0] + s_wave_n[2][0] + s_wave_n[3][0];
+        n_wide = s_wave_n[0][1] + s_wave_n[1][1] + s_wave_n[2][1] + s_wave_n[3][1];
+        __syncthreads();
+    }
+
+    // the small pairs: 256 / L at a time, a group of L lanes each (every lane of the workgroup takes every round: the walk
+    // keeps the lanes of a wave in step, the barriers below the workgroup)
+    const int per = 256 / L, grp = tid / L, sub = tid - grp * L;
+    double *acc_l = s_acc + (TS2 ? 0 : (size_t)grp * n_tex);
+    for (int q0 = 0; q0 < n_small; q0 += per) {
+        const bool face_ok = q0 + grp < n_small;
+        const int fn = face_ok ? s_small[q0 + grp] : 0;
+        Cand cd;
+        cd.n = 0;
+        float face_z[3] = {1.0f, 1.0f, 1.0f};
+        const bool flip = LIT && fn >= Nf;
+        const int cube = flip ? fn - Nf : fn;
+        if (face_ok) {
+            const float *fp = faces_b + (size_t)fn * 9;
+            cd = face_candidates(fp[0], fp[1], fp[3], fp[4], fp[6], fp[7], S);
+            const float *fz = zfaces + (size_t)fn * 9;
+            face_z[0] = fz[2]; face_z[1] = fz[5]; face_z[2] = fz[8];
+        }
+        float acc[24];
+#pragma unroll
+        for (int k = 0; k < 24; k++) acc[k] = 0.0f;
+        bool own = false;
+        walk_owned_pixels<2>(cd, face_ok ? cd.n : 0, fn, a.face_index_map + img, S, sub, L, s_queue, [&](int off) {
+            const size_t p = img + (size_t)off;
+            const float wk[3] = {a.weight_map[3 * p], a.weight_map[3 * p + 1], a.weight_map[3 * p + 2]};
+            const float depth = a.depth_map[p];
+            const float g[3] = {a.g_rgb[3 * p], a.g_rgb[3 * p + 1], a.g_rgb[3 * p + 2]};
+            own = true;
+            Taps t;
+            compute_taps(face_z, wk, depth, ts, a.eps, t, flip);
+#pragma unroll
+            for (int pn = 0; pn < 8; pn++) {
+                if (TS2) {
+                    acc[3 * pn + 0] += t.w[pn] * g[0];  // :780
+                    acc[3 * pn + 1] += t.w[pn] * g[1];
+                    acc[3 * pn + 2] += t.w[pn] * g[2];
+                } else {
+                    if (t.isc[pn] * 3 >= n_tex) continue;  // outside the cube: weight 0 (compute_taps)
+                    double *q = acc_l + t.isc[pn] * 3;
+                    atomicAdd(q + 0, (double)(t.w[pn] * g[0]));
+                    atomicAdd(q + 1, (double)(t.w[pn] * g[1]));
+                    atomicAdd(q + 2, (double)(t.w[pn] * g[2]));
+                }
+            }
+        });
+        const unsigned long long bm = __ballot(own);
+        const bool owned = L == 64 ? bm != 0ull : ((bm >> (tid & 48)) & 0xffffull) != 0ull;
+        float l3[3] = {1.0f, 1.0f, 1.0f};
+        if (LIT && face_ok) {
+            const float *lc = lit.light + ((size_t)b * F + fn) * 3;
+            l3[0] = lc[0]; l3[1] = lc[1]; l3[2] = lc[2];
+        }
+        if (TS2) {  // L == 16: the row's last lane holds the pair's 24 sums (corner pn = texel bitrev3(pn) of the sampled cube)
+#pragma unroll
+            for (int k = 0; k < 24; k++) acc[k] = row16_sum_last(acc[k]);
+            if (face_ok && sub == 15) {
+                float gl[3] = {0.0f, 0.0f, 0.0f};
+                if (owned) {
+                    float tx[24];
+#pragma unroll
+                    for (int k = 0; k < 24; k++) tx[k] = 0.0f;
+                    if (LIT && lit.textures) {  // 96 B per cube, 16 B aligned (nr_hip.h)
+                        const float4 *src = reinterpret_cast<const float4 *>(lit.textures + (size_t)cube * 24);
+#pragma unroll
+                        for (int k = 0; k < 6; k++) {
+                            const float4 v = src[k];
+                            tx[4 * k] = v.x; tx[4 * k + 1] = v.y; tx[4 * k + 2] = v.z; tx[4 * k + 3] = v.w;
+                        }
+                    }
+                    double *dst = a.sums + (size_t)cube * 24;
+#pragma unroll
+                    for (int u = 0; u < 8; u++) {
+                        const int r = (u & 1) * 4 + (u & 2) + (u >> 2);
+#pragma unroll
+                        for (int c = 0; c < 3; c++) {
+                            const float av = flip ? acc[3 * u + c] : acc[3 * r + c];
+                            const float o = LIT ? av * l3[c] : av;
+                            if (LIT) gl[c] += av * tx[3 * u + c];
+                            if (o != 0.0f) atomicAdd(dst + 3 * u + c, (double)o);
+                        }
+                    }
+                }
+                if (grad_light) {
+                    float *gd = grad_light + ((size_t)b * F + fn) * 3;
+                    gd[0] = gl[0]; gd[1] = gl[1]; gd[2] = gl[2];
+                }
+            }
+        } else {
+            __syncthreads();
+            float gl0 = 0.0f, gl1 = 0.0f, gl2 = 0.0f;
+            if (face_ok && owned) {
+                const float *tex = (LIT && lit.textures) ? lit.textures + (size_t)cube * n_tex : nullptr;
+                double *dst = a.sums + (size_t)cube * n_tex;
+                for (int k = sub; k < n_tex; k += L) {
+                    const float av = (float)acc_l[k];
+                    acc_l[k] = 0.0;  // (the next round's zeros)
+                    if (av == 0.0f) continue;
+                    const int c = k % 3;
+                    if (tex) {
+                        const float v = av * tex[k];
+                        gl0 += c == 0 ? v : 0.0f;
+                        gl1 += c == 1 ? v : 0.0f;
+                        gl2 += c == 2 ? v : 0.0f;
+                    }
+                    atomicAdd(dst + k, (double)(LIT ? av * (c == 0 ? l3[0] : (c == 1 ? l3[1] : l3[2])) : av));
+                }
+            }
+            if (grad_light) {
+                gl0 = group_sum(gl0, L); gl1 = group_sum(gl1, L); gl2 = group_sum(gl2, L);
+                if (face_ok && sub == 0) {
+                    float *gd = grad_light + ((size_t)b * F + fn) * 3;
+                    gd[0] = gl0; gd[1] = gl1; gd[2] = gl2;
+                }
+            }
+            __syncthreads();
+        }
+    }
+
+    // the wide pairs: the whole workgroup walks each in turn (coalesced rows), texel sums in the first cube of LDS doubles
+    for (int q = 0; q < n_wide; q++) {
+        const int fn = s_wide[q];
+        const float *fp = faces_b + (size_t)fn * 9;
+        const Cand cd = face_candidates(fp[0], fp[1], fp[3], fp[4], fp[6], fp[7], S);
+        const float *fz = zfaces + (size_t)fn * 9;
+        const float face_z[3] = {fz[2], fz[5], fz[8]};
+        const bool flip = LIT && fn >= Nf;
+        const int cube = flip ? fn - Nf : fn;
+        if (tid < 3) s_gl[tid] = 0.0f;
+        if (tid == 0) s_own = 0;
+        __syncthreads();
+        bool own = false;
+        for (int i = tid; i < cd.n; i += 256) {
+            int x, y;
+            if (!cand_pixel(cd, i, S, x, y)) continue;
+            const size_t p = img + (size_t)y * S + x;
+            if (a.face_index_map[p] != fn) continue;
+            own = true;
+            const float wk[3] = {a.weight_map[3 * p], a.weight_map[3 * p + 1], a.weight_map[3 * p + 2]};
+            const float g[3] = {a.g_rgb[3 * p], a.g_rgb[3 * p + 1], a.g_rgb[3 * p + 2]};
+            Taps t;
+            compute_taps(face_z, wk, a.depth_map[p], ts, a.eps, t, flip);
+#pragma unroll
+            for (int pn = 0; pn < 8; pn++) {
+                if (t.isc[pn] * 3 >= n_tex) continue;  // outside the cube: weight 0 (compute_taps)
+                double *d = s_acc + t.isc[pn] * 3;
+                atomicAdd(d + 0, (double)(t.w[pn] * g[0]));
+                atomicAdd(d + 1, (double)(t.w[pn] * g[1]));
+                atomicAdd(d + 2, (double)(t.w[pn] * g[2]));
+            }
+        }
+        if (own) s_own = 1;
+        __syncthreads();
+        if (s_own) {
+            const float *lc = LIT ? lit.light + ((size_t)b * F + fn) * 3 : nullptr;
+            const float *tex = (LIT && lit.textures) ? lit.textures + (size_t)cube * n_tex : nullptr;
+            double *dst = a.sums + (size_t)cube * n_tex;
+            for (int k = tid; k < n_tex; k += 256) {
+                const float av = (float)s_acc[k];
+                s_acc[k] = 0.0;  // (the next pair's zeros)
+                if (av == 0.0f) continue;
+                const int c = k % 3;
+                if (tex) atomicAdd(&s_gl[c], av * tex[k]);
+                atomicAdd(dst + k, (double)(LIT ? av * lc[c] : av));
+            }
+        }
+        __syncthreads();
+        if (grad_light && tid < 3) grad_light[((size_t)b * F + fn) * 3 + tid] = s_gl[tid];
+        __syncthreads();
+    }
+}
+
+// the shared gather's double sums, rounded once: every element of grad_textures
+__global__ __launch_bounds__(256) void k_round_sums(const double *__restrict__ sums, float *__restrict__ out, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) out[i] = (float)sums[i];
+}
+
 // k_backward_big's grid: one workgroup per range of 256 faces (or list slots), times as many workgroups per range (z) as it
 // takes to put ~4096 workgroups on the chip -- they share out the range's big faces.  (Small launches: a workgroup per 64
 // faces of the call, at least 1024 -- with nothing to do, as on a fine mesh, the kernel costs what dispatching it costs.)
@@ -559,4 +811,53 @@ void nr::gather_depth(const BackwardCall &c, const K6Lists &l)
                        (const int32_t *)nullptr, c.face_inv_map, c.faces, c.faces, c.weight_map, c.depth_map, (const float *)nullptr,
                        (float *)nullptr, n, F, c.S, 2, 0.0, 0, l.vis_list, l.vis_count, c.grad_depth_map, c.grad_faces,
                        c.visible_faces, FaceLight(), (const double *)nullptr);
+}
+
+// ====================================================================================================
+// Texture cubes shared by the batch (include/nr_hip.h): zeros of the double sums, the gather over (image, face) pairs, the rounding
+
+NR_API size_t nr_backward_textures_shared_workspace_bytes(int32_t B, int32_t Nf, int32_t ts)
+{
+    if (B < 1 || B > 65535 || Nf < 1 || ts < 2 || ts > 13) return 0;
+    return align_up((size_t)Nf * ts * ts * ts * 3 * sizeof(double), 256);  // (the batch does not enter)
+}
+
+NR_API int nr_backward_textures_shared(const nr_face_light *lit, const float *faces, const float *faces_z_ref,
+                                       const int32_t *face_index_map, const float *weight_map, const float *depth_map,
+                                       const float *grad_rgb_map, const uint8_t *visible_faces, float *grad_textures, int32_t B,
+                                       int32_t F, int32_t S, int32_t ts, double eps, int32_t flags, void *workspace,
+                                       size_t workspace_bytes, void *stream)
+{
+    if (!faces || !face_index_map || !weight_map || !depth_map || !grad_rgb_map || !grad_textures) return NR_E_NULL;
+    if (int e = check_sizes(B, F, S)) return e;
+    if (ts < 2 || ts > 13) return NR_E_SIZE;
+    SharedGatherArgs a = {};
+    if (int e = face_light_args(lit, F, true, a.lit)) return e;
+    const int Nf = lit ? a.lit.tex_faces : F;
+    const size_t n_tex = (size_t)ts * ts * ts * 3, n = (size_t)Nf * n_tex;
+    if (!workspace || workspace_bytes < nr_backward_textures_shared_workspace_bytes(B, Nf, ts)) return NR_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    a.face_index_map = face_index_map, a.faces = faces, a.zbase = faces_z_ref ? faces_z_ref : faces;
+    a.weight_map = weight_map, a.depth_map = depth_map, a.g_rgb = grad_rgb_map, a.visible = visible_faces;
+    a.sums = (double *)workspace;
+    a.F = F, a.S = S, a.ts = ts, a.eps = eps, a.fix_batch_z = (flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0;
+    // the batched gather's shapes (plan_backward): static taps at texture_size 2, 16 lanes per pair up to 5, a wave up to 8;
+    // above, a cube of doubles per workgroup
+    const bool ts2 = ts == 2 && (float)(1.0 - eps) < 1.0f;
+    a.L = (ts2 || ts <= 5) ? 16 : 64;
+    a.wide_all = ts > 8 ? 1 : 0;
+    a.n_lds = (int)((ts2 || a.wide_all) ? n_tex : (size_t)(256 / a.L) * n_tex);
+    if (int e = fill_bytes(a.sums, 0, n * sizeof(double), st)) return e;
+    const dim3 grid((unsigned)((F + 255) / 256), (unsigned)B);
+    const size_t lds = (size_t)a.n_lds * sizeof(double);
+    if (ts2) {
+        if (lit) hipLaunchKernelGGL((k_shared_gather<true, true>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((k_shared_gather<true, false>), grid, dim3(256), lds, st, a);
+    } else {
+        if (lit) hipLaunchKernelGGL((k_shared_gather<false, true>), grid, dim3(256), lds, st, a);
+        else hipLaunchKernelGGL((k_shared_gather<false, false>), grid, dim3(256), lds, st, a);
+    }
+    if (int e = launch_status()) return e;
+    hipLaunchKernelGGL(k_round_sums, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.sums, grad_textures, n);
+    return launch_status();
 }

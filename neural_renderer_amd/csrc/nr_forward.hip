@@ -530,7 +530,8 @@ struct CubeFace {
     float4 cube[TS2 ? 6 : 1];
 };
 
-template <bool TS2>
+// SHARED (NR_FLAG_SHARED_TEXTURES): one set of cubes for the whole batch -- the texture batch stride is 0, nothing else changes
+template <bool TS2, bool SHARED = false>
 __device__ __forceinline__ void load_cube_face(CubeFace<TS2> &c, int b, int fi, const float *__restrict__ faces,
                                                const float *__restrict__ zbase, const float *__restrict__ textures, int F,
                                                int ts, int fix_batch_z, const FaceLight &lit)
@@ -540,11 +541,11 @@ __device__ __forceinline__ void load_cube_face(CubeFace<TS2> &c, int b, int fi, 
     c.fz[0] = face[2]; c.fz[1] = face[5]; c.fz[2] = face[8];
     if constexpr (TS2) {  // (never with a light)
         c.flip = false;
-        c.texture = textures + ((size_t)b * F + fi) * 24;  // :390
+        c.texture = textures + ((size_t)(SHARED ? 0 : b) * F + fi) * 24;  // :390
     } else {
         // :390; with a light, the cube of the original face: its reversed copy reads it transposed (nr_device.h: FaceLight)
         c.flip = lit.light && fi >= lit.tex_faces;
-        c.texture = textures + ((size_t)b * (lit.light ? lit.tex_faces : F) + (c.flip ? fi - lit.tex_faces : fi)) * ts * ts * ts * 3;
+        c.texture = textures + ((size_t)(SHARED ? 0 : b) * (lit.light ? lit.tex_faces : F) + (c.flip ? fi - lit.tex_faces : fi)) * ts * ts * ts * 3;
         const float *lc = lit.light ? lit.light + ((size_t)b * F + fi) * 3 : face;  // (no light: a readable address, values unused)
         c.lc[0] = lc[0]; c.lc[1] = lc[1]; c.lc[2] = lc[2];
     }
@@ -738,7 +739,7 @@ template <int MODE> using ResolveArgsOf =
 // -- [the `touched` byte,] the z-buffer word, everything that (b, fn) addresses, the taps whose addresses need the weights
 // (none with TS2) -- and all of them in front of the pixel's stores: the pass is bound by the round trips of the workgroups
 // that hold a drawn segment, and this ISA's vmcnt counts stores too, so a load behind stores waits for them.
-template <int MODE, bool TS2>
+template <int MODE, bool TS2, bool SHARED = false>
 __device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size_t i, unsigned long long pk, const float (&bg)[3])
 {
     constexpr bool CUBE = MODE == SHADE_CUBE;
@@ -758,7 +759,7 @@ __device__ __forceinline__ void resolve_pixel(const ResolveArgsOf<MODE> &a, size
         const float *f = faces + ((size_t)b * F + fn) * 9;
         const float fv[9] = {f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7], f[8]};
         CubeFace<TS2> c;
-        if (CUBE && a.rgb_map) load_cube_face(c, b, fn, faces, a.zbase, a.textures, F, a.ts, a.fix_batch_z, a.lit);
+        if (CUBE && a.rgb_map) load_cube_face<TS2, SHARED>(c, b, fn, faces, a.zbase, a.textures, F, a.ts, a.fix_batch_z, a.lit);
         FaceGeo g;
         float inv[9];
         face_geo(fv, S, g, inv);
@@ -827,7 +828,7 @@ __device__ __forceinline__ void reset_queue_counters(const ResolveArgs &a)
     }
 }
 
-template <int MODE>
+template <int MODE, bool SHARED = false>
 __global__ __launch_bounds__(256, 8) void k_resolve(ResolveArgsOf<MODE> a)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -840,7 +841,7 @@ __global__ __launch_bounds__(256, 8) void k_resolve(ResolveArgsOf<MODE> a)
     // 512 bytes of z-buffer behind it are not read (round 4: 33.5 -> ~6 MB of z-buffer reads at the headline size).  Stale
     // bytes of earlier calls carry larger epoch numbers, the initial fill 0xff: no clearing.
     const bool drawn = !a.touched || a.touched[i >> 6] == (unsigned char)a.epoch;
-    resolve_pixel<MODE, false>(a, i, drawn ? a.zbuf[i] : ZEMPTY, bg);
+    resolve_pixel<MODE, false, SHARED>(a, i, drawn ? a.zbuf[i] : ZEMPTY, bg);
 }
 
 // The same pass for epoch mode on rasters with an even side.  Most of what the pass writes is the constant of undrawn pixels
@@ -852,8 +853,8 @@ __global__ __launch_bounds__(256, 8) void k_resolve(ResolveArgsOf<MODE> a)
 // (256 pixels per workgroup: 64 / 128 / 512 / 1024 were measured -- 74.7 / 73.7 / 76.5 / 84.5 us against 69-70)
 // A lane's two `touched` bytes (of the quad it fills, first wave only, and of the pixel it resolves) are requested together
 // at the top, with the workgroup's background colour, and the z-buffer word in front of the fills' stores.
-// TS2: the cube instantiation's static taps (shade_cube)
-template <int MODE, bool TS2 = false>
+// TS2: the cube instantiation's static taps (shade_cube); SHARED: its cubes are one set for the batch (load_cube_face)
+template <int MODE, bool TS2 = false, bool SHARED = false>
 __global__ __launch_bounds__(256, 8) void k_resolve_quads(ResolveArgsOf<MODE> a)
 {
     reset_queue_counters(a);
@@ -896,7 +897,7 @@ __global__ __launch_bounds__(256, 8) void k_resolve_quads(ResolveArgsOf<MODE> a)
             o[2] = make_float4(c[2], c[0], c[1], c[2]);
         }
     }
-    if (ti == ep) resolve_pixel<MODE, TS2>(a, i, pk, bg);
+    if (ti == ep) resolve_pixel<MODE, TS2, SHARED>(a, i, pk, bg);
 }
 
 }  // namespace
@@ -955,7 +956,7 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
                 size_t workspace_bytes, hipStream_t st, const float *faces_z_ref, const float *textures, float *rgb_map,
                 const float *background, int bg_per_batch, float *alpha_map, int ts, double eps, int fix_batch_z,
                 int flags = 0, const FaceLight &lit = FaceLight(), const UVShade *uv = nullptr, bool corner = false,
-                bool corner_light = false)
+                bool corner_light = false, bool shared_cubes = false)
 {
     if (!faces || !face_index_map) return NR_E_NULL;
     if (int e = check_sizes(B, F, S)) return e;
@@ -1026,6 +1027,11 @@ int run_forward(const float *faces, int32_t *face_index_map, float *weight_map, 
     } else if (corner) {  // corner colours (nr_forward_rasterize_corner): ra.textures = corner_colors [B, F, 3, 3]
         if (quads) hipLaunchKernelGGL(k_resolve_quads<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
         else hipLaunchKernelGGL(k_resolve<SHADE_CORNER>, grid, dim3(256), 0, st, ra);
+    } else if (shared_cubes) {  // NR_FLAG_SHARED_TEXTURES: the cube instantiations below with a texture batch stride of 0
+        if (quads && rgb_map && !lit.light && ts == 2 && (float)(1.0 - eps) < 1.0f && ((uintptr_t)textures & 15) == 0)
+            hipLaunchKernelGGL((k_resolve_quads<SHADE_CUBE, true, true>), grid, dim3(256), 0, st, ra);
+        else if (quads) hipLaunchKernelGGL((k_resolve_quads<SHADE_CUBE, false, true>), grid, dim3(256), 0, st, ra);
+        else hipLaunchKernelGGL((k_resolve<SHADE_CUBE, true>), grid, dim3(256), 0, st, ra);
     } else if (quads && rgb_map && !lit.light && ts == 2 && (float)(1.0 - eps) < 1.0f && ((uintptr_t)textures & 15) == 0) {
         // static taps (the backward's rule, nr_backward.hip: no index float reaches 1) on cubes that 16-byte loads can read
         hipLaunchKernelGGL((k_resolve_quads<SHADE_CUBE, true>), grid, dim3(256), 0, st, ra);
@@ -1092,7 +1098,8 @@ NR_API int nr_forward_rasterize_lit(const nr_face_light *lit, const float *faces
     if (int e = face_light_args(rgb_map ? lit : nullptr, F, false, fl)) return e;
     return run_forward(faces, face_index_map, weight_map, depth_map, nullptr, visible_faces, B, F, S, near, far,
                        workspace, workspace_bytes, (hipStream_t)stream, faces_z_ref, textures, rgb_map, background,
-                       bg_per_batch, alpha_map, ts, eps, (flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0, flags, fl);
+                       bg_per_batch, alpha_map, ts, eps, (flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0, flags, fl, nullptr, false,
+                       false, rgb_map && (flags & NR_FLAG_SHARED_TEXTURES));
 }
 
 // host-side check of an nr_uv_images with its nr_face_light (see include/nr_hip.h) -> the kernels' FaceLight / UVShade
@@ -1180,6 +1187,7 @@ NR_API int nr_forward_texture_sampling(const float *faces, const float *faces_z_
 {
     if (!face_index_map) return NR_E_NULL;
     if (!rgb_map && !alpha_map) return NR_E_MODE;
+    if (flags & NR_FLAG_SHARED_TEXTURES) return NR_E_MODE;  // (the staged pass strides the cubes by the batch)
     if (int e = check_sizes(B, F, S)) return e;
     if (rgb_map) {
         if (!faces || !textures || !weight_map || !depth_map || !background) return NR_E_NULL;

@@ -20,6 +20,10 @@ on what else is in the launch (tests/test_sharding_gpu.py; at the metric's shape
 tests/test_full_size_gpu.py::test_headline_batch_equals_its_shards.  With NR_FLAG_K6_LEGACY, k_bpm_fast's float run sums are
 grouped by the arrival order of its line records: <= 1.2e-5 of the largest gradient between two calls, sharded or not).  With
 fix_batch_z (NR_FIX_TEXTURE_BATCH_Z=1) nothing needs to be exchanged.
+
+Texture cubes shared by the batch (`textures [1,Nf,ts,ts,ts,3]`, rasterize.py): a shard's `grad_textures [1,Nf,...]` is the
+sum over the shard's OWN views, a partial sum of the batch's -- all_reduce_shared_grads adds the ranks' up, as it does for
+any parameter the views share.
 """
 import os
 

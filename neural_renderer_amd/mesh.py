@@ -18,12 +18,20 @@ class Mesh(nn.Module):
         self.textures = nn.Parameter(torch.randn(shape, dtype=torch.float32) * 0.05)
         self.texture_size = texture_size
 
-    def get_batch(self, batch_size):
-        # broadcast for minibatch (mesh.py:29-34)
+    def get_batch(self, batch_size, shared_textures=False):
+        """broadcast for minibatch (mesh.py:29-34).  `shared_textures` (not in the reference): the textures come back with a
+        batch of 1, sigmoid(self.textures)[None] -- one set of cubes that Renderer.render and the rasterizer share among the
+        batch_size views, the sigmoid run once -- instead of batch_size expanded copies."""
         vertices = self.vertices[None].expand(batch_size, *self.vertices.shape)
         faces = self.faces[None].expand(batch_size, *self.faces.shape)
+        if shared_textures:
+            return vertices, faces, torch.sigmoid(self.textures)[None]
         textures = torch.sigmoid(self.textures[None].expand(batch_size, *self.textures.shape))
         return vertices, faces, textures
+
+    def forward(self, batch_size, shared_textures=False):
+        """The module's call: get_batch."""
+        return self.get_batch(batch_size, shared_textures)
 
     def set_lr(self, lr_vertices, lr_textures):
         """Per-parameter learning-rate multipliers read by neural_renderer_amd.Adam (mesh.py:36-38)."""

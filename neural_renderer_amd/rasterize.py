@@ -188,10 +188,11 @@ class _Residuals(object):
     """Everything one forward leaves behind for its backward (the reference keeps the same on `self`, rasterize.py:39-58).
     `source` is the call's shading source; textures / light / packed / corner are what that source keeps (the rest None)."""
     __slots__ = ('B', 'F', 'S', 'ts', 'Nf', 'flags', 'faces', 'z_ref', 'face_index_map', 'weight_map', 'depth_map',
-                 'rgb_map', 'alpha_map', 'visible', 'source', 'textures', 'light', 'packed', 'corner')
+                 'rgb_map', 'alpha_map', 'visible', 'source', 'textures', 'light', 'packed', 'corner', 'shared')
 
     def __init__(self):
         self.textures = self.light = None  # cubes [B,Nf,ts,ts,ts,3]; per-face light colours [B,F,3]
+        self.shared = False                # the cubes are [1,Nf,ts,ts,ts,3], one set for all B > 1 images
         self.packed = None                 # per-pixel UV images: their packing [Bi,P,3]
         self.corner = None                 # corner colours [B,F,3,3]
 
@@ -242,6 +243,9 @@ def _launch_backward(lib, cfg, r, lit, grad_textures, g_rgb, g_alpha, g_depth, g
 class _Cubes(object):
     """Shading source: texture cubes [B,Nf,ts,ts,ts,3] as in the reference (None when no rgb is drawn), alone or with per-face
     light colours [B,F,3] (F = Nf or 2 Nf; include/nr_hip.h: nr_face_light).  Inputs of the autograd node: (textures, light).
+    Cubes [1,Nf,ts,ts,ts,3] beside B > 1 images (not in the reference) are ONE set shared by the batch: the forward reads the
+    single copy (NR_FLAG_SHARED_TEXTURES), the backward returns its gradient summed over the images, [1,Nf,...]
+    (nr_backward_textures_shared behind the rasterizer's own backward, which then runs without its texture stage).
 
     A shading source is everything the operator does differently for one kind of `textures`; _source_of picks it, and the
     operator asks it for: `check` (the input checks -> Nf, ts), `keep` (the residuals of the inputs), `saved` / `restore`
@@ -264,14 +268,17 @@ class _Cubes(object):
             if textures.dim() == 6 and textures.shape[1] * 2 == F:
                 Nf = F // 2  # fill_back: face Nf + f is the reversed copy of face f
         sh = textures.shape
-        if (textures.dtype != torch.float32 or textures.dim() != 6 or sh[0] != B or sh[1] != Nf or sh[2] < 2 or
+        if (textures.dtype != torch.float32 or textures.dim() != 6 or sh[0] not in (1, B) or sh[1] != Nf or sh[2] < 2 or
                 sh[2] != sh[3] or sh[3] != sh[4] or sh[5] != 3):
-            raise ValueError('textures must be float32 [batch size, num of faces, ts, ts, ts, 3] with ts >= 2, '
-                             'got %s %s' % (textures.dtype, tuple(sh)))  # rasterize.py:78-90
+            raise ValueError('textures must be float32 [batch size (or 1: shared by the batch), num of faces, ts, ts, ts, 3] '
+                             'with ts >= 2, got %s %s' % (textures.dtype, tuple(sh)))  # rasterize.py:78-90
+        if sh[0] != B and sh[2] > 13:
+            raise ValueError('textures shared by the batch need ts <= 13, got %d: expand them to the batch size' % sh[2])
         return Nf, int(sh[2])
 
     def keep(self, r, inputs):
         textures, light = inputs
+        r.shared = textures is not None and textures.shape[0] != r.B
         r.textures = textures.detach().contiguous() if textures is not None else None  # rasterize.py:473
         r.light = light.detach().contiguous() if light is not None else None
 
@@ -285,10 +292,36 @@ class _Cubes(object):
         # weight_map is a residual only (the backward reads it at covered pixels): the eager operator does not store the zeros
         # of uncovered pixels (NR_FLAG_SPARSE_WEIGHT_MAP; `Rasterize.weight_map` fills them in when somebody reads the attribute)
         lit = _lib.FaceLight(r.light.data_ptr(), r.Nf, None, None) if r.light is not None else None
+        if r.shared:
+            tail = (tail[0] | _lib.NR_FLAG_SHARED_TEXTURES,) + tuple(tail[1:])
         _lib.check(lib.nr_forward_rasterize_lit(lit, r.faces.data_ptr(), _lib.ptr(r.z_ref), _lib.ptr(r.textures), *maps, r.ts,
                                                 cfg.near, cfg.far, cfg.eps, *tail), 'nr_forward_rasterize')
 
+    def _backward_shared(self, lib, cfg, r, want, call):
+        """One set of cubes for the batch: grad_faces from the rasterizer's backward without its texture stage (K6 + K8 do not
+        read the cubes), then the gather over (image, face) pairs that sums the cubes' gradient over the images."""
+        _launch_backward(lib, cfg, r, None, None, *call)
+        g_rgb, stream = call[0], call[-1]
+        if g_rgb is None or not (want[0] or (r.light is not None and want[1])):
+            return None, None
+        B, F, ts = r.B, r.F, r.ts
+        f32, dev = torch.float32, r.faces.device
+        grad_textures = torch.empty((1, r.Nf, ts, ts, ts, 3), dtype=f32, device=dev)
+        grad_light = lit = None
+        if r.light is not None:
+            grad_light = torch.empty((B, F, 3), dtype=f32, device=dev) if want[1] else None
+            lit = _lib.FaceLight(r.light.data_ptr(), r.Nf, r.textures.data_ptr(), _lib.ptr(grad_light))
+        ws_bytes = lib.nr_backward_textures_shared_workspace_bytes(B, r.Nf, ts)
+        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.nr_backward_textures_shared(
+            lit, r.faces.data_ptr(), _lib.ptr(r.z_ref), r.face_index_map.data_ptr(), r.weight_map.data_ptr(),
+            r.depth_map.data_ptr(), g_rgb.data_ptr(), _lib.ptr(r.visible), grad_textures.data_ptr(), B, F, r.S, ts, cfg.eps,
+            r.flags, ws.data_ptr(), ws_bytes, stream), 'nr_backward_textures_shared')
+        return grad_textures, grad_light
+
     def backward(self, lib, cfg, r, want, call):
+        if r.shared:
+            return self._backward_shared(lib, cfg, r, want, call)
         grad_textures = grad_light = lit = None
         if call[0] is not None:  # a gradient of rgb_map: the texture stage (K7) runs inside the rasterizer's backward
             B, F, ts = r.B, r.F, r.ts
@@ -564,7 +597,7 @@ class _RasterizeFunction(torch.autograd.Function):
         ctx.cfg, ctx.source = cfg, src
         # (the node must not hold its own OUTPUTS except through save_for_backward: output -> grad_fn -> node -> output is a
         # cycle through C++ that nothing collects -- every step's maps would stay allocated)
-        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags)
+        ctx.meta = (r.B, r.F, r.S, r.ts, r.Nf, r.flags, r.shared)
         ctx.z_ref, ctx.visible = r.z_ref, r.visible
         ctx.set_materialize_grads(False)  # an unused output arrives as `None` in backward and its terms are skipped
         # residuals (the reference keeps them on `self`, rasterize.py:39-58); outputs and inputs among them go through
@@ -577,7 +610,7 @@ class _RasterizeFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth, _g_fi):
         r = _Residuals()
-        r.B, r.F, r.S, r.ts, r.Nf, r.flags = ctx.meta
+        r.B, r.F, r.S, r.ts, r.Nf, r.flags, r.shared = ctx.meta
         r.z_ref, r.visible, r.source = ctx.z_ref, ctx.visible, ctx.source
         # (unpacking checks the version counters of the saved tensors: an in-place edit since the forward raises)
         saved = ctx.saved_tensors
@@ -710,7 +743,7 @@ class _GraphedRasterizeFunction(torch.autograd.Function):
 
 def _graph_entry(faces, src, inputs, cfg):
     """The cached graphs for this call's device / sizes / configuration, or None when the call is not eligible (replay knows
-    cubes without face_light only; CPU tensors raise in the eager operator; tensor-valued backgrounds or z references that
+    batched cubes without face_light only -- one set of cubes shared by the batch runs eagerly --; CPU tensors raise in the eager operator; tensor-valued backgrounds or z references that
     change between calls are handled by value)."""
     if src is not _CUBES or inputs[1] is not None:
         return None
@@ -873,8 +906,10 @@ class Rasterize(object):
                                                          ws.data_ptr(), ws_bytes, stream), 'nr_forward_face_index_map')
                 self._lazy['face_inv_map'] = out
             else:
-                if r.textures is None or r.light is not None:
-                    return None  # no texture sampling in this call (or per-face light colours: no reference counterpart)
+                if r.textures is None or r.light is not None or r.shared:
+                    # no texture sampling in this call (or per-face light colours: no reference counterpart; or one set of
+                    # cubes for the batch: the staged pass strides the cubes by the batch)
+                    return None
                 si = torch.empty((B, S, S, 8), dtype=torch.int32, device=dev)
                 sw = torch.empty((B, S, S, 8), dtype=f32, device=dev)
                 rgb = torch.empty((B, S, S, 3), dtype=f32, device=dev)
@@ -945,7 +980,9 @@ class Rasterize(object):
     def __call__(self, faces, textures=None, face_light=None):
         """`face_light` (not in the reference; include/nr_hip.h nr_face_light): [B,F,3] colours that multiply the sampled
         colour of each face; `textures` are then the cubes of the original faces ([B,F,...], or [B,F/2,...] when the second
-        half of `faces` are fill_back's reversed copies).  `textures` may be a UVImages (not in the reference): the images are
+        half of `faces` are fill_back's reversed copies).  Cubes with a batch of 1 beside B > 1 faces (not in the reference) are
+        one set shared by the batch: no expanded copy, and their gradient comes back summed over the images, [1,...]; the
+        call runs eagerly, and the sampling maps read as None.  `textures` may be a UVImages (not in the reference): the images are
         sampled at every covered pixel; `face_light` is then required, `faces` has the layout's faces (or twice as many with
         fill_back), and the call runs eagerly whatever graph_replay says."""
         cfg = _Config(self)

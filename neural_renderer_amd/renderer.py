@@ -163,6 +163,16 @@ class Renderer(object):
         replay = self.graph_replay if self.graph_replay is not None else sys.modules[rasterize.__module__].GRAPH_REPLAY
         return not replay and frontend.fusable(self, vertices, faces, textures)
 
+    def _render_shared(self, vertices, faces, textures):
+        """render() with ONE set of cubes [1,Nf,ts,ts,ts,3] for a batch of B > 1 views (not in the reference).  Lit textures
+        would be one copy per view again, so the light goes to the rasterizer as one colour per face (face_light is implied,
+        whatever `face_light` and the texture size say), the cubes as they are: from the fused front-end when it takes the
+        call, else from lighting() on a ones texture behind the module-by-module front-end.  The cubes' gradient comes back
+        summed over the views.  Runs eagerly: graph_replay does not apply."""
+        faces, light = self._frontend(vertices, faces, light_colors=True)
+        return rasterize(faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                         self.background_color, faces_z_ref=self.faces_z_ref, face_light=light)
+
     def _render_uv(self, vertices, faces, uv):
         """render() with a UVImages: the images sampled at every covered pixel (not in the reference).  Per-face light colours
         always (face_light is implied): from the fused front-end when it takes the call, else from lighting() on a ones
@@ -213,7 +223,8 @@ class Renderer(object):
                          self.background_color)
 
     def render(self, vertices, faces, textures):
-        """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference, or (not in the reference) a UVImages whose images are
+        """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference -- or [1,Nf,ts,ts,ts,3] beside B > 1 views (not in the
+        reference): one set shared by the batch, see _render_shared --, or (not in the reference) a UVImages whose images are
         sampled at every covered pixel (uv_textures.py), or a VertexColors (vertex_colors.py), lit as `shading` says."""
         if self.shading not in ('flat', 'smooth'):
             raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
@@ -224,6 +235,9 @@ class Renderer(object):
         if self.shading == 'smooth':
             raise ValueError("Renderer.shading = 'smooth' takes UVImages or VertexColors: texture cubes are lit per face "
                              "('flat') only")
+        if (torch.is_tensor(textures) and textures.dim() == 6 and textures.shape[0] == 1 and torch.is_tensor(vertices)
+                and vertices.dim() == 3 and vertices.shape[0] > 1):
+            return self._render_shared(vertices, faces, textures)
         if self._use_face_light(vertices, faces, textures):
             faces, light = self._frontend(vertices, faces, light_colors=True, fused=True)
             return rasterize(
