@@ -74,7 +74,9 @@ extern "C" {
                           *        nr_corner_light, nr_forward_rasterize_uv_smooth, nr_backward_uv_images_smooth[_workspace_bytes];
                           *        nr_forward_rasterize_corner, nr_backward_corner_colors[_workspace_bytes],
                           *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes;
-                          *        NR_FLAG_SHARED_TEXTURES, nr_backward_textures_shared[_workspace_bytes]);
+                          *        NR_FLAG_SHARED_TEXTURES, nr_backward_textures_shared[_workspace_bytes];
+                          *        nr_laplacian_forward, nr_laplacian_backward, nr_flatness_forward, nr_flatness_backward,
+                          *        nr_mesh_loss_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -719,6 +721,43 @@ int nr_vertex_shade_backward(const float *vertices, const int32_t *faces_idx, co
                              int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t color_batch,
                              int32_t idx_per_batch, int32_t fill_back, int32_t smooth, const nr_light *light, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/*
+ * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices
+ * [B, Nv, 3] with ONE topology for the call, described by host-built int32 tables (neural_renderer_amd/mesh_losses.py).
+ *   N(v): the distinct u != v that share a face with v; nbr_offsets [Nv + 1], nbr [num_nbr]: N(v) = nbr[nbr_offsets[v] ..
+ *     nbr_offsets[v + 1]) ascending, deg v its length.
+ *   quads [E2, 4]: (v0 < v1, v2, v3) for every edge {v0, v1} that lies in exactly two faces (faces with a repeated index
+ *     not counted), v2 / v3 the opposite vertices, v2 from the lower-numbered face; ordered by (v0, v1).
+ *   inc_offsets [Nv + 1], inc [4 E2]: the (quad, slot) pairs 4 q + slot in which vertex v occurs, ascending.
+ * Laplacian: delta_v = x_v - (sum of x_u over N(v), table order) / deg v (0 with deg v = 0), loss[b] = sum_v |delta_v|^2;
+ *   delta [B, Nv, 3] is stored for the backward (NULL: not stored).  Backward from grad_loss [B]:
+ *   grad_vertices[b, v] = 2 g_b (delta_v - sum over N(v) of delta_u / deg u), a gather, N being symmetric.
+ * Flatness, per quad: a = x1 - x0, b_i = x_(i+1) - x0, c_i = b_i - ((a . b_i) / (a . a + eps)) a, l_i = sqrt(c_i . c_i + eps),
+ *   cos = (c1 . c2) / (l1 l2 + eps), loss[b] = sum over the quads of (cos + 1)^2: 0 (up to eps) on a flat mesh, finite for
+ *   every finite input with eps > 0.  eps is rounded to float.  E2 = 0: loss = 0 and zero gradients (quads, inc_offsets,
+ *   inc may be NULL).  Backward: every vertex adds, for each of its (quad, slot) pairs in table order, that slot's
+ *   derivative recomputed from the quad's four vertices.
+ * The float operation order of every formula: the header comment of csrc/nr_mesh_losses.hip.  The losses: per block of
+ * 256 vertices / quads a double sum in a fixed order into the workspace (nr_mesh_loss_workspace_bytes(B, Nv) resp. (B, E2)),
+ * the blocks added in block order in double by a second kernel, rounded once.  No atomics in any kernel: the same bits in
+ * every run.  Every output element is stored; no call synchronises the host; NR_E_* before any launch.
+ */
+size_t nr_mesh_loss_workspace_bytes(int32_t batch_size, int32_t num_items);
+
+int nr_laplacian_forward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr, float *delta, float *loss,
+                         int32_t batch_size, int32_t num_vertices, int32_t num_nbr, void *workspace, size_t workspace_bytes,
+                         void *stream);
+
+int nr_laplacian_backward(const float *delta, const int32_t *nbr_offsets, const int32_t *nbr, const float *grad_loss,
+                          float *grad_vertices, int32_t batch_size, int32_t num_vertices, int32_t num_nbr, void *stream);
+
+int nr_flatness_forward(const float *vertices, const int32_t *quads, float *loss, int32_t batch_size, int32_t num_vertices,
+                        int32_t num_quads, double eps, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_flatness_backward(const float *vertices, const int32_t *quads, const int32_t *inc_offsets, const int32_t *inc,
+                         const float *grad_loss, float *grad_vertices, int32_t batch_size, int32_t num_vertices,
+                         int32_t num_quads, double eps, void *stream);
 
 /*
  * Texture atlas of save_obj(..., textures) (K11, reference save_obj.py:10-146): image [tile_height*tso, tile_width*tso, 3]

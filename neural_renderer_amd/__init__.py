@@ -23,6 +23,8 @@ from .save_obj import save_obj
 from .uv_textures import UVImages, UVLayout, UVTextures, bake_uv_textures
 # not in the reference: per-vertex colours and smooth (vertex-normal) shading, interpolated per pixel
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
+# not in the reference: the Laplacian and flatness losses of a mesh fit (shape priors), HIP in both directions
+from .mesh_losses import flatness_loss, laplacian_loss
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -40,4 +42,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'projection',
            'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
-           'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light']
+           'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
+           'laplacian_loss', 'flatness_loss']

@@ -82,6 +82,11 @@ SIGNATURES = {
     'nr_vertex_shade_workspace_bytes': (_sz, [_i32] * 2),
     'nr_vertex_shade_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
     'nr_vertex_shade_backward': (_c.c_int, [_vp] * 8 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
+    'nr_mesh_loss_workspace_bytes': (_sz, [_i32] * 2),
+    'nr_laplacian_forward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp, _sz, _vp]),
+    'nr_laplacian_backward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
+    'nr_flatness_forward': (_c.c_int, [_vp] * 3 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
+    'nr_flatness_backward': (_c.c_int, [_vp] * 6 + [_i32] * 3 + [_f64, _vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),
     'nr_frontend_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_cam_p, _light_p, _vp]),

@@ -33,6 +33,16 @@ class Mesh(nn.Module):
         """The module's call: get_batch."""
         return self.get_batch(batch_size, shared_textures)
 
+    def laplacian_loss(self, implementation=None):
+        """mesh_losses.laplacian_loss of the module's own vertices and faces (not in the reference): a 0-dim tensor."""
+        from .mesh_losses import laplacian_loss
+        return laplacian_loss(self.vertices, self.faces, implementation)
+
+    def flatness_loss(self, eps=1e-6, implementation=None):
+        """mesh_losses.flatness_loss of the module's own vertices and faces (not in the reference): a 0-dim tensor."""
+        from .mesh_losses import flatness_loss
+        return flatness_loss(self.vertices, self.faces, eps, implementation)
+
     def set_lr(self, lr_vertices, lr_textures):
         """Per-parameter learning-rate multipliers read by neural_renderer_amd.Adam (mesh.py:36-38)."""
         self.vertices.lr = lr_vertices
