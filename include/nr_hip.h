@@ -76,7 +76,9 @@ extern "C" {
                           *        nr_vertex_shade_forward, nr_vertex_shade_backward, nr_vertex_shade_workspace_bytes;
                           *        NR_FLAG_SHARED_TEXTURES, nr_backward_textures_shared[_workspace_bytes];
                           *        nr_laplacian_forward, nr_laplacian_backward, nr_flatness_forward, nr_flatness_backward,
-                          *        nr_mesh_loss_workspace_bytes);
+                          *        nr_mesh_loss_workspace_bytes;
+                          *        nr_lights, nr_lights_grad, nr_light_colors_forward, nr_light_colors_backward,
+                          *        nr_light_colors_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -758,6 +760,75 @@ int nr_flatness_forward(const float *vertices, const int32_t *quads, float *loss
 int nr_flatness_backward(const float *vertices, const int32_t *quads, const int32_t *inc_offsets, const int32_t *inc,
                          const float *grad_loss, float *grad_vertices, int32_t batch_size, int32_t num_vertices,
                          int32_t num_quads, double eps, void *stream);
+
+/*
+ * Learnable lights (not in the reference; DESIGN "Learnable lights"): the light colour of every face (flat) or of every face
+ * corner (smooth) from world-space vertices and light parameters that live in DEVICE memory -- shared by the batch or one per
+ * image, possibly learnable -- with gradients to the vertices and to every parameter.  The result is what the rasterizer
+ * takes as its face light (nr_face_light.light [B, F, 3], nr_corner_light.light [B, F, 3, 3]).
+ *
+ * With n = N / (|N| + 1e-5) = (x, y, z), all float32 in this order, no multiply-add contraction:
+ *   L_c(n) = Ia Ca_c + Id (Cd_c max(n . d, 0)) + sum over k = 0 .. 8, ascending, of sh[k, c] Y_k(n)
+ *   Y0 = c0, Y1 = c1 y, Y2 = c1 z, Y3 = c1 x, Y4 = (c2 x) y, Y5 = (c2 y) z, Y6 = c3 ((3 z) z - 1), Y7 = (c2 x) z,
+ *   Y8 = c4 (x x - y y);  c0 = 0.282095f, c1 = 0.488603f, c2 = 1.092548f, c3 = 0.315392f, c4 = 0.546274f
+ * i.e. amb = Ia Ca_c, then amb + Id (Cd_c cos) exactly as nr_frontend_forward_light / nr_vertex_shade_forward, then the SH
+ * terms added one by one.  n . d = (x d0 + y d1) + z d2; d is not normalised and L is not clamped: the nine sh rows are
+ * IRRADIANCE coefficients (the cosine lobe already folded in).  Both lamp terms are always evaluated (an intensity of 0 is
+ * a device value); the SH term is absent exactly when lights->sh is NULL.
+ *   smooth = 0: N = cross(v0 - v1, v2 - v1) of the face; light_out [B, F, 3], F = Nf * (fill_back ? 2 : 1); the reversed copy
+ *     Nf + f sees -n: max(-(n . d), 0), and Y1 .. Y3 with the opposite sign.
+ *   smooth = 1: N = m_v, the float32 sum of the face normals over the (face, corner) pairs of vertex v in ascending order
+ *     (adj_offsets / adj_entries: the table of nr_vertex_shade_forward); light_out [B, F, 3(corner), 3]: corner k of face f
+ *     takes the front light of its vertex, corner 2 - k of the reversed copy Nf + f the back light, as nr_vertex_shade_forward
+ *     lays out a white mesh.  The workspace holds the two colours of every vertex.
+ * N = 0 (a degenerate face, a vertex without a face) gives n = 0: L = Ia Ca + c0 sh[0] - c3 sh[6], and no gradient to the
+ * vertices.  The derivative of max(., 0) is taken for n . d > 0 strictly.
+ *
+ * Backward from grad_light (the layout of light_out).  grad_vertices [B, Nv, 3] (or NULL): light -> n -> normalisation ->
+ * cross product, every sum around a vertex a gather through the table in ascending order; the directional part has the
+ * operation order of nr_vertex_shade_backward.  The parameter gradients (nr_lights_grad, each with its parameter's layout,
+ * NULL = not needed) are linear in 36 sums per image over the faces (flat) or the vertices (smooth, the corner gradients
+ * around a vertex gathered first), the front and the reversed copy entering with n and -n, G their gradient:
+ *   S[phi, c] = sum phi G_c for phi in {1, cos, Y0 .. Y8};   T = sum [+-n . d > 0] (+-n) (G . Cd)
+ *   g_Ia = sum_c S[1, c] Ca_c,  g_Ca = Ia S[1, .],  g_Id = sum_c S[cos, c] Cd_c,  g_Cd = Id S[cos, .],  g_dir = Id T,
+ *   g_sh[k, .] = S[Y_k, .]
+ * accumulated in double: every block of 256 items writes its sums into the workspace in a fixed order, a second kernel adds
+ * the blocks in block order -- for a shared parameter the images' contributions in image order -- and rounds once.  Sums
+ * whose gradients are all NULL are not formed; without grad_vertices the vertex kernels are not launched.  No atomics: every
+ * output repeats bit for bit, and an image alone gives the bits it has inside a batch.
+ *
+ * Every output element is stored.  nr_lights and nr_lights_grad are HOST structs read during the call; all their pointers
+ * are device memory.  The workspace (nr_light_colors_workspace_bytes; 0 for sizes out of range) serves both directions: the
+ * forward needs it with smooth = 1, the backward for parameter gradients and, with smooth = 1, for grad_vertices.  The
+ * adjacency table is needed by the forward with smooth = 1 and by every backward.  NR_E_* before any launch (NR_E_MODE: a
+ * backward with nothing to compute, smooth not 0 / 1, per_image bits beyond the six); no call synchronises the host.
+ */
+typedef struct nr_lights {
+    const float *intensity_ambient;     /* [1] | [B] */
+    const float *intensity_directional; /* [1] | [B] */
+    const float *color_ambient;         /* [3] | [B, 3] */
+    const float *color_directional;     /* [3] | [B, 3] */
+    const float *direction;             /* [3] | [B, 3] */
+    const float *sh;                    /* [9, 3] | [B, 9, 3]; NULL: no SH term */
+    int32_t per_image;                  /* bit j: parameter j (in the order above) is one per image */
+} nr_lights;
+
+typedef struct nr_lights_grad {
+    float *intensity_ambient, *intensity_directional, *color_ambient, *color_directional, *direction, *sh;
+} nr_lights_grad;
+
+size_t nr_light_colors_workspace_bytes(int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t smooth);
+
+int nr_light_colors_forward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                            const int32_t *adj_entries, const nr_lights *lights, float *light_out, int32_t batch_size,
+                            int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, int32_t fill_back, int32_t smooth,
+                            void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_light_colors_backward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                             const int32_t *adj_entries, const nr_lights *lights, const float *grad_light,
+                             float *grad_vertices, const nr_lights_grad *grads, int32_t batch_size, int32_t num_vertices,
+                             int32_t num_faces, int32_t idx_per_batch, int32_t fill_back, int32_t smooth, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /*
  * Texture atlas of save_obj(..., textures) (K11, reference save_obj.py:10-146): image [tile_height*tso, tile_width*tso, 3]

@@ -25,6 +25,8 @@ from .uv_textures import UVImages, UVLayout, UVTextures, bake_uv_textures
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
 # not in the reference: the Laplacian and flatness losses of a mesh fit (shape priors), HIP in both directions
 from .mesh_losses import flatness_loss, laplacian_loss
+# not in the reference: the light as tensors -- per image, learnable, with spherical-harmonics coefficients -- HIP in both directions
+from .lights import Lights, light_colors
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -43,4 +45,4 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
-           'laplacian_loss', 'flatness_loss']
+           'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors']

@@ -44,8 +44,21 @@ class UVImagesStruct(_c.Structure):
                 ('texture_size', _i32), ('num_images', _i32), ('num_pixels', _i32), ('image_batch', _i32)]
 
 
+class Lights(_c.Structure):
+    """struct nr_lights (include/nr_hip.h): device pointers of the six light parameters (sh or None) and their layouts."""
+    _fields_ = [('intensity_ambient', _vp), ('intensity_directional', _vp), ('color_ambient', _vp),
+                ('color_directional', _vp), ('direction', _vp), ('sh', _vp), ('per_image', _i32)]
+
+
+class LightsGrad(_c.Structure):
+    """struct nr_lights_grad (include/nr_hip.h): where each parameter's gradient goes (None = not needed)."""
+    _fields_ = [('intensity_ambient', _vp), ('intensity_directional', _vp), ('color_ambient', _vp),
+                ('color_directional', _vp), ('direction', _vp), ('sh', _vp)]
+
+
 _cam_p, _light_p, _fl_p, _proj_p = _c.POINTER(Camera), _c.POINTER(Light), _c.POINTER(FaceLight), _c.POINTER(Projection)
 _uv_p, _cl_p = _c.POINTER(UVImagesStruct), _c.POINTER(CornerLight)
+_lights_p, _lights_grad_p = _c.POINTER(Lights), _c.POINTER(LightsGrad)
 
 # name -> (restype, argtypes); mirrors include/nr_hip.h one to one
 SIGNATURES = {
@@ -87,6 +100,9 @@ SIGNATURES = {
     'nr_laplacian_backward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
     'nr_flatness_forward': (_c.c_int, [_vp] * 3 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
     'nr_flatness_backward': (_c.c_int, [_vp] * 6 + [_i32] * 3 + [_f64, _vp]),
+    'nr_light_colors_workspace_bytes': (_sz, [_i32] * 4),
+    'nr_light_colors_forward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
+    'nr_light_colors_backward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp, _vp, _lights_grad_p] + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),
     'nr_frontend_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_cam_p, _light_p, _vp]),

@@ -12,13 +12,14 @@ import torch
 
 from . import frontend
 from .lighting import lighting
+from .lights import light_colors
 from .look import look
 from .look_at import look_at
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
 from .uv_textures import UVImages
-from .vertex_colors import VertexColors, vertex_light, vertex_shade
+from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
 from .vertices_to_faces import vertices_to_faces
 
 # Renderer.face_light default (see the attribute): NR_FACE_LIGHT = 0 | 1 | auto
@@ -91,6 +92,11 @@ class Renderer(object):
         # 'smooth' takes vertex colours (render(vertices, faces, VertexColors(c)), vertex_colors.py) or UV images (UVImages,
         # uv_textures.py); texture cubes are lit per face only.  render_silhouettes and render_depth ignore the attribute.
         self.shading = 'flat'
+        # not in the reference: a Lights (lights.py) -- the light as tensors, shared or one per image, possibly learnable,
+        # with nine spherical-harmonics coefficients next to the lamp.  None: the host attributes `light_*` above, every path
+        # exactly as without the attribute.  With a Lights render() ignores `light_*` and takes its light from light_colors
+        # (see _render_lights); render_silhouettes and render_depth ignore the attribute.
+        self.lights = None
 
     def _project(self, vertices, faces):
         """camera + perspective + gather (renderer.py:40-51, :60-71, :92-103)."""
@@ -222,12 +228,55 @@ class Renderer(object):
         return rasterize(faces, corner, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                          self.background_color)
 
+    def _render_lights(self, vertices, faces, textures):
+        """render() with `lights` set (not in the reference): light_colors computes the light in world space -- HIP kernels
+        on CUDA float32 tensors --, the front-end projects the geometry alone, and the light reaches the rasterizer as its
+        `face_light`: one colour per face for texture cubes (per image, or one set shared by the batch; `face_light` and the
+        texture size are not asked) and for UVImages with flat shading, one per corner for UVImages with smooth shading.
+        VertexColors: the corner colours are `colors[faces]`, flipped for the reversed copies, times the light -- one gather
+        and one multiply in torch --, rasterized as CornerColors.  Runs eagerly: graph_replay does not apply."""
+        if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3):
+            raise ValueError('vertices must be a tensor [batch size, num of vertices, 3]')
+        smooth = self.shading == 'smooth'
+        raster = (self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps, self.background_color)
+        if isinstance(textures, VertexColors):
+            B = vertices.shape[0]
+            if textures.num_vertices != vertices.shape[1]:
+                raise ValueError('VertexColors: %d colours for %d vertices' % (textures.num_vertices, vertices.shape[1]))
+            if textures.color_batch not in (1, B):
+                raise ValueError('VertexColors: batched colours must have the batch size of the vertices (%d), got %d'
+                                 % (B, textures.color_batch))
+            if textures.device != vertices.device:
+                raise ValueError('VertexColors: colours on %s, vertices on %s' % (textures.device, vertices.device))
+            light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=smooth)
+            idx, colors = faces.long(), textures.colors
+            if idx.dim() == 2:
+                idx = idx[None].expand(B, -1, -1)
+            corner = colors[idx] if colors.dim() == 2 else colors[torch.arange(B, device=idx.device)[:, None, None], idx]
+            if self.fill_back:
+                corner = torch.cat((corner, torch.flip(corner, dims=[2])), dim=1)
+            corner = corner * (light if smooth else light[:, :, None, :])
+            projected, _ = self._frontend(vertices, faces)
+            return rasterize(projected, CornerColors(corner), *raster)
+        if isinstance(textures, UVImages):
+            light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=smooth)
+            projected, _ = self._frontend(vertices, faces)
+            return rasterize(projected, textures, *raster, face_light=light)
+        if smooth:
+            raise ValueError("Renderer.shading = 'smooth' takes UVImages or VertexColors: texture cubes are lit per face "
+                             "('flat') only")
+        light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=False)
+        projected, _ = self._frontend(vertices, faces)
+        return rasterize(projected, textures, *raster, faces_z_ref=self.faces_z_ref, face_light=light)
+
     def render(self, vertices, faces, textures):
         """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference -- or [1,Nf,ts,ts,ts,3] beside B > 1 views (not in the
         reference): one set shared by the batch, see _render_shared --, or (not in the reference) a UVImages whose images are
         sampled at every covered pixel (uv_textures.py), or a VertexColors (vertex_colors.py), lit as `shading` says."""
         if self.shading not in ('flat', 'smooth'):
             raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+        if self.lights is not None:
+            return self._render_lights(vertices, faces, textures)
         if isinstance(textures, VertexColors):
             return self._render_vertex_colors(vertices, faces, textures)
         if isinstance(textures, UVImages):
