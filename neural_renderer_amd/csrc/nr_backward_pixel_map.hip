@@ -555,7 +555,12 @@ __device__ __forceinline__ double signed_eps(float dist, unsigned eps_hi, unsign
     return __hiloint2double((int)((0.0f < dist) ? eps_hi : (eps_hi ^ 0x80000000u)), (int)eps_lo);
 }
 
-__global__ __launch_bounds__(256) void k_line_setup(LineSetupArgs a) { line_setup_body(a, (int)blockIdx.x, (int)blockIdx.y); }
+// (ids in working-first order: image_fastest, nr_device.h)
+__global__ __launch_bounds__(256, 8) void k_line_setup(LineSetupArgs a)
+{
+    const SlotImage w = image_fastest(blockIdx.x, a.grid_y);
+    line_setup_body(a, w.bx, w.by);
+}
 
 // exclusive prefix of an image's 2 * n_bands line counts (first wave of the block), the image's total and the verdict
 // whether its records fit the buffer; zeroes the fill cursors
@@ -2126,8 +2131,8 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
 // Nothing in the launch waits for anything: the gather reads nothing the band part writes.  K6's sums are rounded onto
 // grad_faces by k_backward_big behind this launch (FINISH_BIG), the compaction stored grad_faces' zeros (FACE_ZEROS_ALL), and
 // of grad_textures the band workgroups zero the unlisted faces' cubes only -- the gather stores every listed face's cube.
-//   grid = [xcd_grid(band workgroups) | gather_x * B], gather id -> (bx, by) = (id % gather_x, id / gather_x): the order of
-//   the gather's own 2-D grid.
+//   grid = [xcd_grid(band workgroups) | gather_x * B], gather id -> (bx, by) = (id / B, id % B): working-first order
+//   (image_fastest, nr_device.h).
 struct BandRowArgs {
     const int32_t *fi_map;
     const float *rgb_map, *alpha_map, *g_rgb, *g_alpha;
@@ -2145,15 +2150,15 @@ struct BandRowArgs {
 };
 
 template <bool RGB, bool ALPHA, bool DEPTH>
-__global__ __launch_bounds__(rowk::NT, 5) void k_band_gather(BandRowArgs r, FaceGatherArgs g, unsigned band_grid, unsigned gather_x)
+__global__ __launch_bounds__(rowk::NT, 5) void k_band_gather(BandRowArgs r, FaceGatherArgs g, unsigned band_grid)
 {
     if (blockIdx.x < band_grid) {
         bpm_row_body<RGB, ALPHA, K6_FAST, false, true>(r.fi_map, r.rgb_map, r.alpha_map, r.g_rgb, r.g_alpha, r.scratch, r.band_lines,
                                                        r.band_start, r.lines_ok, r.line_buf, r.cap, r.F, r.S, r.W, r.S, r.eps_f, r.eps_d,
                                                        r.B, r.zero16, r.n_zero16, r.zero_slot, r.zero_epf);
     } else {
-        const unsigned id = blockIdx.x - band_grid;
-        face_gather_body<true, DEPTH, false>(g, (int)(id % gather_x), (int)(id / gather_x));
+        const SlotImage w = image_fastest(blockIdx.x - band_grid, (unsigned)r.B);
+        face_gather_body<true, DEPTH, false>(g, w.bx, w.by);
     }
 }
 
@@ -2444,7 +2449,7 @@ int launch_band_gather(const K6Plan &p, const BackwardCall &c, const BackwardPla
         static LdsLimit limit;  // one per instantiation
         if (int rc = limit.ensure((const void *)k_band_gather<RGB, ALPHA, D>, p.row_lds)) return rc;
         hipLaunchKernelGGL((k_band_gather<RGB, ALPHA, D>), dim3(band_grid + gather_x * (unsigned)B), dim3(rowk::NT), p.row_lds, c.st,
-                           ra, ga, band_grid, gather_x);
+                           ra, ga, band_grid);
         return 0;
     };
     return bp.depth_in_gather ? go(std::true_type()) : go(std::false_type());
@@ -2645,7 +2650,7 @@ int nr::run_line_setup(const LineSetupArgs &a, hipStream_t st)
 {
     static LdsLimit ls_limit;
     if (int rc = ls_limit.ensure((const void *)k_line_setup, a.lds_bytes)) return rc;
-    hipLaunchKernelGGL(k_line_setup, dim3(a.grid_x, a.grid_y), dim3(256), a.lds_bytes, st, a);
+    hipLaunchKernelGGL(k_line_setup, dim3(a.grid_x * a.grid_y), dim3(256), a.lds_bytes, st, a);
     return launch_status();
 }
 

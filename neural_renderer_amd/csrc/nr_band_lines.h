@@ -63,7 +63,8 @@ struct LineHead {
     bool live;  // both the in and the out pixel lie inside the image (:578-579)
 };
 
-__device__ __forceinline__ LineHead fast_line_head(const float *__restrict__ fv, int e, int axis, int d0, int S)
+// the part of a head that depends on the face, the edge and the axis alone: cheap to derive again from the face's floats
+__device__ __forceinline__ void line_head_points(LineHead &h, const float *__restrict__ fv, int e, int axis, int d0, int S)
 {
     const float fs = (float)S;
     const int i0 = e, i1 = (e + 1) % 3, i2 = (e + 2) % 3;
@@ -71,11 +72,16 @@ __device__ __forceinline__ LineHead fast_line_head(const float *__restrict__ fv,
 #pragma unroll
     for (int k = 0; k < 3; k++) { fp[k] = to_pixel(fv[3 * k], fs); fp[3 + k] = to_pixel(fv[3 * k + 1], fs); }
     const int ox = axis ? 3 : 0, oy = axis ? 0 : 3;  // p[num][dim] = pp[num][(dim + axis) % 2] (:556)
-    LineHead h;
     h.p0x = fp[ox + i0]; h.p0y = fp[oy + i0]; h.p1x = fp[ox + i1]; h.p1y = fp[oy + i1];
     h.p2x = fp[ox + i2]; h.p2y = fp[oy + i2];
     if (axis == 0) h.direction = (h.p0x < h.p1x) ? -1 : 1; else h.direction = (h.p0x < h.p1x) ? 1 : -1;  // :559-564
     h.d0f = (float)d0;
+}
+
+__device__ __forceinline__ LineHead fast_line_head(const float *__restrict__ fv, int e, int axis, int d0, int S)
+{
+    LineHead h;
+    line_head_points(h, fv, e, axis, d0, S);
     h.d1_cross = (h.p1y - h.p0y) / (h.p1x - h.p0x) * (h.d0f - h.p0x) + h.p0y;                  // :573
     h.d1_in = (0 < h.direction) ? (int)floorf(h.d1_cross) : (int)ceilf(h.d1_cross);             // :574
     h.d1_out = h.d1_in + h.direction;                                                           // :575
@@ -142,6 +148,12 @@ __device__ __forceinline__ BandLine make_fast_line(const float *__restrict__ fv,
 // (every backward test forces that path as well: tests/test_hip_parity.py check_backward, NR_FLAG_K6_SCAN).
 constexpr int LS_UNROLL = 4;  // lines per thread and round of k_line_setup
 constexpr int LS_FACES = 32;  // list positions per workgroup (measured with a thread per item: 64 -> 43 us, 32 -> 29 us, 16 -> 29 us)
+// Under 8 workgroups per CU (four words held per line, 45 VGPRs, no scratch; the parent held the whole head: 75 VGPRs, 6 per
+// CU, 28.7 us) and working-first ids, k_line_setup inside the headline step, us (profiles/sparse_grid_ab.md):
+//   LS_UNROLL 2: 26.0 (39 VGPRs)   4: 25.8 (45)   8: 26.2 (61)      -- flat: the reads in flight do not bound it
+//   LS_FACES: 16 is outside what the body serves (below; a build with 16 hung and was not timed), 64 does not fit the packed
+//   item word; not swept again.
+static_assert(9 * LS_FACES >= 256, "line_setup_body stores s_face[tid] for every thread of the workgroup");
 
 // Adds up the n_sum rows chunk_band[b][.][i] of an image (k_compact_par) into tot[i], i < n2, and takes the exclusive prefix
 // start[i]; returns the image's total.  All 256 threads of the workgroup; tot / start are LDS arrays.
@@ -178,7 +190,7 @@ __device__ __forceinline__ int band_sum_prefix(const int *__restrict__ rows, int
     return total;
 }
 
-// bx, by: the workgroup's place in the line-setup grid (blockIdx of k_line_setup)
+// bx, by: list-position workgroup and image (k_line_setup hands the ids out in working-first order: image_fastest, nr_device.h)
 __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const int bx, const int by)
 {
     const float *__restrict__ faces = a.faces;
@@ -289,39 +301,61 @@ __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const in
     const size_t img = (size_t)b * S * S;
     BandLine *buf_b = line_buf + (size_t)b * cap;
     const int n_items = 6 * n_pos, n_lines = s_lp[n_items];
+    // Across the reads a line holds four words: item | d0 << 8 (item < 6 * LS_FACES <= 256, d0 < 2^14), the crossing point
+    // (a correctly rounded division), d1_in (-1: the line is not live; a live one's lies inside the image) and the ownership
+    // word.  The points, the direction and d1_out come again from s_face when the line is finished -- the same operations
+    // on the same floats, the same bits -- which is what lets the kernel fit 64 VGPRs, i.e. 8 workgroups per CU.
+    static_assert(6 * LS_FACES <= 256, "item | d0 << 8");
     for (int base = 0; base < n_lines; base += LS_UNROLL * 256) {
-        LineHead h[LS_UNROLL];
-        int item[LS_UNROLL], d0v[LS_UNROLL], own[LS_UNROLL];
+        float cross[LS_UNROLL];
+        int item_d0[LS_UNROLL], d1_in[LS_UNROLL], own[LS_UNROLL];
 #pragma unroll
         for (int u = 0; u < LS_UNROLL; u++) {
             const int l = base + u * 256 + tid;
-            item[u] = -1;
+            item_d0[u] = -1;
             own[u] = -1;
+            d1_in[u] = -1;
+            cross[u] = 0.0f;
             if (l < n_lines) {
                 int lo = 0, hi = n_items;  // last item with s_lp[item] <= l
                 while (hi - lo > 1) {
                     const int mid = (lo + hi) >> 1;
                     if (s_lp[mid] <= l) lo = mid; else hi = mid;
                 }
-                item[u] = lo;
                 const int p = lo / 6, ae = lo - 6 * p, axis = ae / 3, e = ae - 3 * axis;
                 const int d0 = (int)(s_rng[lo] & 0xffffu) + (l - s_lp[lo]);
-                d0v[u] = d0;
+                item_d0[u] = lo | (d0 << 8);
                 float fv[9];
 #pragma unroll
                 for (int k = 0; k < 9; k++) fv[k] = s_face[9 * p + k];
-                h[u] = fast_line_head(fv, e, axis, d0, S);
-                if (h[u].live) own[u] = fi_map[axis ? img + (size_t)d0 * S + h[u].d1_in : img + (size_t)h[u].d1_in * S + d0];
+                const LineHead h = fast_line_head(fv, e, axis, d0, S);
+                cross[u] = h.d1_cross;
+                if (h.live) {
+                    d1_in[u] = h.d1_in;
+                    own[u] = fi_map[axis ? img + (size_t)d0 * S + h.d1_in : img + (size_t)h.d1_in * S + d0];
+                }
             }
         }
+        // (the face's floats are read again below, not carried over the ownership reads in registers)
+        asm volatile("" ::: "memory");
 #pragma unroll
         for (int u = 0; u < LS_UNROLL; u++) {
-            if (item[u] < 0) continue;
-            const int p = item[u] / 6, ae = item[u] - 6 * p, axis = ae / 3, e = ae - 3 * axis;
-            const int band = d0v[u] / W, ld = d0v[u] - band * W;
+            if (item_d0[u] < 0) continue;
+            const int it = item_d0[u] & 255, d0 = item_d0[u] >> 8;
+            const int p = it / 6, ae = it - 6 * p, axis = ae / 3, e = ae - 3 * axis;
+            const int band = d0 / W, ld = d0 - band * W;
             const int tgt = (pos0 + p * pstep) | (e << 28) | (((e + 1) % 3) << 30);
             const int bi = axis * n_bands + band;
-            buf_b[s_base[bi] + atomicAdd(s_cnt + bi, 1)] = fast_line_finish(h[u], ld, S, s_fn[p], tgt, own[u], k2s);
+            float fv[9];
+#pragma unroll
+            for (int k = 0; k < 9; k++) fv[k] = s_face[9 * p + k];
+            LineHead h;
+            line_head_points(h, fv, e, axis, d0, S);
+            h.d1_cross = cross[u];
+            h.live = d1_in[u] >= 0;
+            h.d1_in = d1_in[u];
+            h.d1_out = h.d1_in + h.direction;
+            buf_b[s_base[bi] + atomicAdd(s_cnt + bi, 1)] = fast_line_finish(h, ld, S, s_fn[p], tgt, own[u], k2s);
         }
     }
 }

@@ -395,6 +395,22 @@ __device__ __forceinline__ unsigned xcd_block(unsigned n_blocks)
     const unsigned logical = (blockIdx.x % NUM_XCD) * chunk + blockIdx.x / NUM_XCD;
     return logical < n_blocks ? logical : n_blocks;
 }
+
+// Working-first order for the sparse launches over (list slots, image): a grid of gx workgroups for each of B images whose
+// workgroup (bx, by) has work only while bx is below a count of image by (the length of its visible-face list over the
+// workgroup's share: about one in six at the headline size) and otherwise reads that count and leaves.  With bx fastest --
+// the order of a 2-D grid -- every image is a run of working workgroups followed by a long run of leaving ones, and a slot
+// a working workgroup frees is handed to several leaving ones in turn before the next working one gets it.  The launch is
+// 1-D instead, gx * B ids, and the image is fastest: (bx, by) = (id / B, id % B).  Every workgroup that can have work (bx
+// below the longest list's share) is handed out before the first that cannot.  Nothing waits for anything: it is the same
+// set of workgroups in another order.  (With B a multiple of 8 an image's workgroups all land on one XCD.)
+// Used where it measured (profiles/sparse_grid_ab.md): k_line_setup and the gather part of k_band_gather.
+struct SlotImage { int bx, by; };
+__device__ __forceinline__ SlotImage image_fastest(unsigned id, unsigned B)
+{
+    const unsigned bx = id / B;
+    return {(int)bx, (int)(id - bx * B)};
+}
 #endif
 
 inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }

@@ -167,7 +167,8 @@ inline FaceGatherArgs face_gather_args(const BackwardCall &c, const BackwardPlan
             fold ? l.slot_of : nullptr, c.lit};
 }
 
-// bx, by: the workgroup's place in the gather's grid (blockIdx of k_backward_textures_face)
+// bx, by: the workgroup's place in the gather's grid (blockIdx of k_backward_textures_face; k_band_gather hands the same
+// pairs out in working-first order: image_fastest, nr_device.h)
 template <bool TS2, bool DEPTH, bool LIT>
 __device__ __forceinline__ void face_gather_body(const FaceGatherArgs &a, const int bx, const int by)
 {

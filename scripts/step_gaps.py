@@ -4,14 +4,42 @@ steady-state steps (period found from the repetition of the first kernel of the 
 the idle gap in front of it.
 
     python scripts/step_gaps.py x_results.db [anchor-kernel-substring]
+    python scripts/step_gaps.py --json TAG x_results.db [anchor-kernel-substring]
+
+--json TAG: one line of JSON per dispatch of the step instead -- mean, median and 5th / 95th percentile of its duration over the
+steps (us), labelled TAG -- and one for the step, for comparing builds traced in one session.
 """
+import json
+import re
 import sqlite3
+import statistics
 import sys
 
 
+def spread(rows, first, steps, per, tag):
+    """--json: the spread of every dispatch's duration over the steps"""
+    def pct(v, q):
+        v = sorted(v)
+        return v[min(len(v) - 1, int(round(q * (len(v) - 1))))]
+    total = 0.0
+    for k in range(per):
+        d = [(rows[first + s * per + k][2] - rows[first + s * per + k][1]) / 1e3 for s in range(steps)]
+        name = (re.findall(r'k_\w+', rows[first + k][0]) or [rows[first + k][0][:60]])[0]
+        total += sum(d) / steps
+        print(json.dumps({'tag': tag, 'kernel': name, 'mean': round(sum(d) / steps, 2), 'median': round(statistics.median(d), 2),
+                          'p5': round(pct(d, 0.05), 2), 'p95': round(pct(d, 0.95), 2)}))
+    span = [(rows[first + (s + 1) * per][1] - rows[first + s * per][1]) / 1e3 for s in range(steps)]
+    print(json.dumps({'tag': tag, 'steps': steps, 'dispatches': per, 'kernels_us': round(total, 2),
+                      'step_us_median': round(statistics.median(span), 2)}))
+
+
 def main():
-    c = sqlite3.connect(sys.argv[1])
-    anchor = sys.argv[2] if len(sys.argv) > 2 else 'k_face_raster'
+    args = sys.argv[1:]
+    tag = None
+    if args and args[0] == '--json':
+        tag, args = args[1], args[2:]
+    c = sqlite3.connect(args[0])
+    anchor = args[1] if len(args) > 1 else 'k_face_raster'
     t = [r[0] for r in c.execute("select name from sqlite_master where type='table'")]
     disp = [x for x in t if x.startswith('rocpd_kernel_dispatch')][0]
     sym = [x for x in t if x.startswith('rocpd_info_kernel_symbol')][0]
@@ -37,6 +65,9 @@ def main():
         return
     first, last = idx[i0 + 1], idx[i0 + n]  # skip the section's first period
     steps = n - 1
+    if tag is not None:
+        spread(rows, first, steps, per, tag)
+        return
     agg = {}
     for s in range(steps):
         base = first + s * per
