@@ -46,8 +46,8 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
     // launch when there is one that walks faces (texture_size <= 13)
     const bool fold = p.bands && k7 && ts <= 13;
     // Small launches (up to 96 k faces in the call: 16 views of the 4928-face teapot) take the order
-    //   compaction | line setup + gather + zeros of grad_textures in ONE grid | band kernel | the faces the gather left
-    //   out + K6's sums onto grad_faces (one launch)
+    //   compaction | line setup + gather + zeros of grad_textures in ONE grid | band kernel | K6's overflow pass + the faces
+    //   the gather left out + K6's sums onto grad_faces (one launch: big_overflow below)
     // where the line setup and the gather -- two chains of dependent round trips that need nothing of each other -- run side
     // by side (8 views: backward 82 -> 72 us, 16: 111 -> 104; 32: 156 -> 152, not taken).  Larger ones keep
     //   compaction | line setup | band kernel with the fill on the side | gather with K6's finish:
@@ -57,8 +57,8 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
     p.gather_first = fold && (size_t)B * F <= k6::SHARED_LAUNCH_MAX_FACES && !(c.flags & NR_FLAG_SERIAL_BACKWARD);
     // Above that, up to TAIL_GATHER_MAX_FACES, where the gather is the static-tap face gather (texture_size 2, the Renderer's
     // default) and K6 takes k_bpm_row in the default arithmetic on whole lines:
-    //   compaction | line setup | band kernel + gather in ONE grid, the gather's workgroups behind the band's | overflow | the
-    //   faces the gather left out + K6's sums onto grad_faces (one launch)
+    //   compaction | line setup | band kernel + gather in ONE grid, the gather's workgroups behind the band's | K6's overflow
+    //   pass + the faces the gather left out + K6's sums onto grad_faces (one launch: big_overflow below)
     // The gather starts in the slots that the band kernel's last round frees instead of behind a launch boundary on an empty
     // chip (k_band_gather, nr_backward_pixel_map.hip; measured: nr_k6_tune.h).  The band workgroups zero the unlisted faces'
     // cubes of grad_textures only: the gather of the same launch stores the listed ones.
@@ -105,6 +105,11 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
         if (p.tex_zeros == TEX_ZEROS_NONE && (c.lit.light || p.listed || ts > 13)) p.tex_zeros = TEX_ZEROS_FILL;
         p.light_fill = c.lit.light && c.lit.grad_light;
     }
+    // The overflow pass behind k_bpm_row -- normally an empty launch -- rides in k_backward_big's when that launch finishes K6 (the
+    // gather-first and the tail order), in the instantiations these two orders reach: 256-thread band workgroups, static taps, no
+    // per-face light colours.  NR_FLAG_SERIAL_BACKWARD never gets here (neither order is taken).
+    p.big_overflow = k6::MERGE_OVERFLOW && p.finish == FINISH_BIG && p.big && p.k6p.overflow_pass && p.k6p.shape.threads == 256 &&
+                     p.static_taps && p.listed && !c.lit.light;
     p.setup_alone = p.bands && p.k6p.use_records && !p.setup_in_gather;
     p.depth = k8 && !p.depth_in_gather;
     // depth only: no K6 and therefore no lists -- built from the forward's flags when there are any (one launch), so that the
@@ -130,8 +135,8 @@ int nr::run_backward(const BackwardCall &c)
     if (p.fill_faces)
         if (int e = fill_bytes(c.grad_faces, 0, (size_t)c.B * c.F * 9 * sizeof(float), c.st)) return e;
     if (p.depth_lists) l = k6_list_visible(c);
+    LineSetupArgs ls = {};
     if (p.k6) {
-        LineSetupArgs ls = {};
         if (p.bands) {
             if (int rc = k6_compact(c, p.k6p, p.face_zeros, l)) return rc;
             ls = k6_line_setup_args(c, p.k6p);
@@ -146,7 +151,7 @@ int nr::run_backward(const BackwardCall &c)
             if (int rc = fill_texture_zeros(c, p)) return rc;
         const bool band_fill = p.tex_zeros == TEX_ZEROS_BAND || p.tex_zeros == TEX_ZEROS_BAND_UNLISTED;
         if (int rc = k6_band(c, p.k6p, l, ls, band_fill ? c.grad_textures : nullptr, band_fill ? p.tex_bytes : 0,
-                             p.gather_in_tail ? &p : nullptr))
+                             p.gather_in_tail ? &p : nullptr, p.big_overflow))
             return rc;
         if (p.finish == FINISH_KERNEL) k6_finalize(c, l, false);
     }
@@ -155,7 +160,11 @@ int nr::run_backward(const BackwardCall &c)
         if (p.gather == GATHER_FACE)
             if (int rc = gather_faces(c, p, l, nullptr)) return rc;
     }
-    if (p.big) gather_big(c, p, l);
+    if (p.big_overflow) {
+        if (int rc = k6_big_overflow(c, p, l, ls)) return rc;
+    } else if (p.big) {
+        gather_big(c, p, l);
+    }
     if (p.gather == GATHER_ATOMIC) gather_atomic(c);
     if (p.depth) gather_depth(c, l);
     if (p.finish == FINISH_ADD) k6_finalize(c, l, true);

@@ -348,7 +348,7 @@ __global__ __launch_bounds__(VIS_CHUNK) void k_compact_par(const unsigned char *
                                                            double *__restrict__ scratch, int S,
                                                            int *__restrict__ chunk_band, int n_bands, int W,
                                                            int *__restrict__ band_cursor, float *__restrict__ zero_faces,
-                                                           int zero_listed, int use_diff)
+                                                           int zero_listed, int use_diff, int *__restrict__ ticket)
 {
     extern __shared__ int s_band[];  // [2][n_bands] lines per band of this chunk's faces; use_diff: + [2][S + 1] line differences
     __shared__ int s_wcnt[VIS_CHUNK / 64];
@@ -417,6 +417,7 @@ __global__ __launch_bounds__(VIS_CHUNK) void k_compact_par(const unsigned char *
         for (int w = 0; w < VIS_CHUNK / 64; ++w) base += s_part[w];
         vis_count[b] = base + own;
     }
+    if (chunk == 0 && b == 0 && tid == 0) *ticket = 0;  // (the overflow pass's ticket counter: k_big_overflow)
 }
 
 // the lists alone (depth-only backward: no K6, but the K8 gather still wants to visit only the faces that own a pixel)
@@ -589,8 +590,9 @@ __device__ __forceinline__ void band_prefix(const int *cnt, int n2, int *__restr
 
 __global__ __launch_bounds__(256) void k_band_scan(const int *__restrict__ band_lines, int *__restrict__ band_start,
                                                    int *__restrict__ band_cursor, int *__restrict__ lines_ok, int n_bands,
-                                                   size_t cap, int force_scan)
+                                                   size_t cap, int force_scan, int *__restrict__ ticket)
 {
+    if (blockIdx.x == 0 && threadIdx.x == 0) *ticket = 0;  // (the overflow pass's ticket counter: k_big_overflow)
     const size_t o = (size_t)blockIdx.x * 2 * n_bands;
     band_prefix(band_lines + o, 2 * n_bands, band_start + o, band_cursor + o, lines_ok + blockIdx.x, force_scan ? 0 : cap);
 }
@@ -1171,14 +1173,18 @@ __device__ __forceinline__ void fast_sweeps(const FastPx &px, const BandLine *s_
 // The band kernel, NT threads per workgroup (band_shape below).  (launch bounds: what the LDS of a shape admits -- six waves
 // per SIMD for three 512-thread workgroups per CU, four for four 256-thread ones; the generic exact form carries a double
 // division: four)
-template <bool RGB, bool ALPHA, int MODE, int NT, bool OVF = false>
-__global__ __launch_bounds__(NT, MODE == K6_EXACT ? 4 : (NT == 256 ? k6::MINWAVES_256 : 6)) void k_bpm_fast(
+// (the kernel's body as a function: the overflow-only form also runs on the first workgroups of k_big_overflow's launch.  block,
+// n_blocks: the workgroup's number among the n_blocks that run the body -- blockIdx.x and gridDim.x of k_bpm_fast.  Returns whether
+// the workgroup walked bands as part of an overflow pass, i.e. found an image over the line buffer.)
+template <bool RGB, bool ALPHA, int MODE, int NT, bool OVF>
+__device__ __forceinline__ bool bpm_fast_body(
     const float *__restrict__ faces, const int32_t *__restrict__ fi_map, const float *__restrict__ rgb_map,
     const float *__restrict__ alpha_map, const float *__restrict__ g_rgb, const float *__restrict__ g_alpha,
     const int *__restrict__ vis_list, const int *__restrict__ vis_count, const unsigned *__restrict__ rng,
     double *__restrict__ scratch, const int *__restrict__ band_lines, const int *__restrict__ band_start,
     const int *__restrict__ lines_ok, const BandLine *__restrict__ line_buf, size_t cap, int F, int S, int W, int SP,
-    double eps, float k2s, int B, int win_lines, int qcap, uint4 *__restrict__ zero16, size_t n_zero16)
+    double eps, float k2s, int B, int win_lines, int qcap, uint4 *__restrict__ zero16, size_t n_zero16, const unsigned block,
+    const unsigned n_blocks)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int tid = threadIdx.x;
@@ -1334,15 +1340,31 @@ __global__ __launch_bounds__(NT, MODE == K6_EXACT ? 4 : (NT == 256 ? k6::MINWAVE
     if constexpr (!OVF) {
         const unsigned logical = xcd_block(total_wg);
         if (logical < total_wg) band_body(logical);
+        return false;
     } else {
         int any = 0;
         for (int i = tid; i < B; i += NT) any |= lines_ok[i] == 0;
-        if (!__syncthreads_or(any)) return;
-        for (unsigned logical = blockIdx.x; logical < total_wg; logical += gridDim.x) {
+        if (!__syncthreads_or(any)) return false;
+        for (unsigned logical = block; logical < total_wg; logical += n_blocks) {
             band_body(logical);
             __syncthreads();  // (the next band re-uses the LDS)
         }
+        return true;
     }
+}
+
+template <bool RGB, bool ALPHA, int MODE, int NT, bool OVF = false>
+__global__ __launch_bounds__(NT, MODE == K6_EXACT ? 4 : (NT == 256 ? k6::MINWAVES_256 : 6)) void k_bpm_fast(
+    const float *__restrict__ faces, const int32_t *__restrict__ fi_map, const float *__restrict__ rgb_map,
+    const float *__restrict__ alpha_map, const float *__restrict__ g_rgb, const float *__restrict__ g_alpha,
+    const int *__restrict__ vis_list, const int *__restrict__ vis_count, const unsigned *__restrict__ rng,
+    double *__restrict__ scratch, const int *__restrict__ band_lines, const int *__restrict__ band_start,
+    const int *__restrict__ lines_ok, const BandLine *__restrict__ line_buf, size_t cap, int F, int S, int W, int SP,
+    double eps, float k2s, int B, int win_lines, int qcap, uint4 *__restrict__ zero16, size_t n_zero16)
+{
+    bpm_fast_body<RGB, ALPHA, MODE, NT, OVF>(faces, fi_map, rgb_map, alpha_map, g_rgb, g_alpha, vis_list, vis_count, rng, scratch,
+                                             band_lines, band_start, lines_ok, line_buf, cap, F, S, W, SP, eps, k2s, B, win_lines, qcap,
+                                             zero16, n_zero16, blockIdx.x, gridDim.x);
 }
 
 // k_bpm_row: how many of a line's n_parts waves (a power of two) share one of its windows -- n_parts over the number of windows
@@ -1498,7 +1520,17 @@ __device__ __forceinline__ void bpm_row_body(
     }
     const unsigned bandidx = logical / n_ch;  // (the chunks of a band next to each other: they read the same records)
     const int c0 = CHUNKED ? (int)(logical - bandidx * n_ch) * CH : 0, SL = CHUNKED ? min(CH, S - c0) : S;  // the chunk: pixels [c0, c0 + SL) of the band's lines
-    const int band = (int)(bandidx % n_bands), axis = (int)((bandidx / n_bands) & 1u), b = (int)(bandidx / (2u * n_bands));
+    const int band = (int)(bandidx % n_bands), axis = (int)((bandidx / n_bands) & 1u);
+    int b = (int)(bandidx / (2u * n_bands));
+    // xcd_block gives XCD x the images x B / 8 ... (x + 1) B / 8 - 1: neighbouring views, whose line records rise and fall together
+    // (edge extents of the headline's 64 views: the eight XCDs hold 0.955 ... 1.025 of the mean).  In the merged launch, when the
+    // batch is a multiple of 8 and at least 16, the images are dealt across instead -- XCD x takes x, x + 8, ... (0.998 ... 1.001):
+    // all bands of an image still on one XCD, in the same order, neighbouring bands on neighbouring ids.  (k_bpm_row's own launch,
+    // which NR_FLAG_SERIAL_BACKWARD takes, keeps the mapping.)
+    if constexpr (UNLISTED && k6::ROW_DEAL_IMAGES) {
+        const int q = B >> 3;
+        if ((B & 7) == 0 && q >= 2) b = (b % q) * 8 + b / q;
+    }
     if (lines_ok[b] == 0) return;  // records beyond the buffer: k_bpm_fast's scan path serves this image
     const int band_lo = band * W, nld = min(W, S - band_lo);
     const size_t lt = ((size_t)b * 2 + axis) * S + band_lo;  // the band's lines in the per-line tables (band width 1)
@@ -2132,7 +2164,7 @@ __global__ __launch_bounds__(rowk::NT, MODE == K6_FAST ? 5 : 4) void k_bpm_row(
 // grad_faces by k_backward_big behind this launch (FINISH_BIG), the compaction stored grad_faces' zeros (FACE_ZEROS_ALL), and
 // of grad_textures the band workgroups zero the unlisted faces' cubes only -- the gather stores every listed face's cube.
 //   grid = [xcd_grid(band workgroups) | gather_x * B], gather id -> (bx, by) = (id / B, id % B): working-first order
-//   (image_fastest, nr_device.h).
+//   (image_fastest, nr_device.h); gather_x = ceil(F / 16) slots over k6::SLOT_STRIDE, a workgroup looping over its slots.
 struct BandRowArgs {
     const int32_t *fi_map;
     const float *rgb_map, *alpha_map, *g_rgb, *g_alpha;
@@ -2150,15 +2182,18 @@ struct BandRowArgs {
 };
 
 template <bool RGB, bool ALPHA, bool DEPTH>
-__global__ __launch_bounds__(rowk::NT, 5) void k_band_gather(BandRowArgs r, FaceGatherArgs g, unsigned band_grid)
+__global__ __launch_bounds__(rowk::NT, 5) void k_band_gather(BandRowArgs r, FaceGatherArgs g, unsigned band_grid, unsigned gather_x)
 {
     if (blockIdx.x < band_grid) {
         bpm_row_body<RGB, ALPHA, K6_FAST, false, true>(r.fi_map, r.rgb_map, r.alpha_map, r.g_rgb, r.g_alpha, r.scratch, r.band_lines,
                                                        r.band_start, r.lines_ok, r.line_buf, r.cap, r.F, r.S, r.W, r.S, r.eps_f, r.eps_d,
                                                        r.B, r.zero16, r.n_zero16, r.zero_slot, r.zero_epf);
     } else {
+        // gather_x slots per image in the launch, fewer than the longest list may need: slot bx, bx + gather_x, ... while the
+        // image's list lasts (a wave's four faces need nothing of the workgroup's other waves: no barrier between two slots)
         const SlotImage w = image_fastest(blockIdx.x - band_grid, (unsigned)r.B);
-        face_gather_body<true, DEPTH, false>(g, w.bx, w.by);
+        const int n_vis = g.vis_count[w.by];
+        for (int bx = w.bx; bx * 16 < n_vis; bx += (int)gather_x) face_gather_body<true, DEPTH, false>(g, bx, w.by);
     }
 }
 
@@ -2196,11 +2231,87 @@ __global__ __launch_bounds__(256) void k_bpm_finalize(const double *__restrict__
     }
 }
 
+// --------------------------------------------------------------------------------------------------
+// The overflow pass behind k_bpm_row and k_backward_big with K6's finish (FINISH_BIG) in ONE launch: as a launch of its own the
+// overflow pass -- which normally finds no image over the line buffer and leaves -- cost 4.6 us of every step.
+//   grid = [n_ovf overflow workgroups | k_backward_big's (ranges, images, shares), x fastest]
+// This launch is nearly empty -- a few hundred workgroups that leave, and the big faces' -- so the larger of the two bodies'
+// registers and LDS costs nothing here (in the band launch k_bpm_fast's 40 KB would cost k_bpm_row a workgroup per CU).
+// Nothing waits: with no image over the buffer the overflow workgroups leave after their one look at the verdicts, and
+// k_backward_big's threads finish every listed face as before.  Otherwise those threads spare the listed faces of the overflowed
+// images, whose sums are still arriving, and the overflow workgroups take a ticket each when their bands are done (the sums
+// released at device scope in front of it); whoever draws the last one has thereby acquired all of them and finishes those faces:
+// K6's sums, read at device scope, onto grad_faces with the operands and the rule of backward_big_body -- float atomics for a face
+// above BIG_PX candidates, whose K8 sums arrive in this launch too (the two additions onto the gather's zero commute), a plain
+// read-modify-write for every other, which no one else touches.
+struct FastOverflowArgs {
+    const float *faces;
+    const int32_t *fi_map;
+    const float *rgb_map, *alpha_map, *g_rgb, *g_alpha;
+    const int *vis_list, *vis_count;
+    const unsigned *rng;
+    double *scratch;
+    const int *band_lines, *band_start, *lines_ok;
+    const BandLine *line_buf;
+    size_t cap;
+    int F, S, W, SP;
+    double eps;
+    float k2s;
+    int B, win_lines, qcap;
+    int *ticket;     // zeroed by the compaction
+    unsigned n_ovf;  // overflow workgroups in front of k_backward_big's
+    unsigned big_x, big_y, big_z;
+};
+
+template <bool RGB, bool ALPHA, int MODE, bool DEPTH>
+__global__ __launch_bounds__(256, 4) void k_big_overflow(FastOverflowArgs f, BigArgs g)
+{
+    if (blockIdx.x >= f.n_ovf) {
+        const unsigned id = blockIdx.x - f.n_ovf, row = id / f.big_x;
+        backward_big_body<2, DEPTH, false>(g, make_uint3(id - row * f.big_x, row % f.big_y, row / f.big_y), f.big_z);
+        return;
+    }
+    if (!bpm_fast_body<RGB, ALPHA, MODE, 256, true>(f.faces, f.fi_map, f.rgb_map, f.alpha_map, f.g_rgb, f.g_alpha, f.vis_list,
+                                                     f.vis_count, f.rng, f.scratch, f.band_lines, f.band_start, f.lines_ok, f.line_buf,
+                                                     f.cap, f.F, f.S, f.W, f.SP, f.eps, f.k2s, f.B, f.win_lines, f.qcap, nullptr, 0,
+                                                     blockIdx.x, f.n_ovf))
+        return;
+    __shared__ int s_last;
+    const int tid = threadIdx.x;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");  // this thread's additions to the sums, in front of the barrier and the ticket
+    __syncthreads();
+    if (tid == 0) s_last = __hip_atomic_fetch_add(f.ticket, 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT) == (int)f.n_ovf - 1;
+    __syncthreads();
+    if (!s_last) return;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+    const int F = f.F;
+    for (int b = 0; b < f.B; ++b) {
+        if (f.lines_ok[b] != 0) continue;
+        const int n_vis = f.vis_count[b];
+        for (int slot = tid; slot < n_vis; slot += 256) {
+            const size_t gi = (size_t)b * F + f.vis_list[(size_t)b * F + slot];
+            const double *sc = f.scratch + ((size_t)b * F + slot) * 6;
+            const float *fv = f.faces + gi * 9;
+            const bool big = face_candidates(fv[0], fv[1], fv[3], fv[4], fv[6], fv[7], f.S).n > BIG_PX;
+            float *gf = g.grad_faces + gi * 9;
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+#pragma unroll
+                for (int k = 0; k < 2; k++) {
+                    const float k6v = (float)__hip_atomic_load(sc + 2 * v + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if (big) atomicAdd(gf + 3 * v + k, k6v);
+                    else gf[3 * v + k] = k6v + gf[3 * v + k];
+                }
+            }
+        }
+    }
+}
+
 // ====================================================================================================
 
 struct BpmLayout {
     size_t flags_off, scratch_off, count_off, chunk_off, cband_off, list_off, rng_off, slot_off, band_off, start_off, cursor_off, ok_off,
-        lines_off, total, cap;
+        ticket_off, lines_off, total, cap;
     int n_chunks;
 };
 
@@ -2239,7 +2350,8 @@ BpmLayout bpm_layout(int B, int F, int S)
     L.start_off = L.band_off + per_band;
     L.cursor_off = L.start_off + per_band;
     L.ok_off = L.cursor_off + per_band;
-    L.lines_off = L.ok_off + align_up((size_t)B * sizeof(int), 256);
+    L.ticket_off = L.ok_off + align_up((size_t)B * sizeof(int), 256);  // one int: the overflow pass's ticket counter (k_big_overflow)
+    L.lines_off = L.ticket_off + 256;
     L.cap = line_capacity(F, S);
     L.total = L.lines_off + (size_t)B * L.cap * sizeof(BandLine);
     return L;
@@ -2358,8 +2470,9 @@ int launch_fast(const K6Plan &p, const BackwardCall &c, const K6Lists &l, const 
     const int B = c.B, S = c.S;
     const unsigned total_wg = (unsigned)((S + p.W_fast - 1) / p.W_fast) * 2u * (unsigned)B;
     // 1-D grid: the kernel maps ids to (image, axis, band) per XCD
-    // (overflow-only launch behind k_bpm_row: a resident grid that strides over the bands, k6::OVF_GRID workgroups.  With nothing
-    // to do it costs 4.6 us in a step whatever the grid -- a launch (1.3 us for up to 256 workgroups that leave at once,
+    // (overflow-only launch behind k_bpm_row -- where the plan does not put the pass into k_backward_big's launch, k_big_overflow:
+    // a resident grid that strides over the bands, k6::OVF_GRID workgroups.  With nothing to do it costs 4.6 us in a traced step
+    // whatever the grid -- a launch (1.3 us for up to 256 workgroups that leave at once,
     // scripts/dev/empty_launch_probe.hip) and one dependent load of the images' verdicts from memory the line setup wrote with
     // atomics; with every image over the line buffer -- 32 teapot views at 1024^2 -- 1024 workgroups took 5.0 ms against 7.3 at 256)
     const unsigned grid = OVF ? (total_wg < k6::OVF_GRID ? total_wg : k6::OVF_GRID) : xcd_grid(total_wg);
@@ -2439,7 +2552,7 @@ int launch_band_gather(const K6Plan &p, const BackwardCall &c, const BackwardPla
 {
     const int B = c.B, F = c.F, S = c.S, W = p.W_row;
     const unsigned total_wg = (unsigned)((S + W - 1) / W) * 2u * (unsigned)B, band_grid = xcd_grid(total_wg);
-    const unsigned gather_x = (unsigned)((F + 15) / 16);
+    const unsigned gather_x = ((unsigned)((F + 15) / 16) + k6::SLOT_STRIDE - 1) / k6::SLOT_STRIDE;  // (k_band_gather loops)
     const BandRowArgs ra = {c.face_index_map, c.rgb_map, c.alpha_map, c.grad_rgb_map, c.grad_alpha_map, l.scratch, ls.band_lines,
                             ls.band_start, ls.lines_ok, ls.line_buf, ls.cap, F, S, W, B, (float)c.eps, c.eps, (uint4 *)fill,
                             fill_bytes / 16, l.slot_of, 6u};
@@ -2449,7 +2562,7 @@ int launch_band_gather(const K6Plan &p, const BackwardCall &c, const BackwardPla
         static LdsLimit limit;  // one per instantiation
         if (int rc = limit.ensure((const void *)k_band_gather<RGB, ALPHA, D>, p.row_lds)) return rc;
         hipLaunchKernelGGL((k_band_gather<RGB, ALPHA, D>), dim3(band_grid + gather_x * (unsigned)B), dim3(rowk::NT), p.row_lds, c.st,
-                           ra, ga, band_grid);
+                           ra, ga, band_grid, gather_x);
         return 0;
     };
     return bp.depth_in_gather ? go(std::true_type()) : go(std::false_type());
@@ -2591,7 +2704,8 @@ int nr::k6_compact(const BackwardCall &c, const K6Plan &plan, int face_zeros, K6
     int *vis_list = (int *)(ws + L.list_off);
     int *slot_of = (int *)(ws + L.slot_off);
     unsigned *rng = (unsigned *)(ws + L.rng_off);
-    out = {vis_list, vis_count, slot_of, scratch};
+    int *ticket = (int *)(ws + L.ticket_off);
+    out = {vis_list, vis_count, slot_of, scratch, ticket};
     const unsigned char *vflags = c.visible_faces;
     if (!vflags) {  // the forward's flags were not kept: one pass over face_index_map rebuilds them
         unsigned char *f = ws + L.flags_off;
@@ -2612,7 +2726,7 @@ int nr::k6_compact(const BackwardCall &c, const K6Plan &plan, int face_zeros, K6
         hipLaunchKernelGGL(k_compact_par, dim3((unsigned)L.n_chunks, (unsigned)B), dim3(VIS_CHUNK),
                            (size_t)(2 * n_bands + (use_diff ? 2 * (S + 1) : 0)) * sizeof(int), st, vflags, vis_list, vis_count,
                            slot_of, F, L.n_chunks, c.faces, rng, scratch, S, chunk_band, n_bands, W, band_cursor, zero_faces,
-                           zero_listed, use_diff);
+                           zero_listed, use_diff, ticket);
         if (!plan.use_records)
             hipLaunchKernelGGL(k_band_total, dim3((unsigned)B), dim3(256), 0, st, chunk_band, L.n_chunks, band_lines, band_start,
                                lines_ok, n_bands);
@@ -2627,7 +2741,7 @@ int nr::k6_compact(const BackwardCall &c, const K6Plan &plan, int face_zeros, K6
                            zero_listed);
         // (capacity 0: every image is told to take the scan path)
         hipLaunchKernelGGL(k_band_scan, dim3((unsigned)B), dim3(256), 0, st, band_lines, band_start, band_cursor, lines_ok,
-                           n_bands, plan.use_records ? L.cap : 0, 0);
+                           n_bands, plan.use_records ? L.cap : 0, 0, ticket);
     }
     return launch_status();
 }
@@ -2639,10 +2753,13 @@ LineSetupArgs nr::k6_line_setup_args(const BackwardCall &c, const K6Plan &plan)
     const int n_bands = plan.n_bands;
     // the distance coefficients of a record: x 2 / S up front in the tolerance mode, as the reference has them in the exact one
     const float k2s = (c.flags & NR_FLAG_EXACT_GRADIENT) ? 1.0f : 2.0f / (float)c.S;
+    // workgroups per image: a slot of LS_FACES list positions each, or every k6::SLOT_STRIDE-th slot and a loop (line_setup_body)
+    const unsigned slots = (unsigned)((c.F + LS_FACES - 1) / LS_FACES);
+    const unsigned stride = (c.flags & NR_FLAG_SERIAL_BACKWARD) ? 1u : k6::SLOT_STRIDE;
     return {c.faces, c.face_index_map, (const int *)(ws + L.list_off), (const int *)(ws + L.count_off),
             (const unsigned *)(ws + L.rng_off), (const int *)(ws + L.cband_off), compact_in_one_launch(L, n_bands) ? L.n_chunks : 0,
             (int *)(ws + L.band_off), (int *)(ws + L.start_off), (int *)(ws + L.cursor_off), (int *)(ws + L.ok_off),
-            (BandLine *)(ws + L.lines_off), L.cap, c.F, c.S, plan.W, n_bands, k2s, (unsigned)((c.F + LS_FACES - 1) / LS_FACES),
+            (BandLine *)(ws + L.lines_off), L.cap, c.F, c.S, plan.W, n_bands, k2s, (slots + stride - 1) / stride,
             (unsigned)c.B, (size_t)6 * n_bands * sizeof(int)};
 }
 
@@ -2658,9 +2775,9 @@ int nr::run_line_setup(const LineSetupArgs &a, hipStream_t st)
 // and then the overflow-only k_bpm_fast launch behind k_bpm_row: the images whose records exceed the line buffer, by the face
 // scan, no fill.  (l, ls: the compaction's lists and the band tables and line records of k6_line_setup_args.)
 // tail: the plan of a fused backward whose K7 / K8 gather shares k_bpm_row's launch (gather_in_tail; the fill then spares the
-// listed faces' cubes), else NULL.
+// listed faces' cubes), else NULL.  overflow_later: the overflow pass rides in k_backward_big's launch (k6_big_overflow).
 int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes,
-                const BackwardPlan *tail)
+                const BackwardPlan *tail, bool overflow_later)
 {
     if (plan.kernel == K6_KERNEL_GLOBAL) {
         auto global = [&](auto r, auto a) {
@@ -2695,7 +2812,35 @@ int nr::k6_band(const BackwardCall &c, const K6Plan &plan, const K6Lists &l, con
     NR_BAND_TIMER_START(c.st, plan.kernel);
     int rc = tail ? band_gather() : (plan.kernel == K6_KERNEL_ROW ? band_row() : band_fast(std::false_type(), fill, fill_bytes));
     NR_BAND_TIMER_STOP(c.st);
-    if (rc == 0 && plan.overflow_pass) rc = band_fast(std::true_type(), nullptr, 0);
+    if (rc == 0 && plan.overflow_pass && !overflow_later) rc = band_fast(std::true_type(), nullptr, 0);
+    return rc ? rc : launch_status();
+}
+
+// k_bpm_fast's overflow pass and k_backward_big with K6's finish in one launch (k_big_overflow; BackwardPlan::big_overflow)
+int nr::k6_big_overflow(const BackwardCall &c, const BackwardPlan &bp, const K6Lists &l, const LineSetupArgs &ls)
+{
+    const K6Plan &p = bp.k6p;
+    const int B = c.B, S = c.S;
+    const unsigned total_wg = (unsigned)((S + p.W_fast - 1) / p.W_fast) * 2u * (unsigned)B;
+    const unsigned n_ovf = total_wg < k6::OVF_GRID ? total_wg : k6::OVF_GRID;
+    BigArgs ga = big_args(c, bp, l);
+    ga.lines_ok = ls.lines_ok;
+    const dim3 big = big_grid(ga.vis_list != nullptr, B, c.F);
+    const FastOverflowArgs fa = {c.faces, c.face_index_map, c.rgb_map, c.alpha_map, c.grad_rgb_map, c.grad_alpha_map, l.vis_list,
+                                 l.vis_count, ls.rng, l.scratch, ls.band_lines, ls.band_start, ls.lines_ok, ls.line_buf, ls.cap, c.F, S,
+                                 p.W_fast, S + 4, c.eps, ls.k2s, B, p.win_lines, p.qcap, l.ticket, n_ovf, big.x, big.y, big.z};
+    const size_t n_wg = (size_t)n_ovf + (size_t)big.x * big.y * big.z;
+    if (n_wg > 0x7fffffffull) return NR_E_SIZE;
+    const int rc = with_k6_types(c.rgb, c.alpha, p.mode, [&](auto r, auto a, auto m) {
+        auto go = [&](auto depth) {
+            static LdsLimit limit;  // one per instantiation
+            auto kern = k_big_overflow<decltype(r)::value, decltype(a)::value, decltype(m)::value, decltype(depth)::value>;
+            if (int e = limit.ensure((const void *)kern, p.fast_lds)) return e;
+            hipLaunchKernelGGL(kern, dim3((unsigned)n_wg), dim3(256), p.fast_lds, c.st, fa, ga);
+            return 0;
+        };
+        return ga.g_depth ? go(std::true_type()) : go(std::false_type());
+    });
     return rc ? rc : launch_status();
 }
 

@@ -31,7 +31,8 @@ struct LineSetupArgs {
     size_t cap;
     int F, S, W, n_bands;
     float k2s;
-    unsigned grid_x, grid_y;  // the launch: ceil(F / LS_FACES) x B workgroups of 256 threads, lds_bytes of dynamic LDS
+    unsigned grid_x, grid_y;  // the launch: grid_x x B workgroups of 256 threads, lds_bytes of dynamic LDS; grid_x = ceil(F / LS_FACES)
+                              // slots over k6::SLOT_STRIDE (nr_k6_tune.h): a workgroup takes the slots bx, bx + grid_x, ...
     size_t lds_bytes;
 };
 
@@ -137,7 +138,8 @@ __device__ __forceinline__ BandLine make_fast_line(const float *__restrict__ fv,
 // k_line_setup: the line records of every (visible face, edge, axis, line d0), written band by band into line_buf so that
 // a band workgroup finds its lines as one dense array: no face scan, no record compaction, no line setup inside the band
 // kernel (together ~40 % of its cycles when they ran there, on <= 256 of its 512 threads).
-//   One workgroup takes LS_FACES list positions of one image (dealt out in turn, see the kernel).  Binning without a
+//   A workgroup takes LS_FACES list positions of one image at a time (dealt out in turn, see the kernel; every
+//   k6::SLOT_STRIDE-th such slot of the image in a loop).  Binning without a
 //   device-wide atomic per line (1.2 M same-address atomics across the 8 L2s of the chip cost 230 us): (1) the workgroup
 //   counts its own lines per band in LDS, (2) reserves its block of each non-empty band with ONE global atomic (band_cursor),
 //   (3) computes the records and places each at band start + block base + an LDS cursor.  The order inside a band is
@@ -218,10 +220,14 @@ __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const in
     // The ceil(n_vis / LS_FACES) workgroups that have work deal the list positions out in turn (position = workgroup + k *
     // workgroups): neighbours in the list are neighbours in the mesh, and a block of 32 large faces has three times the lines
     // of an average one -- the kernel is one round of workgroups and as slow as its slowest.
+    // The launch has grid_x workgroups per image, which may be fewer than the slots of the longest list (most images list a
+    // fifth of their faces, and a workgroup whose slot lies behind the list only reads the list's length and leaves): workgroup
+    // bx takes the slots bx, bx + grid_x, ... below n_wg, each exactly as a workgroup of its own would.
     const int n_vis = vis_count[b];
     const int n_wg = (n_vis + LS_FACES - 1) / LS_FACES;
-    const int pos0 = bx, pstep = n_wg;  // position of slot p: pos0 + p * pstep
-    const int n_pos = bx < n_wg ? (n_vis - pos0 + pstep - 1) / pstep : 0;
+    int pos0 = bx;             // the slot: position of its item p: pos0 + p * pstep
+    const int pstep = n_wg;
+    int n_pos = bx < n_wg ? (n_vis - pos0 + pstep - 1) / pstep : 0;
     if (n_pos == 0 && !first) return;
     unsigned r_own = RNG_EMPTY;
     int fn_own = 0;
@@ -247,6 +253,12 @@ __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const in
         for (int i = tid; i < 2 * n_bands; i += 256) s_start[i] = band_start[(size_t)b * 2 * n_bands + i];
     }
     if (n_pos == 0 || !ok) return;
+    const int tid_all = tid;
+    for (;;) {
+    // (what a thread derives from its number alone -- item, axis, edge, face float -- is derived again in every round: carried
+    // around the loop in registers it cost the kernel its eight workgroups per CU)
+    int tid = tid_all;
+    asm volatile("" : "+v"(tid));
     __syncthreads();
     for (int i = tid; i < 2 * n_bands; i += 256) s_cnt[i] = 0;
     if (tid < 6 * LS_FACES) s_rng[tid] = r_own;
@@ -357,6 +369,17 @@ __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const in
             h.d1_out = h.d1_in + h.direction;
             buf_b[s_base[bi] + atomicAdd(s_cnt + bi, 1)] = fast_line_finish(h, ld, S, s_fn[p], tgt, own[u], k2s);
         }
+    }
+    // the workgroup's next slot, if the image's list reaches it (uniform: every thread reads the same n_wg)
+    pos0 += (int)a.grid_x;
+    if (pos0 >= n_wg) return;  // (the barrier at the loop's top stands between this slot's LDS tables and the next one's)
+    n_pos = (n_vis - pos0 + pstep - 1) / pstep;
+    r_own = RNG_EMPTY;
+    if (tid < 6 * n_pos) {
+        const int p = tid / 6, ae = tid - 6 * p, axis = ae / 3, e = ae - 3 * axis;
+        r_own = rng[(((size_t)b * 2 + axis) * F + pos0 + p * pstep) * 3 + e];
+    }
+    if (tid < n_pos) fn_own = vis_list[(size_t)b * F + pos0 + tid * pstep];
     }
 }
 

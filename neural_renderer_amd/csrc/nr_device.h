@@ -404,7 +404,8 @@ __device__ __forceinline__ unsigned xcd_block(unsigned n_blocks)
 // 1-D instead, gx * B ids, and the image is fastest: (bx, by) = (id / B, id % B).  Every workgroup that can have work (bx
 // below the longest list's share) is handed out before the first that cannot.  Nothing waits for anything: it is the same
 // set of workgroups in another order.  (With B a multiple of 8 an image's workgroups all land on one XCD.)
-// Used where it measured (profiles/sparse_grid_ab.md): k_line_setup and the gather part of k_band_gather.
+// Used where it measured (profiles/sparse_grid_ab.md, profiles/idle_workgroups_ab.md): k_line_setup, the gather part of
+// k_band_gather and k_setup_gather.
 struct SlotImage { int bx, by; };
 __device__ __forceinline__ SlotImage image_fastest(unsigned id, unsigned B)
 {
@@ -529,6 +530,7 @@ struct BackwardPlan {
     size_t gather_lds;     // ... its dynamic LDS
     bool depth_in_gather;  // K8 rides in the K7 gather (and its k_backward_big)
     bool big;              // k_backward_big behind the face gather (texture_size <= 8)
+    bool big_overflow;     // ... with K6's overflow pass in its launch (k_big_overflow) instead of behind the band kernel
     int finish;            // K6Finish
     bool depth;            // K8 as launches of its own (k_backward_depth_face + k_backward_big)
     bool fill_faces;       // depth-only fused call: grad_faces zero-filled
@@ -542,6 +544,7 @@ int run_backward(const BackwardCall &c);  // plan_backward, then the plan's step
 struct K6Lists {
     const int *vis_list, *vis_count, *slot_of;
     double *scratch;
+    int *ticket;  // the overflow pass's ticket counter (k_big_overflow), zeroed by the compaction
 };
 struct LineSetupArgs;  // nr_band_lines.h
 
@@ -550,7 +553,8 @@ int k6_compact(const BackwardCall &c, const K6Plan &p, int face_zeros, K6Lists &
 LineSetupArgs k6_line_setup_args(const BackwardCall &c, const K6Plan &p);
 int run_line_setup(const LineSetupArgs &a, hipStream_t st);
 int k6_band(const BackwardCall &c, const K6Plan &p, const K6Lists &l, const LineSetupArgs &ls, void *fill, size_t fill_bytes,
-            const BackwardPlan *tail);  // k_bpm_global, or band kernel (tail: with the gather behind it) + overflow
+            const BackwardPlan *tail, bool overflow_later);  // k_bpm_global, or band kernel (tail: with the gather behind it) [+ overflow]
+int k6_big_overflow(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l, const LineSetupArgs &ls);  // overflow + k_backward_big
 void k6_finalize(const BackwardCall &c, const K6Lists &l, bool add);
 bool k6_lists_fit(int B, int F, size_t workspace_bytes);  // k_list_visible's lists fit the workspace and one launch
 K6Lists k6_list_visible(const BackwardCall &c);

@@ -474,5 +474,292 @@ __device__ __forceinline__ void zero_unlisted_body(const ZeroArgs &z, const int 
     }
 }
 
+
+// --------------------------------------------------------------------------------------------------
+// Faces with many candidate pixels (a ground plane, a backdrop, the strip of a needle) would keep one 16-lane group of
+// the kernels above busy for thousands of iterations while the rest of the chip idles.  Those kernels therefore leave
+// every face whose candidate set exceeds BIG_PX pixels untouched (zeros stored / nothing added), and this
+// kernel, launched right after them, gives each such face a whole workgroup: one thread per face finds the big ones of a
+// 256-face range, then all 256 lanes walk each of them in turn (coalesced rows), texel sums in LDS doubles, depth sums
+// through a wave + LDS reduction.  With no big face in the range the workgroup exits after ~150 instructions.
+// TEX: 0 no textures, 1 grad_textures through per-face LDS double accumulators (any texture_size <= 8), 2 texture_size 2 with
+// static taps (24 register sums per lane, as in the TS2 gather); DEPTH: the K8 terms.
+struct BigArgs {
+    const int32_t *face_index_map;
+    const float *sampling_weight_map;
+    const int32_t *sampling_index_map;
+    const float *face_inv_map, *faces, *zbase, *weight_map, *depth_map, *g_rgb;
+    float *grad_textures;
+    int n_faces_total, F, S, ts;
+    double eps;
+    int fix_batch_z;
+    const int *vis_list, *vis_count;
+    const float *g_depth;
+    float *grad_faces;
+    const unsigned char *visible;
+    FaceLight lit;
+    const double *k6_scratch;
+    const int *lines_ok;  // K6's finish spares the listed faces of the images marked 0 here (NULL: none; k_big_overflow)
+};
+
+// bid = (range of 256 faces or list slots, image, share), nz shares per range: blockIdx and gridDim.z of k_backward_big
+template <int TEX, bool DEPTH, bool LIT>
+__device__ __forceinline__ void backward_big_body(const BigArgs &a, const uint3 bid, const unsigned nz)
+{
+    const int32_t *__restrict__ face_index_map = a.face_index_map;
+    const float *__restrict__ sampling_weight_map = a.sampling_weight_map;
+    const int32_t *__restrict__ sampling_index_map = a.sampling_index_map;
+    const float *__restrict__ face_inv_map = a.face_inv_map, *__restrict__ faces = a.faces, *__restrict__ zbase = a.zbase,
+                *__restrict__ weight_map = a.weight_map, *__restrict__ depth_map = a.depth_map, *__restrict__ g_rgb = a.g_rgb;
+    float *__restrict__ grad_textures = a.grad_textures;
+    const int n_faces_total = a.n_faces_total, F = a.F, S = a.S, ts = a.ts;
+    const double eps = a.eps;
+    const int fix_batch_z = a.fix_batch_z;
+    const int *__restrict__ vis_list = a.vis_list, *__restrict__ vis_count = a.vis_count;
+    const float *__restrict__ g_depth = a.g_depth;
+    float *__restrict__ grad_faces = a.grad_faces;
+    const unsigned char *__restrict__ visible = a.visible;
+    const FaceLight &lit = a.lit;
+    const double *__restrict__ k6_scratch = a.k6_scratch;
+    extern __shared__ __attribute__((aligned(16))) double s_tex[];  // [ts^3 * 3] texel sums of the face being walked
+    __shared__ int s_list[256];
+    __shared__ int s_wave_n[4];
+    // 9 depth sums + 24 texel sums (TEX == 2) per WAVE, added up in wave order by whoever reads them (red() below: float atomics
+    // of the four waves onto one word arrived in any order, and the bits of a big face's gradients changed from run to run) +
+    // 3 light-colour sums (lit; row 0)
+    __shared__ float s_red[4][36];
+    __shared__ int s_own;        // lit: the face being walked owns a pixel
+    const int tid = threadIdx.x;
+    if (vis_list && (int)bid.x * 256 >= vis_count[bid.y]) return;  // slots behind the image's list
+    int n_big;
+    {   // one face per thread: is its candidate set this kernel's business?  The list is built in thread order, so that the
+        // (int)nz workgroups that scan the same range agree on it and can share it out (entry q -> workgroup q % (int)nz:
+        // with one workgroup per range a 2048 x 2048 view, whose faces are all "big", kept 20 workgroups busy for 5 ms).
+        int gi = bid.x * 256 + tid;
+        bool ok = gi < n_faces_total;
+        if (vis_list) {
+            ok = gi < vis_count[bid.y];
+            gi = ok ? (int)bid.y * F + vis_list[(size_t)bid.y * F + gi] : 0;
+        }
+        // K6's last step for the listed faces rides in this launch (the fused backward whose gather did not wait for the band
+        // kernel: grad_faces holds the gather's K8 sums, or zeros): K6's double sums of the face's list position, rounded, go
+        // on top, requested here beside the face's vertices.  A face of this kernel's own also receives its K8 sums from one
+        // of the launch's workgroups (below): float atomics for it, the two additions onto the gather's zero commute.  Every
+        // other face's entries are this thread's alone: a plain read-modify-write (58 k listed faces at the headline size:
+        // 350 k float atomics took this launch from 4.6 to 16 us).
+        // (an image whose records overflowed the line buffer receives its K6 sums in this very launch -- k_big_overflow -- and is
+        // finished by the overflow pass's last workgroup)
+        const bool finish = k6_scratch && ok && bid.z == 0 && !(a.lines_ok && a.lines_ok[bid.y] == 0);
+        float k6v[6], had[6];
+        float *gf = grad_faces + (size_t)gi * 9;
+        if (finish) {
+            const double *sc = k6_scratch + ((size_t)bid.y * F + bid.x * 256 + tid) * 6;
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+                k6v[2 * v + 0] = (float)sc[2 * v + 0]; k6v[2 * v + 1] = (float)sc[2 * v + 1];
+                had[2 * v + 0] = gf[3 * v + 0]; had[2 * v + 1] = gf[3 * v + 1];
+            }
+        }
+        bool big = false;
+        if (ok && !vis_list && visible && !visible[gi]) ok = false;
+        if (ok) {
+            const float *f = faces + (size_t)gi * 9;
+            const Cand cd = face_candidates(f[0], f[1], f[3], f[4], f[6], f[7], S);
+            big = cd.n > BIG_PX;
+        }
+        if (finish) {
+#pragma unroll
+            for (int v = 0; v < 3; v++) {
+                if (big) {
+                    atomicAdd(gf + 3 * v + 0, k6v[2 * v + 0]);
+                    atomicAdd(gf + 3 * v + 1, k6v[2 * v + 1]);
+                } else {
+                    gf[3 * v + 0] = k6v[2 * v + 0] + had[2 * v + 0];
+                    gf[3 * v + 1] = k6v[2 * v + 1] + had[2 * v + 1];
+                }
+            }
+        }
+        const unsigned long long m = __ballot(big);
+        const int lane = tid & 63, wave = tid >> 6;
+        if (lane == 0) s_wave_n[wave] = __popcll(m);
+        __syncthreads();
+        int before = 0;
+        for (int w = 0; w < wave; w++) before += s_wave_n[w];
+        if (big) s_list[before + __popcll(m & ((1ull << lane) - 1ull))] = gi;
+        n_big = s_wave_n[0] + s_wave_n[1] + s_wave_n[2] + s_wave_n[3];
+        __syncthreads();
+    }
+    const int n_tex = TEX ? ts * ts * ts * 3 : 0;
+    const int n_lds = TEX == 1 ? n_tex : 0;
+    for (int q = bid.z; q < n_big; q += (int)nz) {
+        const int gi = s_list[q];
+        const int b = gi / F, fn = gi - b * F;
+        const float *fp = faces + (size_t)gi * 9;
+        float f[9];
+#pragma unroll
+        for (int k = 0; k < 9; k++) f[k] = fp[k];
+        const Cand cd = face_candidates(f[0], f[1], f[3], f[4], f[6], f[7], S);
+        DepthConst dc;
+        if (DEPTH) dc = depth_constants(f, S);
+        const float *fz = (fix_batch_z ? faces + (size_t)b * F * 9 : zbase) + (size_t)fn * 9;  // :389, Q1
+        const float face_z[3] = {fz[2], fz[5], fz[8]};
+        const bool flip = TEX && LIT && fn >= lit.tex_faces;  // the reversed copy: taps in the original cube's layout
+        for (int k = tid; k < n_lds; k += 256) s_tex[k] = 0.0;
+        if (tid < 4 * 36) (&s_red[0][0])[tid] = 0.0f;
+        if (LIT && tid == 0) s_own = 0;
+        __syncthreads();
+        bool own = false;
+        float dacc[9], tacc[24];
+#pragma unroll
+        for (int k = 0; k < 9; k++) dacc[k] = 0.0f;
+#pragma unroll
+        for (int k = 0; k < 24; k++) tacc[k] = 0.0f;
+        const size_t img = (size_t)b * S * S;
+        for (int i = tid; i < cd.n; i += 256) {
+            int x, y;
+            if (!cand_pixel(cd, i, S, x, y)) continue;
+            const size_t p = img + (size_t)y * S + x;
+            if (face_index_map[p] != fn) continue;
+            if (LIT) own = true;
+            float wk[3] = {0.0f, 0.0f, 0.0f}, depth = 0.0f;
+            if (weight_map) { wk[0] = weight_map[3 * p]; wk[1] = weight_map[3 * p + 1]; wk[2] = weight_map[3 * p + 2]; }
+            if (depth_map) depth = depth_map[p];
+            if (TEX) {
+                Taps t;
+                if (sampling_weight_map) {
+#pragma unroll
+                    for (int pn = 0; pn < 8; pn++) {
+                        t.w[pn] = sampling_weight_map[8 * p + pn];
+                        t.isc[pn] = sampling_index_map[8 * p + pn];
+                    }
+                } else {
+                    compute_taps(face_z, wk, depth, ts, eps, t, flip);
+                }
+                const float g[3] = {g_rgb[3 * p], g_rgb[3 * p + 1], g_rgb[3 * p + 2]};
+#pragma unroll
+                for (int pn = 0; pn < 8; pn++) {
+                    if (TEX == 2) {
+                        tacc[3 * pn + 0] += t.w[pn] * g[0];  // :780
+                        tacc[3 * pn + 1] += t.w[pn] * g[1];
+                        tacc[3 * pn + 2] += t.w[pn] * g[2];
+                    } else {
+                        if (t.isc[pn] * 3 >= n_tex) continue;  // outside the cube: weight 0 (compute_taps)
+                        double *a = s_tex + t.isc[pn] * 3;
+                        atomicAdd(a + 0, (double)(t.w[pn] * g[0]));
+                        atomicAdd(a + 1, (double)(t.w[pn] * g[1]));
+                        atomicAdd(a + 2, (double)(t.w[pn] * g[2]));
+                    }
+                }
+            }
+            if (DEPTH) {  // rasterize.py:824-837, as in k_backward_depth_face
+                const float gd = g_depth[p];
+                const float depth2 = depth * depth;
+                float tmp[3] = {dc.tmp[0], dc.tmp[1], dc.tmp[2]};
+                if (face_inv_map) {  // the reference's per-pixel residual: its values, its divisions
+                    tmp[0] = tmp[1] = tmp[2] = 0.0f;
+#pragma unroll
+                    for (int k = 0; k < 3; k++)
+#pragma unroll
+                        for (int l = 0; l < 3; l++) tmp[k] += -face_inv_map[9 * p + 3 * l + k] / f[3 * l + 2];
+                }
+#pragma unroll
+                for (int k = 0; k < 3; k++) dacc[3 * k + 2] += gd * wk[k] * depth2 / dc.zz[k];
+#pragma unroll
+                for (int k = 0; k < 3; k++)
+#pragma unroll
+                    for (int l = 0; l < 2; l++) dacc[3 * k + l] += -gd * tmp[l] * wk[k] * depth2 * (float)S / 2.0f;
+            }
+        }
+        if (DEPTH) {
+#pragma unroll
+            for (int k = 0; k < 9; k++) {
+                const float v = group_sum(dacc[k], 64);
+                if ((tid & 63) == 0) s_red[tid >> 6][k] = v;
+            }
+        }
+        if (TEX == 2) {
+#pragma unroll
+            for (int k = 0; k < 24; k++) {
+                const float v = group_sum(tacc[k], 64);
+                if ((tid & 63) == 0) s_red[tid >> 6][9 + k] = v;
+            }
+        }
+        if (TEX && LIT && own) s_own = 1;
+        __syncthreads();
+        auto red = [&](int k) { return ((s_red[0][k] + s_red[1][k]) + s_red[2][k]) + s_red[3][k]; };
+        if (TEX && LIT) {  // the original cube, times the face's light colour; only a face that owns a pixel stores
+            if (s_own) {
+                const size_t cube = (size_t)b * lit.tex_faces + (flip ? fn - lit.tex_faces : fn);
+                const float *lc = lit.light + (size_t)gi * 3;
+                const float *tex = lit.textures ? lit.textures + cube * n_tex : nullptr;
+                float *dst = grad_textures + cube * n_tex;
+                for (int k = tid; k < n_tex; k += 256) {
+                    const int q = k / 3, c = k - 3 * q;
+                    int u = k;
+                    float a;
+                    if (TEX == 2) {  // k = 3 * corner + c, the corner's texel as in the TS2 gather
+                        u = 3 * (flip ? q : (q & 1) * 4 + (q & 2) + (q >> 2)) + c;
+                        a = red(9 + k);
+                    } else {
+                        a = (float)s_tex[k];
+                    }
+                    dst[u] = a * lc[c];
+                    if (tex && a != 0.0f) atomicAdd(&s_red[0][33 + c], a * tex[u]);
+                }
+                if (lit.grad_light) {
+                    __syncthreads();
+                    if (tid < 3) lit.grad_light[(size_t)gi * 3 + tid] = s_red[0][33 + tid];
+                }
+            }
+        } else {
+        if (TEX == 1) {
+            float *dst = grad_textures + (size_t)gi * n_tex;
+            for (int k = tid; k < n_tex; k += 256) dst[k] = (float)s_tex[k];
+        }
+        if (TEX == 2 && tid < 24) {  // corner pn = tid / 3 -> texel (pn & 1) * 4 + ((pn >> 1) & 1) * 2 + ((pn >> 2) & 1)
+            const int pn = tid / 3, c = tid - 3 * pn;
+            const int isc = (pn & 1) * 4 + ((pn >> 1) & 1) * 2 + ((pn >> 2) & 1);
+            grad_textures[(size_t)gi * 24 + 3 * isc + c] = red(9 + tid);
+        }
+        }
+        if (DEPTH && tid < 9) {
+            if (k6_scratch) atomicAdd(grad_faces + (size_t)gi * 9 + tid, red(tid));  // (see the top of the kernel)
+            else grad_faces[(size_t)gi * 9 + tid] += red(tid);
+        }
+        __syncthreads();
+    }
+}
+
+
+// k_backward_big's arguments for a call and its plan (K8 riding along and K6's finish as the plan says)
+inline BigArgs big_args(const BackwardCall &c, const BackwardPlan &p, const K6Lists &l)
+{
+    const double *finish_k6 = p.finish == FINISH_BIG ? l.scratch : nullptr;
+    BigArgs a = {};
+    a.face_index_map = c.face_index_map, a.sampling_weight_map = c.sampling_weight_map, a.sampling_index_map = c.sampling_index_map;
+    a.faces = c.faces, a.zbase = c.faces_z_ref ? c.faces_z_ref : c.faces, a.weight_map = c.weight_map, a.depth_map = c.depth_map;
+    a.g_rgb = c.grad_rgb_map, a.grad_textures = c.grad_textures;
+    a.n_faces_total = c.B * c.F, a.F = c.F, a.S = c.S, a.ts = c.ts, a.eps = c.eps;
+    a.fix_batch_z = (c.flags & NR_FLAG_FIX_TEXTURE_BATCH_Z) ? 1 : 0;
+    a.vis_list = p.listed ? l.vis_list : nullptr, a.vis_count = l.vis_count;
+    a.g_depth = p.depth_in_gather ? c.grad_depth_map : nullptr;
+    a.grad_faces = (p.depth_in_gather || finish_k6) ? c.grad_faces : nullptr;
+    a.lit = c.lit, a.k6_scratch = finish_k6;
+    return a;
+}
+
+// k_backward_big's grid: one workgroup per range of 256 faces (or list slots), times as many workgroups per range (z) as it
+// takes to put ~4096 workgroups on the chip -- they share out the range's big faces.  (Small launches: a workgroup per 64
+// faces of the call, at least 1024 -- with nothing to do, as on a fine mesh, the kernel costs what dispatching it costs.)
+inline dim3 big_grid(bool listed, int B, int F)
+{
+    const size_t n = (size_t)B * F;
+    const dim3 g = listed ? dim3((unsigned)((F + 255) / 256), (unsigned)B) : dim3((unsigned)((n + 255) / 256));
+    const size_t ranges = (size_t)g.x * g.y;
+    const size_t target = n / 64 < 1024 ? 1024 : (n / 64 > 4096 ? 4096 : n / 64);
+    const size_t z = target / ranges;
+    return dim3(g.x, g.y, (unsigned)(z < 1 ? 1 : (z > 64 ? 64 : z)));
+}
+
 }  // namespace
 }  // namespace nr

@@ -59,9 +59,31 @@
                                          // gather's grid of F / 16 workgroups per image (most of which only read their list's length)
                                          // is long, and the fill inside the band kernel and the finish inside the gather are worth more.
                                          // Configs 4 and 5 (texture sizes 4 and 8) have no static-tap gather: serial order as before.
+// The fused backward without its idle workgroups (profiles/idle_workgroups_ab.md; fused backward, us per call, medians of 7 rounds
+// of 30 calls, the builds alternating in one process; teapot views at 256^2 unless said otherwise):
+#ifndef NR_SLOT_STRIDE      // k_line_setup (alone or inside k_setup_gather) and the gather part of k_band_gather: a launch has ceil(slots /
+#define NR_SLOT_STRIDE 4    // this) workgroups per image, each looping over slots that far apart while the image's list lasts (1: a
+#endif                      // workgroup per slot).  A teapot view lists 19 % of its faces: at 4 almost no workgroup loops and three in four
+                            // of those that only read their list's length and leave are not dispatched.  1 / 2 / 4 / 8: 64 views 178.8 /
+                            // 179.3 / 178.8 / 179.2 (working-first order had taken it all there), 16 views 80.4 / 79.7 / 79.1 / 80.6,
+                            // 8 views 60.7 / 60.7 / 59.9 / 65.1, 32 views 111.3 / 110.9 / 110.9 / 116.8, 1024 views at 32^2 457.8 /
+                            // 437.7 / 428.6 / 425.0 -- at 8 the working workgroups of a view loop and the launch has a second round
+#ifndef NR_MERGE_OVERFLOW   // 1: the overflow pass behind k_bpm_row rides in k_backward_big's launch where the plan finishes K6 there
+#define NR_MERGE_OVERFLOW 1 // (k_big_overflow, nr_backward_pixel_map.hip); 0: a launch of its own, always.  0 / 1: 64 views 180.0 / 178.8,
+#endif                      // 16 views 80.5 / 79.1, 8 views 61.6 / 59.9 (back to back the empty launch cost 1.2 ... 1.7 us, not the 4.6 of its trace)
+#ifndef NR_SETUP_GATHER_IMAGE_FASTEST    // k_setup_gather's ids: 1 image fastest (working workgroups first, as k_line_setup's), 0 the
+#define NR_SETUP_GATHER_IMAGE_FASTEST 1  // 2-D grid's order.  0 / 1: 16 views 84.5 / 79.1, 8 views 65.0 / 59.9
+#endif
+#ifndef NR_ROW_DEAL_IMAGES    // k_band_gather's band part: 1 the images dealt across the XCDs (batches of 16, 24, ...), 0 eight runs of
+#define NR_ROW_DEAL_IMAGES 1  // neighbouring images (bpm_row_body).  0 / 1: 64 views 179.0 / 175.3, 32 views 110.7 / 108.0, 128 views
+#endif                        // 344.9 / 333.3, 64 views at 512^2 575.5 / 572.0
 
 namespace nr {
 namespace k6 {
+constexpr bool ROW_DEAL_IMAGES = NR_ROW_DEAL_IMAGES != 0;
+constexpr unsigned SLOT_STRIDE = NR_SLOT_STRIDE;
+static_assert(SLOT_STRIDE >= 1, "slots per workgroup of the strided launches");
+constexpr bool MERGE_OVERFLOW = NR_MERGE_OVERFLOW != 0;
 constexpr int FB = NR_K6_FB;
 constexpr int U_GROUP = NR_K6_U_GROUP;
 static_assert(U_GROUP >= 1 && U_GROUP <= 4, "a super-piece's count travels in two bits");
