@@ -78,7 +78,9 @@ extern "C" {
                           *        nr_laplacian_forward, nr_laplacian_backward, nr_flatness_forward, nr_flatness_backward,
                           *        nr_mesh_loss_workspace_bytes;
                           *        nr_lights, nr_lights_grad, nr_light_colors_forward, nr_light_colors_backward,
-                          *        nr_light_colors_workspace_bytes);
+                          *        nr_light_colors_workspace_bytes;
+                          *        nr_iou_loss_forward, nr_iou_loss_backward, nr_squared_error_forward, nr_squared_error_backward,
+                          *        nr_image_loss_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -760,6 +762,46 @@ int nr_flatness_forward(const float *vertices, const int32_t *quads, float *loss
 int nr_flatness_backward(const float *vertices, const int32_t *quads, const int32_t *inc_offsets, const int32_t *inc,
                          const float *grad_loss, float *grad_vertices, int32_t batch_size, int32_t num_vertices,
                          int32_t num_quads, double eps, void *stream);
+
+/*
+ * Image losses (not in the reference; DESIGN "Image losses"): the objective of a fit on images, one loss per image, on an
+ * image pyramid of `levels` in 1 .. 5 levels.  P_0(z) = z; P_l(z) is the 2 x 2 mean of P_(l-1)(z),
+ * (((p00 + p01) + p10) + p11) * 0.25f with the upper row first, in float32.  H and W must be multiples of 2^(levels - 1)
+ * (NR_E_SIZE).  level_weights is a HOST array of `levels` doubles, read during the call and handed to the kernels by value.
+ *   IoU, alpha [B, H, W], target [B, H, W] (target_per_image = 1) or [H, W] (0: one target for the batch, read in place):
+ *     a_l = P_l(alpha), t_l = P_l(target), I_l = sum a_l t_l, U_l = sum (a_l + t_l - a_l t_l),
+ *     loss[b] = sum_l w_l (1 - I_l / (U_l + eps)).  Two empty silhouettes give exactly sum w_l.  sums [B, 2 levels] doubles
+ *     (or NULL) receives I_0, U_0, I_1, U_1, ... for the backward, which reads the target and these sums, not alpha:
+ *     grad_alpha[b, p] = -g_b sum_l w_l 4^-l (t_l(P) (U_l + eps) - I_l (1 - t_l(P))) / (U_l + eps)^2, P the level-l block of p.
+ *   Squared error, images [B, C, H, W], target [B, C, H, W] or [C, H, W], mask [B, H, W] or [H, W] or NULL (= 1), the mask
+ *     applied to every channel: d = mask (images - target), d_l = P_l(d), loss[b] = sum_l w_l sum_(c, P) d_l^2;
+ *     grad_images[b, c, p] = sum_l 2 g_b w_l 4^-l mask(p) d_l(c, P), the differences recomputed.
+ * No gradient to target or mask.  The sums of an image: per tile of 64 x 16 pixels a double sum per level in a fixed order
+ * into the workspace (nr_image_loss_workspace_bytes; 0 for sizes out of range), the tiles added in tile order in double by a
+ * second kernel, the loss evaluated in double and rounded once.  Each backward is one launch.  No atomics in any kernel: the
+ * same bits in every run, and an image alone gives the bits it has in a batch.  16-byte loads when W is a multiple of 4
+ * and the pointers are 16-byte aligned.  The float operation order: the header comment of csrc/nr_image_losses.hip.  Every
+ * output element is stored; no call synchronises the host or reads device memory on the host; NR_E_* before any launch.
+ */
+size_t nr_image_loss_workspace_bytes(int32_t batch_size, int32_t height, int32_t width, int32_t levels);
+
+int nr_iou_loss_forward(const float *alpha, const float *target, int32_t target_per_image, const double *level_weights,
+                        float *loss, double *sums, int32_t batch_size, int32_t height, int32_t width, int32_t levels,
+                        double eps, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_iou_loss_backward(const float *target, int32_t target_per_image, const double *sums, const double *level_weights,
+                         const float *grad_loss, float *grad_alpha, int32_t batch_size, int32_t height, int32_t width,
+                         int32_t levels, double eps, void *stream);
+
+int nr_squared_error_forward(const float *images, const float *target, const float *mask, int32_t target_per_image,
+                             int32_t mask_per_image, const double *level_weights, float *loss, int32_t batch_size,
+                             int32_t channels, int32_t height, int32_t width, int32_t levels, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+int nr_squared_error_backward(const float *images, const float *target, const float *mask, int32_t target_per_image,
+                              int32_t mask_per_image, const double *level_weights, const float *grad_loss,
+                              float *grad_images, int32_t batch_size, int32_t channels, int32_t height, int32_t width,
+                              int32_t levels, void *stream);
 
 /*
  * Learnable lights (not in the reference; DESIGN "Learnable lights"): the light colour of every face (flat) or of every face

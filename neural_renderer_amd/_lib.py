@@ -103,6 +103,11 @@ SIGNATURES = {
     'nr_light_colors_workspace_bytes': (_sz, [_i32] * 4),
     'nr_light_colors_forward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_light_colors_backward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp, _vp, _lights_grad_p] + [_i32] * 6 + [_vp, _sz, _vp]),
+    'nr_image_loss_workspace_bytes': (_sz, [_i32] * 4),
+    'nr_iou_loss_forward': (_c.c_int, [_vp, _vp, _i32, _vp, _vp, _vp] + [_i32] * 4 + [_f64, _vp, _sz, _vp]),
+    'nr_iou_loss_backward': (_c.c_int, [_vp, _i32] + [_vp] * 4 + [_i32] * 4 + [_f64, _vp]),
+    'nr_squared_error_forward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 2 + [_i32] * 5 + [_vp, _sz, _vp]),
+    'nr_squared_error_backward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 3 + [_i32] * 5 + [_vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),
     'nr_frontend_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_cam_p, _light_p, _vp]),

@@ -17,7 +17,7 @@ from .look import look
 from .look_at import look_at
 from .perspective import perspective
 from .projection import projection
-from .rasterize import rasterize, rasterize_depth, rasterize_silhouettes
+from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
 from .uv_textures import UVImages
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
 from .vertices_to_faces import vertices_to_faces
@@ -176,8 +176,7 @@ class Renderer(object):
         call, else from lighting() on a ones texture behind the module-by-module front-end.  The cubes' gradient comes back
         summed over the views.  Runs eagerly: graph_replay does not apply."""
         faces, light = self._frontend(vertices, faces, light_colors=True)
-        return rasterize(faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                         self.background_color, faces_z_ref=self.faces_z_ref, face_light=light)
+        return faces, textures, dict(faces_z_ref=self.faces_z_ref, face_light=light)
 
     def _render_uv(self, vertices, faces, uv):
         """render() with a UVImages: the images sampled at every covered pixel (not in the reference).  Per-face light colours
@@ -186,8 +185,7 @@ class Renderer(object):
         if self.shading == 'smooth':
             return self._render_uv_smooth(vertices, faces, uv)
         faces, light = self._frontend(vertices, faces, light_colors=True)
-        return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                         self.background_color, face_light=light)
+        return faces, uv, dict(face_light=light)
 
     def _render_uv_smooth(self, vertices, faces, uv):
         """render() with a UVImages and shading = 'smooth' (not in the reference): vertex_light computes the light at the
@@ -201,8 +199,7 @@ class Renderer(object):
                              self.light_color_ambient, self.light_color_directional, self.light_direction,
                              fill_back=self.fill_back, smooth=True, implementation=None if fused else 'torch')
         faces, _ = self._frontend(vertices, faces, fused=fused)
-        return rasterize(faces, uv, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                         self.background_color, face_light=light)
+        return faces, uv, dict(face_light=light)
 
     def _render_vertex_colors(self, vertices, faces, vc):
         """render() with a VertexColors (not in the reference): vertex_shade lights the colours per corner, in world space,
@@ -225,8 +222,7 @@ class Renderer(object):
                               fill_back=self.fill_back, smooth=self.shading == 'smooth',
                               implementation=None if fused else 'torch')
         faces, _ = self._frontend(vertices, faces, fused=fused)
-        return rasterize(faces, corner, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                         self.background_color)
+        return faces, corner, {}
 
     def _render_lights(self, vertices, faces, textures):
         """render() with `lights` set (not in the reference): light_colors computes the light in world space -- HIP kernels
@@ -238,7 +234,6 @@ class Renderer(object):
         if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3):
             raise ValueError('vertices must be a tensor [batch size, num of vertices, 3]')
         smooth = self.shading == 'smooth'
-        raster = (self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps, self.background_color)
         if isinstance(textures, VertexColors):
             B = vertices.shape[0]
             if textures.num_vertices != vertices.shape[1]:
@@ -257,22 +252,21 @@ class Renderer(object):
                 corner = torch.cat((corner, torch.flip(corner, dims=[2])), dim=1)
             corner = corner * (light if smooth else light[:, :, None, :])
             projected, _ = self._frontend(vertices, faces)
-            return rasterize(projected, CornerColors(corner), *raster)
+            return projected, CornerColors(corner), {}
         if isinstance(textures, UVImages):
             light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=smooth)
             projected, _ = self._frontend(vertices, faces)
-            return rasterize(projected, textures, *raster, face_light=light)
+            return projected, textures, dict(face_light=light)
         if smooth:
             raise ValueError("Renderer.shading = 'smooth' takes UVImages or VertexColors: texture cubes are lit per face "
                              "('flat') only")
         light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=False)
         projected, _ = self._frontend(vertices, faces)
-        return rasterize(projected, textures, *raster, faces_z_ref=self.faces_z_ref, face_light=light)
+        return projected, textures, dict(faces_z_ref=self.faces_z_ref, face_light=light)
 
-    def render(self, vertices, faces, textures):
-        """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference -- or [1,Nf,ts,ts,ts,3] beside B > 1 views (not in the
-        reference): one set shared by the batch, see _render_shared --, or (not in the reference) a UVImages whose images are
-        sampled at every covered pixel (uv_textures.py), or a VertexColors (vertex_colors.py), lit as `shading` says."""
+    def _shade(self, vertices, faces, textures):
+        """The one dispatch of render() and render_rgbad(): everything in front of the rasterizer for the shading source
+        `textures` -> (projected faces [B,F,3,3], what the rasterizer takes second, its keyword arguments)."""
         if self.shading not in ('flat', 'smooth'):
             raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
         if self.lights is not None:
@@ -289,10 +283,36 @@ class Renderer(object):
             return self._render_shared(vertices, faces, textures)
         if self._use_face_light(vertices, faces, textures):
             faces, light = self._frontend(vertices, faces, light_colors=True, fused=True)
-            return rasterize(
-                faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-                self.background_color, faces_z_ref=self.faces_z_ref, face_light=light)
+            return faces, textures, dict(faces_z_ref=self.faces_z_ref, face_light=light)
         faces, textures = self._frontend(vertices, faces, textures)
-        return rasterize(
-            faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
-            self.background_color, faces_z_ref=self.faces_z_ref, graph_replay=self.graph_replay)
+        return faces, textures, dict(faces_z_ref=self.faces_z_ref, graph_replay=self.graph_replay)
+
+    def render(self, vertices, faces, textures):
+        """`textures`: cubes [B,Nf,ts,ts,ts,3] as in the reference -- or [1,Nf,ts,ts,ts,3] beside B > 1 views (not in the
+        reference): one set shared by the batch, see _render_shared --, or (not in the reference) a UVImages whose images are
+        sampled at every covered pixel (uv_textures.py), or a VertexColors (vertex_colors.py), lit as `shading` says."""
+        faces, textures, kw = self._shade(vertices, faces, textures)
+        return rasterize(faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                         self.background_color, **kw)
+
+    def render_rgbad(self, vertices, faces, textures, return_rgb=True, return_alpha=True, return_depth=True):
+        """Not in the reference: render()'s image together with the silhouette and the depth image from ONE rasterization --
+        the dict of rasterize_rgbad, 'rgb' [B,3,is,is], 'alpha' and 'depth' [B,is,is], None for an output that is not asked
+        for (its work is skipped).  `textures` is anything render() takes, through render()'s own dispatch (`lights`,
+        VertexColors, UVImages flat and smooth, shared cubes, `face_light`, the lit-texture path with `graph_replay`), and
+        'rgb' is render()'s image bit for bit.  Without return_rgb only the geometry goes through the front-end, as in
+        render_silhouettes, and `textures` is not looked at.
+
+        Alpha and depth here are rasterized with the renderer's `near`, `far` and `rasterizer_eps`, which render_silhouettes
+        and render_depth do not forward (quirk Q2 of the reference: they run with the rasterizer's defaults).  Under the
+        default near / far the forward images are the same, bit for bit; the BACKWARD differs: the silhouette gradient here
+        is taken with eps = rasterizer_eps (1e-3, as render's), render_silhouettes' with 1e-4."""
+        if return_rgb:
+            faces, textures, kw = self._shade(vertices, faces, textures)
+        else:
+            if self.shading not in ('flat', 'smooth'):
+                raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+            faces, _ = self._frontend(vertices, faces)
+            textures, kw = None, dict(graph_replay=self.graph_replay)
+        return rasterize_rgbad(faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
+                               self.background_color, return_rgb, return_alpha, return_depth, **kw)
