@@ -80,7 +80,8 @@ extern "C" {
                           *        nr_lights, nr_lights_grad, nr_light_colors_forward, nr_light_colors_backward,
                           *        nr_light_colors_workspace_bytes;
                           *        nr_iou_loss_forward, nr_iou_loss_backward, nr_squared_error_forward, nr_squared_error_backward,
-                          *        nr_image_loss_workspace_bytes);
+                          *        nr_image_loss_workspace_bytes;
+                          *        nr_stencil_apply);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -802,6 +803,31 @@ int nr_squared_error_backward(const float *images, const float *target, const fl
                               int32_t mask_per_image, const double *level_weights, const float *grad_loss,
                               float *grad_images, int32_t batch_size, int32_t channels, int32_t height, int32_t width,
                               int32_t levels, void *stream);
+
+/*
+ * Mesh subdivision (not in the reference; DESIGN "Mesh subdivision"): one level of Loop or midpoint refinement is a sparse
+ * linear operator on per-vertex data, given as a host-built CSR table (neural_renderer_amd/subdivision.py) with a row per
+ * output vertex; the backward of a level is the transposed table, a row per input vertex, applied by the same call.
+ *   One level on faces [F, 3] over Nv vertices.  Edges: every unordered pair {p < q} that is a side of a face, E of them,
+ *   ordered by (p, q); edge e owns new vertex Nv + e and old vertices keep their indices, Nv' = Nv + E.  m(e): the (face,
+ *   side) occurrences of e, duplicate faces counted; e is sharp when m(e) != 2.  Face f = (a, b, c) becomes faces
+ *   4 f .. 4 f + 3 = (a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca).
+ *     midpoint: old vertex {v: 1}; edge vertex {p: 1/2, q: 1/2}.
+ *     loop, N(v) the distinct vertices joined to v by an edge, n = |N(v)|, s(v) the sharp edges at v:
+ *       old vertex: n = 0: {v: 1};  s = 0: beta = 3/16 if n = 3 else 3 / (8 n), {v: 1 - n beta, u: beta for u in N(v)};
+ *                   s = 2: {v: 3/4, the two sharp neighbours: 1/8 each};  any other s: {v: 1};
+ *       edge vertex: sharp: {p: 1/2, q: 1/2};  m = 2: {p: 3/8, q: 3/8, o1: 1/8, o2: 1/8}, o1 / o2 the opposite vertices.
+ *   Weights in float64, entries of a row with one column added in float64, rounded to float32 once; rows sum to 1.
+ * nr_stencil_apply: x [B, num_in, C] -> y [B, num_out, C], C = channels in 1 .. 16 (NR_E_SIZE otherwise, as batch_size >
+ * 65535), with row_offsets [num_out + 1], cols and weights [num_entries], the entries of a row in ascending column:
+ *   acc = w_0 * x_0 (one rounding), then acc = fmaf(w_k, x_k, acc) in table order; a row without entries gives 0.
+ * A row {v: 1} copies its input bit for bit.  No atomics; every output element is stored; the same bits in every run, and
+ * an image alone gives the bits it has inside a batch.  One launch; the call does not synchronise the host or read device
+ * memory on the host; NR_E_* before any launch.
+ */
+int nr_stencil_apply(const float *x, const int32_t *row_offsets, const int32_t *cols, const float *weights, float *y,
+                     int32_t batch_size, int32_t num_in, int32_t num_out, int32_t channels, int32_t num_entries,
+                     void *stream);
 
 /*
  * Learnable lights (not in the reference; DESIGN "Learnable lights"): the light colour of every face (flat) or of every face

@@ -30,6 +30,9 @@ from .lights import Lights, light_colors
 # not in the reference: the objective of a fit on images -- silhouette IoU and masked squared error, optionally on an image
 # pyramid -- HIP in both directions
 from .image_losses import silhouette_iou_loss, squared_error_loss
+# not in the reference: mesh subdivision -- Loop and midpoint refinement of per-vertex data as a differentiable step, a sphere
+# template -- HIP in both directions
+from .subdivision import Subdivision, icosphere, subdivide, subdivision
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -48,4 +51,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
-           'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss']
+           'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
+           'Subdivision', 'subdivision', 'subdivide', 'icosphere']

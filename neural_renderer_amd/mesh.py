@@ -43,6 +43,29 @@ class Mesh(nn.Module):
         from .mesh_losses import flatness_loss
         return flatness_loss(self.vertices, self.faces, eps, implementation)
 
+    def subdivide(self, levels=1, scheme='loop'):
+        """Refine the mesh in place by `levels` levels of subdivision.subdivision (not in the reference; 'loop' or 'midpoint'):
+        `vertices` becomes a NEW nn.Parameter holding the refined positions, the `faces` buffer is replaced, `num_vertices`
+        and `num_faces` are updated, and every child face gets a copy of its parent's texture cube, textures[face_parent],
+        as a new nn.Parameter.  Optimiser state for the old parameters is void: build a new optimiser afterwards (the
+        multipliers of set_lr are carried over).  Each child repeats its parent's WHOLE cube, so the picture on the surface
+        is not resampled: it appears four times per parent, smaller.  Returns the plan (its face_parent maps the new faces
+        to the old)."""
+        from .subdivision import subdivision
+        plan = subdivision(self.faces, self.num_vertices, levels, scheme)
+        if plan.levels == 0:
+            return plan
+        with torch.no_grad():
+            vertices = nn.Parameter(plan(self.vertices.detach()).contiguous())
+            textures = nn.Parameter(self.textures.detach()[plan.face_parent].contiguous())
+        for new, old in ((vertices, self.vertices), (textures, self.textures)):
+            if hasattr(old, 'lr'):
+                new.lr = old.lr
+        self.vertices, self.textures = vertices, textures
+        self.faces = plan.faces.clone()
+        self.num_vertices, self.num_faces = int(vertices.shape[0]), int(self.faces.shape[0])
+        return plan
+
     def set_lr(self, lr_vertices, lr_textures):
         """Per-parameter learning-rate multipliers read by neural_renderer_amd.Adam (mesh.py:36-38)."""
         self.vertices.lr = lr_vertices
