@@ -33,6 +33,9 @@ from .image_losses import silhouette_iou_loss, squared_error_loss
 # not in the reference: mesh subdivision -- Loop and midpoint refinement of per-vertex data as a differentiable step, a sphere
 # template -- HIP in both directions
 from .subdivision import Subdivision, icosphere, subdivide, subdivision
+# not in the reference: point-cloud terms of a 3-D fit -- surface sampling, nearest neighbours and the chamfer distance -- HIP in
+# both directions
+from .point_losses import SurfaceSamples, chamfer_distance, nearest_points, sample_surface, sample_surface_points
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -52,4 +55,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
            'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
-           'Subdivision', 'subdivision', 'subdivide', 'icosphere']
+           'Subdivision', 'subdivision', 'subdivide', 'icosphere',
+           'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points']

@@ -43,6 +43,12 @@ class Mesh(nn.Module):
         from .mesh_losses import flatness_loss
         return flatness_loss(self.vertices, self.faces, eps, implementation)
 
+    def sample_points(self, num_samples, generator=None):
+        """point_losses.sample_surface_points of the module's own vertices and faces (not in the reference): (points
+        [num_samples, 3], differentiable in self.vertices, and their SurfaceSamples)."""
+        from .point_losses import sample_surface_points
+        return sample_surface_points(self.vertices, self.faces, num_samples, generator)
+
     def subdivide(self, levels=1, scheme='loop'):
         """Refine the mesh in place by `levels` levels of subdivision.subdivision (not in the reference; 'loop' or 'midpoint'):
         `vertices` becomes a NEW nn.Parameter holding the refined positions, the `faces` buffer is replaced, `num_vertices`
