@@ -39,7 +39,10 @@
  *
  * Conventions
  *   - plain device pointers (hipMalloc / torch caching allocator memory), C-contiguous, float32 / int32, every buffer
- *     16-byte aligned (hipMalloc gives 256, torch 512: the kernels move maps, textures and workspaces as 16-byte words);
+ *     16-byte aligned (hipMalloc gives 256, torch 512: the kernels move maps, textures and workspaces as 16-byte words).
+ *     The library does not check this for every entry; the Python package enforces it by copying: every tensor of a
+ *     caller and every upstream gradient goes through _lib.dense, which hands a view that is strided or off the grid
+ *     over as a contiguous, aligned copy ("Tensor boundary").  Other callers must align themselves;
  *     sizes are int32; near / far / eps are doubles because the reference pastes their Python repr into
  *     the kernel source as double literals (rasterize.py:226-234, 428-433, 737-743).
  *   - the library owns no memory and keeps no state between calls (it reads no environment variable; the one thing it

@@ -3,7 +3,11 @@ library is missing or an entry point fails, this raises."""
 import ctypes
 import os
 
+import torch
+
 from . import _build
+
+_CONTIGUOUS = torch.contiguous_format
 
 _c = ctypes
 _vp, _i32, _f64, _sz = _c.c_void_p, _c.c_int32, _c.c_double, _c.c_size_t
@@ -209,3 +213,16 @@ def check(code, what):
 def ptr(t):
     """data_ptr of a tensor or None."""
     return None if t is None else t.data_ptr()
+
+
+def dense(t):
+    """The tensor boundary: `t` itself when it is contiguous and starts on a 16-byte boundary -- what
+    include/nr_hip.h asks of every buffer, because the kernels move maps, textures and workspaces as 16-byte words --, else a
+    contiguous copy that does (torch's allocators align fresh storage to 64 bytes and more).  None stays None.  A view that
+    is contiguous but starts 4, 8 or 12 bytes off the grid (a slice of a flat parameter vector, a gradient-bucket view)
+    is returned unchanged by .contiguous(): hence the clone."""
+    if t is None:
+        return None
+    if not t.is_contiguous():
+        t = t.contiguous()
+    return t if t.data_ptr() % 16 == 0 else t.clone(memory_format=_CONTIGUOUS)

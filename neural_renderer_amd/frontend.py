@@ -190,11 +190,11 @@ class _FrontEnd(torch.autograd.Function):
         lib = _lib.load()
         cam, dist, light, fill_back, colors = setup
         dev = vertices.device
-        v = vertices.detach().contiguous()
-        idx = faces_idx.detach().to(torch.int32).contiguous()
-        tex = textures.detach().contiguous() if textures is not None else None
-        camera = tuple(x.detach().contiguous() for x in camera)
-        d = dist.detach().contiguous() if dist is not None else None
+        v = _lib.dense(vertices.detach())
+        idx = _lib.dense(faces_idx.detach().to(torch.int32))
+        tex = _lib.dense(textures.detach()) if textures is not None else None
+        camera = tuple(_lib.dense(x.detach()) for x in camera)
+        d = _lib.dense(dist.detach()) if dist is not None else None
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
         F = Nf * 2 if fill_back else Nf
@@ -237,9 +237,8 @@ class _FrontEnd(torch.autograd.Function):
         F = Nf * 2 if fill_back else Nf
         if g_faces is None:
             g_faces = torch.zeros((B, F, 3, 3), dtype=torch.float32, device=dev)
-        g_faces = g_faces.contiguous()
-        if g_second is not None:
-            g_second = g_second.contiguous()
+        g_faces = _lib.dense(g_faces)
+        g_second = _lib.dense(g_second)
         g_tex_out = g_second if tex is not None else None
         g_light = g_second if colors else None
         grad_v = torch.empty((B, Nv, 3), dtype=torch.float32, device=dev) if need_v else None

@@ -192,8 +192,8 @@ class _LightColors(torch.autograd.Function):
     def forward(ctx, setup, vertices, *params):
         lib = _lib.load()
         idx, off, ent, per_batch, flags, fill_back, smooth = setup
-        v = vertices.detach().contiguous()
-        params = tuple(None if p is None else p.detach().contiguous() for p in params)
+        v = _lib.dense(vertices.detach())
+        params = tuple(None if p is None else _lib.dense(p.detach()) for p in params)
         dev = v.device
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
@@ -221,7 +221,7 @@ class _LightColors(torch.autograd.Function):
         dev = v.device
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
-        g = grad_light.contiguous()
+        g = _lib.dense(grad_light)
         grad_v = torch.empty_like(v) if need[0] else None
         grads = tuple(torch.empty_like(p) if (n and p is not None) else None for p, n in zip(params, need[1:]))
         out = _lib.LightsGrad()

@@ -203,7 +203,7 @@ class _LaplacianLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, t):
         lib = _lib.load()
-        v = vertices.detach().contiguous()
+        v = _lib.dense(vertices.detach())
         dev = v.device
         B, Nv = v.shape[:2]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -227,7 +227,7 @@ class _LaplacianLoss(torch.autograd.Function):
         t = ctx.tables
         dev = delta.device
         B, Nv = delta.shape[:2]
-        g = grad_loss.contiguous()
+        g = _lib.dense(grad_loss)
         grad_v = torch.empty_like(delta)
         with torch.cuda.device(dev):
             _lib.check(lib.nr_laplacian_backward(delta.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr), g.data_ptr(),
@@ -242,7 +242,7 @@ class _FlatnessLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, t, eps):
         lib = _lib.load()
-        v = vertices.detach().contiguous()
+        v = _lib.dense(vertices.detach())
         dev = v.device
         B, Nv = v.shape[:2]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
@@ -265,7 +265,7 @@ class _FlatnessLoss(torch.autograd.Function):
         t = ctx.tables
         dev = v.device
         B, Nv = v.shape[:2]
-        g = grad_loss.contiguous()
+        g = _lib.dense(grad_loss)
         grad_v = torch.empty_like(v)
         some = t.num_quads > 0
         with torch.cuda.device(dev):

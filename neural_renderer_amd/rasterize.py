@@ -279,8 +279,8 @@ class _Cubes(object):
     def keep(self, r, inputs):
         textures, light = inputs
         r.shared = textures is not None and textures.shape[0] != r.B
-        r.textures = textures.detach().contiguous() if textures is not None else None  # rasterize.py:473
-        r.light = light.detach().contiguous() if light is not None else None
+        r.textures = _lib.dense(textures.detach()) if textures is not None else None  # rasterize.py:473
+        r.light = _lib.dense(light.detach()) if light is not None else None
 
     def saved(self, r):
         return (r.textures if r.light is not None else None), r.light  # (the backward reads the cubes only with light)
@@ -370,7 +370,7 @@ class _UVSource(object):
         return Nf, uv.layout.texture_size
 
     def keep(self, r, inputs):
-        r.light = inputs[0].detach().contiguous()
+        r.light = _lib.dense(inputs[0].detach())
         r.packed = pack_images(inputs[1:], self.uv.batch).detach()
 
     def saved(self, r):
@@ -444,7 +444,7 @@ class _CornerSource(object):
         return F, 0
 
     def keep(self, r, inputs):
-        r.corner = inputs[0].detach().contiguous()
+        r.corner = _lib.dense(inputs[0].detach())
 
     def saved(self, r):
         return r.corner,
@@ -513,7 +513,7 @@ def _forward_impl(cfg, faces, src, inputs):
     S = cfg.image_size
     r = _Residuals()
     r.B, r.F, r.S, r.ts, r.Nf, r.source = B, F, S, ts, Nf, src
-    r.faces = faces.detach().contiguous()  # rasterize.py:470
+    r.faces = _lib.dense(faces.detach())  # rasterize.py:470
     src.keep(r, inputs)
     with _on_device(dev):
         stream = _stream_ptr(dev)
@@ -524,7 +524,7 @@ def _forward_impl(cfg, faces, src, inputs):
         if cfg.return_rgb:
             bg = cfg.background_color
             if torch.is_tensor(bg):
-                background = bg.detach().to(device=dev, dtype=torch.float32).contiguous()
+                background = _lib.dense(bg.detach().to(device=dev, dtype=torch.float32))
             else:
                 background = _background_tensor(bg, dev)
             if tuple(background.shape) == (B, 3):
@@ -535,7 +535,7 @@ def _forward_impl(cfg, faces, src, inputs):
         # batch element 0 of the GLOBAL batch when this call holds a shard of it (include/nr_hip.h)
         z_ref = cfg.faces_z_ref
         if z_ref is not None:
-            z_ref = z_ref.detach().to(device=dev, dtype=torch.float32).contiguous()
+            z_ref = _lib.dense(z_ref.detach().to(device=dev, dtype=torch.float32))
             if tuple(z_ref.shape) != (F, 3, 3):
                 raise ValueError('faces_z_ref must have shape (num of faces, 3, 3), got %s' % (tuple(z_ref.shape),))
         r.z_ref = z_ref
@@ -561,9 +561,9 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want):
     dev = r.faces.device
     with _on_device(dev):
         stream = _stream_ptr(dev)
-        g_rgb = g_rgb.contiguous() if use_rgb else None
-        g_alpha = g_alpha.contiguous() if use_alpha else None
-        g_depth = g_depth.contiguous() if use_depth else None
+        g_rgb = _lib.dense(g_rgb) if use_rgb else None
+        g_alpha = _lib.dense(g_alpha) if use_alpha else None
+        g_depth = _lib.dense(g_depth) if use_depth else None
         grad_faces = torch.empty_like(r.faces)  # stored by the library (zeros when neither rgb nor alpha)
         key = (B, F, S, use_rgb, use_alpha)
         ws_bytes = _BWD_WS_BYTES.get(key)
@@ -787,7 +787,7 @@ class _ImageEpilogue(torch.autograd.Function):
     @staticmethod
     def forward(ctx, rgb_map, alpha_map, depth_map, anti_aliasing):
         lib = _lib.load()
-        maps = [m.detach().contiguous() if m is not None else None for m in (rgb_map, alpha_map, depth_map)]
+        maps = [_lib.dense(m.detach()) if m is not None else None for m in (rgb_map, alpha_map, depth_map)]
         ref = next(m for m in maps if m is not None)
         dev = ref.device
         B, S = ref.shape[0], ref.shape[1]
@@ -809,7 +809,7 @@ class _ImageEpilogue(torch.autograd.Function):
     def backward(ctx, g_rgb, g_alpha, g_depth):
         lib = _lib.load()
         B, S, aa = ctx.dims
-        grads = [g.contiguous() if g is not None else None for g in (g_rgb, g_alpha, g_depth)]
+        grads = [_lib.dense(g) for g in (g_rgb, g_alpha, g_depth)]
         ref = next((g for g in grads if g is not None), None)
         if ref is None:
             return None, None, None, None
@@ -914,10 +914,11 @@ class Rasterize(object):
                 sw = torch.empty((B, S, S, 8), dtype=f32, device=dev)
                 rgb = torch.empty((B, S, S, 3), dtype=f32, device=dev)
                 bg = self.background_color if self.background_color is not None else DEFAULT_BACKGROUND_COLOR
-                bg = bg.detach().to(device=dev, dtype=f32).contiguous() if torch.is_tensor(bg) else _background_tensor(bg, dev)
+                bg = _lib.dense(bg.detach().to(device=dev, dtype=f32)) if torch.is_tensor(bg) else _background_tensor(bg, dev)
+                wm = _lib.dense(self.weight_map)  # (the attribute may have been assigned by the caller)
                 _lib.check(lib.nr_forward_texture_sampling(
                     r.faces.data_ptr(), _lib.ptr(r.z_ref), r.textures.data_ptr(), r.face_index_map.data_ptr(),
-                    self.weight_map.data_ptr(), r.depth_map.data_ptr(), rgb.data_ptr(), si.data_ptr(), sw.data_ptr(), bg.data_ptr(),
+                    wm.data_ptr(), r.depth_map.data_ptr(), rgb.data_ptr(), si.data_ptr(), sw.data_ptr(), bg.data_ptr(),
                     int(tuple(bg.shape) == (B, 3)), None, B, F, S, ts, float(self.eps), r.flags, stream),
                     'nr_forward_texture_sampling')
                 self._lazy['sampling_index_map'], self._lazy['sampling_weight_map'] = si, sw

@@ -171,7 +171,7 @@ def _apply_torch(x, t):
 
 def _apply_hip(x, t):
     lib = _lib.load()
-    x = x.contiguous()
+    x = _lib.dense(x)
     B, _, C = x.shape
     y = torch.empty((B, t.num_out, C), dtype=torch.float32, device=x.device)
     with torch.cuda.device(x.device):

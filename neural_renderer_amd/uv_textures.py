@@ -100,7 +100,10 @@ class UVLayout(object):
         return state
 
     def inverse_map(self, device):
-        """(row_ptr [P+1], entry_texel, entry_weight) on `device`: built by nr_uv_texture_map on first use, then cached."""
+        """(row_ptr [P+1], entry_texel, entry_weight) on `device`: built by nr_uv_texture_map on first use, then cached.
+        The build is one launch on the stream that is current at that moment; a later call on ANOTHER stream waits for it
+        (an event, dropped once it has passed), so that the tables are never read ahead of the kernel that writes them.
+        (Inside a graph capture nothing is waited for: a capture needs an eager call in front of it anyway.)"""
         state = self._tensors(device)
         if 'row_ptr' not in state:
             lib = _lib.load()
@@ -110,15 +113,28 @@ class UVLayout(object):
                 wsb = lib.nr_uv_texture_map_workspace_bytes(F, ts, M, P)
                 if wsb == 0:
                     raise _lib.NRError('nr_uv_texture_map_workspace_bytes: layout out of range (F=%d ts=%d P=%d)' % (F, ts, P))
+                stream = torch.cuda.current_stream(device)
                 ws = torch.empty(wsb, dtype=torch.uint8, device=device)
-                row_ptr = torch.empty(P + 1, dtype=torch.int32, device=device)
-                entry_texel = torch.empty(n, dtype=torch.int32, device=device)
-                entry_weight = torch.empty(n, dtype=torch.float32, device=device)
+                # (zeros, once per layout: whatever reads the tables out of order finds empty rows, not stale indices)
+                row_ptr = torch.zeros(P + 1, dtype=torch.int32, device=device)
+                entry_texel = torch.zeros(n, dtype=torch.int32, device=device)
+                entry_weight = torch.zeros(n, dtype=torch.float32, device=device)
                 _lib.check(lib.nr_uv_texture_map(state['table'].data_ptr(), state['faces_uv'].data_ptr(),
                                                  state['face_image'].data_ptr(), row_ptr.data_ptr(), entry_texel.data_ptr(),
                                                  entry_weight.data_ptr(), F, ts, M, P, ws.data_ptr(), wsb,
-                                                 torch.cuda.current_stream(device).cuda_stream), 'nr_uv_texture_map')
-            state.update(row_ptr=row_ptr, entry_texel=entry_texel, entry_weight=entry_weight, workspace=ws)
+                                                 stream.cuda_stream), 'nr_uv_texture_map')
+                built = torch.cuda.Event()
+                built.record(stream)
+            state.update(row_ptr=row_ptr, entry_texel=entry_texel, entry_weight=entry_weight, workspace=ws,
+                         built=(built, stream.cuda_stream))
+        elif state.get('built') is not None and not torch.cuda.is_current_stream_capturing():
+            built, on = state['built']
+            if built.query():
+                state['built'] = None
+            else:
+                stream = torch.cuda.current_stream(device)
+                if stream.cuda_stream != on:
+                    stream.wait_event(built)
         return state['row_ptr'], state['entry_texel'], state['entry_weight']
 
 
@@ -155,7 +171,7 @@ def pack_images(images, batch):
     when others are batched -- the packing the kernels read (include/nr_hip.h: images [Bi,P,3])."""
     Bi = batch or 1
     flat = [(im if im.dim() == 4 else im[None].expand(Bi, -1, -1, -1)).reshape(Bi, -1, 3) for im in images]
-    return (flat[0] if len(flat) == 1 else torch.cat(flat, 1)).contiguous()
+    return _lib.dense(flat[0] if len(flat) == 1 else torch.cat(flat, 1))
 
 
 def unpack_image_gradients(layout, grad_packed):
@@ -188,7 +204,7 @@ class _BakeUV(torch.autograd.Function):
     def backward(ctx, grad_textures):
         layout, Bi, device = ctx.layout, ctx.batch, ctx.device
         row_ptr, entry_texel, entry_weight = layout.inverse_map(device)
-        grad_textures = grad_textures.contiguous()
+        grad_textures = _lib.dense(grad_textures)
         P = layout.num_pixels
         grad_packed = torch.empty((Bi, P, 3), dtype=torch.float32, device=device)
         lib = _lib.load()

@@ -192,8 +192,8 @@ class _VertexShade(torch.autograd.Function):
     def forward(ctx, vertices, colors, setup):
         lib = _lib.load()
         idx, off, ent, per_batch, light, fill_back, smooth = setup
-        v = vertices.detach().contiguous()
-        c = colors.detach().contiguous()
+        v = _lib.dense(vertices.detach())
+        c = _lib.dense(colors.detach())
         dev = v.device
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
@@ -224,7 +224,7 @@ class _VertexShade(torch.autograd.Function):
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
         Bc = 1 if c.dim() == 2 else int(c.shape[0])
-        g = grad_corner.contiguous()
+        g = _lib.dense(grad_corner)
         grad_v = torch.empty_like(v) if need_v else None
         grad_c = torch.empty_like(c) if need_c else None
         with torch.cuda.device(dev):

@@ -13,8 +13,8 @@ class _VerticesToFaces(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, faces):
         lib = _lib.load()
-        v = vertices.detach().contiguous()
-        f = faces.detach().to(torch.int32).contiguous()
+        v = _lib.dense(vertices.detach())
+        f = _lib.dense(faces.detach().to(torch.int32))
         B, Nv = v.shape[:2]
         Nf = f.shape[1]
         out = torch.empty((B, Nf, 3, 3), dtype=torch.float32, device=v.device)
@@ -31,7 +31,7 @@ class _VerticesToFaces(torch.autograd.Function):
         lib = _lib.load()
         f, = ctx.saved_tensors
         B, Nv, Nf = ctx.dims
-        g = grad_faces.contiguous()
+        g = _lib.dense(grad_faces)
         grad_vertices = torch.empty((B, Nv, 3), dtype=torch.float32, device=g.device)
         with torch.cuda.device(g.device):
             _lib.check(lib.nr_vertices_to_faces_backward(g.data_ptr(), f.data_ptr(), grad_vertices.data_ptr(), B, Nv, Nf,
