@@ -7,3 +7,4 @@ python examples/example1.py
 python examples/example2.py
 python examples/example3.py
 python examples/example4.py
+python examples/example_normals.py

@@ -84,7 +84,10 @@ extern "C" {
                           *        nr_light_colors_workspace_bytes;
                           *        nr_iou_loss_forward, nr_iou_loss_backward, nr_squared_error_forward, nr_squared_error_backward,
                           *        nr_image_loss_workspace_bytes;
-                          *        nr_stencil_apply);
+                          *        nr_stencil_apply;
+                          *        nr_vertex_normals_forward, nr_vertex_normals_backward, nr_face_normals_forward,
+                          *        nr_face_normals_backward, nr_corner_normals_forward, nr_corner_normals_backward,
+                          *        nr_normals_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -729,6 +732,58 @@ int nr_vertex_shade_backward(const float *vertices, const int32_t *faces_idx, co
                              int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t color_batch,
                              int32_t idx_per_batch, int32_t fill_back, int32_t smooth, const nr_light *light, void *workspace,
                              size_t workspace_bytes, void *stream);
+
+/*
+ * Normals (not in the reference): the normals that vertex shading forms and folds into a light colour, as outputs of their
+ * own, from world-space vertices [B, Nv, 3] and faces_idx [Nf, 3] (or [B, Nf, 3] with idx_per_batch).  All float32, in the
+ * operation order of nr_vertex_shade_forward, so that the two agree bit for bit:
+ *   N_f = cross(v0 - v1, v2 - v1) (lighting.py:36-39), n_f = N_f / (|N_f| + 1e-5): face normals [B, Nf, 3];
+ *   m_v = the sum of N_f over the (face, corner) pairs of vertex v in ascending (f, k) order (area-weighted),
+ *     n_v = m_v / (|m_v| + 1e-5): vertex normals [B, Nv, 3].
+ *   A vertex without a face, a zero normal sum and a zero-area face give exactly 0.
+ * Corner normals [B, F, 3, 3] (F = Nf * (fill_back ? 2 : 1)), the rasterizer's corner colours (nr_forward_rasterize_corner):
+ *   smooth = 0: corner[b, f, k] = n_f; smooth = 1: corner[b, f, k] = n_(v_k); the reversed copy of a face carries the negated
+ *   normal in its own flipped corner order, corner[b, Nf + f, k] = -corner[b, f, 2 - k] (nr_vertex_shade_forward's layout).
+ * adj_offsets / adj_entries: the vertex -> (face, corner) table of nr_vertex_shade_forward.  The vertex normals and the
+ * smooth corner normals need it forward, every backward needs it; nr_face_normals_forward does not.
+ *
+ * Backward: grad_vertices [B, Nv, 3], the exact adjoint, through normalize's backward g / (r + eps) - v (g . v) / ((r + eps)^2 r)
+ * (the second term 0 where r = 0) and the cross product.  Two launches: the first brings the upstream gradient (for corner
+ * normals: front minus flipped back, summed over the corners of a face or around a vertex in table order) to a gradient of
+ * N_f or m_v in the workspace, the second gathers it to the vertices; a smooth face takes (g_m(v0) + g_m(v1)) + g_m(v2).
+ * Every sum is a gather through the table in ascending entry order: no atomics, every output element is stored, the same
+ * bits in every run and for an image alone or inside a batch.  The workspace (nr_normals_workspace_bytes; 0 for sizes out of
+ * range) is needed by every backward and by nr_corner_normals_forward with smooth = 1.  No call synchronises the host;
+ * NR_E_* before any launch.
+ */
+size_t nr_normals_workspace_bytes(int32_t batch_size, int32_t num_vertices, int32_t num_faces);
+
+int nr_vertex_normals_forward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                              const int32_t *adj_entries, float *normals, int32_t batch_size, int32_t num_vertices,
+                              int32_t num_faces, int32_t idx_per_batch, void *stream);
+
+int nr_vertex_normals_backward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                               const int32_t *adj_entries, const float *grad_normals, float *grad_vertices,
+                               int32_t batch_size, int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch,
+                               void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_face_normals_forward(const float *vertices, const int32_t *faces_idx, float *normals, int32_t batch_size,
+                            int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, void *stream);
+
+int nr_face_normals_backward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                             const int32_t *adj_entries, const float *grad_normals, float *grad_vertices, int32_t batch_size,
+                             int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, void *workspace,
+                             size_t workspace_bytes, void *stream);
+
+int nr_corner_normals_forward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                              const int32_t *adj_entries, float *corner, int32_t batch_size, int32_t num_vertices,
+                              int32_t num_faces, int32_t idx_per_batch, int32_t fill_back, int32_t smooth, void *workspace,
+                              size_t workspace_bytes, void *stream);
+
+int nr_corner_normals_backward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
+                               const int32_t *adj_entries, const float *grad_corner, float *grad_vertices, int32_t batch_size,
+                               int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, int32_t fill_back,
+                               int32_t smooth, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

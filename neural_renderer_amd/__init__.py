@@ -36,6 +36,9 @@ from .subdivision import Subdivision, icosphere, subdivide, subdivision
 # not in the reference: point-cloud terms of a 3-D fit -- surface sampling, nearest neighbours and the chamfer distance -- HIP in
 # both directions
 from .point_losses import SurfaceSamples, chamfer_distance, nearest_points, sample_surface, sample_surface_points
+# not in the reference: vertex, face and corner normals -- HIP in both directions -- for Renderer.render_normals, and the
+# rotation of a renderer's camera
+from .normals import camera_rotation, corner_normals, face_normals, vertex_normals
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -56,4 +59,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
            'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
-           'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points']
+           'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
+           'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation']

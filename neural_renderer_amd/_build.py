@@ -11,7 +11,7 @@ SOURCES = [os.path.join(HERE, 'csrc', n) for n in ('nr_forward.hip', 'nr_backwar
                                                       'nr_backward_gather.hip', 'nr_geometry.hip',
                                                       'nr_image.hip', 'nr_frontend.hip', 'nr_texture_io.hip', 'nr_optim.hip',
                                                       'nr_uv_pixel.hip', 'nr_vertex_colors.hip', 'nr_mesh_losses.hip', 'nr_lights.hip',
-                                                      'nr_image_losses.hip', 'nr_subdivision.hip')]
+                                                      'nr_image_losses.hip', 'nr_subdivision.hip', 'nr_normals.hip')]
 HEADERS = [os.path.join(os.path.dirname(HERE), 'include', 'nr_hip.h'), os.path.join(os.path.dirname(HERE), 'include', 'nr_hip_profile.h'),
            os.path.join(HERE, 'csrc', 'nr_device.h'),
            os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h'), os.path.join(HERE, 'csrc', 'nr_face_gather.h'),

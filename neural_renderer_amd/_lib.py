@@ -99,6 +99,13 @@ SIGNATURES = {
     'nr_vertex_shade_workspace_bytes': (_sz, [_i32] * 2),
     'nr_vertex_shade_forward': (_c.c_int, [_vp] * 6 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
     'nr_vertex_shade_backward': (_c.c_int, [_vp] * 8 + [_i32] * 7 + [_light_p, _vp, _sz, _vp]),
+    'nr_normals_workspace_bytes': (_sz, [_i32] * 3),
+    'nr_vertex_normals_forward': (_c.c_int, [_vp] * 5 + [_i32] * 4 + [_vp]),
+    'nr_vertex_normals_backward': (_c.c_int, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    'nr_face_normals_forward': (_c.c_int, [_vp] * 3 + [_i32] * 4 + [_vp]),
+    'nr_face_normals_backward': (_c.c_int, [_vp] * 6 + [_i32] * 4 + [_vp, _sz, _vp]),
+    'nr_corner_normals_forward': (_c.c_int, [_vp] * 5 + [_i32] * 6 + [_vp, _sz, _vp]),
+    'nr_corner_normals_backward': (_c.c_int, [_vp] * 6 + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_mesh_loss_workspace_bytes': (_sz, [_i32] * 2),
     'nr_laplacian_forward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp, _sz, _vp]),
     'nr_laplacian_backward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),

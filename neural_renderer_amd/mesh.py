@@ -49,6 +49,11 @@ class Mesh(nn.Module):
         from .point_losses import sample_surface_points
         return sample_surface_points(self.vertices, self.faces, num_samples, generator)
 
+    def vertex_normals(self, implementation=None):
+        """normals.vertex_normals of the module's own vertices and faces (not in the reference): [num_vertices, 3]."""
+        from .normals import vertex_normals
+        return vertex_normals(self.vertices, self.faces, implementation)
+
     def subdivide(self, levels=1, scheme='loop'):
         """Refine the mesh in place by `levels` levels of subdivision.subdivision (not in the reference; 'loop' or 'midpoint'):
         `vertices` becomes a NEW nn.Parameter holding the refined positions, the `faces` buffer is replaced, `num_vertices`

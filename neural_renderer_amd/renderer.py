@@ -15,6 +15,7 @@ from .lighting import lighting
 from .lights import light_colors
 from .look import look
 from .look_at import look_at
+from .normals import camera_rotation, corner_normals
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
@@ -316,3 +317,45 @@ class Renderer(object):
             textures, kw = None, dict(graph_replay=self.graph_replay)
         return rasterize_rgbad(faces, textures, self.image_size, self.anti_aliasing, self.near, self.far, self.rasterizer_eps,
                                self.background_color, return_rgb, return_alpha, return_depth, **kw)
+
+    def render_normals(self, vertices, faces, space='world', normalize=False, return_dict=False):
+        """Not in the reference: a normal map [B,3,is,is] -- the channels are the x, y, z of the surface normal at the pixel,
+        signed (lighting()'s sign: a light along `d` lights the faces with n . d > 0), 0 on the background whatever
+        `background_color` says.  corner_normals (normals.py) gives every face corner
+        its normal in world space -- the face's with shading = 'flat', the area-weighted vertex normal with 'smooth', the
+        negated normals on the reversed copies of `fill_back` --, the front-end projects the geometry, once, and the
+        rasterizer interpolates the nine numbers of a face perspective-correctly, as it does corner colours, with the
+        renderer's image_size, anti_aliasing, near, far and rasterizer_eps.  Interpolated normals are shorter than 1 between
+        the vertices of a smooth mesh and fade to 0 across an anti-aliased silhouette; normalize = True divides every pixel
+        by |n| + 1e-5 afterwards.
+
+        space = 'world': the axes of `vertices`.  space = 'camera': the normals are rotated by the camera's rotation
+        (normals.camera_rotation) before they are rasterized: the axes of look_at / look -- x right, y up, z away from the
+        camera --, in 'projection' mode those of `R` (OpenCV: y down).  It is the rotation alone, not the perspective map.
+        The gradient reaches the vertices, through the normals and through the geometry, and with 'camera' a learnable `eye`
+        or `R`.
+
+        return_dict = True: the dict {'normals', 'alpha', 'depth'} from the one rasterization ('alpha' and 'depth' as
+        render_rgbad's).  `lights` and the light_* attributes are ignored: no light enters a normal map.  Runs eagerly:
+        graph_replay does not apply (a whole step can be captured once one eager step has built the vertex adjacency
+        table)."""
+        if self.shading not in ('flat', 'smooth'):
+            raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+        if space not in ('world', 'camera'):
+            raise ValueError("render_normals: space must be 'world' or 'camera', got %r" % (space,))
+        if not (torch.is_tensor(vertices) and vertices.dim() == 3 and vertices.shape[2] == 3):
+            raise ValueError('vertices must be a tensor [batch size, num of vertices, 3]')
+        corner = corner_normals(vertices, faces, smooth=self.shading == 'smooth', fill_back=self.fill_back).colors
+        if space == 'camera':
+            B, F = corner.shape[:2]
+            r = camera_rotation(self, B, vertices)
+            corner = torch.matmul(corner.reshape(B, 3 * F, 3), r.transpose(1, 2)).reshape(B, F, 3, 3)
+        faces, _ = self._frontend(vertices, faces)
+        out = rasterize_rgbad(faces, CornerColors(corner), self.image_size, self.anti_aliasing, self.near, self.far,
+                              self.rasterizer_eps, [0, 0, 0], True, bool(return_dict), bool(return_dict))
+        normals = out['rgb']
+        if normalize:
+            normals = normals / (torch.sqrt((normals * normals).sum(1, keepdim=True)) + 1e-5)
+        if return_dict:
+            return {'normals': normals, 'alpha': out['alpha'], 'depth': out['depth']}
+        return normals
