@@ -3,6 +3,7 @@
 hipcc cross-compiles without a GPU, so this runs in the authoring container; the resulting .so is
 git-ignored but travels to the GPU box with the working tree.
 """
+import glob
 import os
 import subprocess
 
@@ -12,10 +13,9 @@ SOURCES = [os.path.join(HERE, 'csrc', n) for n in ('nr_forward.hip', 'nr_backwar
                                                       'nr_image.hip', 'nr_frontend.hip', 'nr_texture_io.hip', 'nr_optim.hip',
                                                       'nr_uv_pixel.hip', 'nr_vertex_colors.hip', 'nr_mesh_losses.hip', 'nr_lights.hip',
                                                       'nr_image_losses.hip', 'nr_subdivision.hip', 'nr_normals.hip')]
-HEADERS = [os.path.join(os.path.dirname(HERE), 'include', 'nr_hip.h'), os.path.join(os.path.dirname(HERE), 'include', 'nr_hip_profile.h'),
-           os.path.join(HERE, 'csrc', 'nr_device.h'),
-           os.path.join(HERE, 'csrc', 'nr_k6_tune.h'), os.path.join(HERE, 'csrc', 'nr_band_lines.h'), os.path.join(HERE, 'csrc', 'nr_face_gather.h'),
-           os.path.join(HERE, 'csrc', 'nr_shade.h')]
+# every header the sources can include: a header missing here would let needs_build() skip a needed rebuild
+HEADERS = [os.path.join(os.path.dirname(HERE), 'include', n) for n in ('nr_hip.h', 'nr_hip_profile.h')] + \
+    sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h')))
 LIB_PATH = os.path.join(HERE, 'libnr_hip.so')
 # the measurement build: the same sources with -DNR_PROFILE_HOOK (include/nr_hip_profile.h); bench.py times the dominant kernel with it
 PROFILE_LIB_PATH = os.path.join(HERE, 'libnr_hip_prof.so')

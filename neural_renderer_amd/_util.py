@@ -19,6 +19,32 @@ _INDEX_ATTR = '_nr_index_ok'  # verdict stashed on a tensor OBJECT: it dies with
                                # be hit by an unrelated tensor that the caching allocator places at the same address)
 
 
+def cached_on_index(faces, attr, key, build, not_built_message):
+    """What `build()` derives on the host from the index tensor `faces` (and `key`: the vertex count, ...), cached on the
+    tensor object -- and, for a view (`faces[None]`, `.expand`), on the tensor it is a view of, which lives on -- in a dict
+    `attr` under the tensor's identity: data_ptr, shape, strides, version counter (an in-place edit builds anew), device,
+    and `key`.  A build reads the indices back, so inside a HIP-graph capture a miss raises `not_built_message`."""
+    stamp = (faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), faces._version, str(faces.device)) + tuple(key)
+    holders = [faces] + ([faces._base] if faces._base is not None else [])
+    for h in holders:
+        hit = getattr(h, attr, {}).get(stamp)
+        if hit is not None:
+            return hit
+    if faces.is_cuda and torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(not_built_message)
+    hit = build()
+    for h in holders:
+        try:
+            table = getattr(h, attr, None)
+            if table is None or len(table) > 8:
+                table = {}
+                setattr(h, attr, table)
+            table[stamp] = hit
+        except Exception:  # (a tensor subclass without __dict__: built every time)
+            pass
+    return hit
+
+
 def _stamp(t, num_vertices):
     return (t._version, int(num_vertices), tuple(t.shape), tuple(t.stride()), t.storage_offset())
 

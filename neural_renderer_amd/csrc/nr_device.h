@@ -55,6 +55,8 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
+
 __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }
 __device__ __forceinline__ int bcast_i(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 __device__ __forceinline__ float bcast_f(float v, int src)

@@ -9,17 +9,17 @@
 //   k_vertex_light         smooth forward 1: (image, vertex) -> both colours into the workspace
 //   k_corner_light         smooth forward 2: (image, face) -> the colours of its corners (the reversed copy's flipped)
 //   k_vertex_grad<SMOOTH>  (image, vertex): flat: grad_vertices; smooth: g_m, the gradient of the vertex's normal sum
-//   k_normals_to_vertices  smooth 2: (image, vertex): grad_vertices from g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
+//   k_normals_gather<true> smooth 2 (nr_mesh_gather.h): (image, vertex): grad_vertices from g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
 //   k_light_sums<SMOOTH>   (image, block of 256 faces / vertices): the 36 double sums of the block into the workspace
 //   k_light_finish         (image, gradient element): the blocks in block order (a shared parameter: the images in image order),
 //                          the gradient formed in double and rounded once
 //
-// The geometry helpers restate nr_vertex_colors.hip's (load_face, adjacency, normal_sum, normal_to_corner) instead of
-// sharing them through a header: moving them would touch the code generated for the existing kernels.  With sh = NULL the
-// forward is bit for bit nr_vertex_shade_forward's light of a white mesh and grad_vertices nr_vertex_shade_backward's -- a
-// change to the arithmetic of either file has to be made in both (tests/test_lights_gpu.py compares them).
-#include "nr_device.h"
-#include "nr_shade.h"
+// The mesh arguments and the geometry helpers (load_face, adjacency, face_normal, normal_sum, normal_to_corner) are
+// nr_mesh_gather.h's, shared with nr_vertex_colors.hip and nr_normals.hip.  With sh = NULL the forward is bit for bit
+// nr_vertex_shade_forward's light of a white mesh and grad_vertices nr_vertex_shade_backward's: the light's own arithmetic
+// (light_eval, normal_bwd) follows nr_shade.h's face_light and nr_vertex_colors.hip's light_dot_bwd term by term
+// (tests/test_lights_gpu.py compares them).
+#include "nr_mesh_gather.h"
 
 using namespace nr;
 
@@ -34,22 +34,14 @@ enum { NEED_ONE = 1, NEED_COS = 2, NEED_SH = 4, NEED_DIR = 8 };
 // the gradient elements of an image: g_Ia, g_Id, g_Ca[3], g_Cd[3], g_dir[3], g_sh[27]
 constexpr int NELEM = 38;
 
-struct LArgs {
-    const float *vertices;   // [B, Nv, 3] world space
-    const int32_t *idx;      // [Bt, Nf, 3]
-    const int32_t *adj_off;  // [Bt, Nv + 1]
-    const int32_t *adj_ent;  // [Bt, 3 Nf]: 3 f + k, ascending within a vertex
+struct LArgs : MeshArgs {
     nr_lights lights;        // device pointers
-    int B, Nv, Nf;
-    int idx_per_batch, fill_back;
 };
 
 // the light of one image in registers (sh: only with a.lights.sh)
 struct Lamp {
     float ia, id, ca[3], cd[3], d[3], sh[27];
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __device__ __forceinline__ const float *param(const LArgs &a, const float *p, int bit, int b, int n)
 {
@@ -73,69 +65,6 @@ __device__ __forceinline__ void load_lamp(const LArgs &a, int b, Lamp &L)
 #pragma unroll
         for (int j = 0; j < 27; j++) L.sh[j] = sh[j];
     }
-}
-
-// face f of image b: its vertex numbers (clamped for memory safety; the host validates them) and world-space vertices
-__device__ __forceinline__ void load_face(const LArgs &a, int b, int f, int vi[3], float w[3][3])
-{
-    const int32_t *idx = a.idx + ((size_t)(a.idx_per_batch ? b : 0) * a.Nf + f) * 3;
-    const float *vb = a.vertices + (size_t)b * a.Nv * 3;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        vi[k] = clampi(idx[k], 0, a.Nv - 1);
-        const float *src = vb + (size_t)vi[k] * 3;
-        w[k][0] = src[0];
-        w[k][1] = src[1];
-        w[k][2] = src[2];
-    }
-}
-
-// the table entries of vertex v in image b: [e0, e1) into the returned array
-__device__ __forceinline__ const int32_t *adjacency(const LArgs &a, int b, int v, int &e0, int &e1)
-{
-    const size_t t = a.idx_per_batch ? b : 0;
-    const int32_t *off = a.adj_off + t * ((size_t)a.Nv + 1);
-    e0 = clampi(off[v], 0, 3 * a.Nf);
-    e1 = clampi(off[v + 1], e0, 3 * a.Nf);
-    return a.adj_ent + t * 3 * (size_t)a.Nf;
-}
-
-// unnormalised face normal cross(v0 - v1, v2 - v1), and the two edges
-__device__ __forceinline__ void face_normal(const float w[3][3], float *v10, float *v12, float *n)
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        v10[c] = w[0][c] - w[1][c];
-        v12[c] = w[2][c] - w[1][c];
-    }
-    cross3(v10, v12, n);
-}
-
-// m_v: the face normals around vertex v, summed in float32 in ascending (face, corner) order
-__device__ __forceinline__ void normal_sum(const LArgs &a, int b, int v, float *m)
-{
-    m[0] = m[1] = m[2] = 0.0f;
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    for (int e = e0; e < e1; e++) {
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3];
-        load_face(a, b, clampi(ent[e], 0, 3 * a.Nf - 1) / 3, vi, w);
-        face_normal(w, v10, v12, n);
-        m[0] += n[0];
-        m[1] += n[1];
-        m[2] += n[2];
-    }
-}
-
-// gradient of corner k of a face from the gradient gn of its unnormalised normal n = v10 x v12
-__device__ __forceinline__ void normal_to_corner(const float *v10, const float *v12, const float *gn, int k, float *o)
-{
-    float ga[3], gb[3];
-    cross3(v12, gn, ga);  // g_v10
-    cross3(gn, v10, gb);  // g_v12
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = k == 0 ? ga[c] : (k == 2 ? gb[c] : -(ga[c] + gb[c]));
 }
 
 // Y_0 .. Y_8 at the unit vector u
@@ -347,34 +276,6 @@ __global__ __launch_bounds__(BLOCK) void k_vertex_grad(LArgs a, const float *__r
     out[2] = o3[2];
 }
 
-__global__ __launch_bounds__(BLOCK) void k_normals_to_vertices(LArgs a, const float *__restrict__ gm,
-                                                               float *__restrict__ grad_vertices)
-{
-    const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (v >= a.Nv) return;
-    float g[3] = {0.0f, 0.0f, 0.0f};
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    const float *gmb = gm + (size_t)b * a.Nv * 3;
-    for (int e = e0; e < e1; e++) {
-        const int fk = clampi(ent[e], 0, 3 * a.Nf - 1), f = fk / 3, k = fk - 3 * f;
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3], gn[3], o[3];
-        load_face(a, b, f, vi, w);
-        face_normal(w, v10, v12, n);
-#pragma unroll
-        for (int c = 0; c < 3; c++) gn[c] = (gmb[(size_t)vi[0] * 3 + c] + gmb[(size_t)vi[1] * 3 + c]) + gmb[(size_t)vi[2] * 3 + c];
-        normal_to_corner(v10, v12, gn, k, o);
-        g[0] += o[0];
-        g[1] += o[1];
-        g[2] += o[2];
-    }
-    float *out = grad_vertices + ((size_t)b * a.Nv + v) * 3;
-    out[0] = g[0];
-    out[1] = g[1];
-    out[2] = g[2];
-}
-
 // --------------------------------------------------------------------------------------------------------------------
 // backward to the light
 
@@ -521,12 +422,6 @@ __global__ __launch_bounds__(BLOCK) void k_light_finish(LArgs a, const double *_
 
 inline int n_blocks_of(int n) { return (n + BLOCK - 1) / BLOCK; }
 
-bool sizes_ok(int B, int Nv, int Nf)
-{
-    if (B < 1 || B > 65535 || Nv < 1 || Nf < 1) return false;
-    return (size_t)B * (size_t)Nf <= 0x7fffffffull / 18 && (size_t)B * (size_t)Nv <= 0x7fffffffull / 6;
-}
-
 // the workspace: the blocks' sums, then (smooth) six floats per vertex -- the forward's two colours, the backward's g_m
 size_t partial_bytes(int B, int Nv, int Nf, int smooth)
 {
@@ -542,30 +437,25 @@ int light_args(const float *vertices, const int32_t *faces_idx, const int32_t *a
                const nr_lights *lights, int B, int Nv, int Nf, int idx_per_batch, int fill_back, int smooth, bool need_adjacency,
                LArgs &a)
 {
-    if (!vertices || !faces_idx || !lights) return NR_E_NULL;
+    a = {};
+    // every NR_E_NULL, then every NR_E_MODE, in front of the mesh's NR_E_SIZE
+    const int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, need_adjacency, a);
+    if (e == NR_E_NULL || !lights) return NR_E_NULL;
     if (!lights->intensity_ambient || !lights->intensity_directional || !lights->color_ambient || !lights->color_directional ||
         !lights->direction)
         return NR_E_NULL;
-    if (need_adjacency && (!adj_offsets || !adj_entries)) return NR_E_NULL;
     if (smooth != 0 && smooth != 1) return NR_E_MODE;
     if (lights->per_image < 0 || lights->per_image > 63) return NR_E_MODE;
-    if (!sizes_ok(B, Nv, Nf)) return NR_E_SIZE;
-    a = {};
-    a.vertices = vertices; a.idx = faces_idx; a.adj_off = adj_offsets; a.adj_ent = adj_entries;
+    if (e) return e;
     a.lights = *lights;
-    a.B = B; a.Nv = Nv; a.Nf = Nf;
-    a.idx_per_batch = idx_per_batch != 0;
-    a.fill_back = fill_back != 0;
     return 0;
 }
-
-dim3 grid_of(int n, int B) { return dim3((unsigned)n_blocks_of(n), (unsigned)B); }
 
 }  // namespace
 
 NR_API size_t nr_light_colors_workspace_bytes(int32_t B, int32_t Nv, int32_t Nf, int32_t smooth)
 {
-    if (!sizes_ok(B, Nv, Nf) || (smooth != 0 && smooth != 1)) return 0;
+    if (!mesh_sizes_ok(B, Nv, Nf) || (smooth != 0 && smooth != 1)) return 0;
     return workspace_bytes_of(B, Nv, Nf, smooth);
 }
 
@@ -632,6 +522,6 @@ NR_API int nr_light_colors_backward(const float *vertices, const int32_t *faces_
     float *gm = (float *)((char *)workspace + partial_bytes(B, Nv, Nf, 1));
     hipLaunchKernelGGL(k_vertex_grad<true>, grid_of(Nv, B), dim3(BLOCK), 0, st, a, grad_light, gm);
     if (int rc = launch_status()) return rc;
-    hipLaunchKernelGGL(k_normals_to_vertices, grid_of(Nv, B), dim3(BLOCK), 0, st, a, gm, grad_vertices);
+    hipLaunchKernelGGL(k_normals_gather<true>, grid_of(Nv, B), dim3(BLOCK), 0, st, (const MeshArgs &)a, gm, grad_vertices);
     return launch_status();
 }

@@ -33,8 +33,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 __device__ __forceinline__ float dot3f(const float *p, const float *q) { return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2]; }
 
 // The block's sum of v in one fixed order: the wave's butterfly (every lane ends with the same bits), then the waves' sums

@@ -13,93 +13,19 @@
 //   k_vertex_stage<CORNER>    backward 1, smooth: (image, vertex) -> g_m, the gradient of the vertex's normal sum, from
 //                             grad_normals or from the corner gradients around the vertex (front minus flipped back)
 //   k_face_stage<CORNER>      backward 1, flat: (image, face) -> g_N, the gradient of the face's unnormalised normal
-//   k_normals_gather<SMOOTH>  backward 2: (image, vertex) -> grad_vertices, corner k's share of g_N(f) summed over the faces
-//                             around the vertex; smooth: g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
-// The static helpers are those of nr_vertex_colors.hip, restated here so that that file stays as it is.
-#include "nr_device.h"
-#include "nr_shade.h"
+//   k_normals_gather<SMOOTH>  backward 2 (nr_mesh_gather.h): (image, vertex) -> grad_vertices, corner k's share of g_N(f)
+//                             summed over the faces around the vertex; smooth: g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
+// The mesh arguments, the geometry helpers and k_normals_gather are nr_mesh_gather.h's, shared with nr_vertex_colors.hip and
+// nr_lights.hip.
+#include "nr_mesh_gather.h"
 
 using namespace nr;
 
 namespace {
 
-struct NArgs {
-    const float *vertices;     // [B, Nv, 3] world space
-    const int32_t *idx;        // [Bt, Nf, 3]
-    const int32_t *adj_off;    // [Bt, Nv + 1]
-    const int32_t *adj_ent;    // [Bt, 3 Nf]: 3 f + k, ascending within a vertex
-    int B, Nv, Nf;
-    int idx_per_batch, fill_back;
-};
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// face f of image b: its vertex numbers (clamped for memory safety; the host validates them) and world-space vertices
-__device__ __forceinline__ void load_face(const NArgs &a, int b, int f, int vi[3], float w[3][3])
-{
-    const int32_t *idx = a.idx + ((size_t)(a.idx_per_batch ? b : 0) * a.Nf + f) * 3;
-    const float *vb = a.vertices + (size_t)b * a.Nv * 3;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        vi[k] = clampi(idx[k], 0, a.Nv - 1);
-        const float *src = vb + (size_t)vi[k] * 3;
-        w[k][0] = src[0];
-        w[k][1] = src[1];
-        w[k][2] = src[2];
-    }
-}
-
-// the table entries of vertex v in image b: [e0, e1) into `ent`
-__device__ __forceinline__ const int32_t *adjacency(const NArgs &a, int b, int v, int &e0, int &e1)
-{
-    const size_t t = a.idx_per_batch ? b : 0;
-    const int32_t *off = a.adj_off + t * ((size_t)a.Nv + 1);
-    e0 = clampi(off[v], 0, 3 * a.Nf);
-    e1 = clampi(off[v + 1], e0, 3 * a.Nf);
-    return a.adj_ent + t * 3 * (size_t)a.Nf;
-}
-
-// unnormalised face normal cross(v0 - v1, v2 - v1) (lighting.py:36-39), and the two edges
-__device__ __forceinline__ void face_normal(const float w[3][3], float *v10, float *v12, float *n)
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        v10[c] = w[0][c] - w[1][c];
-        v12[c] = w[2][c] - w[1][c];
-    }
-    cross3(v10, v12, n);
-}
-
-// m_v: the face normals around vertex v, summed in float32 in ascending (face, corner) order (area-weighted)
-__device__ __forceinline__ void normal_sum(const NArgs &a, int b, int v, float *m)
-{
-    m[0] = m[1] = m[2] = 0.0f;
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    for (int e = e0; e < e1; e++) {
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3];
-        load_face(a, b, clampi(ent[e], 0, 3 * a.Nf - 1) / 3, vi, w);
-        face_normal(w, v10, v12, n);
-        m[0] += n[0];
-        m[1] += n[1];
-        m[2] += n[2];
-    }
-}
-
-// gradient of corner k of a face from the gradient gn of its unnormalised normal n = v10 x v12
-__device__ __forceinline__ void normal_to_corner(const float *v10, const float *v12, const float *gn, int k, float *o)
-{
-    float ga[3], gb[3];
-    cross3(v12, gn, ga);  // g_v10
-    cross3(gn, v10, gb);  // g_v12
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = k == 0 ? ga[c] : (k == 2 ? gb[c] : -(ga[c] + gb[c]));
-}
-
 // the gradient of corner k of face f's normal from grad_corner of image b: the front copy's minus the reversed copy's, which
 // carries the negated normal at corner 2 - k
-__device__ __forceinline__ void corner_grad(const NArgs &a, const float *__restrict__ gcb, int f, int k, float *g)
+__device__ __forceinline__ void corner_grad(const MeshArgs &a, const float *__restrict__ gcb, int f, int k, float *g)
 {
     const float *gf = gcb + (size_t)f * 9 + 3 * k;
     g[0] = gf[0];
@@ -116,7 +42,7 @@ __device__ __forceinline__ void corner_grad(const NArgs &a, const float *__restr
 // --------------------------------------------------------------------------------------------------------------------
 // forward
 
-__global__ __launch_bounds__(256) void k_vertex_normals(NArgs a, float *__restrict__ normals)
+__global__ __launch_bounds__(256) void k_vertex_normals(MeshArgs a, float *__restrict__ normals)
 {
     const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (v >= a.Nv) return;
@@ -129,7 +55,7 @@ __global__ __launch_bounds__(256) void k_vertex_normals(NArgs a, float *__restri
     o[2] = n[2];
 }
 
-__global__ __launch_bounds__(256) void k_face_normals(NArgs a, float *__restrict__ normals)
+__global__ __launch_bounds__(256) void k_face_normals(MeshArgs a, float *__restrict__ normals)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (f >= a.Nf) return;
@@ -146,7 +72,7 @@ __global__ __launch_bounds__(256) void k_face_normals(NArgs a, float *__restrict
 
 // vn: the vertex normals [B, Nv, 3] of k_vertex_normals (SMOOTH)
 template <bool SMOOTH>
-__global__ __launch_bounds__(256) void k_corner_normals(NArgs a, const float *__restrict__ vn, float *__restrict__ corner)
+__global__ __launch_bounds__(256) void k_corner_normals(MeshArgs a, const float *__restrict__ vn, float *__restrict__ corner)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (f >= a.Nf) return;
@@ -186,7 +112,7 @@ __global__ __launch_bounds__(256) void k_corner_normals(NArgs a, const float *__
 
 // g_m [B, Nv, 3]; g: grad_normals [B, Nv, 3], or (CORNER) grad_corner [B, F, 3, 3]
 template <bool CORNER>
-__global__ __launch_bounds__(256) void k_vertex_stage(NArgs a, const float *__restrict__ g, float *__restrict__ gm)
+__global__ __launch_bounds__(256) void k_vertex_stage(MeshArgs a, const float *__restrict__ g, float *__restrict__ gm)
 {
     const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (v >= a.Nv) return;
@@ -220,7 +146,7 @@ __global__ __launch_bounds__(256) void k_vertex_stage(NArgs a, const float *__re
 
 // g_N [B, Nf, 3]; g: grad_normals [B, Nf, 3], or (CORNER) grad_corner [B, F, 3, 3]: (g_0 + g_1) + g_2 over the corners
 template <bool CORNER>
-__global__ __launch_bounds__(256) void k_face_stage(NArgs a, const float *__restrict__ g, float *__restrict__ gN)
+__global__ __launch_bounds__(256) void k_face_stage(MeshArgs a, const float *__restrict__ g, float *__restrict__ gN)
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (f >= a.Nf) return;
@@ -250,80 +176,25 @@ __global__ __launch_bounds__(256) void k_face_stage(NArgs a, const float *__rest
     out[2] = o[2];
 }
 
-// grad_vertices[b, v] = the sum over the faces around v, in table order, of corner k's share of g_N(f); ws: g_N [B, Nf, 3], or
-// (SMOOTH) g_m [B, Nv, 3] with g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
-template <bool SMOOTH>
-__global__ __launch_bounds__(256) void k_normals_gather(NArgs a, const float *__restrict__ ws, float *__restrict__ grad_vertices)
-{
-    const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (v >= a.Nv) return;
-    float g[3] = {0.0f, 0.0f, 0.0f};
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    const float *wsb = ws + (size_t)b * (SMOOTH ? a.Nv : a.Nf) * 3;
-    for (int e = e0; e < e1; e++) {
-        const int fk = clampi(ent[e], 0, 3 * a.Nf - 1), f = fk / 3, k = fk - 3 * f;
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3], gn[3], o[3];
-        load_face(a, b, f, vi, w);
-        face_normal(w, v10, v12, n);
-#pragma unroll
-        for (int c = 0; c < 3; c++)
-            gn[c] = SMOOTH ? (wsb[(size_t)vi[0] * 3 + c] + wsb[(size_t)vi[1] * 3 + c]) + wsb[(size_t)vi[2] * 3 + c]
-                           : wsb[(size_t)f * 3 + c];
-        normal_to_corner(v10, v12, gn, k, o);
-        g[0] += o[0];
-        g[1] += o[1];
-        g[2] += o[2];
-    }
-    float *out = grad_vertices + ((size_t)b * a.Nv + v) * 3;
-    out[0] = g[0];
-    out[1] = g[1];
-    out[2] = g[2];
-}
-
 // --------------------------------------------------------------------------------------------------------------------
 // host
 
-bool sizes_ok(int B, int Nv, int Nf)
-{
-    if (B < 1 || B > 65535 || Nv < 1 || Nf < 1) return false;
-    return (size_t)B * (size_t)Nf <= 0x7fffffffull / 18 && (size_t)B * (size_t)Nv <= 0x7fffffffull / 6;
-}
-
-// every argument check the calls share, then the kernels' arguments
-int n_args(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets, const int32_t *adj_entries, int B, int Nv,
-           int Nf, int idx_per_batch, int fill_back, bool need_adjacency, NArgs &a)
-{
-    if (!vertices || !faces_idx) return NR_E_NULL;
-    if (need_adjacency && (!adj_offsets || !adj_entries)) return NR_E_NULL;
-    if (!sizes_ok(B, Nv, Nf)) return NR_E_SIZE;
-    a = {};
-    a.vertices = vertices; a.idx = faces_idx; a.adj_off = adj_offsets; a.adj_ent = adj_entries;
-    a.B = B; a.Nv = Nv; a.Nf = Nf;
-    a.idx_per_batch = idx_per_batch != 0;
-    a.fill_back = fill_back != 0;
-    return 0;
-}
-
 size_t n_workspace(int B, int Nv, int Nf) { return (size_t)B * (size_t)(Nv > Nf ? Nv : Nf) * 3 * sizeof(float); }
-
-dim3 grid_of(int n, int B) { return dim3((unsigned)((n + 255) / 256), (unsigned)B); }
 
 }  // namespace
 
 NR_API size_t nr_normals_workspace_bytes(int32_t B, int32_t Nv, int32_t Nf)
 {
-    return sizes_ok(B, Nv, Nf) ? n_workspace(B, Nv, Nf) : 0;
+    return mesh_sizes_ok(B, Nv, Nf) ? n_workspace(B, Nv, Nf) : 0;
 }
 
 NR_API int nr_vertex_normals_forward(const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
                                      const int32_t *adj_entries, float *normals, int32_t B, int32_t Nv, int32_t Nf,
                                      int32_t idx_per_batch, void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!normals) return NR_E_NULL;
-    if (int e = n_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
     hipLaunchKernelGGL(k_vertex_normals, grid_of(Nv, B), dim3(256), 0, (hipStream_t)stream, a, normals);
     return launch_status();
 }
@@ -333,9 +204,9 @@ NR_API int nr_vertex_normals_backward(const float *vertices, const int32_t *face
                                       int32_t B, int32_t Nv, int32_t Nf, int32_t idx_per_batch, void *workspace,
                                       size_t workspace_bytes, void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!grad_normals || !grad_vertices) return NR_E_NULL;
-    if (int e = n_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
     if (!workspace || workspace_bytes < n_workspace(B, Nv, Nf)) return NR_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float *gm = (float *)workspace;
@@ -348,9 +219,9 @@ NR_API int nr_vertex_normals_backward(const float *vertices, const int32_t *face
 NR_API int nr_face_normals_forward(const float *vertices, const int32_t *faces_idx, float *normals, int32_t B, int32_t Nv,
                                    int32_t Nf, int32_t idx_per_batch, void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!normals) return NR_E_NULL;
-    if (int e = n_args(vertices, faces_idx, nullptr, nullptr, B, Nv, Nf, idx_per_batch, 0, false, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, nullptr, nullptr, B, Nv, Nf, idx_per_batch, 0, false, a)) return e;
     hipLaunchKernelGGL(k_face_normals, grid_of(Nf, B), dim3(256), 0, (hipStream_t)stream, a, normals);
     return launch_status();
 }
@@ -360,9 +231,9 @@ NR_API int nr_face_normals_backward(const float *vertices, const int32_t *faces_
                                     int32_t Nv, int32_t Nf, int32_t idx_per_batch, void *workspace, size_t workspace_bytes,
                                     void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!grad_normals || !grad_vertices) return NR_E_NULL;
-    if (int e = n_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, 0, true, a)) return e;
     if (!workspace || workspace_bytes < n_workspace(B, Nv, Nf)) return NR_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float *gN = (float *)workspace;
@@ -377,10 +248,10 @@ NR_API int nr_corner_normals_forward(const float *vertices, const int32_t *faces
                                      int32_t idx_per_batch, int32_t fill_back, int32_t smooth, void *workspace,
                                      size_t workspace_bytes, void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!corner) return NR_E_NULL;
     if (smooth != 0 && smooth != 1) return NR_E_MODE;
-    if (int e = n_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, smooth != 0, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, smooth != 0, a)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (!smooth) {
         hipLaunchKernelGGL(k_corner_normals<false>, grid_of(Nf, B), dim3(256), 0, st, a, nullptr, corner);
@@ -399,10 +270,10 @@ NR_API int nr_corner_normals_backward(const float *vertices, const int32_t *face
                                       int32_t Nv, int32_t Nf, int32_t idx_per_batch, int32_t fill_back, int32_t smooth,
                                       void *workspace, size_t workspace_bytes, void *stream)
 {
-    NArgs a;
+    MeshArgs a;
     if (!grad_corner || !grad_vertices) return NR_E_NULL;
     if (smooth != 0 && smooth != 1) return NR_E_MODE;
-    if (int e = n_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, true, a)) return e;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, true, a)) return e;
     if (!workspace || workspace_bytes < n_workspace(B, Nv, Nf)) return NR_E_WORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     float *ws = (float *)workspace;

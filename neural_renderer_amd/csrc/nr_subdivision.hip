@@ -45,8 +45,6 @@ namespace {
 constexpr int BLOCK = 256;
 constexpr int MAX_CHANNELS = 16;
 
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
 // Images per thread (a row's offsets, columns and weights are read once for that many images) and entries of a row whose
 // columns, weights and inputs are requested together: measured against their alternatives (LAB-NOTEBOOK "mesh subdivision").
 // A call of more than IMAGES images spans several groups on grid.y, the last one possibly partial

@@ -21,9 +21,10 @@
 //                           gradient of the vertex's normal sum, into the workspace
 //   k_vs_backward_shared<SMOOTH>  colours shared by the batch: a wave per vertex, the lanes take the images, double sums
 //                           combined in the fixed order of the butterfly
-//   k_vs_backward_normals   smooth 2: (image, vertex) -> grad_vertices from g_N(f) = g_m(v0) + g_m(v1) + g_m(v2)
-#include "nr_device.h"
-#include "nr_shade.h"
+//   k_normals_gather<true>  smooth 2 (nr_mesh_gather.h): (image, vertex) -> grad_vertices from g_N(f) = g_m(v0) + g_m(v1) + g_m(v2)
+// The mesh arguments and the geometry helpers (load_face, adjacency, face_normal, normal_sum, normal_to_corner) are
+// nr_mesh_gather.h's, shared with nr_normals.hip and nr_lights.hip.
+#include "nr_mesh_gather.h"
 
 using namespace nr;
 
@@ -167,75 +168,15 @@ __global__ __launch_bounds__(256) void k_corner_round(const double *__restrict__
 // --------------------------------------------------------------------------------------------------------------------
 // vertex shading
 
-struct VSArgs {
-    const float *vertices;     // [B, Nv, 3] world space
-    const int32_t *idx;        // [Bt, Nf, 3]
+struct VSArgs : MeshArgs {
     const float *colors;       // [Bc, Nv, 3]
-    const int32_t *adj_off;    // [Bt, Nv + 1]
-    const int32_t *adj_ent;    // [Bt, 3 Nf]: 3 f + k, ascending within a vertex
-    int B, Nv, Nf;
-    int colors_shared, idx_per_batch, fill_back;
+    int colors_shared;
     FrontendParams P;          // the light (the camera fields stay 0)
 };
-
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
-
-// face f of image b: its vertex numbers (clamped for memory safety; the host validates them) and world-space vertices
-__device__ __forceinline__ void load_face(const VSArgs &a, int b, int f, int vi[3], float w[3][3])
-{
-    const int32_t *idx = a.idx + ((size_t)(a.idx_per_batch ? b : 0) * a.Nf + f) * 3;
-    const float *vb = a.vertices + (size_t)b * a.Nv * 3;
-#pragma unroll
-    for (int k = 0; k < 3; k++) {
-        vi[k] = clampi(idx[k], 0, a.Nv - 1);
-        const float *src = vb + (size_t)vi[k] * 3;
-        w[k][0] = src[0];
-        w[k][1] = src[1];
-        w[k][2] = src[2];
-    }
-}
 
 __device__ __forceinline__ const float *color_of(const VSArgs &a, int b, int v)
 {
     return a.colors + ((size_t)(a.colors_shared ? 0 : b) * a.Nv + v) * 3;
-}
-
-// the table entries of vertex v in image b: [e0, e1) into `ent`
-__device__ __forceinline__ const int32_t *adjacency(const VSArgs &a, int b, int v, int &e0, int &e1)
-{
-    const size_t t = a.idx_per_batch ? b : 0;
-    const int32_t *off = a.adj_off + t * ((size_t)a.Nv + 1);
-    e0 = clampi(off[v], 0, 3 * a.Nf);
-    e1 = clampi(off[v + 1], e0, 3 * a.Nf);
-    return a.adj_ent + t * 3 * (size_t)a.Nf;
-}
-
-// unnormalised face normal cross(v0 - v1, v2 - v1) (lighting.py:36-39), and the two edges
-__device__ __forceinline__ void face_normal(const float w[3][3], float *v10, float *v12, float *n)
-{
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-        v10[c] = w[0][c] - w[1][c];
-        v12[c] = w[2][c] - w[1][c];
-    }
-    cross3(v10, v12, n);
-}
-
-// m_v: the face normals around vertex v, summed in float32 in ascending (face, corner) order (area-weighted)
-__device__ __forceinline__ void normal_sum(const VSArgs &a, int b, int v, float *m)
-{
-    m[0] = m[1] = m[2] = 0.0f;
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    for (int e = e0; e < e1; e++) {
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3];
-        load_face(a, b, clampi(ent[e], 0, 3 * a.Nf - 1) / 3, vi, w);
-        face_normal(w, v10, v12, n);
-        m[0] += n[0];
-        m[1] += n[1];
-        m[2] += n[2];
-    }
 }
 
 // face_light's arithmetic on a vertex's normal sum m: the colours seen by the faces and by their reversed copies
@@ -268,16 +209,6 @@ __device__ __forceinline__ float light_dot_bwd(const FrontendParams &P, float do
     if (dotn > 0.0f) gdot += gcf;
     if (-dotn > 0.0f) gdot -= gcb;
     return gdot;
-}
-
-// gradient of corner k of a face from the gradient gn of its unnormalised normal n = v10 x v12
-__device__ __forceinline__ void normal_to_corner(const float *v10, const float *v12, const float *gn, int k, float *o)
-{
-    float ga[3], gb[3];
-    cross3(v12, gn, ga);  // g_v10
-    cross3(gn, v10, gb);  // g_v12
-#pragma unroll
-    for (int c = 0; c < 3; c++) o[c] = k == 0 ? ga[c] : (k == 2 ? gb[c] : -(ga[c] + gb[c]));
 }
 
 __global__ __launch_bounds__(256) void k_vertex_light(VSArgs a, float *__restrict__ vlight)
@@ -456,51 +387,18 @@ __global__ __launch_bounds__(256) void k_vs_backward_shared(VSArgs a, const floa
     }
 }
 
-// smooth, second gather: grad_vertices[b, v] = sum over the faces around v of corner k's share of g_N(f), with
-// g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)  (every face around a vertex takes part in the normal sums of its three vertices)
-__global__ __launch_bounds__(256) void k_vs_backward_normals(VSArgs a, const float *__restrict__ gm, float *__restrict__ grad_vertices)
-{
-    const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
-    if (v >= a.Nv) return;
-    float g[3] = {0.0f, 0.0f, 0.0f};
-    int e0, e1;
-    const int32_t *ent = adjacency(a, b, v, e0, e1);
-    const float *gmb = gm + (size_t)b * a.Nv * 3;
-    for (int e = e0; e < e1; e++) {
-        const int fk = clampi(ent[e], 0, 3 * a.Nf - 1), f = fk / 3, k = fk - 3 * f;
-        int vi[3];
-        float w[3][3], v10[3], v12[3], n[3], gn[3], o[3];
-        load_face(a, b, f, vi, w);
-        face_normal(w, v10, v12, n);
-#pragma unroll
-        for (int c = 0; c < 3; c++) gn[c] = (gmb[(size_t)vi[0] * 3 + c] + gmb[(size_t)vi[1] * 3 + c]) + gmb[(size_t)vi[2] * 3 + c];
-        normal_to_corner(v10, v12, gn, k, o);
-        g[0] += o[0];
-        g[1] += o[1];
-        g[2] += o[2];
-    }
-    float *out = grad_vertices + ((size_t)b * a.Nv + v) * 3;
-    out[0] = g[0];
-    out[1] = g[1];
-    out[2] = g[2];
-}
-
 // every argument check of the two vertex-shading calls, then the kernels' arguments
 int vs_args(const float *vertices, const int32_t *faces_idx, const float *colors, const int32_t *adj_offsets,
             const int32_t *adj_entries, int B, int Nv, int Nf, int color_batch, int idx_per_batch, int fill_back,
             const nr_light *light, bool need_adjacency, VSArgs &a)
 {
-    if (!vertices || !faces_idx || !colors || !light) return NR_E_NULL;
-    if (need_adjacency && (!adj_offsets || !adj_entries)) return NR_E_NULL;
-    if (B < 1 || B > 65535 || Nv < 1 || Nf < 1) return NR_E_SIZE;
-    if ((size_t)B * (size_t)Nf > 0x7fffffffull / 18 || (size_t)B * (size_t)Nv > 0x7fffffffull / 6) return NR_E_SIZE;
-    if (color_batch != 1 && color_batch != B) return NR_E_SIZE;
+    if (!colors || !light) return NR_E_NULL;
     a = {};
-    a.vertices = vertices; a.idx = faces_idx; a.colors = colors; a.adj_off = adj_offsets; a.adj_ent = adj_entries;
-    a.B = B; a.Nv = Nv; a.Nf = Nf;
+    if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, Nf, idx_per_batch, fill_back, need_adjacency, a))
+        return e;
+    if (color_batch != 1 && color_batch != B) return NR_E_SIZE;
+    a.colors = colors;
     a.colors_shared = (color_batch == 1 && B > 1) ? 1 : 0;
-    a.idx_per_batch = idx_per_batch != 0;
-    a.fill_back = fill_back != 0;
     a.P.fill_back = a.fill_back;
     a.P.ia = light->intensity_ambient;
     a.P.id = light->intensity_directional;
@@ -514,8 +412,6 @@ int vs_args(const float *vertices, const int32_t *faces_idx, const float *colors
 }
 
 size_t vs_workspace(int B, int Nv) { return (size_t)B * Nv * 6 * sizeof(float); }
-
-dim3 grid_of(int n, int B) { return dim3((unsigned)((n + 255) / 256), (unsigned)B); }
 
 }  // namespace
 
@@ -610,6 +506,6 @@ NR_API int nr_vertex_shade_backward(const float *vertices, const int32_t *faces_
     hipLaunchKernelGGL(k_vs_backward<true>, grid_of(Nv, B), dim3(256), 0, st, a, grad_corner, per_image_colors, gm);
     if (int rc = launch_status()) return rc;
     if (!grad_vertices) return 0;
-    hipLaunchKernelGGL(k_vs_backward_normals, grid_of(Nv, B), dim3(256), 0, st, a, gm, grad_vertices);
+    hipLaunchKernelGGL(k_normals_gather<true>, grid_of(Nv, B), dim3(256), 0, st, (const MeshArgs &)a, gm, grad_vertices);
     return launch_status();
 }

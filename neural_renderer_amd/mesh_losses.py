@@ -83,32 +83,17 @@ def build_tables(faces_idx, num_vertices):
 def _tables(faces, num_vertices):
     """-> MeshTables on faces' device, cached on the index tensor (and for a view on the tensor it is a view of) under its
     identity: data_ptr, shape, strides, version counter and the vertex count."""
-    stamp = (faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), faces._version, int(num_vertices), str(faces.device))
-    holders = [faces] + ([faces._base] if faces._base is not None else [])
-    for h in holders:
-        hit = getattr(h, _TABLES_ATTR, {}).get(stamp)
-        if hit is not None:
-            return hit
-    if faces.is_cuda and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('the mesh loss tables of this index tensor are not built yet, and building them reads the '
-                           'indices on the host: call laplacian_loss / flatness_loss once with it before the capture')
-    host = faces.detach().cpu().numpy()
-    if host.ndim == 3:
-        if not (host == host[0:1]).all():
-            raise ValueError('mesh losses: the faces of all images must be equal (one topology per call)')
-        host = host[0]
-    dev = faces.device
-    hit = MeshTables(*(torch.from_numpy(a).to(dev) for a in build_tables(host, num_vertices)))
-    for h in holders:
-        try:
-            table = getattr(h, _TABLES_ATTR, None)
-            if table is None or len(table) > 8:
-                table = {}
-                setattr(h, _TABLES_ATTR, table)
-            table[stamp] = hit
-        except Exception:  # (a tensor subclass without __dict__: built every time)
-            pass
-    return hit
+    def build():
+        host = faces.detach().cpu().numpy()
+        if host.ndim == 3:
+            if not (host == host[0:1]).all():
+                raise ValueError('mesh losses: the faces of all images must be equal (one topology per call)')
+            host = host[0]
+        return MeshTables(*(torch.from_numpy(a).to(faces.device) for a in build_tables(host, num_vertices)))
+
+    return _util.cached_on_index(faces, _TABLES_ATTR, (int(num_vertices),), build,
+                                 'the mesh loss tables of this index tensor are not built yet, and building them reads the '
+                                 'indices on the host: call laplacian_loss / flatness_loss once with it before the capture')
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -265,39 +265,26 @@ def subdivision(faces, num_vertices, levels=1, scheme='loop'):
     if F * 4 ** levels > _INT32_MAX:
         raise ValueError('subdivision: %d faces after %d levels do not fit in int32' % (F * 4 ** levels, levels))
     _util.check_face_indices(faces, Nv)   # (the vertex and entry counts of every level: build_level, ahead of any launch)
-    stamp = (faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), faces._version, str(faces.device), Nv, levels, scheme)
-    holders = [faces] + ([faces._base] if faces._base is not None else [])
-    for h in holders:
-        hit = getattr(h, _PLANS_ATTR, {}).get(stamp)
-        if hit is not None:
-            return hit
-    if faces.is_cuda and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('the subdivision plan of this index tensor is not built yet, and building it reads the indices on '
-                           'the host: call subdivision / subdivide once with it before the capture')
-    host = faces.detach().cpu().numpy()
-    if host.ndim == 3:
-        if not (host == host[0:1]).all():
-            raise ValueError('subdivision: the faces of all images must be equal (one topology per call)')
-        host = host[0]
-    dev = faces.device
-    f, nv, tables = host, Nv, []
-    for _ in range(levels):
-        f, nv_out, table = build_level(f, nv, scheme)
-        tables.append(_Level(table, nv, dev))
-        nv = nv_out
-    out_faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(dev)
-    parent = torch.arange(out_faces.shape[0], dtype=torch.int64, device=dev) // (4 ** levels)
-    hit = Subdivision(out_faces, parent, Nv, nv, levels, scheme, tables)
-    for h in holders:
-        try:
-            plans = getattr(h, _PLANS_ATTR, None)
-            if plans is None or len(plans) > 8:
-                plans = {}
-                setattr(h, _PLANS_ATTR, plans)
-            plans[stamp] = hit
-        except Exception:  # (a tensor subclass without __dict__: built every time)
-            pass
-    return hit
+
+    def build():
+        host = faces.detach().cpu().numpy()
+        if host.ndim == 3:
+            if not (host == host[0:1]).all():
+                raise ValueError('subdivision: the faces of all images must be equal (one topology per call)')
+            host = host[0]
+        dev = faces.device
+        f, nv, tables = host, Nv, []
+        for _ in range(levels):
+            f, nv_out, table = build_level(f, nv, scheme)
+            tables.append(_Level(table, nv, dev))
+            nv = nv_out
+        out_faces = torch.from_numpy(np.ascontiguousarray(f.astype(np.int32))).to(dev)
+        parent = torch.arange(out_faces.shape[0], dtype=torch.int64, device=dev) // (4 ** levels)
+        return Subdivision(out_faces, parent, Nv, nv, levels, scheme, tables)
+
+    return _util.cached_on_index(faces, _PLANS_ATTR, (Nv, levels, scheme), build,
+                                 'the subdivision plan of this index tensor is not built yet, and building it reads the indices '
+                                 'on the host: call subdivision / subdivide once with it before the capture')
 
 
 def subdivide(vertices, faces, levels=1, scheme='loop', implementation=None):

@@ -90,34 +90,20 @@ def build_adjacency(faces_idx, num_vertices):
 def _adjacency(faces, num_vertices):
     """-> (indices int32 [T,Nf,3], offsets, entries, per_batch) on faces' device, cached on the index tensor (and for a view
     on the tensor it is a view of) under its identity: data_ptr, shape, strides, version counter and the vertex count."""
-    stamp = (faces.data_ptr(), tuple(faces.shape), tuple(faces.stride()), faces._version, int(num_vertices), str(faces.device))
-    holders = [faces] + ([faces._base] if faces._base is not None else [])
-    for h in holders:
-        hit = getattr(h, _ADJ_ATTR, {}).get(stamp)
-        if hit is not None:
-            return hit
-    if faces.is_cuda and torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('the vertex adjacency table of this index tensor is not built yet, and building it reads the '
+    def build():
+        host = faces.detach().cpu().numpy()
+        if host.ndim == 2:
+            host = host[None]
+        if host.shape[0] > 1 and (host == host[0:1]).all():
+            host = host[0:1]  # one topology for the whole batch
+        offsets, entries = build_adjacency(host, num_vertices)
+        dev = faces.device
+        return (torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev), torch.from_numpy(offsets).to(dev),
+                torch.from_numpy(entries).to(dev), host.shape[0] > 1)
+
+    return _util.cached_on_index(faces, _ADJ_ATTR, (int(num_vertices),), build,
+                           'the vertex adjacency table of this index tensor is not built yet, and building it reads the '
                            'indices on the host: call vertex_shade / Renderer.render once with it before the capture')
-    host = faces.detach().cpu().numpy()
-    if host.ndim == 2:
-        host = host[None]
-    if host.shape[0] > 1 and (host == host[0:1]).all():
-        host = host[0:1]  # one topology for the whole batch
-    offsets, entries = build_adjacency(host, num_vertices)
-    dev = faces.device
-    hit = (torch.from_numpy(np.ascontiguousarray(host.astype(np.int32))).to(dev), torch.from_numpy(offsets).to(dev),
-           torch.from_numpy(entries).to(dev), host.shape[0] > 1)
-    for h in holders:
-        try:
-            table = getattr(h, _ADJ_ATTR, None)
-            if table is None or len(table) > 8:
-                table = {}
-                setattr(h, _ADJ_ATTR, table)
-            table[stamp] = hit
-        except Exception:  # (a tensor subclass without __dict__: built every time)
-            pass
-    return hit
 
 
 # ---------------------------------------------------------------------------------------------------------------------

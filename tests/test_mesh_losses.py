@@ -90,6 +90,38 @@ def test_table_cache():
     assert ML._tables(faces[None].expand(3, -1, -1), 42) is not exp
 
 
+def _adjacency_tensors(hit):
+    return hit[:3]
+
+
+def _plan_tensors(plan):
+    return [plan.faces] + [t for level in plan._levels for t in (level.forward.offsets, level.forward.cols, level.forward.weights)]
+
+
+@pytest.mark.parametrize('which', ['adjacency', 'subdivision'])
+def test_table_cache_of_the_other_index_tables(which):
+    """test_table_cache's assertions on the other users of _util.cached_on_index"""
+    import neural_renderer_amd as nr
+    from neural_renderer_amd import vertex_colors as VC
+    get, tensors = {'adjacency': (VC._adjacency, _adjacency_tensors), 'subdivision': (nr.subdivision, _plan_tensors)}[which]
+    _, f = R.inputs('ico1')
+    faces = torch.tensor(f)
+    t = get(faces, 42)
+    assert get(faces, 42) is t                                        # a second call
+    assert get(faces, 43) is not t                                    # another vertex count
+    view = get(faces[None], 42)
+    assert get(faces[None], 42) is view                               # a view built anew: found on the tensor it views
+    exp = get(faces[None].expand(3, -1, -1), 42)
+    assert get(faces[None].expand(3, -1, -1), 42) is exp              # .expand
+    for other in (view, exp):
+        assert all(torch.equal(a.reshape(-1), b.reshape(-1)) for a, b in zip(tensors(other), tensors(t)))
+    if which == 'subdivision':
+        assert get(faces, 42, levels=2) is not t and get(faces, 42, scheme='midpoint') is not t   # the rest of its key
+    faces[0, 0] = faces[0, 0]                                         # an in-place edit: the version counter moves
+    assert get(faces, 42) is not t
+    assert get(faces[None].expand(3, -1, -1), 42) is not exp
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the torch paths against the restatement
 
