@@ -87,7 +87,8 @@ extern "C" {
                           *        nr_stencil_apply;
                           *        nr_vertex_normals_forward, nr_vertex_normals_backward, nr_face_normals_forward,
                           *        nr_face_normals_backward, nr_corner_normals_forward, nr_corner_normals_backward,
-                          *        nr_normals_workspace_bytes);
+                          *        nr_normals_workspace_bytes;
+                          *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -784,6 +785,44 @@ int nr_corner_normals_backward(const float *vertices, const int32_t *faces_idx, 
                                const int32_t *adj_entries, const float *grad_corner, float *grad_vertices, int32_t batch_size,
                                int32_t num_vertices, int32_t num_faces, int32_t idx_per_batch, int32_t fill_back,
                                int32_t smooth, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Soft silhouettes (not in the reference): a probabilistic silhouette of the Soft Rasterizer family, with the exact
+ * gradient of its definition.  faces [B, F, 3, 3] as for the rasterizer (x, y in NDC with y up, z the positive camera depth),
+ * WITHOUT fill_back copies (a duplicated face would count twice); alpha, transmittance, grad_alpha [B, S, S] with row 0 the
+ * BOTTOM row, pixel centres (2 i + 1 - S) / S; no anti-aliasing.  All float32.
+ *   A face contributes iff its nine coordinates are finite and near <= z_k <= far at its three vertices; any other face is
+ *   absent from every product and has a zero gradient.  Orientation plays no role.
+ *   Per contributing face f and pixel p, with the segments 0, 1, 2 = v0v1, v1v2, v2v0: c_k the nearest point of segment k to
+ *   p (parameter clamped to [0, 1]; a zero-length segment gives its endpoint), d2 = min_k |p - c_k|^2 (the lowest k on a tie);
+ *   s = +1 if the three edge functions of p are all > 0 or all < 0, else -1 (a zero-area face has no inside);
+ *   x = s d2 / sigma, D = 1 / (1 + e^-x).
+ *   Q_p = the product over f, ascending, of 1 - D_pf evaluated as 1 / (1 + e^x); alpha_p = 1 - Q_p; transmittance = Q.
+ *   Backward, with G_p = grad_alpha_p Q_p: dL/dx_pf = G_p D_pf (no division by 1 - D).  For the chosen segment a -> b with
+ *   nearest point c = a + t (b - a) and r = p - c: d d2 / da = -2 (1 - t) r, d d2 / db = -2 t r (a clamped t hands the whole
+ *   of -2 r to that endpoint), times s / sigma, summed over the pixels.  The third vertex and every z receive 0.
+ *   A (pixel, face) pair is taken iff the pixel lies in the face's box: the pixel range of the triangle's bounding box grown
+ *   by sqrt(17 sigma).  A pair outside it is outside the triangle with d2 > 17 sigma, D < 2^-24, and is left out of the
+ *   product and of the gradient.
+ * Coordinates: results are finite for |x|, |y| up to about 1e18; beyond that the squares of the edge lengths overflow in
+ * float32 and alpha, transmittance and grad_faces of the pixels and faces concerned may be NaN (no index depends on them:
+ * the boxes are clamped before the conversion to int).
+ * sigma: 1e-30 <= sigma <= 1e30 (NR_E_MODE otherwise, as for a NaN near or far), no gradient.  Sizes: 1 <= batch_size <= 65535,
+ * 1 <= image_size <= 16384, 1 <= num_faces <= 2^24 and batch_size * num_faces * 9 < 2^31 (NR_E_SIZE otherwise).
+ * The forward stores alpha and transmittance; the backward takes the forward's transmittance (not 1 - alpha) and stores
+ * every entry of grad_faces [B, F, 3, 3].  Both need a workspace of nr_soft_silhouette_workspace_bytes (0 for sizes out of
+ * range), in which each writes a record per face first; nothing is kept in it between calls.  No atomics: the same bits in
+ * every run and for an image alone or inside a batch.  No call synchronises the host; NR_E_* before any launch.
+ */
+size_t nr_soft_silhouette_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t image_size);
+
+int nr_soft_silhouette_forward(const float *faces, float *alpha, float *transmittance, int32_t batch_size, int32_t num_faces,
+                               int32_t image_size, double sigma, double near, double far, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+int nr_soft_silhouette_backward(const float *faces, const float *transmittance, const float *grad_alpha, float *grad_faces,
+                                int32_t batch_size, int32_t num_faces, int32_t image_size, double sigma, double near, double far,
+                                void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

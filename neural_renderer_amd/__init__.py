@@ -39,6 +39,9 @@ from .point_losses import SurfaceSamples, chamfer_distance, nearest_points, samp
 # not in the reference: vertex, face and corner normals -- HIP in both directions -- for Renderer.render_normals, and the
 # rotation of a renderer's camera
 from .normals import camera_rotation, corner_normals, face_normals, vertex_normals
+# not in the reference: soft silhouettes -- distance-based coverage with its exact gradient, HIP in both directions -- for
+# Renderer.render_soft_silhouettes
+from .soft_silhouette import soft_silhouettes, soft_silhouettes_torch
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -60,4 +63,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
-           'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation']
+           'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation',
+           'soft_silhouettes', 'soft_silhouettes_torch']

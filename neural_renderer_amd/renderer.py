@@ -19,6 +19,7 @@ from .normals import camera_rotation, corner_normals
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
+from .soft_silhouette import soft_silhouettes
 from .uv_textures import UVImages
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
 from .vertices_to_faces import vertices_to_faces
@@ -98,6 +99,8 @@ class Renderer(object):
         # exactly as without the attribute.  With a Lights render() ignores `light_*` and takes its light from light_colors
         # (see _render_lights); render_silhouettes and render_depth ignore the attribute.
         self.lights = None
+        # not in the reference: the sigma of render_soft_silhouettes (soft_silhouette.py), in squared NDC units
+        self.soft_sigma = 1e-4
 
     def _project(self, vertices, faces):
         """camera + perspective + gather (renderer.py:40-51, :60-71, :92-103)."""
@@ -159,6 +162,15 @@ class Renderer(object):
     def render_depth(self, vertices, faces):
         faces, _ = self._frontend(vertices, faces)
         return rasterize_depth(faces, self.image_size, self.anti_aliasing, graph_replay=self.graph_replay)  # renderer.py:72 (Q2)
+
+    def render_soft_silhouettes(self, vertices, faces, sigma=None):
+        """Not in the reference: the soft silhouette [B,S,S] of soft_silhouette.py, whose exact gradient reaches a face from
+        pixels it does not cover.  `sigma` (None: `soft_sigma`) sets the width of the transition.  The geometry is the
+        front-end's, without the fill_back copies (a duplicated face would count twice; orientation plays no role); `near`
+        and `far` select the faces; `anti_aliasing`, the lights and `shading` are ignored."""
+        nf = faces.shape[1]
+        faces, _ = self._frontend(vertices, faces)
+        return soft_silhouettes(faces[:, :nf], self.image_size, self.soft_sigma if sigma is None else sigma, self.near, self.far)
 
     def _use_face_light(self, vertices, faces, textures):
         if self.face_light is False or not (torch.is_tensor(textures) and textures.dim() == 6):
