@@ -88,7 +88,8 @@ extern "C" {
                           *        nr_vertex_normals_forward, nr_vertex_normals_backward, nr_face_normals_forward,
                           *        nr_face_normals_backward, nr_corner_normals_forward, nr_corner_normals_backward,
                           *        nr_normals_workspace_bytes;
-                          *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes);
+                          *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes;
+                          *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -823,6 +824,49 @@ int nr_soft_silhouette_forward(const float *faces, float *alpha, float *transmit
 int nr_soft_silhouette_backward(const float *faces, const float *transmittance, const float *grad_alpha, float *grad_faces,
                                 int32_t batch_size, int32_t num_faces, int32_t image_size, double sigma, double near, double far,
                                 void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Soft colour rendering (not in the reference): the soft silhouette's coverage aggregated over the faces by Soft Rasterizer's
+ * depth-weighted softmax, with the exact gradient of its definition to x, y, z and the face colours.  faces [B, F, 3, 3] as
+ * for nr_soft_silhouette_forward; colors [B, F, 3] (colors_per_batch = 1) or [F, 3] shared by the batch and read in place
+ * (colors_per_batch = 0), one RGB colour per face; rgba, grad_rgba [B, 4, S, S], transmittance [B, S, S] and normaliser
+ * [B, 2, S, S] (m, then Z) with row 0 the BOTTOM row, pixel centres (2 i + 1 - S) / S; no anti-aliasing.  All float32.
+ *   A face contributes iff its nine coordinates are finite, near <= z_k <= far at its three vertices and its doubled area
+ *   (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0), evaluated in double, is not 0 (a zero-area face has no plane to take a depth from).
+ *   Per contributing face f and pixel p: d2, the chosen segment k (the lowest on a tie), its clamped t, r = p - c, the side s,
+ *   x = s d2 / sigma and D = 1 / (1 + e^-x), 1 - D = 1 / (1 + e^x) as for the soft silhouette; c_0, c_1, c_2 the edge
+ *   functions of the segments v0v1, v1v2, v2v0 at p.  The pair is TAKEN iff s = +1 or d2 <= 17 sigma: part of the definition.
+ *   Inverse depth: inside, A = c_0 + c_1 + c_2, lambda_0 = c_1 / A, lambda_1 = c_2 / A, lambda_2 = c_0 / A; outside, at the
+ *   nearest point of the chosen segment a -> b, lambda_a = 1 - t, lambda_b = t, the third 0;
+ *   iz = lambda_0 / z0 + lambda_1 / z1 + lambda_2 / z2 (continuous across every edge), zp = 1 / iz,
+ *   zn = (far - zp) / (far - near).
+ *   Over the taken pairs of p in ascending f, with m = max(eps, max_f zn_f): w_f = D_f exp((zn_f - m) / gamma),
+ *   w_b = exp((eps - m) / gamma), Z = w_b + sum w_f, rgb = (w_b background + sum w_f C_f) / Z, Q = prod 1 / (1 + e^x_f),
+ *   alpha = 1 - Q; transmittance = Q, normaliser = (m, Z).
+ *   Backward, per taken pair, from the stored rgb, Q, m and Z: W = D exp((zn - m) / gamma) / Z, h = g_rgb . (C_f - rgb);
+ *   dL/dC_f += W g_rgb; dL/dx = h W (1 - D) + g_alpha Q D; dL/dzn = h W / gamma.  dx goes to the two ends of the chosen
+ *   segment as in nr_soft_silhouette_backward; dzn/dzp = -1 / (far - near), dzp/diz = -zp^2, diz/dz_k = -lambda_k / z_k^2;
+ *   diz reaches x and y through lambda (inside) or through t where 0 < t < 1 (outside; a clamped t has derivative 0).
+ * colors shared by the batch get their gradient [F, 3] as the sum over the images in ascending b, in double, rounded once.
+ * sigma and gamma in [1e-30, 1e30], far > near, near, far, eps and the background finite, colors_per_batch 0 or 1 (NR_E_MODE
+ * otherwise); no gradients for them.  Sizes as for nr_soft_silhouette_forward (NR_E_SIZE).  The forward stores every element of
+ * rgba, transmittance and normaliser; the backward takes them back and stores every entry of grad_faces [B, F, 3, 3] and of
+ * grad_colors ([B, F, 3] or [F, 3]).  Both need a workspace of nr_soft_render_workspace_bytes (0 for sizes out of range), in
+ * which each writes a record per face first; nothing is kept in it between calls.  No atomics: the same bits in every run
+ * and for an image alone or inside a batch.  No call synchronises the host; NR_E_* before any launch.
+ */
+size_t nr_soft_render_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t image_size);
+
+int nr_soft_render_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
+                           int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
+                           double gamma, double near, double far, double eps, double background_r, double background_g,
+                           double background_b, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_soft_render_backward(const float *faces, const float *colors, const float *rgba, const float *transmittance,
+                            const float *normaliser, const float *grad_rgba, float *grad_faces, float *grad_colors,
+                            int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
+                            double gamma, double near, double far, double eps, double background_r, double background_g,
+                            double background_b, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

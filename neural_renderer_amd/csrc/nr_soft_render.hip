@@ -1,0 +1,437 @@
+// nr_soft_render.hip -- soft colour rendering: the soft silhouette's coverage, aggregated over the faces with a depth-weighted
+// softmax, and the exact gradient of that definition to x, y, z and the face colours (include/nr_hip.h; DESIGN "Soft colour
+// rendering").
+//
+// A face contributes iff its nine coordinates are finite, near <= z <= far at its three vertices and its doubled area
+// (x1 - x0)(y2 - y0) - (x2 - x0)(y1 - y0), taken in double, is not 0.  Per contributing face f and pixel p: d2, the chosen
+// segment k, its clamped t, r, the side s and x = s d2 / sigma are soft_pair's (nr_soft_pair.h); c_0, c_1, c_2 are the edge
+// functions of the segments v0v1, v1v2, v2v0 at p.  The pair is TAKEN iff s = +1 or d2 <= 17 sigma (the box of the record,
+// the bounding box grown by sqrt(17 sigma), is the coarse filter in front of this test).  Inverse depth at the pixel:
+//   inside   A = c_0 + c_1 + c_2, lambda_0 = c_1 / A, lambda_1 = c_2 / A, lambda_2 = c_0 / A
+//   outside  lambda = 1 - t at the first vertex of segment k, t at its second, 0 at the third
+//   iz = lambda_0 / z0 + lambda_1 / z1 + lambda_2 / z2,  zp = 1 / iz,  zn = (far - zp) / (far - near)
+// Over the taken pairs of p in ascending f, with m = max(eps, max_f zn_f), D = 1 / (1 + e^-x):
+//   w_f = D_f exp((zn_f - m) / gamma),  w_b = exp((eps - m) / gamma),  Z = w_b + sum w_f
+//   rgb = (w_b C_b + sum w_f C_f) / Z,  Q = prod 1 / (1 + e^x_f),  alpha = 1 - Q
+//   k_render_setup     (image, face) -> an 80-byte record: the silhouette record's 48 bytes (the flag with the area rule),
+//                      1 / z_k, the colour
+//   k_render_forward   a workgroup of four waves owns a 16 x 16 pixel tile, a lane a pixel; the records go through LDS in
+//                      chunks of 256 (20 KiB), the compact list ascending in f by ballot + prefix count, a wave-uniform trip
+//                      count.  TWO walks of the image's records: the first finds m, the second sums.  Stores rgba, Q, (m, Z).
+//   k_render_backward  a wave owns an (image, face): it walks the pixels of the box, lanes strided, recomputes the pair, sums
+//                      six xy, three z and three colour gradients per lane, reduces them in the fixed xor tree, one store
+//                      per entry.
+//   k_render_colors    shared colours: the B partial colour gradients added in ascending b in double.
+// No atomics, no host synchronisation, every output element stored; the same bits in every run and for an image alone or
+// inside a batch: a pixel's sums depend on the set of its taken pairs and their order in f alone.
+#include "nr_soft_pair.h"
+
+using namespace nr;
+
+namespace {
+
+constexpr int RENDER_TILE = 16;       // pixels per side of a workgroup's tile (a wave: 8 x 8)
+constexpr int RENDER_CHUNK = 256;     // face records per LDS chunk, one per thread
+constexpr int RENDER_REC = 5;         // float4 per record
+constexpr float RENDER_REACH = 17.0f;   // a pair outside is taken up to d2 = RENDER_REACH sigma
+constexpr int RENDER_MAX_F = 1 << 24;
+
+// what a record holds beyond the silhouette's: (1 / z0, 1 / z1, 1 / z2, red), (green, blue, 0, 0)
+struct FaceShade {
+    float iz0, iz1, iz2, cr, cg, cb;
+};
+
+__device__ __forceinline__ FaceShade unpack_shade(const float4 &d, const float4 &e)
+{
+    FaceShade r;
+    r.iz0 = d.x; r.iz1 = d.y; r.iz2 = d.z; r.cr = d.w;
+    r.cg = e.x; r.cb = e.y;
+    return r;
+}
+
+// the edge function of segment a -> b at p, in soft_segment's own operations
+__device__ __forceinline__ float edge_function(float px, float py, float ax, float ay, float bx, float by)
+{
+    const float ex = bx - ax, ey = by - ay, wx = px - ax, wy = py - ay;
+    return ex * wy - ey * wx;
+}
+
+// the depth of a pair: the weights lambda of the three vertices (perspective-correct barycentric inside, the nearest point's
+// outside), 1 / A, iz, zp and zn
+struct PairDepth {
+    float l0, l1, l2, rA, iz, zp, zn;
+    bool taken;
+};
+
+__device__ __forceinline__ PairDepth pair_depth(float px, float py, const SoftFace &f, const FaceShade &h, const SoftPair &p,
+                                                float cut, float far, float inv_range)
+{
+    PairDepth q;
+    const float c0 = edge_function(px, py, f.x0, f.y0, f.x1, f.y1);
+    const float c1 = edge_function(px, py, f.x1, f.y1, f.x2, f.y2);
+    const float c2 = edge_function(px, py, f.x2, f.y2, f.x0, f.y0);
+    q.rA = 1.0f / ((c0 + c1) + c2);   // (used inside only, where the three have one sign)
+    const float t1 = 1.0f - p.t;
+    const int k = p.k;
+    const float o0 = k == 0 ? t1 : (k == 2 ? p.t : 0.0f);
+    const float o1 = k == 1 ? t1 : (k == 0 ? p.t : 0.0f);
+    const float o2 = k == 2 ? t1 : (k == 1 ? p.t : 0.0f);
+    q.l0 = p.inside ? c1 * q.rA : o0;
+    q.l1 = p.inside ? c2 * q.rA : o1;
+    q.l2 = p.inside ? c0 * q.rA : o2;
+    q.iz = (q.l0 * h.iz0 + q.l1 * h.iz1) + q.l2 * h.iz2;
+    q.zp = 1.0f / q.iz;
+    q.zn = (far - q.zp) * inv_range;
+    q.taken = p.inside || (p.rx * p.rx + p.ry * p.ry) <= cut;   // (soft_segment's own d2)
+    return q;
+}
+
+struct RenderArgs {
+    float inv_sigma, inv_gamma, cut, far, inv_range, eps;
+    float bg_r, bg_g, bg_b;
+};
+
+// --------------------------------------------------------------------------------------------------------------------
+// set-up
+
+__global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ faces, const float *__restrict__ colors,
+                                                      float4 *__restrict__ rec, int F, int S, size_t color_stride, float reach,
+                                                      double near, double far)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (f >= F) return;
+    const float *v = faces + ((size_t)b * F + f) * 9;
+    const float *col = colors + (size_t)b * color_stride + (size_t)f * 3;
+    float c[9];
+#pragma unroll
+    for (int k = 0; k < 9; k++) c[k] = v[k];
+    bool on = true;
+#pragma unroll
+    for (int k = 0; k < 9; k++) on = on && (fabsf(c[k]) < __builtin_inff());   // false for a NaN too
+#pragma unroll
+    for (int k = 2; k < 9; k += 3) on = on && (double)c[k] >= near && (double)c[k] <= far;
+    // the doubled area in double: the differences and products of floats are exact there, one rounding in the subtraction
+    const double area = ((double)c[3] - (double)c[0]) * ((double)c[7] - (double)c[1]) -
+                        ((double)c[6] - (double)c[0]) * ((double)c[4] - (double)c[1]);
+    on = on && area != 0.0;
+    int ix_lo = S, iy_lo = S, ix_hi = -1, iy_hi = -1;   // empty
+    if (on) {
+        const float fs = (float)S;
+        const float xmin = fminf(fminf(c[0], c[3]), c[6]) - reach, xmax = fmaxf(fmaxf(c[0], c[3]), c[6]) + reach;
+        const float ymin = fminf(fminf(c[1], c[4]), c[7]) - reach, ymax = fmaxf(fmaxf(c[1], c[4]), c[7]) + reach;
+        // as k_soft_setup: floor below and ceil above keep up to a pixel more than needed; clamped before the conversion
+        const float lo_c = -1.0f, hi_c = fs;
+        ix_lo = max((int)floorf(fminf(fmaxf(to_pixel(xmin, fs), lo_c), hi_c)), 0);
+        ix_hi = min((int)ceilf(fminf(fmaxf(to_pixel(xmax, fs), lo_c), hi_c)), S - 1);
+        iy_lo = max((int)floorf(fminf(fmaxf(to_pixel(ymin, fs), lo_c), hi_c)), 0);
+        iy_hi = min((int)ceilf(fminf(fmaxf(to_pixel(ymax, fs), lo_c), hi_c)), S - 1);
+        if (ix_lo > ix_hi || iy_lo > iy_hi) { ix_lo = iy_lo = S; ix_hi = iy_hi = -1; }
+    }
+    float4 *o = rec + ((size_t)b * F + f) * RENDER_REC;
+    o[0] = make_float4(c[0], c[1], c[3], c[4]);
+    o[1] = make_float4(c[6], c[7], __int_as_float(ix_lo), __int_as_float(iy_lo));
+    o[2] = make_float4(__int_as_float(ix_hi), __int_as_float(iy_hi), __int_as_float(on ? 1 : 0), 0.0f);
+    o[3] = make_float4(1.0f / c[2], 1.0f / c[5], 1.0f / c[8], col[0]);
+    o[4] = make_float4(col[1], col[2], 0.0f, 0.0f);
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// forward
+
+// one chunk of records into the compact LDS list of those whose box meets the tile, ascending in f -> their number
+__device__ __forceinline__ int filter_chunk(const float4 *__restrict__ rb, int c0, int F, int tid, int wave, int lane, int tx0,
+                                            int ty0, int tx1, int ty1, float4 *list, int *wave_count)
+{
+    const int f = c0 + tid;
+    float4 r0, r1, r2, r3, r4;
+    bool hit = false;
+    if (f < F) {
+        const float4 *src = rb + (size_t)f * RENDER_REC;
+        r0 = src[0]; r1 = src[1]; r2 = src[2]; r3 = src[3]; r4 = src[4];
+        const SoftFace s = unpack(r0, r1, r2);
+        hit = s.on != 0 && s.ix_lo <= tx1 && s.ix_hi >= tx0 && s.iy_lo <= ty1 && s.iy_hi >= ty0;
+    }
+    const unsigned long long m = __ballot(hit);
+    const int before = __popcll(m & ((1ull << lane) - 1ull));
+    if (lane == 0) wave_count[wave] = __popcll(m);
+    __syncthreads();
+    int base = 0, n = 0;
+#pragma unroll
+    for (int w = 0; w < 4; w++) {
+        const int cnt = wave_count[w];
+        base += w < wave ? cnt : 0;
+        n += cnt;
+    }
+    if (hit) {   // thread order is face order: the list stays ascending in f
+        const int at = (base + before) * RENDER_REC;   // < RENDER_CHUNK * RENDER_REC: at most one entry per thread
+        list[at] = r0; list[at + 1] = r1; list[at + 2] = r2; list[at + 3] = r3; list[at + 4] = r4;
+    }
+    __syncthreads();
+    return rfl(n);
+}
+
+__global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict__ rec, float *__restrict__ rgba,
+                                                        float *__restrict__ trans, float *__restrict__ norm, int F, int S,
+                                                        int tiles_x, RenderArgs a)
+{
+    __shared__ float4 list[RENDER_CHUNK * RENDER_REC];
+    __shared__ int wave_count[4];
+    const int b = blockIdx.y, tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int tx0 = tile_x * RENDER_TILE, ty0 = tile_y * RENDER_TILE;
+    const int tx1 = min(tx0 + RENDER_TILE - 1, S - 1), ty1 = min(ty0 + RENDER_TILE - 1, S - 1);
+    const int xi = tx0 + (wave & 1) * 8 + (lane & 7), yi = ty0 + (wave >> 1) * 8 + (lane >> 3);
+    const float px = pixel_center(min(xi, S - 1), S), py = pixel_center(min(yi, S - 1), S);
+    const float4 *rb = rec + (size_t)b * F * RENDER_REC;
+    // the first walk: m = max(eps, the zn of the taken pairs) -- a maximum of the very floats the second walk subtracts it from
+    float m = a.eps;
+    for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
+        const int n = filter_chunk(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+        for (int j = 0; j < n; j++) {
+            const float4 *l = list + j * RENDER_REC;
+            const SoftFace s = unpack(l[0], l[1], l[2]);
+            const FaceShade h = unpack_shade(l[3], l[4]);
+            const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
+            const PairDepth q = pair_depth(px, py, s, h, p, a.cut, a.far, a.inv_range);
+            m = (q.taken && in_box(s, xi, yi)) ? fmaxf(m, q.zn) : m;
+        }
+        __syncthreads();   // the list and the counts are rewritten by the next chunk
+    }
+    // the second walk
+    const float wb = expf((a.eps - m) * a.inv_gamma);
+    float Z = wb, cr = wb * a.bg_r, cg = wb * a.bg_g, cb = wb * a.bg_b, Q = 1.0f;
+    for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
+        const int n = filter_chunk(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+        for (int j = 0; j < n; j++) {
+            const float4 *l = list + j * RENDER_REC;
+            const SoftFace s = unpack(l[0], l[1], l[2]);
+            const FaceShade h = unpack_shade(l[3], l[4]);
+            const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
+            const PairDepth q = pair_depth(px, py, s, h, p, a.cut, a.far, a.inv_range);
+            const bool take = q.taken && in_box(s, xi, yi);
+            const float D = 1.0f / (1.0f + expf(-p.x));
+            const float w = D * expf((q.zn - m) * a.inv_gamma);
+            const float q1 = Q * (1.0f / (1.0f + expf(p.x)));   // 1 - D as 1 / (1 + e^x), never as a subtraction
+            Z = take ? Z + w : Z;
+            cr = take ? cr + w * h.cr : cr;
+            cg = take ? cg + w * h.cg : cg;
+            cb = take ? cb + w * h.cb : cb;
+            Q = take ? q1 : Q;
+        }
+        __syncthreads();
+    }
+    if (xi < S && yi < S) {
+        const size_t SS = (size_t)S * S, o = (size_t)yi * S + xi;
+        float *img = rgba + (size_t)b * 4 * SS;
+        img[o] = cr / Z;
+        img[SS + o] = cg / Z;
+        img[2 * SS + o] = cb / Z;
+        img[3 * SS + o] = 1.0f - Q;
+        trans[(size_t)b * SS + o] = Q;
+        norm[(size_t)b * 2 * SS + o] = m;
+        norm[(size_t)b * 2 * SS + SS + o] = Z;
+    }
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// backward
+
+__global__ __launch_bounds__(256) void k_render_backward(const float4 *__restrict__ rec, const float *__restrict__ rgba,
+                                                         const float *__restrict__ trans, const float *__restrict__ norm,
+                                                         const float *__restrict__ grad_rgba, float *__restrict__ grad_faces,
+                                                         float *__restrict__ grad_colors, int F, int S, RenderArgs a)
+{
+    const int b = blockIdx.y, lane = threadIdx.x & 63;
+    const int f = rfl(blockIdx.x * 4 + (threadIdx.x >> 6));
+    if (f >= F) return;
+    const float4 *r = rec + ((size_t)b * F + f) * RENDER_REC;
+    const SoftFace s = unpack(r[0], r[1], r[2]);
+    const FaceShade h = unpack_shade(r[3], r[4]);
+    float g0x = 0.0f, g0y = 0.0f, g1x = 0.0f, g1y = 0.0f, g2x = 0.0f, g2y = 0.0f;
+    float g0z = 0.0f, g1z = 0.0f, g2z = 0.0f, gcr = 0.0f, gcg = 0.0f, gcb = 0.0f;
+    // the record's box lies inside the raster or is empty (k_render_setup); clamped again, the workspace being the caller's
+    const int x_lo = max(s.ix_lo, 0), x_hi = min(s.ix_hi, S - 1), y_lo = max(s.iy_lo, 0), y_hi = min(s.iy_hi, S - 1);
+    if (s.on != 0 && x_lo <= x_hi && y_lo <= y_hi) {
+        const int bw = x_hi - x_lo + 1, n = bw * (y_hi - y_lo + 1);   // <= S * S <= 2^28
+        const size_t SS = (size_t)S * S;
+        const float *img = rgba + (size_t)b * 4 * SS, *gi = grad_rgba + (size_t)b * 4 * SS;
+        const float *qb = trans + (size_t)b * SS, *nb = norm + (size_t)b * 2 * SS;
+        const float e0x = s.x1 - s.x0, e0y = s.y1 - s.y0, e1x = s.x2 - s.x1, e1y = s.y2 - s.y1, e2x = s.x0 - s.x2, e2y = s.y0 - s.y2;
+        const float ee0 = e0x * e0x + e0y * e0y, ee1 = e1x * e1x + e1y * e1y, ee2 = e2x * e2x + e2y * e2y;   // soft_segment's ee
+        const float s0 = h.iz0 * h.iz0, s1 = h.iz1 * h.iz1, s2 = h.iz2 * h.iz2;   // 1 / z_k^2
+        for (int i = lane; i < n; i += WAVE) {
+            const int row = i / bw, xi = x_lo + (i - row * bw), yi = y_lo + row;
+            const float px = pixel_center(xi, S), py = pixel_center(yi, S);
+            const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
+            const PairDepth q = pair_depth(px, py, s, h, p, a.cut, a.far, a.inv_range);
+            const size_t o = (size_t)yi * S + xi;
+            const float R = img[o], G = img[SS + o], Bl = img[2 * SS + o];
+            const float gr = gi[o], gg = gi[SS + o], gb = gi[2 * SS + o], ga = gi[3 * SS + o];
+            const float Qp = qb[o], m = nb[o], Z = nb[SS + o];
+            const float D = 1.0f / (1.0f + expf(-p.x)), D1 = 1.0f / (1.0f + expf(p.x));
+            float W = (D * expf((q.zn - m) * a.inv_gamma)) / Z;
+            W = q.taken ? W : 0.0f;                        // a pair not taken: every term below is an exact 0
+            const float Ga = q.taken ? ga * Qp : 0.0f;
+            const float hh = (gr * (h.cr - R) + gg * (h.cg - G)) + gb * (h.cb - Bl);
+            const float hW = hh * W;
+            gcr += W * gr;
+            gcg += W * gg;
+            gcb += W * gb;
+            // x -> d2 -> the two ends of the chosen segment, as k_soft_backward
+            float C = (hW * D1 + Ga * D) * a.inv_sigma;
+            C = p.inside ? C : -C;
+            const float t1 = 1.0f - p.t;
+            const float ca = (-2.0f * t1) * C, cb = (-2.0f * p.t) * C;
+            // zn -> zp -> iz
+            const float diz = ((hW * a.inv_gamma) * a.inv_range) * (q.zp * q.zp);
+            g0z += -(diz * q.l0) * s0;
+            g1z += -(diz * q.l1) * s1;
+            g2z += -(diz * q.l2) * s2;
+            // iz -> x, y.  Outside, through a free t of segment a -> b: iz = (1 - t) / z_a + t / z_b, dt/da = (-(1 - t) e - r) / ee,
+            // dt/db = (r - t e) / ee
+            const int k = p.k;
+            const float iza = k == 0 ? h.iz0 : (k == 1 ? h.iz1 : h.iz2), izb = k == 0 ? h.iz1 : (k == 1 ? h.iz2 : h.iz0);
+            const float ex = k == 0 ? e0x : (k == 1 ? e1x : e2x), ey = k == 0 ? e0y : (k == 1 ? e1y : e2y);
+            const float ee = k == 0 ? ee0 : (k == 1 ? ee1 : ee2);
+            const bool free_t = !p.inside && p.t > 0.0f && p.t < 1.0f;
+            const float T = free_t ? (diz * (izb - iza)) / ee : 0.0f;
+            const float ra = ca - T, rb = cb + T, ea = -(t1 * T), eb = -(p.t * T);
+            const float ax = ra * p.rx + ea * ex, ay = ra * p.ry + ea * ey;
+            const float bx = rb * p.rx + eb * ex, by = rb * p.ry + eb * ey;
+            // inside, through lambda: d iz / d c_j = (iz of the vertex that c_j weighs - iz) / A, and c_j moves with its two ends
+            const float dA = p.inside ? diz * q.rA : 0.0f;
+            const float q0 = dA * (h.iz2 - q.iz), q1 = dA * (h.iz0 - q.iz), q2 = dA * (h.iz1 - q.iz);
+            const float p0x = px - s.x0, p0y = py - s.y0, p1x = px - s.x1, p1y = py - s.y1, p2x = px - s.x2, p2y = py - s.y2;
+            g0x += (k == 0 ? ax : (k == 2 ? bx : 0.0f)) + (q2 * p2y - q0 * p1y);
+            g0y += (k == 0 ? ay : (k == 2 ? by : 0.0f)) + (q0 * p1x - q2 * p2x);
+            g1x += (k == 1 ? ax : (k == 0 ? bx : 0.0f)) + (q0 * p0y - q1 * p2y);
+            g1y += (k == 1 ? ay : (k == 0 ? by : 0.0f)) + (q1 * p2x - q0 * p0x);
+            g2x += (k == 2 ? ax : (k == 1 ? bx : 0.0f)) + (q1 * p1y - q2 * p0y);
+            g2y += (k == 2 ? ay : (k == 1 ? by : 0.0f)) + (q2 * p0x - q1 * p1x);
+        }
+    }
+    g0x = wave_sum(g0x); g0y = wave_sum(g0y); g0z = wave_sum(g0z);
+    g1x = wave_sum(g1x); g1y = wave_sum(g1y); g1z = wave_sum(g1z);
+    g2x = wave_sum(g2x); g2y = wave_sum(g2y); g2z = wave_sum(g2z);
+    gcr = wave_sum(gcr); gcg = wave_sum(gcg); gcb = wave_sum(gcb);
+    if (lane == 0) {
+        float *o = grad_faces + ((size_t)b * F + f) * 9;
+        o[0] = g0x; o[1] = g0y; o[2] = g0z;
+        o[3] = g1x; o[4] = g1y; o[5] = g1z;
+        o[6] = g2x; o[7] = g2y; o[8] = g2z;
+        float *c = grad_colors + ((size_t)b * F + f) * 3;
+        c[0] = gcr; c[1] = gcg; c[2] = gcb;
+    }
+}
+
+// shared colours: the B partial gradients of an entry in ascending b, in double, rounded once
+__global__ __launch_bounds__(256) void k_render_colors(const float *__restrict__ part, float *__restrict__ grad_colors, int B,
+                                                       int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    double sum = 0.0;
+    for (int b = 0; b < B; b++) sum += (double)part[(size_t)b * n + i];
+    grad_colors[i] = (float)sum;
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// host
+
+bool render_sizes_ok(int B, int F, int S) { return check_sizes(B, F, S) == 0 && F <= RENDER_MAX_F; }
+
+size_t render_records(int B, int F) { return (size_t)B * (size_t)F * RENDER_REC * sizeof(float4); }
+
+// the records, then the per-image colour gradients of a call with shared colours
+size_t render_workspace(int B, int F) { return render_records(B, F) + align_up((size_t)B * (size_t)F * 3 * sizeof(float), 16); }
+
+struct RenderCall {
+    const float *faces, *colors;
+    int B, F, S, colors_per_batch;
+    double sigma, gamma, near, far, eps;
+    const double *bg;
+    void *workspace;
+    size_t workspace_bytes;
+};
+
+int render_check(const RenderCall &c)
+{
+    if (!c.faces || !c.colors) return NR_E_NULL;
+    if (!render_sizes_ok(c.B, c.F, c.S)) return NR_E_SIZE;
+    const auto finite = [](double v) { return v - v == 0.0; };
+    if (!(c.sigma >= 1.0e-30 && c.sigma <= 1.0e30) || !(c.gamma >= 1.0e-30 && c.gamma <= 1.0e30)) return NR_E_MODE;
+    if (!finite(c.near) || !finite(c.far) || !(c.far > c.near) || !finite(c.eps)) return NR_E_MODE;
+    if (!finite(c.bg[0]) || !finite(c.bg[1]) || !finite(c.bg[2])) return NR_E_MODE;
+    if (c.colors_per_batch != 0 && c.colors_per_batch != 1) return NR_E_MODE;
+    if (!c.workspace || c.workspace_bytes < render_workspace(c.B, c.F)) return NR_E_WORKSPACE;
+    return 0;
+}
+
+RenderArgs render_args(const RenderCall &c)
+{
+    RenderArgs a;
+    a.inv_sigma = (float)(1.0 / c.sigma);
+    a.inv_gamma = (float)(1.0 / c.gamma);
+    a.cut = (float)((double)RENDER_REACH * c.sigma);
+    a.far = (float)c.far;
+    a.inv_range = (float)(1.0 / (c.far - c.near));
+    a.eps = (float)c.eps;
+    a.bg_r = (float)c.bg[0]; a.bg_g = (float)c.bg[1]; a.bg_b = (float)c.bg[2];
+    return a;
+}
+
+int render_setup(const RenderCall &c, hipStream_t st)
+{
+    const float reach = sqrtf(RENDER_REACH * (float)c.sigma) * 1.0001f;   // (the margin covers the roundings of this line)
+    hipLaunchKernelGGL(k_render_setup, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces, c.colors,
+                       (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * 3 : (size_t)0, reach, c.near, c.far);
+    return launch_status();
+}
+
+}  // namespace
+
+NR_API size_t nr_soft_render_workspace_bytes(int32_t B, int32_t F, int32_t S)
+{
+    return render_sizes_ok(B, F, S) ? render_workspace(B, F) : 0;
+}
+
+NR_API int nr_soft_render_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
+                                  int32_t B, int32_t F, int32_t S, int32_t colors_per_batch, double sigma, double gamma,
+                                  double near, double far, double eps, double background_r, double background_g,
+                                  double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser) return NR_E_NULL;
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes};
+    if (int e = render_check(c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = render_setup(c, st)) return rc;
+    const int tiles = (S + RENDER_TILE - 1) / RENDER_TILE;
+    hipLaunchKernelGGL(k_render_forward, dim3((unsigned)(tiles * tiles), (unsigned)B), dim3(256), 0, st,
+                       (const float4 *)workspace, rgba, transmittance, normaliser, F, S, tiles, render_args(c));
+    return launch_status();
+}
+
+NR_API int nr_soft_render_backward(const float *faces, const float *colors, const float *rgba, const float *transmittance,
+                                   const float *normaliser, const float *grad_rgba, float *grad_faces, float *grad_colors,
+                                   int32_t B, int32_t F, int32_t S, int32_t colors_per_batch, double sigma, double gamma,
+                                   double near, double far, double eps, double background_r, double background_g,
+                                   double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser || !grad_rgba || !grad_faces || !grad_colors) return NR_E_NULL;
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes};
+    if (int e = render_check(c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = render_setup(c, st)) return rc;   // the caller's workspace holds nothing
+    float *part = colors_per_batch ? grad_colors : (float *)((char *)workspace + render_records(B, F));
+    hipLaunchKernelGGL(k_render_backward, dim3((unsigned)((F + 3) / 4), (unsigned)B), dim3(256), 0, st,
+                       (const float4 *)workspace, rgba, transmittance, normaliser, grad_rgba, grad_faces, part, F, S,
+                       render_args(c));
+    if (int rc = launch_status()) return rc;
+    if (!colors_per_batch) {
+        const int n = F * 3;
+        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, grad_colors, B, n);
+    }
+    return launch_status();
+}

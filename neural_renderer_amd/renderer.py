@@ -19,6 +19,7 @@ from .normals import camera_rotation, corner_normals
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
+from .soft_render import soft_render
 from .soft_silhouette import soft_silhouettes
 from .uv_textures import UVImages
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
@@ -101,6 +102,9 @@ class Renderer(object):
         self.lights = None
         # not in the reference: the sigma of render_soft_silhouettes (soft_silhouette.py), in squared NDC units
         self.soft_sigma = 1e-4
+        # not in the reference: render_soft's sharpness of the depth order and the background's place in it (soft_render.py)
+        self.soft_gamma = 1e-4
+        self.soft_eps = 1e-3
 
     def _project(self, vertices, faces):
         """camera + perspective + gather (renderer.py:40-51, :60-71, :92-103)."""
@@ -171,6 +175,52 @@ class Renderer(object):
         nf = faces.shape[1]
         faces, _ = self._frontend(vertices, faces)
         return soft_silhouettes(faces[:, :nf], self.image_size, self.soft_sigma if sigma is None else sigma, self.near, self.far)
+
+    def _soft_face_colors(self, vertices, faces, colors):
+        """render_soft's colour of every face before the light, [B|1,F,3]: a face-colour tensor as it is, the mean of a
+        VertexColors' three vertex colours, the mean of a texture cube.  Plain torch, differentiable."""
+        if isinstance(colors, VertexColors):
+            B = vertices.shape[0]
+            if colors.num_vertices != vertices.shape[1]:
+                raise ValueError('VertexColors: %d colours for %d vertices' % (colors.num_vertices, vertices.shape[1]))
+            if colors.color_batch not in (1, B):
+                raise ValueError('VertexColors: batched colours must have the batch size of the vertices (%d), got %d'
+                                 % (B, colors.color_batch))
+            idx, vc = faces.long(), colors.colors
+            if vc.dim() == 2:
+                return (vc[idx] if idx.dim() == 3 else vc[idx][None]).mean(2)
+            if idx.dim() == 2:
+                idx = idx[None].expand(B, -1, -1)
+            return vc[torch.arange(B, device=idx.device)[:, None, None], idx].mean(2)
+        if torch.is_tensor(colors) and colors.is_floating_point():
+            if colors.dim() == 6 and colors.shape[5] == 3:
+                return colors.mean((2, 3, 4))
+            if colors.dim() == 3 and colors.shape[2] == 3:
+                return colors
+            if colors.dim() == 2 and colors.shape[1] == 3:
+                return colors[None]
+        raise ValueError('render_soft: colors must be face colours [B|1,F,3] or [F,3], a VertexColors or texture cubes '
+                         '[B|1,F,ts,ts,ts,3]')
+
+    def render_soft(self, vertices, faces, colors, sigma=None, gamma=None):
+        """Not in the reference: the soft colour image rgba [B,4,S,S] of soft_render.py -- coverage as in
+        render_soft_silhouettes, the faces' colours aggregated by a depth-weighted softmax -- whose exact gradient reaches
+        hidden faces and every z.  `colors`: one colour per face, [B,F,3] / [1,F,3] / [F,3]; a VertexColors (a face takes the
+        mean of its three vertex colours); or texture cubes [B|1,F,ts,ts,ts,3] (a face takes the mean of its cube).  The
+        colour is multiplied by the per-face light of the face's front copy (the host attributes `light_*`, or `lights`).
+        `sigma` (None: `soft_sigma`) sets the width of the coverage's transition, `gamma` (None: `soft_gamma`) the sharpness
+        of the depth order; `soft_eps`, `background_color`, `near` and `far` come from the renderer.  The geometry is the
+        front-end's, without the fill_back copies; `anti_aliasing` and `shading` are ignored."""
+        nf = faces.shape[1]
+        color = self._soft_face_colors(vertices, faces, colors)
+        if self.lights is not None:
+            light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=False)
+            projected, _ = self._frontend(vertices, faces)
+        else:
+            projected, light = self._frontend(vertices, faces, light_colors=True)
+        return soft_render(projected[:, :nf], color.to(light.dtype) * light[:, :nf], self.image_size,
+                           self.soft_sigma if sigma is None else sigma, self.soft_gamma if gamma is None else gamma,
+                           self.near, self.far, self.soft_eps, self.background_color)
 
     def _use_face_light(self, vertices, faces, textures):
         if self.face_light is False or not (torch.is_tensor(textures) and textures.dim() == 6):
