@@ -89,7 +89,8 @@ extern "C" {
                           *        nr_face_normals_backward, nr_corner_normals_forward, nr_corner_normals_backward,
                           *        nr_normals_workspace_bytes;
                           *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes;
-                          *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes);
+                          *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes;
+                          *        nr_soft_corners_forward, nr_soft_corners_backward, nr_soft_corners_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -867,6 +868,35 @@ int nr_soft_render_backward(const float *faces, const float *colors, const float
                             int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
                             double gamma, double near, double far, double eps, double background_r, double background_g,
                             double background_b, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Soft colour rendering with corner colours: nr_soft_render_* with three colours per face, interpolated at the pixel.
+ * colors [B, F, 3, 3] (colors_per_batch = 1) or [F, 3, 3] shared by the batch and read in place (colors_per_batch = 0),
+ * indexed (face, corner, rgb); grad_colors has the shape of colors.  Everything else -- the contribution rule, the taken
+ * rule, lambda_k, iz, zp, zn, m, w_f, w_b, Z, Q, alpha, the layouts, the ranges, the NR_E_* codes before any launch and the
+ * workspace rule (nr_soft_corners_workspace_bytes) -- is nr_soft_render_*'s, except the colour of a taken pair:
+ *   u_k = lambda_k / z_k,  mu_k = u_k zp  (the perspective-correct weights; they add up to 1 in exact arithmetic),
+ *   C_f(p) = (mu_0 C_f0 + mu_1 C_f1) + mu_2 C_f2 per channel,  rgb = (w_b background + sum w_f C_f(p)) / Z.
+ *   Inside lambda is the rasterizer's barycentric form; outside lambda = (1 - t, t, 0) on the chosen segment: the colour at
+ *   the nearest boundary point, continuous across every edge and single-valued (the nearest point of a triangle is unique).
+ *   Backward, per taken pair: h = g_rgb . (C_f(p) - rgb); dL/dC_fk += W mu_k g_rgb; with E_k = W zp (g_rgb . (C_fk - C_f(p)))
+ *   and d_k = diz + E_k (diz: nr_soft_render_backward's dL/diz): dL/dlambda_k = d_k / z_k, dL/dz_k = -d_k lambda_k / z_k^2;
+ *   inside dL/dc_i = (dL/dlambda_v(i) - diz iz) / A with v(0) = 2, v(1) = 0, v(2) = 1 (sum_k lambda_k dL/dlambda_k = diz iz
+ *   in exact arithmetic); outside with a free t on a -> b: dL/dt = d_b / z_b - d_a / z_a; a clamped t has derivative 0;
+ *   dL/dx is nr_soft_render_backward's.  Three equal corner colours: every E_k = 0 and the gradient is the flat one.
+ */
+size_t nr_soft_corners_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t image_size);
+
+int nr_soft_corners_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
+                            int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
+                            double gamma, double near, double far, double eps, double background_r, double background_g,
+                            double background_b, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_soft_corners_backward(const float *faces, const float *colors, const float *rgba, const float *transmittance,
+                             const float *normaliser, const float *grad_rgba, float *grad_faces, float *grad_colors,
+                             int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
+                             double gamma, double near, double far, double eps, double background_r, double background_g,
+                             double background_b, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

@@ -22,6 +22,17 @@
 //                      six xy, three z and three colour gradients per lane, reduces them in the fixed xor tree, one store
 //                      per entry.
 //   k_render_colors    shared colours: the B partial colour gradients added in ascending b in double.
+// Corner colours (nr_soft_corners_*; DESIGN "Soft colour rendering", Corner colours): colors carry nine floats per face,
+// (corner, rgb), and the colour of a taken pair is interpolated at the pixel with the depth's own weights,
+//   u_k = lambda_k / z_k,  mu_k = u_k zp,  C_f(p) = (mu_0 C_f0 + mu_1 C_f1) + mu_2 C_f2   per channel
+// -- perspective-correct inside, the colour of the nearest boundary point outside.  The three kernels are the <true>
+// instantiations of the same templates: a 96-byte record (the 48 bytes, 1 / z_k, nine colour floats; 24 KiB per chunk), nine
+// colour sums per lane next to the nine of the coordinates.  Backward, with E_k = (W zp) (g_rgb . (C_fk - C_f(p))):
+//   dL/dC_fk += (W g_rgb) mu_k,  dL/dz_k = -((diz + E_k) lambda_k) / z_k^2,
+//   free t on a -> b   T = (diz (iz_b - iz_a) + (E_b iz_b - E_a iz_a)) / ee
+//   inside             q_j = (diz / A) (iz_v(j) - iz) + (E_v(j) iz_v(j)) / A,  v(0) = 2, v(1) = 0, v(2) = 1
+// the flat terms plus one addition each (sum_k lambda_k dL/dlambda_k taken as diz iz: sum_k u_k E_k = 0 in exact arithmetic).
+// The <false> instantiations are the flat kernels, instruction for instruction.
 // No atomics, no host synchronisation, every output element stored; the same bits in every run and for an image alone or
 // inside a batch: a pixel's sums depend on the set of its taken pairs and their order in f alone.
 #include "nr_soft_pair.h"
@@ -33,6 +44,7 @@ namespace {
 constexpr int RENDER_TILE = 16;       // pixels per side of a workgroup's tile (a wave: 8 x 8)
 constexpr int RENDER_CHUNK = 256;     // face records per LDS chunk, one per thread
 constexpr int RENDER_REC = 5;         // float4 per record
+constexpr int CORNER_REC = 6;         // ... with corner colours
 constexpr float RENDER_REACH = 17.0f;   // a pair outside is taken up to d2 = RENDER_REACH sigma
 constexpr int RENDER_MAX_F = 1 << 24;
 
@@ -86,6 +98,36 @@ __device__ __forceinline__ PairDepth pair_depth(float px, float py, const SoftFa
     return q;
 }
 
+// what a corner record holds beyond FaceShade's 1 / z_k: (., ., ., c00), (c01, c02, c10, c11), (c12, c20, c21, c22) -- c[corner][rgb]
+struct CornerColor {
+    float c00, c01, c02, c10, c11, c12, c20, c21, c22;
+};
+
+__device__ __forceinline__ CornerColor unpack_corners(const float4 &d, const float4 &e, const float4 &g)
+{
+    CornerColor r;
+    r.c00 = d.w; r.c01 = e.x; r.c02 = e.y; r.c10 = e.z; r.c11 = e.w;
+    r.c12 = g.x; r.c20 = g.y; r.c21 = g.z; r.c22 = g.w;
+    return r;
+}
+
+// the perspective-correct weights of a pair and its colour at the pixel; u_k are pair_depth's own products
+struct PairColor {
+    float mu0, mu1, mu2, r, g, b;
+};
+
+__device__ __forceinline__ PairColor pair_color(const PairDepth &q, const FaceShade &h, const CornerColor &c)
+{
+    PairColor o;
+    o.mu0 = (q.l0 * h.iz0) * q.zp;
+    o.mu1 = (q.l1 * h.iz1) * q.zp;
+    o.mu2 = (q.l2 * h.iz2) * q.zp;
+    o.r = (o.mu0 * c.c00 + o.mu1 * c.c10) + o.mu2 * c.c20;
+    o.g = (o.mu0 * c.c01 + o.mu1 * c.c11) + o.mu2 * c.c21;
+    o.b = (o.mu0 * c.c02 + o.mu1 * c.c12) + o.mu2 * c.c22;
+    return o;
+}
+
 struct RenderArgs {
     float inv_sigma, inv_gamma, cut, far, inv_range, eps;
     float bg_r, bg_g, bg_b;
@@ -94,6 +136,7 @@ struct RenderArgs {
 // --------------------------------------------------------------------------------------------------------------------
 // set-up
 
+template <bool CORNERS>
 __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ faces, const float *__restrict__ colors,
                                                       float4 *__restrict__ rec, int F, int S, size_t color_stride, float reach,
                                                       double near, double far)
@@ -101,7 +144,7 @@ __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ 
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (f >= F) return;
     const float *v = faces + ((size_t)b * F + f) * 9;
-    const float *col = colors + (size_t)b * color_stride + (size_t)f * 3;
+    const float *col = colors + (size_t)b * color_stride + (size_t)f * (CORNERS ? 9 : 3);
     float c[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) c[k] = v[k];
@@ -127,27 +170,35 @@ __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ 
         iy_hi = min((int)ceilf(fminf(fmaxf(to_pixel(ymax, fs), lo_c), hi_c)), S - 1);
         if (ix_lo > ix_hi || iy_lo > iy_hi) { ix_lo = iy_lo = S; ix_hi = iy_hi = -1; }
     }
-    float4 *o = rec + ((size_t)b * F + f) * RENDER_REC;
+    float4 *o = rec + ((size_t)b * F + f) * (CORNERS ? CORNER_REC : RENDER_REC);
     o[0] = make_float4(c[0], c[1], c[3], c[4]);
     o[1] = make_float4(c[6], c[7], __int_as_float(ix_lo), __int_as_float(iy_lo));
     o[2] = make_float4(__int_as_float(ix_hi), __int_as_float(iy_hi), __int_as_float(on ? 1 : 0), 0.0f);
     o[3] = make_float4(1.0f / c[2], 1.0f / c[5], 1.0f / c[8], col[0]);
-    o[4] = make_float4(col[1], col[2], 0.0f, 0.0f);
+    if constexpr (CORNERS) {
+        o[4] = make_float4(col[1], col[2], col[3], col[4]);
+        o[5] = make_float4(col[5], col[6], col[7], col[8]);
+    } else {
+        o[4] = make_float4(col[1], col[2], 0.0f, 0.0f);
+    }
 }
 
 // --------------------------------------------------------------------------------------------------------------------
 // forward
 
 // one chunk of records into the compact LDS list of those whose box meets the tile, ascending in f -> their number
+template <bool CORNERS>
 __device__ __forceinline__ int filter_chunk(const float4 *__restrict__ rb, int c0, int F, int tid, int wave, int lane, int tx0,
                                             int ty0, int tx1, int ty1, float4 *list, int *wave_count)
 {
+    constexpr int REC = CORNERS ? CORNER_REC : RENDER_REC;
     const int f = c0 + tid;
-    float4 r0, r1, r2, r3, r4;
+    float4 r0, r1, r2, r3, r4, r5;
     bool hit = false;
     if (f < F) {
-        const float4 *src = rb + (size_t)f * RENDER_REC;
+        const float4 *src = rb + (size_t)f * REC;
         r0 = src[0]; r1 = src[1]; r2 = src[2]; r3 = src[3]; r4 = src[4];
+        if constexpr (CORNERS) r5 = src[5];
         const SoftFace s = unpack(r0, r1, r2);
         hit = s.on != 0 && s.ix_lo <= tx1 && s.ix_hi >= tx0 && s.iy_lo <= ty1 && s.iy_hi >= ty0;
     }
@@ -163,18 +214,21 @@ __device__ __forceinline__ int filter_chunk(const float4 *__restrict__ rb, int c
         n += cnt;
     }
     if (hit) {   // thread order is face order: the list stays ascending in f
-        const int at = (base + before) * RENDER_REC;   // < RENDER_CHUNK * RENDER_REC: at most one entry per thread
+        const int at = (base + before) * REC;   // < RENDER_CHUNK * REC: at most one entry per thread
         list[at] = r0; list[at + 1] = r1; list[at + 2] = r2; list[at + 3] = r3; list[at + 4] = r4;
+        if constexpr (CORNERS) list[at + 5] = r5;
     }
     __syncthreads();
     return rfl(n);
 }
 
+template <bool CORNERS>
 __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict__ rec, float *__restrict__ rgba,
                                                         float *__restrict__ trans, float *__restrict__ norm, int F, int S,
                                                         int tiles_x, RenderArgs a)
 {
-    __shared__ float4 list[RENDER_CHUNK * RENDER_REC];
+    constexpr int REC = CORNERS ? CORNER_REC : RENDER_REC;
+    __shared__ float4 list[RENDER_CHUNK * REC];
     __shared__ int wave_count[4];
     const int b = blockIdx.y, tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
@@ -182,13 +236,13 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
     const int tx1 = min(tx0 + RENDER_TILE - 1, S - 1), ty1 = min(ty0 + RENDER_TILE - 1, S - 1);
     const int xi = tx0 + (wave & 1) * 8 + (lane & 7), yi = ty0 + (wave >> 1) * 8 + (lane >> 3);
     const float px = pixel_center(min(xi, S - 1), S), py = pixel_center(min(yi, S - 1), S);
-    const float4 *rb = rec + (size_t)b * F * RENDER_REC;
+    const float4 *rb = rec + (size_t)b * F * REC;
     // the first walk: m = max(eps, the zn of the taken pairs) -- a maximum of the very floats the second walk subtracts it from
     float m = a.eps;
     for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
-        const int n = filter_chunk(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+        const int n = filter_chunk<CORNERS>(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
         for (int j = 0; j < n; j++) {
-            const float4 *l = list + j * RENDER_REC;
+            const float4 *l = list + j * REC;
             const SoftFace s = unpack(l[0], l[1], l[2]);
             const FaceShade h = unpack_shade(l[3], l[4]);
             const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
@@ -201,9 +255,9 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
     const float wb = expf((a.eps - m) * a.inv_gamma);
     float Z = wb, cr = wb * a.bg_r, cg = wb * a.bg_g, cb = wb * a.bg_b, Q = 1.0f;
     for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
-        const int n = filter_chunk(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+        const int n = filter_chunk<CORNERS>(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
         for (int j = 0; j < n; j++) {
-            const float4 *l = list + j * RENDER_REC;
+            const float4 *l = list + j * REC;
             const SoftFace s = unpack(l[0], l[1], l[2]);
             const FaceShade h = unpack_shade(l[3], l[4]);
             const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
@@ -213,9 +267,16 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
             const float w = D * expf((q.zn - m) * a.inv_gamma);
             const float q1 = Q * (1.0f / (1.0f + expf(p.x)));   // 1 - D as 1 / (1 + e^x), never as a subtraction
             Z = take ? Z + w : Z;
-            cr = take ? cr + w * h.cr : cr;
-            cg = take ? cg + w * h.cg : cg;
-            cb = take ? cb + w * h.cb : cb;
+            if constexpr (CORNERS) {
+                const PairColor pc = pair_color(q, h, unpack_corners(l[3], l[4], l[5]));
+                cr = take ? cr + w * pc.r : cr;
+                cg = take ? cg + w * pc.g : cg;
+                cb = take ? cb + w * pc.b : cb;
+            } else {
+                cr = take ? cr + w * h.cr : cr;
+                cg = take ? cg + w * h.cg : cg;
+                cb = take ? cb + w * h.cb : cb;
+            }
             Q = take ? q1 : Q;
         }
         __syncthreads();
@@ -236,6 +297,7 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
 // --------------------------------------------------------------------------------------------------------------------
 // backward
 
+template <bool CORNERS>
 __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restrict__ rec, const float *__restrict__ rgba,
                                                          const float *__restrict__ trans, const float *__restrict__ norm,
                                                          const float *__restrict__ grad_rgba, float *__restrict__ grad_faces,
@@ -244,11 +306,14 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int f = rfl(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (f >= F) return;
-    const float4 *r = rec + ((size_t)b * F + f) * RENDER_REC;
+    const float4 *r = rec + ((size_t)b * F + f) * (CORNERS ? CORNER_REC : RENDER_REC);
     const SoftFace s = unpack(r[0], r[1], r[2]);
     const FaceShade h = unpack_shade(r[3], r[4]);
+    CornerColor cc = {};
+    if constexpr (CORNERS) cc = unpack_corners(r[3], r[4], r[5]);
     float g0x = 0.0f, g0y = 0.0f, g1x = 0.0f, g1y = 0.0f, g2x = 0.0f, g2y = 0.0f;
     float g0z = 0.0f, g1z = 0.0f, g2z = 0.0f, gcr = 0.0f, gcg = 0.0f, gcb = 0.0f;
+    float g1r = 0.0f, g1g = 0.0f, g1b = 0.0f, g2r = 0.0f, g2g = 0.0f, g2b = 0.0f;   // (corners 1 and 2; gcr, gcg, gcb are corner 0's)
     // the record's box lies inside the raster or is empty (k_render_setup); clamped again, the workspace being the caller's
     const int x_lo = max(s.ix_lo, 0), x_hi = min(s.ix_hi, S - 1), y_lo = max(s.iy_lo, 0), y_hi = min(s.iy_hi, S - 1);
     if (s.on != 0 && x_lo <= x_hi && y_lo <= y_hi) {
@@ -272,11 +337,24 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             float W = (D * expf((q.zn - m) * a.inv_gamma)) / Z;
             W = q.taken ? W : 0.0f;                        // a pair not taken: every term below is an exact 0
             const float Ga = q.taken ? ga * Qp : 0.0f;
-            const float hh = (gr * (h.cr - R) + gg * (h.cg - G)) + gb * (h.cb - Bl);
+            float hh, E0 = 0.0f, E1 = 0.0f, E2 = 0.0f;   // E_k: what corner k's colour adds to diz, 0 for a flat colour
+            if constexpr (CORNERS) {
+                const PairColor pc = pair_color(q, h, cc);
+                hh = (gr * (pc.r - R) + gg * (pc.g - G)) + gb * (pc.b - Bl);
+                const float wr = W * gr, wg = W * gg, wb = W * gb, Wz = W * q.zp;
+                gcr += wr * pc.mu0; gcg += wg * pc.mu0; gcb += wb * pc.mu0;
+                g1r += wr * pc.mu1; g1g += wg * pc.mu1; g1b += wb * pc.mu1;
+                g2r += wr * pc.mu2; g2g += wg * pc.mu2; g2b += wb * pc.mu2;
+                E0 = Wz * ((gr * (cc.c00 - pc.r) + gg * (cc.c01 - pc.g)) + gb * (cc.c02 - pc.b));
+                E1 = Wz * ((gr * (cc.c10 - pc.r) + gg * (cc.c11 - pc.g)) + gb * (cc.c12 - pc.b));
+                E2 = Wz * ((gr * (cc.c20 - pc.r) + gg * (cc.c21 - pc.g)) + gb * (cc.c22 - pc.b));
+            } else {
+                hh = (gr * (h.cr - R) + gg * (h.cg - G)) + gb * (h.cb - Bl);
+                gcr += W * gr;
+                gcg += W * gg;
+                gcb += W * gb;
+            }
             const float hW = hh * W;
-            gcr += W * gr;
-            gcg += W * gg;
-            gcb += W * gb;
             // x -> d2 -> the two ends of the chosen segment, as k_soft_backward
             float C = (hW * D1 + Ga * D) * a.inv_sigma;
             C = p.inside ? C : -C;
@@ -284,9 +362,15 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             const float ca = (-2.0f * t1) * C, cb = (-2.0f * p.t) * C;
             // zn -> zp -> iz
             const float diz = ((hW * a.inv_gamma) * a.inv_range) * (q.zp * q.zp);
-            g0z += -(diz * q.l0) * s0;
-            g1z += -(diz * q.l1) * s1;
-            g2z += -(diz * q.l2) * s2;
+            if constexpr (CORNERS) {
+                g0z += -((diz + E0) * q.l0) * s0;
+                g1z += -((diz + E1) * q.l1) * s1;
+                g2z += -((diz + E2) * q.l2) * s2;
+            } else {
+                g0z += -(diz * q.l0) * s0;
+                g1z += -(diz * q.l1) * s1;
+                g2z += -(diz * q.l2) * s2;
+            }
             // iz -> x, y.  Outside, through a free t of segment a -> b: iz = (1 - t) / z_a + t / z_b, dt/da = (-(1 - t) e - r) / ee,
             // dt/db = (r - t e) / ee
             const int k = p.k;
@@ -294,13 +378,25 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             const float ex = k == 0 ? e0x : (k == 1 ? e1x : e2x), ey = k == 0 ? e0y : (k == 1 ? e1y : e2y);
             const float ee = k == 0 ? ee0 : (k == 1 ? ee1 : ee2);
             const bool free_t = !p.inside && p.t > 0.0f && p.t < 1.0f;
-            const float T = free_t ? (diz * (izb - iza)) / ee : 0.0f;
+            float T;
+            if constexpr (CORNERS) {   // ... and the colour moves along the segment with t
+                const float Ea = k == 0 ? E0 : (k == 1 ? E1 : E2), Eb = k == 0 ? E1 : (k == 1 ? E2 : E0);
+                T = free_t ? (diz * (izb - iza) + (Eb * izb - Ea * iza)) / ee : 0.0f;
+            } else {
+                T = free_t ? (diz * (izb - iza)) / ee : 0.0f;
+            }
             const float ra = ca - T, rb = cb + T, ea = -(t1 * T), eb = -(p.t * T);
             const float ax = ra * p.rx + ea * ex, ay = ra * p.ry + ea * ey;
             const float bx = rb * p.rx + eb * ex, by = rb * p.ry + eb * ey;
             // inside, through lambda: d iz / d c_j = (iz of the vertex that c_j weighs - iz) / A, and c_j moves with its two ends
             const float dA = p.inside ? diz * q.rA : 0.0f;
-            const float q0 = dA * (h.iz2 - q.iz), q1 = dA * (h.iz0 - q.iz), q2 = dA * (h.iz1 - q.iz);
+            float q0 = dA * (h.iz2 - q.iz), q1 = dA * (h.iz0 - q.iz), q2 = dA * (h.iz1 - q.iz);
+            if constexpr (CORNERS) {   // ... and the colour with lambda: c_j weighs vertex v(j) = 2, 0, 1
+                const float rA = p.inside ? q.rA : 0.0f;
+                q0 += (E2 * h.iz2) * rA;
+                q1 += (E0 * h.iz0) * rA;
+                q2 += (E1 * h.iz1) * rA;
+            }
             const float p0x = px - s.x0, p0y = py - s.y0, p1x = px - s.x1, p1y = py - s.y1, p2x = px - s.x2, p2y = py - s.y2;
             g0x += (k == 0 ? ax : (k == 2 ? bx : 0.0f)) + (q2 * p2y - q0 * p1y);
             g0y += (k == 0 ? ay : (k == 2 ? by : 0.0f)) + (q0 * p1x - q2 * p2x);
@@ -314,13 +410,21 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
     g1x = wave_sum(g1x); g1y = wave_sum(g1y); g1z = wave_sum(g1z);
     g2x = wave_sum(g2x); g2y = wave_sum(g2y); g2z = wave_sum(g2z);
     gcr = wave_sum(gcr); gcg = wave_sum(gcg); gcb = wave_sum(gcb);
+    if constexpr (CORNERS) {
+        g1r = wave_sum(g1r); g1g = wave_sum(g1g); g1b = wave_sum(g1b);
+        g2r = wave_sum(g2r); g2g = wave_sum(g2g); g2b = wave_sum(g2b);
+    }
     if (lane == 0) {
         float *o = grad_faces + ((size_t)b * F + f) * 9;
         o[0] = g0x; o[1] = g0y; o[2] = g0z;
         o[3] = g1x; o[4] = g1y; o[5] = g1z;
         o[6] = g2x; o[7] = g2y; o[8] = g2z;
-        float *c = grad_colors + ((size_t)b * F + f) * 3;
+        float *c = grad_colors + ((size_t)b * F + f) * (CORNERS ? 9 : 3);
         c[0] = gcr; c[1] = gcg; c[2] = gcb;
+        if constexpr (CORNERS) {
+            c[3] = g1r; c[4] = g1g; c[5] = g1b;
+            c[6] = g2r; c[7] = g2g; c[8] = g2b;
+        }
     }
 }
 
@@ -340,10 +444,17 @@ __global__ __launch_bounds__(256) void k_render_colors(const float *__restrict__
 
 bool render_sizes_ok(int B, int F, int S) { return check_sizes(B, F, S) == 0 && F <= RENDER_MAX_F; }
 
-size_t render_records(int B, int F) { return (size_t)B * (size_t)F * RENDER_REC * sizeof(float4); }
+// corners = 0: one colour per face, 1: one per corner
+size_t render_records(int B, int F, int corners)
+{
+    return (size_t)B * (size_t)F * (corners ? CORNER_REC : RENDER_REC) * sizeof(float4);
+}
 
 // the records, then the per-image colour gradients of a call with shared colours
-size_t render_workspace(int B, int F) { return render_records(B, F) + align_up((size_t)B * (size_t)F * 3 * sizeof(float), 16); }
+size_t render_workspace(int B, int F, int corners)
+{
+    return render_records(B, F, corners) + align_up((size_t)B * (size_t)F * (corners ? 9 : 3) * sizeof(float), 16);
+}
 
 struct RenderCall {
     const float *faces, *colors;
@@ -352,6 +463,7 @@ struct RenderCall {
     const double *bg;
     void *workspace;
     size_t workspace_bytes;
+    int corners;
 };
 
 int render_check(const RenderCall &c)
@@ -363,7 +475,7 @@ int render_check(const RenderCall &c)
     if (!finite(c.near) || !finite(c.far) || !(c.far > c.near) || !finite(c.eps)) return NR_E_MODE;
     if (!finite(c.bg[0]) || !finite(c.bg[1]) || !finite(c.bg[2])) return NR_E_MODE;
     if (c.colors_per_batch != 0 && c.colors_per_batch != 1) return NR_E_MODE;
-    if (!c.workspace || c.workspace_bytes < render_workspace(c.B, c.F)) return NR_E_WORKSPACE;
+    if (!c.workspace || c.workspace_bytes < render_workspace(c.B, c.F, c.corners)) return NR_E_WORKSPACE;
     return 0;
 }
 
@@ -380,11 +492,46 @@ RenderArgs render_args(const RenderCall &c)
     return a;
 }
 
+template <bool CORNERS>
 int render_setup(const RenderCall &c, hipStream_t st)
 {
     const float reach = sqrtf(RENDER_REACH * (float)c.sigma) * 1.0001f;   // (the margin covers the roundings of this line)
-    hipLaunchKernelGGL(k_render_setup, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces, c.colors,
-                       (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * 3 : (size_t)0, reach, c.near, c.far);
+    hipLaunchKernelGGL(k_render_setup<CORNERS>, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces,
+                       c.colors, (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * (CORNERS ? 9 : 3) : (size_t)0,
+                       reach, c.near, c.far);
+    return launch_status();
+}
+
+template <bool CORNERS>
+int render_forward(const RenderCall &c, float *rgba, float *transmittance, float *normaliser, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser) return NR_E_NULL;
+    if (int e = render_check(c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = render_setup<CORNERS>(c, st)) return rc;
+    const int tiles = (c.S + RENDER_TILE - 1) / RENDER_TILE;
+    hipLaunchKernelGGL(k_render_forward<CORNERS>, dim3((unsigned)(tiles * tiles), (unsigned)c.B), dim3(256), 0, st,
+                       (const float4 *)c.workspace, rgba, transmittance, normaliser, c.F, c.S, tiles, render_args(c));
+    return launch_status();
+}
+
+template <bool CORNERS>
+int render_backward(const RenderCall &c, const float *rgba, const float *transmittance, const float *normaliser,
+                    const float *grad_rgba, float *grad_faces, float *grad_colors, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser || !grad_rgba || !grad_faces || !grad_colors) return NR_E_NULL;
+    if (int e = render_check(c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = render_setup<CORNERS>(c, st)) return rc;   // the caller's workspace holds nothing
+    float *part = c.colors_per_batch ? grad_colors : (float *)((char *)c.workspace + render_records(c.B, c.F, c.corners));
+    hipLaunchKernelGGL(k_render_backward<CORNERS>, dim3((unsigned)((c.F + 3) / 4), (unsigned)c.B), dim3(256), 0, st,
+                       (const float4 *)c.workspace, rgba, transmittance, normaliser, grad_rgba, grad_faces, part, c.F, c.S,
+                       render_args(c));
+    if (int rc = launch_status()) return rc;
+    if (!c.colors_per_batch) {
+        const int n = c.F * (CORNERS ? 9 : 3);
+        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, grad_colors, c.B, n);
+    }
     return launch_status();
 }
 
@@ -392,7 +539,7 @@ int render_setup(const RenderCall &c, hipStream_t st)
 
 NR_API size_t nr_soft_render_workspace_bytes(int32_t B, int32_t F, int32_t S)
 {
-    return render_sizes_ok(B, F, S) ? render_workspace(B, F) : 0;
+    return render_sizes_ok(B, F, S) ? render_workspace(B, F, 0) : 0;
 }
 
 NR_API int nr_soft_render_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
@@ -400,16 +547,9 @@ NR_API int nr_soft_render_forward(const float *faces, const float *colors, float
                                   double near, double far, double eps, double background_r, double background_g,
                                   double background_b, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!rgba || !transmittance || !normaliser) return NR_E_NULL;
     const double bg[3] = {background_r, background_g, background_b};
-    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes};
-    if (int e = render_check(c)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = render_setup(c, st)) return rc;
-    const int tiles = (S + RENDER_TILE - 1) / RENDER_TILE;
-    hipLaunchKernelGGL(k_render_forward, dim3((unsigned)(tiles * tiles), (unsigned)B), dim3(256), 0, st,
-                       (const float4 *)workspace, rgba, transmittance, normaliser, F, S, tiles, render_args(c));
-    return launch_status();
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    return render_forward<false>(c, rgba, transmittance, normaliser, stream);
 }
 
 NR_API int nr_soft_render_backward(const float *faces, const float *colors, const float *rgba, const float *transmittance,
@@ -418,20 +558,33 @@ NR_API int nr_soft_render_backward(const float *faces, const float *colors, cons
                                    double near, double far, double eps, double background_r, double background_g,
                                    double background_b, void *workspace, size_t workspace_bytes, void *stream)
 {
-    if (!rgba || !transmittance || !normaliser || !grad_rgba || !grad_faces || !grad_colors) return NR_E_NULL;
     const double bg[3] = {background_r, background_g, background_b};
-    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes};
-    if (int e = render_check(c)) return e;
-    hipStream_t st = (hipStream_t)stream;
-    if (int rc = render_setup(c, st)) return rc;   // the caller's workspace holds nothing
-    float *part = colors_per_batch ? grad_colors : (float *)((char *)workspace + render_records(B, F));
-    hipLaunchKernelGGL(k_render_backward, dim3((unsigned)((F + 3) / 4), (unsigned)B), dim3(256), 0, st,
-                       (const float4 *)workspace, rgba, transmittance, normaliser, grad_rgba, grad_faces, part, F, S,
-                       render_args(c));
-    if (int rc = launch_status()) return rc;
-    if (!colors_per_batch) {
-        const int n = F * 3;
-        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, grad_colors, B, n);
-    }
-    return launch_status();
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    return render_backward<false>(c, rgba, transmittance, normaliser, grad_rgba, grad_faces, grad_colors, stream);
+}
+
+NR_API size_t nr_soft_corners_workspace_bytes(int32_t B, int32_t F, int32_t S)
+{
+    return render_sizes_ok(B, F, S) ? render_workspace(B, F, 1) : 0;
+}
+
+NR_API int nr_soft_corners_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
+                                   int32_t B, int32_t F, int32_t S, int32_t colors_per_batch, double sigma, double gamma,
+                                   double near, double far, double eps, double background_r, double background_g,
+                                   double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 1};
+    return render_forward<true>(c, rgba, transmittance, normaliser, stream);
+}
+
+NR_API int nr_soft_corners_backward(const float *faces, const float *colors, const float *rgba, const float *transmittance,
+                                    const float *normaliser, const float *grad_rgba, float *grad_faces, float *grad_colors,
+                                    int32_t B, int32_t F, int32_t S, int32_t colors_per_batch, double sigma, double gamma,
+                                    double near, double far, double eps, double background_r, double background_g,
+                                    double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, colors, B, F, S, colors_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 1};
+    return render_backward<true>(c, rgba, transmittance, normaliser, grad_rgba, grad_faces, grad_colors, stream);
 }

@@ -202,7 +202,52 @@ class Renderer(object):
         raise ValueError('render_soft: colors must be face colours [B|1,F,3] or [F,3], a VertexColors or texture cubes '
                          '[B|1,F,ts,ts,ts,3]')
 
-    def render_soft(self, vertices, faces, colors, sigma=None, gamma=None):
+    def _soft_corner_colors(self, vertices, faces, colors):
+        """render_soft(per_pixel=True): -> (projected faces [B,F',3,3], lit corner colours [B|1,F',3,3]), F' the front-end's
+        face count.  A VertexColors goes through render()'s own preparation (_render_vertex_colors, or _render_lights with
+        `lights`); a tensor is multiplied by the light, per face ('flat') or per corner ('smooth')."""
+        if self.shading not in ('flat', 'smooth'):
+            raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+        if isinstance(colors, VertexColors):
+            if self.lights is not None:
+                projected, corner, _ = self._render_lights(vertices, faces, colors)
+            else:
+                projected, corner, _ = self._render_vertex_colors(vertices, faces, colors)
+            return projected, corner.colors
+        nf = faces.shape[1]
+        if not (torch.is_tensor(colors) and colors.is_floating_point()):
+            raise ValueError('render_soft: colors must be a float tensor or a VertexColors')
+        if colors.dim() == 6:
+            raise ValueError('render_soft: per_pixel=True takes a VertexColors, corner colours [B|1,F,3,3] / [F,3,3] or face '
+                             'colours [B|1,F,3] / [F,3]; texture cubes are not sampled per pixel')
+        shape = tuple(colors.shape)
+        if colors.dim() == 4 and shape[1:] == (nf, 3, 3):
+            corner = colors
+        elif colors.dim() == 3 and shape[1:] == (nf, 3):          # (with three faces [3,3,3] reads as face colours)
+            corner = colors[:, :, None, :].expand(-1, -1, 3, -1)
+        elif colors.dim() == 3 and shape == (nf, 3, 3):
+            corner = colors[None]
+        elif colors.dim() == 2 and shape == (nf, 3):
+            corner = colors[None, :, None, :].expand(-1, -1, 3, -1)
+        else:
+            raise ValueError('render_soft: per_pixel=True takes a VertexColors, corner colours [B|1,F,3,3] / [F,3,3] or face '
+                             'colours [B|1,F,3] / [F,3] (F = %d), got %s' % (nf, shape))
+        smooth = self.shading == 'smooth'
+        if self.lights is not None:
+            light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=smooth)
+            projected, _ = self._frontend(vertices, faces)
+        elif smooth:
+            fused = frontend.fusable(self, vertices, faces, None) and frontend.light_fusable(self)
+            light = vertex_light(vertices, faces, self.light_intensity_ambient, self.light_intensity_directional,
+                                 self.light_color_ambient, self.light_color_directional, self.light_direction,
+                                 fill_back=self.fill_back, smooth=True, implementation=None if fused else 'torch')
+            projected, _ = self._frontend(vertices, faces, fused=fused)
+        else:
+            projected, light = self._frontend(vertices, faces, light_colors=True)
+        light = light[:, :nf]
+        return projected[:, :nf], corner.to(light.dtype) * (light if smooth else light[:, :, None, :])
+
+    def render_soft(self, vertices, faces, colors, sigma=None, gamma=None, per_pixel=False):
         """Not in the reference: the soft colour image rgba [B,4,S,S] of soft_render.py -- coverage as in
         render_soft_silhouettes, the faces' colours aggregated by a depth-weighted softmax -- whose exact gradient reaches
         hidden faces and every z.  `colors`: one colour per face, [B,F,3] / [1,F,3] / [F,3]; a VertexColors (a face takes the
@@ -210,7 +255,21 @@ class Renderer(object):
         colour is multiplied by the per-face light of the face's front copy (the host attributes `light_*`, or `lights`).
         `sigma` (None: `soft_sigma`) sets the width of the coverage's transition, `gamma` (None: `soft_gamma`) the sharpness
         of the depth order; `soft_eps`, `background_color`, `near` and `far` come from the renderer.  The geometry is the
-        front-end's, without the fill_back copies; `anti_aliasing` and `shading` are ignored."""
+        front-end's, without the fill_back copies; `anti_aliasing` and `shading` are ignored.
+
+        per_pixel=True: the colour varies inside a face -- three lit colours per face, one per corner, interpolated
+        perspective-correctly at every pixel (soft_render with corner colours), and `shading` is honoured.  A VertexColors
+        gives exactly the corner colours render() would rasterize (lit per face with 'flat', at the vertices with 'smooth';
+        from `lights` when set).  A tensor [B,F,3,3] / [1,F,3,3] / [F,3,3] gives the corner colours themselves, a tensor of
+        face colours [B,F,3] / [1,F,3] / [F,3] the face colour at all three corners; both are multiplied by the light, per
+        face with 'flat', per corner with 'smooth'.  (With exactly three faces a [3,3,3] tensor reads as face colours.)
+        Texture cubes raise ValueError: they are not sampled per pixel."""
+        if per_pixel:
+            nf = faces.shape[1]
+            projected, corner = self._soft_corner_colors(vertices, faces, colors)
+            return soft_render(projected[:, :nf], corner[:, :nf], self.image_size,
+                               self.soft_sigma if sigma is None else sigma, self.soft_gamma if gamma is None else gamma,
+                               self.near, self.far, self.soft_eps, self.background_color)
         nf = faces.shape[1]
         color = self._soft_face_colors(vertices, faces, colors)
         if self.lights is not None:

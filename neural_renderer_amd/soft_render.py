@@ -5,7 +5,8 @@ the image.  Here the image can pull a hidden face forward and push an occluder b
 
 `faces` [B,F,3,3] are the rasterizer's own input -- x, y in NDC with y up, z the positive camera depth -- WITHOUT fill_back
 copies, exactly as soft_silhouettes takes them; `colors` [B,F,3], or [1,F,3] shared by the batch and read in place, one RGB
-colour per face.  The output is rgba [B,4,S,S], row 0 the top row, rendered at S directly (no anti-aliasing); pixel centres
+colour per face -- or corner colours [B,F,3,3] / [1,F,3,3], indexed (image, face, corner, rgb), interpolated at every pixel
+(below).  The output is rgba [B,4,S,S], row 0 the top row, rendered at S directly (no anti-aliasing); pixel centres
 (2 i + 1 - S) / S.
 
     A face contributes iff its nine coordinates are finite, near <= z_k <= far at its three vertices and its doubled area
@@ -29,13 +30,22 @@ colour per face.  The output is rgba [B,4,S,S], row 0 the top row, rendered at S
     dzn/dzp = -1 / (far - near), dzp/diz = -zp^2, diz/dz_k = -lambda_k / z_k^2; diz also reaches x and y, through lambda
     inside and through t outside where 0 < t < 1 -- a clamped t has derivative 0.
 
-sigma, gamma, eps, near, far and the background colour are host numbers without gradients.  On float32 CUDA tensors inside
-the ranges of include/nr_hip.h both directions are HIP kernels (nr_soft_render_*); `soft_render_torch` serves everything else
-in plain torch with the same definition.  No host tables: a first call may be captured (graph.capture) -- but capture before
-any eager backward on the same leaves, or make the eager calls under no_grad, as for soft_silhouettes (DESIGN "Soft
-silhouettes", Stream capture).
+    Corner colours: for a taken pair u_k = lambda_k / z_k, mu_k = u_k zp (the perspective-correct weights, sum 1) and
+      C_f(p) = (mu_0 C_f0 + mu_1 C_f1) + mu_2 C_f2 per channel
+    stands where C_f stood: inside the colour the rasterizer would interpolate, outside the colour at the nearest boundary
+    point -- continuous across every edge, single-valued because the nearest point of a triangle is unique.  Gradient: with
+    h = g_rgb . (C_f(p) - rgb), dL/dC_fk += W mu_k g_rgb; with E_k = W zp (g_rgb . (C_fk - C_f(p))) and d_k = diz + E_k,
+    dL/dlambda_k = d_k / z_k and dL/dz_k = -d_k lambda_k / z_k^2; inside dL/dc_i = (dL/dlambda_v(i) - diz iz) / A with
+    v(0) = 2, v(1) = 0, v(2) = 1; outside with a free t on a -> b, dL/dt = d_b / z_b - d_a / z_a.  Three equal corner colours
+    give E_k = 0 and the flat gradient.
 
-Not done: per-corner colours or textures sampled at the pixel, a learnable sigma / gamma, anti-aliasing, a spatial index.
+sigma, gamma, eps, near, far and the background colour are host numbers without gradients.  On float32 CUDA tensors inside
+the ranges of include/nr_hip.h both directions are HIP kernels (nr_soft_render_*, for corner colours nr_soft_corners_*);
+`soft_render_torch` serves everything else in plain torch with the same definition.  No host tables: a first call may be
+captured (graph.capture) -- but capture before any eager backward on the same leaves, or make the eager calls under no_grad,
+as for soft_silhouettes (DESIGN "Soft silhouettes", Stream capture).
+
+Not done: textures sampled at the pixel, a learnable sigma / gamma, anti-aliasing, a spatial index.
 """
 import math
 
@@ -78,7 +88,11 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
     iz = 1 / torch.where(on[:, :, None], z, one)
     v = [[xy[:, None, None, :, k, c] for c in range(2)] for k in range(3)]   # [B,1,1,F]
     izv = [iz[:, None, None, :, k] for k in range(3)]
-    col = colors.to(faces.dtype).expand(B, F, 3)[:, None, None]              # [B,1,1,F,3]
+    corners = colors.dim() == 4
+    if corners:
+        col = colors.to(faces.dtype).expand(B, F, 3, 3)[:, None, None]       # [B,1,1,F,3 corners,3]
+    else:
+        col = colors.to(faces.dtype).expand(B, F, 3)[:, None, None]          # [B,1,1,F,3]
     on = on[:, None, None, :]
     centre = (2 * torch.arange(S, device=faces.device, dtype=torch.float64) + 1 - S) / S
     centre = centre.to(faces.dtype)
@@ -102,7 +116,8 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
         l0 = torch.where(inside, c1 / A, torch.where(k0, 1 - t, torch.where(s2, t, zero)))
         l1 = torch.where(inside, c2 / A, torch.where(k1, 1 - t, torch.where(k0, t, zero)))
         l2 = torch.where(inside, c0 / A, torch.where(s2, 1 - t, torch.where(k1, t, zero)))
-        zp = 1 / (l0 * izv[0] + l1 * izv[1] + l2 * izv[2])
+        u0, u1, u2 = l0 * izv[0], l1 * izv[1], l2 * izv[2]
+        zp = 1 / (u0 + u1 + u2)
         zn = (far - zp) / (far - near)
         taken = on & (inside | (d.detach() <= REACH * sigma))
         x = torch.where(inside, d, -d) / sigma
@@ -110,7 +125,12 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
         w = torch.where(taken, torch.sigmoid(x) * torch.exp(torch.where(taken, (zn - m[..., None]) / gamma, zero)), zero)
         wb = torch.exp((eps - m) / gamma)
         Z = wb + w.sum(3)
-        rgb = [(wb * bg[c] + (w * col[..., c]).sum(3)) / Z for c in range(3)]
+        if corners:   # the colour at the pixel: the perspective-correct weights mu_k = u_k zp
+            mu0, mu1, mu2 = u0 * zp, u1 * zp, u2 * zp
+            at = [mu0 * col[..., 0, c] + mu1 * col[..., 1, c] + mu2 * col[..., 2, c] for c in range(3)]
+        else:
+            at = [col[..., c] for c in range(3)]
+        rgb = [(wb * bg[c] + (w * at[c]).sum(3)) / Z for c in range(3)]
         # alpha = 1 - Q as in soft_silhouettes_torch: the value from the product, the derivative from Q times the logarithms
         q = torch.where(taken, torch.sigmoid(-x), torch.ones_like(x)).prod(3).detach()
         ln_q = torch.where(taken, torch.nn.functional.logsigmoid(-x), torch.zeros_like(x)).sum(3)
@@ -123,8 +143,8 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
 # HIP
 
 class _SoftRender(torch.autograd.Function):
-    """forward(ctx, faces [B,F,3,3], colors [B|1,F,3], image_size, sigma, gamma, near, far, eps, background) -> rgba
-    [B,4,S,S], row 0 the top row."""
+    """forward(ctx, faces [B,F,3,3], colors [B|1,F,3] or [B|1,F,3,3], image_size, sigma, gamma, near, far, eps, background)
+    -> rgba [B,4,S,S], row 0 the top row.  4-dim colours take the nr_soft_corners_* entries, 3-dim ones nr_soft_render_*."""
 
     @staticmethod
     def forward(ctx, faces, colors, image_size, sigma, gamma, near, far, eps, background):
@@ -132,35 +152,36 @@ class _SoftRender(torch.autograd.Function):
         f, c = _lib.dense(faces.detach()), _lib.dense(colors.detach())
         B, F, S = int(f.shape[0]), int(f.shape[1]), image_size
         per_batch = 1 if int(c.shape[0]) == B else 0   # else [1,F,3]: one set for the batch, read in place
+        entry = 'nr_soft_corners' if c.dim() == 4 else 'nr_soft_render'
         rgba = torch.empty((B, 4, S, S), dtype=torch.float32, device=f.device)
         q = torch.empty((B, S, S), dtype=torch.float32, device=f.device)
         norm = torch.empty((B, 2, S, S), dtype=torch.float32, device=f.device)
         with torch.cuda.device(f.device):
-            wsb = lib.nr_soft_render_workspace_bytes(B, F, S)
+            wsb = getattr(lib, entry + '_workspace_bytes')(B, F, S)
             ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(lib.nr_soft_render_forward(
+            _lib.check(getattr(lib, entry + '_forward')(
                 f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(), B, F, S, per_batch, sigma, gamma,
                 near, far, eps, background[0], background[1], background[2], ws.data_ptr(), wsb,
-                torch.cuda.current_stream(f.device).cuda_stream), 'nr_soft_render_forward')
+                torch.cuda.current_stream(f.device).cuda_stream), entry + '_forward')
         ctx.save_for_backward(f, c, rgba, q, norm)
-        ctx.args = (S, per_batch, sigma, gamma, near, far, eps, background)
+        ctx.args = (S, per_batch, sigma, gamma, near, far, eps, background, entry)
         return rgba.flip(2)
 
     @staticmethod
     def backward(ctx, grad_rgba):
         lib = _lib.load()
         f, c, rgba, q, norm = ctx.saved_tensors
-        S, per_batch, sigma, gamma, near, far, eps, background = ctx.args
+        S, per_batch, sigma, gamma, near, far, eps, background, entry = ctx.args
         B, F = int(f.shape[0]), int(f.shape[1])
         g = _lib.dense(grad_rgba.flip(2))
         grad_faces, grad_colors = torch.empty_like(f), torch.empty_like(c)
         with torch.cuda.device(f.device):
-            wsb = lib.nr_soft_render_workspace_bytes(B, F, S)
+            wsb = getattr(lib, entry + '_workspace_bytes')(B, F, S)
             ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(lib.nr_soft_render_backward(
+            _lib.check(getattr(lib, entry + '_backward')(
                 f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(), g.data_ptr(), grad_faces.data_ptr(),
                 grad_colors.data_ptr(), B, F, S, per_batch, sigma, gamma, near, far, eps, background[0], background[1],
-                background[2], ws.data_ptr(), wsb, torch.cuda.current_stream(f.device).cuda_stream), 'nr_soft_render_backward')
+                background[2], ws.data_ptr(), wsb, torch.cuda.current_stream(f.device).cuda_stream), entry + '_backward')
         return (grad_faces, grad_colors) + (None,) * 7
 
 
@@ -174,9 +195,10 @@ def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, backgr
             and faces.shape[0] >= 1 and faces.shape[1] >= 1):
         raise ValueError('%s: faces must be a non-empty float tensor [batch size, num of faces, 3, 3]' % name)
     B, F = int(faces.shape[0]), int(faces.shape[1])
-    if not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() == 3
-            and tuple(colors.shape[1:]) == (F, 3) and colors.shape[0] in (1, B)):
-        raise ValueError('%s: colors must be a float tensor [batch size or 1, num of faces (%d), 3]' % (name, F))
+    if not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() in (3, 4)
+            and tuple(colors.shape[1:]) in ((F, 3), (F, 3, 3)) and colors.shape[0] in (1, B)):
+        raise ValueError('%s: colors must be a float tensor [batch size or 1, num of faces (%d), 3], or [batch size or 1, '
+                         'num of faces, 3, 3] for corner colours' % (name, F))
     if colors.device != faces.device:
         raise ValueError('%s: colors on %s, faces on %s' % (name, colors.device, faces.device))
     if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
@@ -214,7 +236,8 @@ def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, backgr
 def soft_render(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
                 background_color=(0, 0, 0), implementation=None):
     """rgba [B,4,S,S] (row 0 the top row): faces [B,F,3,3] -- the rasterizer's input, without fill_back copies -- with one
-    colour per face, colors [B,F,3] or [1,F,3], aggregated by coverage and depth (module docstring).  Differentiable in
+    colour per face, colors [B,F,3] or [1,F,3] -- or one per corner, [B,F,3,3] or [1,F,3,3], interpolated
+    perspective-correctly at every pixel --, aggregated by coverage and depth (module docstring).  Differentiable in
     faces (x, y and z) and colors, once.  sigma (squared NDC units) sets the width of the coverage's transition, gamma the
     sharpness of the depth order (in units of the normalised depth), eps the background's place in that order; host floats
     without gradients, like near, far and background_color.  `implementation`: None picks the HIP kernels for float32 CUDA
