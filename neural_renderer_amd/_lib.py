@@ -188,13 +188,15 @@ def load():
     return lib
 
 
-# the measurement build's two extra exports (include/nr_hip_profile.h)
+# the measurement build's extra exports (include/nr_hip_profile.h)
 PROFILE_SIGNATURES = {
     'nr_profile_band_kernel': (_c.c_int, [_i32]),
     'nr_profile_band_kernel_ms': (_c.c_float, []),
     'nr_profile_band_kernel_which': (_c.c_int, []),
     'nr_profile_k6_choice': (_c.c_int, [_i32, _i32, _i32, _i32, _i32, _c.c_double, _i32]),
+    'nr_profile_backward_plan': (_c.c_int, [_i32] * 7 + [_f64] + [_i32] * 5 + [_sz, _c.POINTER(_c.c_int64)]),
 }
+NR_PLAN_FIELDS = 35  # include/nr_hip_profile.h
 _profile_lib = None
 
 

@@ -225,15 +225,15 @@ NR_API int nr_backward_rasterize(const float *faces, const float *faces_z_ref, c
                                      eps, flags, visible_faces, workspace, workspace_bytes, stream);
 }
 
-NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *faces, const float *faces_z_ref,
-                                     const int32_t *face_index_map, const float *weight_map, const float *depth_map,
-                                     const float *rgb_map, const float *alpha_map, const float *grad_rgb_map,
-                                     const float *grad_alpha_map, const float *grad_depth_map, float *grad_faces,
-                                     float *grad_textures, int32_t B, int32_t F, int32_t S, int32_t ts, double eps,
-                                     int32_t flags, const uint8_t *visible_faces, void *workspace, size_t workspace_bytes,
-                                     void *stream)
+// The fused call as plan_backward and run_backward see it: what the entry point below hands on (and what the measurement build's
+// nr_profile_backward_plan plans without launching)
+static int fused_call(const nr_face_light *lit, const float *faces, const float *faces_z_ref, const int32_t *face_index_map,
+                      const float *weight_map, const float *depth_map, const float *rgb_map, const float *alpha_map,
+                      const float *grad_rgb_map, const float *grad_alpha_map, const float *grad_depth_map, float *grad_faces,
+                      float *grad_textures, int32_t B, int32_t F, int32_t S, int32_t ts, double eps, int32_t flags,
+                      const uint8_t *visible_faces, void *workspace, size_t workspace_bytes, void *stream, BackwardCall &c)
 {
-    BackwardCall c = {};
+    c = {};
     // per-face light colours: only the texture gather sees them (the geometry gradients do not)
     if (int e = face_light_args(grad_rgb_map && grad_textures ? lit : nullptr, F, true, c.lit)) return e;
     c.stages = STAGE_ALL, c.rgb = grad_rgb_map != nullptr, c.alpha = grad_alpha_map != nullptr;
@@ -243,5 +243,59 @@ NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *face
     c.grad_faces = grad_faces, c.grad_textures = grad_textures;
     c.B = B, c.F = F, c.S = S, c.ts = ts, c.eps = eps, c.flags = flags, c.visible_faces = visible_faces;
     c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.st = (hipStream_t)stream;
+    return 0;
+}
+
+NR_API int nr_backward_rasterize_lit(const nr_face_light *lit, const float *faces, const float *faces_z_ref,
+                                     const int32_t *face_index_map, const float *weight_map, const float *depth_map,
+                                     const float *rgb_map, const float *alpha_map, const float *grad_rgb_map,
+                                     const float *grad_alpha_map, const float *grad_depth_map, float *grad_faces,
+                                     float *grad_textures, int32_t B, int32_t F, int32_t S, int32_t ts, double eps,
+                                     int32_t flags, const uint8_t *visible_faces, void *workspace, size_t workspace_bytes,
+                                     void *stream)
+{
+    BackwardCall c;
+    if (int e = fused_call(lit, faces, faces_z_ref, face_index_map, weight_map, depth_map, rgb_map, alpha_map, grad_rgb_map,
+                           grad_alpha_map, grad_depth_map, grad_faces, grad_textures, B, F, S, ts, eps, flags, visible_faces,
+                           workspace, workspace_bytes, stream, c))
+        return e;
     return run_backward(c);
 }
+
+// Measurement build only (include/nr_hip_profile.h): the plan of a fused call, read without a launch and without a device.  The
+// pointers are stand-ins that nothing dereferences: plan_backward looks at which are given and at grad_textures' low bits.
+#ifdef NR_PROFILE_HOOK
+#include "../../include/nr_hip_profile.h"
+NR_API int nr_profile_backward_plan(int32_t B, int32_t F, int32_t S, int32_t ts, int32_t grad_rgb, int32_t grad_alpha,
+                                    int32_t grad_depth, double eps, int32_t flags, int32_t light_texture_faces, int32_t grad_light,
+                                    int32_t grad_textures_low_bits, int32_t visible_faces, size_t workspace_bytes, int64_t *out)
+{
+    if (!out) return NR_E_NULL;
+    for (int i = 0; i < NR_PLAN_FIELDS; ++i) out[i] = -1;
+    float *const given = reinterpret_cast<float *>((uintptr_t)1 << 20);  // a 16-byte aligned stand-in address
+    float *const gt = grad_textures_low_bits < 0 ? nullptr  // (a call whose colours come from another shading source: no K7)
+                                                 : reinterpret_cast<float *>(((uintptr_t)1 << 21) + (uintptr_t)(grad_textures_low_bits & 15));
+    nr_face_light lit = {};
+    lit.light = given, lit.texture_faces = light_texture_faces, lit.textures = given, lit.grad_light = grad_light ? given : nullptr;
+    if (workspace_bytes == 0) workspace_bytes = nr_backward_workspace_bytes(B, F, S, grad_rgb != 0, grad_alpha != 0);
+    BackwardCall c;
+    if (int e = fused_call(light_texture_faces ? &lit : nullptr, given, nullptr, (const int32_t *)given, given, given, given, given,
+                           grad_rgb ? given : nullptr, grad_alpha ? given : nullptr, grad_depth ? given : nullptr, given,
+                           gt, B, F, S, ts, eps, flags, visible_faces ? (const uint8_t *)given : nullptr,
+                           given, workspace_bytes, nullptr, c))
+        return e;
+    BackwardPlan p;
+    if (int e = plan_backward(c, p)) return e;
+    const K6Plan &k = p.k6p;
+    const int64_t v[NR_PLAN_FIELDS] = {
+        p.k6, p.k6 ? k.kernel : -1, k.use_records, k.overflow_pass, k.row_chunked, p.k6 ? k.shape.threads : 0,
+        p.bands, p.face_zeros, p.gather_first, p.gather_in_tail, p.setup_alone, p.setup_in_gather, p.tex_zeros, p.light_fill,
+        p.gather, p.listed, p.static_taps, p.lanes, p.depth_in_gather, p.big, p.big_overflow, p.finish, p.depth, p.fill_faces,
+        p.depth_lists,
+        (int64_t)p.tex_bytes, (int64_t)p.gather_lds, (int64_t)k.fast_lds, (int64_t)k.row_lds, (int64_t)k.fill_max, k.W_fast, k.W_row,
+        k.W, k.n_bands,
+        p.bands && k.use_records ? (int64_t)k6_line_setup_args(c, k).lds_bytes : 0};
+    for (int i = 0; i < NR_PLAN_FIELDS; ++i) out[i] = v[i];
+    return 0;
+}
+#endif

@@ -106,24 +106,53 @@ def host(t):
     return None if t is None else t.detach().cpu().numpy()
 
 
-def backward_fused(fw, g_rgb=None, g_alpha=None, g_depth=None, k6_flags=0, use_visible=True):
-    """nr_backward_rasterize (K6 -> K7 -> K8 behind one call) on the residuals of `forward`."""
+def backward_fused(fw, g_rgb=None, g_alpha=None, g_depth=None, k6_flags=0, use_visible=True, tex_offset=0, workspace_bytes=None,
+                   face_light=None):
+    """nr_backward_rasterize (K6 -> K7 -> K8 behind one call) on the residuals of `forward`.
+    tex_offset: grad_textures starts that many floats off a 16-byte boundary (1: 4 bytes off the grid).
+    workspace_bytes: the size of the workspace handed over (None: what nr_backward_workspace_bytes asks for).
+    face_light: per-face light colours (nr_backward_rasterize_lit) -- dict(light=[B, F, 3], textures=the original cubes
+    [B, Nf, ts, ts, ts, 3], grad_light=bool): grad_textures is then the original cubes' gradient and a third value, grad_light
+    [B, F, 3] or None, is returned."""
     lib = _lib.load()
     B, F, S, ts = fw['B'], fw['F'], fw['S'], fw['ts']
     gr = dev(g_rgb, torch.float32) if g_rgb is not None else None
     ga = dev(g_alpha, torch.float32) if g_alpha is not None else None
     gd = dev(g_depth, torch.float32) if g_depth is not None else None
     grad_faces = torch.full((B, F, 3, 3), float('nan'), device='cuda')
-    grad_textures = torch.full((B, F, ts, ts, ts, 3), float('nan'), device='cuda') if gr is not None else None
-    wsb = lib.nr_backward_workspace_bytes(B, F, S, int(gr is not None), int(ga is not None))
+    grad_textures = grad_light = lit = None
+    keep = []
+    if gr is not None:
+        shape = (B, F, ts, ts, ts, 3)
+        if face_light is not None:
+            light, cubes = dev(face_light['light'], torch.float32), dev(face_light['textures'], torch.float32)
+            keep += [light, cubes]
+            shape = tuple(cubes.shape)
+            if face_light.get('grad_light'):
+                grad_light = torch.full((B, F, 3), float('nan'), device='cuda')
+            lit = _lib.FaceLight(light.data_ptr(), shape[1], cubes.data_ptr(), _lib.ptr(grad_light))
+        n = int(np.prod(shape))
+        flat = torch.full((n + 4,), float('nan'), device='cuda')
+        grad_textures = flat[tex_offset:tex_offset + n].view(shape)
+        assert grad_textures.data_ptr() % 16 == 4 * tex_offset % 16
+    wsb = lib.nr_backward_workspace_bytes(B, F, S, int(gr is not None), int(ga is not None)) if workspace_bytes is None \
+        else workspace_bytes
     ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device='cuda')
-    _lib.check(lib.nr_backward_rasterize(
-        fw['faces'].data_ptr(), _lib.ptr(fw.get('faces_z_ref')), fw['face_index_map'].data_ptr(),
-        _lib.ptr(fw.get('weight_map')), _lib.ptr(fw.get('depth_map')), _lib.ptr(fw.get('rgb_map')),
-        _lib.ptr(fw.get('alpha_map')), _lib.ptr(gr), _lib.ptr(ga), _lib.ptr(gd), grad_faces.data_ptr(),
-        _lib.ptr(grad_textures), B, F, S, ts, fw['eps'], fw['flags'] | k6_flags,
-        _lib.ptr(fw.get('visible_faces')) if use_visible else None, ws.data_ptr(), wsb, _stream()), 'bwd fused')
+    args = (fw['faces'].data_ptr(), _lib.ptr(fw.get('faces_z_ref')), fw['face_index_map'].data_ptr(),
+            _lib.ptr(fw.get('weight_map')), _lib.ptr(fw.get('depth_map')), _lib.ptr(fw.get('rgb_map')),
+            _lib.ptr(fw.get('alpha_map')), _lib.ptr(gr), _lib.ptr(ga), _lib.ptr(gd), grad_faces.data_ptr(),
+            _lib.ptr(grad_textures), B, F, S, ts, fw['eps'], fw['flags'] | k6_flags,
+            _lib.ptr(fw.get('visible_faces')) if use_visible else None, ws.data_ptr(), wsb, _stream())
+    if face_light is None:
+        _lib.check(lib.nr_backward_rasterize(*args), 'bwd fused')
+    else:
+        _lib.check(lib.nr_backward_rasterize_lit(lit, *args), 'bwd fused lit')
     torch.cuda.synchronize()
+    if grad_textures is not None:  # the guard words around grad_textures: a 16-byte fill must not round its ends outwards
+        n = grad_textures.numel()
+        assert bool(torch.isnan(flat[:tex_offset]).all()) and bool(torch.isnan(flat[tex_offset + n:]).all()), 'a store outside grad_textures'
+    if face_light is not None:
+        return grad_faces, grad_textures, grad_light
     return grad_faces, grad_textures
 
 

@@ -195,6 +195,28 @@ def above_1e4(got, ref_d):
     return int((np.abs(got[ok] - ref_d[ok]) > 1e-4 * np.abs(ref_d[ok])).sum())
 
 
+def grad_faces_bounds(ref_float, ref_d):
+    """(noise, bound of the default mode, bound of the exact mode) for grad_faces in the parity metric (rel_err): the north
+    star's 1e-4 (the exact mode with a depth gradient: 2e-5) of the reference's terms summed exactly (`ref_d`:
+    accumulate_double=True), plus twice the reference's own float-summation noise on the scene -- `ref_float`, its serial float
+    sums, against the same exact sum (test_fuzz_gpu.py::test_fuzz_unusual_parameters has the reasoning)."""
+    okn = np.isfinite(ref_d) & np.isfinite(ref_float)
+    noise = rel_err(ref_float[okn], ref_d[okn]) if okn.any() else 0.0
+    return noise, 1e-4 + 2 * noise, 2e-5 + 2 * noise
+
+
+def err_default(got, ref_d, ref_k6, ok):
+    """The default mode's grad_faces error over the entries `ok`: against the larger of the total (`ref_d`) and its K6 part
+    (`ref_k6`: the same call with a zero depth gradient), element by element, floor at 1e-3 of the larger maximum -- K6's
+    sums and K8's can cancel (test_fuzz_gpu.py::test_fuzz_unusual_parameters)."""
+    okk = ok & np.isfinite(ref_k6)
+    if not okk.any():
+        return 0.0
+    mag = np.maximum(np.abs(ref_d[okk]), np.abs(ref_k6[okk]))
+    den = np.maximum(mag, 1e-3 * mag.max())
+    return float((np.abs(got[okk] - ref_d[okk]) / np.where(den > 0, den, 1.0)).max())
+
+
 _display = None
 
 

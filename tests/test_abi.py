@@ -83,7 +83,8 @@ def test_host_only_entry_points(lib_path):
     assert lib.nr_forward_workspace_bytes(1, 1, 20000) == 0
     # the measurement hook is not part of the product library (include/nr_hip_profile.h: libnr_hip_prof.so only)
     assert not any(hasattr(lib, n) for n in ('nr_profile_band_kernel', 'nr_profile_band_kernel_ms', 'nr_profile_band_kernel_which',
-                                             'nr_profile_k6_choice'))
+                                             'nr_profile_k6_choice', 'nr_profile_backward_plan'))
+    assert hasattr(_lib.load_profile(), 'nr_profile_backward_plan')
 
 
 def test_k6_band_kernel_choice_table(lib_path):
