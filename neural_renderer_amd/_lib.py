@@ -13,7 +13,6 @@ _c = ctypes
 _vp, _i32, _f64, _sz = _c.c_void_p, _c.c_int32, _c.c_double, _c.c_size_t
 
 
-
 class Camera(_c.Structure):
     """struct nr_camera (include/nr_hip.h)."""
     _fields_ = [('mode', _i32), ('perspective', _i32), ('target', _c.c_float * 3), ('up', _c.c_float * 3),
@@ -231,6 +230,53 @@ def check(code, what):
 def ptr(t):
     """data_ptr of a tensor or None."""
     return None if t is None else t.data_ptr()
+
+
+_RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
+
+
+def stream_ptr(device):
+    """hipStream_t of torch's current stream on `device` (the raw query: no Stream object per call)."""
+    if _RAW_STREAM is not None:
+        return _RAW_STREAM(device.index)
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+class _NoGuard(object):
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        return False
+
+
+_NO_GUARD = _NoGuard()
+
+
+def on_device(device):
+    """Context that makes `device` the current HIP device for the launches -- nothing at all when it already is (one process
+    per GPU: always), torch.cuda.device otherwise."""
+    return _NO_GUARD if torch.cuda.current_device() == device.index else torch.cuda.device(device)
+
+
+def workspace_bytes(name, *sizes):
+    """What the host-only size query `name` (an nr_*_workspace_bytes entry) answers for `sizes`."""
+    return getattr(load(), name)(*sizes)
+
+
+def launch(name, device, *args, workspace_bytes=None):
+    """Call entry point `name` for tensors on `device`: makes `device` current for the call (no guard when it already is), passes
+    torch's current stream on it as the last argument, raises through check().  The entry is looked up on the loaded library
+    at every call (tests and tools replace its attributes).  workspace_bytes None: the entry has no workspace parameters.
+    An int (0 allowed): a fresh uint8 workspace of max(bytes, 1) on `device`, allocated inside the guard and alive until
+    the call returns, passed as (pointer, bytes) in front of the stream -- include/nr_hip.h's trailing convention."""
+    with on_device(device):
+        fn = getattr(load(), name)
+        if workspace_bytes is None:
+            check(fn(*args, stream_ptr(device)), name)
+        else:
+            ws = torch.empty((max(workspace_bytes, 1),), dtype=torch.uint8, device=device)
+            check(fn(*args, ws.data_ptr(), workspace_bytes, stream_ptr(device)), name)
 
 
 def dense(t):

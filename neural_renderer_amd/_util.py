@@ -1,5 +1,10 @@
+import math
+
 import numpy as np
 import torch
+
+SOFT_MAX_FACES = 2 ** 24    # the soft operators' limits (include/nr_hip.h)
+SOFT_MAX_SIZE = 16384
 
 
 def normalize(x, eps=1e-5):
@@ -13,6 +18,28 @@ def as_tensor_like(value, ref, dtype=torch.float32):
     if torch.is_tensor(value):
         return value.to(device=ref.device, dtype=dtype)
     return torch.as_tensor(np.asarray(value, dtype=np.float32), device=ref.device).to(dtype)
+
+
+def number(name, what, v):
+    """float(v) of a host number for the operator `name`'s argument `what`; a bool, a NaN or anything else raises."""
+    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
+        raise ValueError('%s: %s must be a number, got %r' % (name, what, v))
+    return float(v)
+
+
+def check_implementation(name, implementation):
+    """The first half of takes_hip, for an operator that raises other argument errors before it knows whether the call fits."""
+    if implementation not in (None, 'torch', 'hip'):
+        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
+
+
+def takes_hip(name, implementation, fits, needs):
+    """True when the call takes the HIP kernels: `fits` them and is not sent to 'torch'.  Raises ValueError for an unknown
+    `implementation`, and for 'hip' when `fits` is false with `needs`, the operator's own sentence."""
+    check_implementation(name, implementation)
+    if implementation == 'hip' and not fits:
+        raise ValueError('%s: %s' % (name, needs))
+    return fits and implementation != 'torch'
 
 
 _INDEX_ATTR = '_nr_index_ok'  # verdict stashed on a tensor OBJECT: it dies with the tensor (a cache keyed on data_ptr would

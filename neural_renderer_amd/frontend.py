@@ -33,7 +33,7 @@ def _vec3(value):
     return arr if arr.shape == (3,) else None
 
 
-def _number(value):
+def _is_number(value):
     return isinstance(value, (int, float, np.integer, np.floating)) and not isinstance(value, bool)
 
 
@@ -64,12 +64,12 @@ def _projection_fusable(renderer, batch_size):
     if d is not None and ((torch.is_tensor(d) and d.requires_grad) or _projection_layout(d, batch_size, (5,)) is None):
         return False  # (a learnable dist_coeffs: the torch path gives its gradient)
     size = renderer.orig_size
-    return _number(size) and 0 < float(size) < float('inf')
+    return _is_number(size) and 0 < float(size) < float('inf')
 
 
 def light_fusable(renderer):
     """The light parameters are host numbers / 3-vectors, as the fused kernels take them (nr_light)."""
-    if not (_number(renderer.light_intensity_ambient) and _number(renderer.light_intensity_directional)):
+    if not (_is_number(renderer.light_intensity_ambient) and _is_number(renderer.light_intensity_directional)):
         return False
     return all(_vec3(v) is not None for v in (renderer.light_color_ambient, renderer.light_color_directional,
                                               renderer.light_direction))
@@ -98,7 +98,7 @@ def fusable(renderer, vertices, faces, textures):
             return False
     elif renderer.camera_mode != 'look_at':
         return False
-    if renderer.perspective and not _number(renderer.viewing_angle):
+    if renderer.perspective and not _is_number(renderer.viewing_angle):
         return False
     eye = renderer.eye
     if torch.is_tensor(eye):
@@ -187,7 +187,6 @@ class _FrontEnd(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, textures, faces_idx, setup, *camera):
-        lib = _lib.load()
         cam, dist, light, fill_back, colors = setup
         dev = vertices.device
         v = _lib.dense(vertices.detach())
@@ -204,19 +203,17 @@ class _FrontEnd(torch.autograd.Function):
         light_out = torch.empty((B, F, 3), dtype=torch.float32, device=dev) if colors else None
         proj = _projection_struct(*camera, d, cam) if len(camera) == 3 else None
         if proj is not None:
-            fn, args = lib.nr_frontend_forward_projection, (_lib.ptr(tex), faces_out.data_ptr(), _lib.ptr(tex_out),
-                                                            _lib.ptr(light_out), B, Nv, Nf, ts, 1, int(fill_back), proj)
+            fn, args = 'nr_frontend_forward_projection', (_lib.ptr(tex), faces_out.data_ptr(), _lib.ptr(tex_out),
+                                                          _lib.ptr(light_out), B, Nv, Nf, ts, 1, int(fill_back), proj)
         else:
             e = camera[0]
             if colors:
-                fn, args = lib.nr_frontend_forward_light, (e.data_ptr(), faces_out.data_ptr(), light_out.data_ptr(), B, Nv,
-                                                           Nf, 1, int(e.dim() == 2), int(fill_back), cam)
+                fn, args = 'nr_frontend_forward_light', (e.data_ptr(), faces_out.data_ptr(), light_out.data_ptr(), B, Nv,
+                                                         Nf, 1, int(e.dim() == 2), int(fill_back), cam)
             else:
-                fn, args = lib.nr_frontend_forward, (_lib.ptr(tex), e.data_ptr(), faces_out.data_ptr(), _lib.ptr(tex_out),
-                                                     B, Nv, Nf, ts, 1, int(e.dim() == 2), int(fill_back), cam)
-        with torch.cuda.device(dev):
-            _lib.check(fn(v.data_ptr(), idx.data_ptr(), *args, light, torch.cuda.current_stream(dev).cuda_stream),
-                       fn.__name__)
+                fn, args = 'nr_frontend_forward', (_lib.ptr(tex), e.data_ptr(), faces_out.data_ptr(), _lib.ptr(tex_out),
+                                                   B, Nv, Nf, ts, 1, int(e.dim() == 2), int(fill_back), cam)
+        _lib.launch(fn, dev, v.data_ptr(), idx.data_ptr(), *args, light)
         ctx.save_for_backward(v, idx, tex, d, *camera)
         ctx.params = (cam, light, proj, bool(fill_back), bool(colors), B, Nv, Nf, ts)
         ctx.set_materialize_grads(False)
@@ -224,7 +221,6 @@ class _FrontEnd(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g_faces, g_second):
-        lib = _lib.load()
         v, idx, tex, _, *camera = ctx.saved_tensors
         cam, light, proj, fill_back, colors, B, Nv, Nf, ts = ctx.params
         dev = v.device
@@ -246,25 +242,23 @@ class _FrontEnd(torch.autograd.Function):
         grad_cam = tuple(torch.empty_like(x) if n else None for x, n in zip(camera, need[4:]))
         ws_bytes = 0
         if need_cam:
-            ws_bytes = (lib.nr_frontend_projection_workspace_bytes if proj is not None else lib.nr_frontend_workspace_bytes)(B)
-        ws = torch.empty((max(ws_bytes, 1),), dtype=torch.uint8, device=dev)
+            ws_bytes = _lib.workspace_bytes('nr_frontend_projection_workspace_bytes' if proj is not None else
+                                            'nr_frontend_workspace_bytes', B)
         if proj is not None:
-            fn, args = lib.nr_frontend_backward_projection, (
+            fn, args = 'nr_frontend_backward_projection', (
                 _lib.ptr(tex), g_faces.data_ptr(), _lib.ptr(g_tex_out), _lib.ptr(g_light), _lib.ptr(grad_v), _lib.ptr(grad_tex),
                 *(_lib.ptr(g) for g in grad_cam), B, Nv, Nf, ts, 1, int(fill_back), proj)
         else:
             e = camera[0]
             if colors:
-                fn, args = lib.nr_frontend_backward_light, (e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_light),
-                                                            grad_v.data_ptr(), _lib.ptr(grad_cam[0]), B, Nv, Nf, 1,
-                                                            int(e.dim() == 2), int(fill_back), cam)
+                fn, args = 'nr_frontend_backward_light', (e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_light),
+                                                          grad_v.data_ptr(), _lib.ptr(grad_cam[0]), B, Nv, Nf, 1,
+                                                          int(e.dim() == 2), int(fill_back), cam)
             else:
-                fn, args = lib.nr_frontend_backward, (_lib.ptr(tex), e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_tex_out),
-                                                      _lib.ptr(grad_v), _lib.ptr(grad_tex), _lib.ptr(grad_cam[0]), B, Nv, Nf,
-                                                      ts, 1, int(e.dim() == 2), int(fill_back), cam)
-        with torch.cuda.device(dev):
-            _lib.check(fn(v.data_ptr(), idx.data_ptr(), *args, light, ws.data_ptr(), ws_bytes,
-                          torch.cuda.current_stream(dev).cuda_stream), fn.__name__)
+                fn, args = 'nr_frontend_backward', (_lib.ptr(tex), e.data_ptr(), g_faces.data_ptr(), _lib.ptr(g_tex_out),
+                                                    _lib.ptr(grad_v), _lib.ptr(grad_tex), _lib.ptr(grad_cam[0]), B, Nv, Nf,
+                                                    ts, 1, int(e.dim() == 2), int(fill_back), cam)
+        _lib.launch(fn, dev, v.data_ptr(), idx.data_ptr(), *args, light, workspace_bytes=ws_bytes)
         return ((grad_v if need[0] else None), grad_tex, None, None) + grad_cam
 
 

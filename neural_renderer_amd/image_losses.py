@@ -27,7 +27,7 @@ import ctypes
 import torch
 import torch.nn.functional as F
 
-from . import _lib
+from . import _lib, _util
 
 MAX_LEVELS = 5
 
@@ -92,18 +92,15 @@ def _check(name, what, images, target, mask):
 
 
 def _use_hip(name, implementation, images, others):
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
     B, C, H, W = images.shape
     fits = (images.is_cuda and images.dtype == torch.float32 and B <= 65535 and C * H * W < 2 ** 31 and H <= 32768
             and W <= 32768)
     learnable = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in others)
-    if implementation == 'hip':
-        if not fits:
-            raise ValueError('%s: the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most' % name)
-        if learnable:
-            raise ValueError('%s: the HIP kernels give no gradient to target or mask' % name)
-    return fits and not learnable and implementation != 'torch'
+    hip = _util.takes_hip(name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at '
+                          'most')
+    if implementation == 'hip' and learnable:
+        raise ValueError('%s: the HIP kernels give no gradient to target or mask' % name)
+    return hip and not learnable
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -156,18 +153,12 @@ def _weights_array(weights):
     return (ctypes.c_double * MAX_LEVELS)(*weights)
 
 
-def _workspace(lib, B, H, W, levels, dev):
-    wsb = lib.nr_image_loss_workspace_bytes(B, H, W, levels)
-    return torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev), wsb
-
-
 class _IoULoss(torch.autograd.Function):
     """forward(ctx, alpha [B,1,H,W], target [B or 1,1,H,W], weights, eps) -> loss [B]; the target and the 2 levels sums of
     every image are kept for the backward when one can follow."""
 
     @staticmethod
     def forward(ctx, alpha, target, weights, eps):
-        lib = _lib.load()
         a, t = alpha.detach().contiguous(), target.detach().contiguous()
         dev = a.device
         B, _, H, W = a.shape
@@ -175,12 +166,9 @@ class _IoULoss(torch.autograd.Function):
         want = ctx.needs_input_grad[0]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
         sums = torch.empty((B, 2 * levels), dtype=torch.float64, device=dev) if want else None
-        with torch.cuda.device(dev):
-            ws, wsb = _workspace(lib, B, H, W, levels, dev)
-            _lib.check(lib.nr_iou_loss_forward(a.data_ptr(), t.data_ptr(), int(t.shape[0] != 1 or B == 1),
-                                               _weights_array(weights), loss.data_ptr(), _lib.ptr(sums), B, H, W, levels, eps,
-                                               ws.data_ptr(), wsb, torch.cuda.current_stream(dev).cuda_stream),
-                       'nr_iou_loss_forward')
+        _lib.launch('nr_iou_loss_forward', dev, a.data_ptr(), t.data_ptr(), int(t.shape[0] != 1 or B == 1),
+                    _weights_array(weights), loss.data_ptr(), _lib.ptr(sums), B, H, W, levels, eps,
+                    workspace_bytes=_lib.workspace_bytes('nr_image_loss_workspace_bytes', B, H, W, levels))
         if want:
             ctx.save_for_backward(t, sums)
         ctx.weights, ctx.eps, ctx.shape = weights, eps, (B, H, W)
@@ -190,17 +178,13 @@ class _IoULoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        lib = _lib.load()
         t, sums = ctx.saved_tensors
         dev = t.device
         B, H, W = ctx.shape
         g = grad_loss.contiguous()
         grad = torch.empty((B, 1, H, W), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_iou_loss_backward(t.data_ptr(), int(t.shape[0] != 1 or B == 1), sums.data_ptr(),
-                                                _weights_array(ctx.weights), g.data_ptr(), grad.data_ptr(), B, H, W,
-                                                len(ctx.weights), ctx.eps, torch.cuda.current_stream(dev).cuda_stream),
-                       'nr_iou_loss_backward')
+        _lib.launch('nr_iou_loss_backward', dev, t.data_ptr(), int(t.shape[0] != 1 or B == 1), sums.data_ptr(),
+                    _weights_array(ctx.weights), g.data_ptr(), grad.data_ptr(), B, H, W, len(ctx.weights), ctx.eps)
         return grad, None, None, None
 
 
@@ -210,20 +194,15 @@ class _SquaredError(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, images, target, mask, weights):
-        lib = _lib.load()
         x, t = images.detach().contiguous(), target.detach().contiguous()
         m = None if mask is None else mask.detach().contiguous()
         dev = x.device
         B, C, H, W = x.shape
         levels = len(weights)
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws, wsb = _workspace(lib, B, H, W, levels, dev)
-            _lib.check(lib.nr_squared_error_forward(x.data_ptr(), t.data_ptr(), _lib.ptr(m), int(t.shape[0] != 1 or B == 1),
-                                                    int(m is not None and (m.shape[0] != 1 or B == 1)),
-                                                    _weights_array(weights), loss.data_ptr(), B, C, H, W, levels,
-                                                    ws.data_ptr(), wsb, torch.cuda.current_stream(dev).cuda_stream),
-                       'nr_squared_error_forward')
+        _lib.launch('nr_squared_error_forward', dev, x.data_ptr(), t.data_ptr(), _lib.ptr(m), int(t.shape[0] != 1 or B == 1),
+                    int(m is not None and (m.shape[0] != 1 or B == 1)), _weights_array(weights), loss.data_ptr(), B, C, H, W,
+                    levels, workspace_bytes=_lib.workspace_bytes('nr_image_loss_workspace_bytes', B, H, W, levels))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(*((x, t) if m is None else (x, t, m)))
         ctx.weights = weights
@@ -233,19 +212,15 @@ class _SquaredError(torch.autograd.Function):
     def backward(ctx, grad_loss):
         if not ctx.needs_input_grad[0]:
             return None, None, None, None
-        lib = _lib.load()
         x, t = ctx.saved_tensors[:2]
         m = ctx.saved_tensors[2] if len(ctx.saved_tensors) > 2 else None
         dev = x.device
         B, C, H, W = x.shape
         g = grad_loss.contiguous()
         grad = torch.empty_like(x)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_squared_error_backward(x.data_ptr(), t.data_ptr(), _lib.ptr(m), int(t.shape[0] != 1 or B == 1),
-                                                     int(m is not None and (m.shape[0] != 1 or B == 1)),
-                                                     _weights_array(ctx.weights), g.data_ptr(), grad.data_ptr(), B, C, H, W,
-                                                     len(ctx.weights), torch.cuda.current_stream(dev).cuda_stream),
-                       'nr_squared_error_backward')
+        _lib.launch('nr_squared_error_backward', dev, x.data_ptr(), t.data_ptr(), _lib.ptr(m),
+                    int(t.shape[0] != 1 or B == 1), int(m is not None and (m.shape[0] != 1 or B == 1)),
+                    _weights_array(ctx.weights), g.data_ptr(), grad.data_ptr(), B, C, H, W, len(ctx.weights))
         return grad, None, None, None
 
 

@@ -190,7 +190,6 @@ class _LightColors(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, setup, vertices, *params):
-        lib = _lib.load()
         idx, off, ent, per_batch, flags, fill_back, smooth = setup
         v = _lib.dense(vertices.detach())
         params = tuple(None if p is None else _lib.dense(p.detach()) for p in params)
@@ -199,20 +198,15 @@ class _LightColors(torch.autograd.Function):
         Nf = idx.shape[1]
         F = 2 * Nf if fill_back else Nf
         out = torch.empty((B, F, 3, 3) if smooth else (B, F, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            wsb = lib.nr_light_colors_workspace_bytes(B, Nv, Nf, 1) if smooth else 0
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_light_colors_forward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), _lights_struct(params, flags), out.data_ptr(),
-                B, Nv, Nf, int(per_batch), int(fill_back), int(smooth), ws.data_ptr(), wsb,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_light_colors_forward')
+        _lib.launch('nr_light_colors_forward', dev, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    _lights_struct(params, flags), out.data_ptr(), B, Nv, Nf, int(per_batch), int(fill_back), int(smooth),
+                    workspace_bytes=_lib.workspace_bytes('nr_light_colors_workspace_bytes', B, Nv, Nf, 1) if smooth else 0)
         ctx.save_for_backward(v, *params)
         ctx.setup = setup
         return out
 
     @staticmethod
     def backward(ctx, grad_light):
-        lib = _lib.load()
         v, *params = ctx.saved_tensors
         idx, off, ent, per_batch, flags, fill_back, smooth = ctx.setup
         need = ctx.needs_input_grad[1:]
@@ -227,13 +221,9 @@ class _LightColors(torch.autograd.Function):
         out = _lib.LightsGrad()
         for name, t in zip(NAMES, grads):
             setattr(out, name, _lib.ptr(t))
-        with torch.cuda.device(dev):
-            wsb = lib.nr_light_colors_workspace_bytes(B, Nv, Nf, int(smooth))
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_light_colors_backward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), _lights_struct(params, flags), g.data_ptr(),
-                _lib.ptr(grad_v), out, B, Nv, Nf, int(per_batch), int(fill_back), int(smooth), ws.data_ptr(), wsb,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_light_colors_backward')
+        _lib.launch('nr_light_colors_backward', dev, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    _lights_struct(params, flags), g.data_ptr(), _lib.ptr(grad_v), out, B, Nv, Nf, int(per_batch), int(fill_back),
+                    int(smooth), workspace_bytes=_lib.workspace_bytes('nr_light_colors_workspace_bytes', B, Nv, Nf, int(smooth)))
         return (None, grad_v) + grads
 
 
@@ -246,12 +236,9 @@ def light_colors(vertices, faces, lights, fill_back=True, smooth=False, implemen
     The HIP path builds the vertex adjacency table of an index tensor on the host the first time it sees it: inside a graph
     capture an unknown index tensor raises -- call once eagerly first."""
     B, Nv, Nf, params, flags = _check(vertices, faces, lights)
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("light_colors: implementation must be None, 'torch' or 'hip'")
     fits = vertices.is_cuda and vertices.dtype == torch.float32 and B <= 65535
-    if implementation == 'hip' and not fits:
-        raise ValueError('light_colors: the HIP kernels take float32 CUDA tensors and at most 65535 images')
-    if implementation == 'torch' or not fits:
+    if not _util.takes_hip('light_colors', implementation, fits, 'the HIP kernels take float32 CUDA tensors and at most 65535 '
+                           'images'):
         return light_colors_torch(vertices, faces, lights, fill_back, smooth)
     _util.check_face_indices(faces, Nv, vertices.device)
     idx, off, ent, per_batch = _adjacency(faces, Nv)

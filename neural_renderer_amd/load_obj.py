@@ -90,19 +90,16 @@ def load_textures(filename_obj, filename_mtl, texture_size, device='cuda'):
     if len(texture_filenames) == 0:
         return textures
 
-    lib = _lib.load()
     dev = torch.device(device)
     with torch.cuda.device(dev):
         textures_d = torch.from_numpy(textures).to(dev)
         faces_uv_d = torch.from_numpy(np.ascontiguousarray(faces_uv)).to(dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
         for name, filename_texture in texture_filenames.items():   # :80-143
             image = read_texture_image(filename_obj, filename_texture)
             image_d = torch.from_numpy(np.ascontiguousarray(image[::-1])).to(dev)    # vertical flip, :85
             is_update = torch.from_numpy((material_names == name).astype('int32')).to(dev)
-            _lib.check(lib.nr_load_textures(image_d.data_ptr(), faces_uv_d.data_ptr(), is_update.data_ptr(),
-                                            textures_d.data_ptr(), num_faces, texture_size, image.shape[0], image.shape[1],
-                                            stream), 'nr_load_textures')
+            _lib.launch('nr_load_textures', textures_d.device, image_d.data_ptr(), faces_uv_d.data_ptr(), is_update.data_ptr(),
+                        textures_d.data_ptr(), num_faces, texture_size, image.shape[0], image.shape[1])
         return textures_d.cpu().numpy()                            # :144 (`textures.get()`)
 
 

@@ -121,14 +121,12 @@ def _check(name, vertices, faces):
 def _prepare(name, vertices, faces, implementation):
     """-> (vertices [B,Nv,3], squeeze, tables, use_hip)"""
     vertices, squeeze = _check(name, vertices, faces)
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
     B, Nv = int(vertices.shape[0]), int(vertices.shape[1])
     fits = vertices.is_cuda and vertices.dtype == torch.float32 and B <= 65535
-    if implementation == 'hip' and not fits:
-        raise ValueError('%s: the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most' % name)
+    hip = _util.takes_hip(name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at '
+                          'most')
     _util.check_face_indices(faces, Nv, vertices.device)
-    return vertices, squeeze, _tables(faces, Nv), fits and implementation != 'torch'
+    return vertices, squeeze, _tables(faces, Nv), hip
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -177,27 +175,19 @@ def flatness_loss_torch(vertices, faces, eps=1e-6):
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
-def _workspace(lib, B, N, dev):
-    wsb = lib.nr_mesh_loss_workspace_bytes(B, N)
-    return torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev), wsb
-
-
 class _LaplacianLoss(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], tables) -> loss [B]; delta [B,Nv,3] is kept for the backward when one can follow."""
 
     @staticmethod
     def forward(ctx, vertices, t):
-        lib = _lib.load()
         v = _lib.dense(vertices.detach())
         dev = v.device
         B, Nv = v.shape[:2]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
         delta = torch.empty_like(v) if ctx.needs_input_grad[0] else None
-        with torch.cuda.device(dev):
-            ws, wsb = _workspace(lib, B, Nv, dev)
-            _lib.check(lib.nr_laplacian_forward(v.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr), _lib.ptr(delta),
-                                                loss.data_ptr(), B, Nv, int(t.nbr.shape[0]), ws.data_ptr(), wsb,
-                                                torch.cuda.current_stream(dev).cuda_stream), 'nr_laplacian_forward')
+        _lib.launch('nr_laplacian_forward', dev, v.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr), _lib.ptr(delta),
+                    loss.data_ptr(), B, Nv, int(t.nbr.shape[0]),
+                    workspace_bytes=_lib.workspace_bytes('nr_mesh_loss_workspace_bytes', B, Nv))
         if delta is not None:
             ctx.save_for_backward(delta)
         ctx.tables = t
@@ -207,17 +197,14 @@ class _LaplacianLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         if not ctx.needs_input_grad[0]:
             return None, None
-        lib = _lib.load()
         delta, = ctx.saved_tensors
         t = ctx.tables
         dev = delta.device
         B, Nv = delta.shape[:2]
         g = _lib.dense(grad_loss)
         grad_v = torch.empty_like(delta)
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_laplacian_backward(delta.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr), g.data_ptr(),
-                                                 grad_v.data_ptr(), B, Nv, int(t.nbr.shape[0]),
-                                                 torch.cuda.current_stream(dev).cuda_stream), 'nr_laplacian_backward')
+        _lib.launch('nr_laplacian_backward', dev, delta.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr), g.data_ptr(),
+                    grad_v.data_ptr(), B, Nv, int(t.nbr.shape[0]))
         return grad_v, None
 
 
@@ -226,16 +213,12 @@ class _FlatnessLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, t, eps):
-        lib = _lib.load()
         v = _lib.dense(vertices.detach())
         dev = v.device
         B, Nv = v.shape[:2]
         loss = torch.empty((B,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            ws, wsb = _workspace(lib, B, t.num_quads, dev)
-            _lib.check(lib.nr_flatness_forward(v.data_ptr(), _lib.ptr(t.quads) if t.num_quads else None, loss.data_ptr(), B, Nv,
-                                               t.num_quads, eps, ws.data_ptr(), wsb,
-                                               torch.cuda.current_stream(dev).cuda_stream), 'nr_flatness_forward')
+        _lib.launch('nr_flatness_forward', dev, v.data_ptr(), _lib.ptr(t.quads) if t.num_quads else None, loss.data_ptr(), B, Nv,
+                    t.num_quads, eps, workspace_bytes=_lib.workspace_bytes('nr_mesh_loss_workspace_bytes', B, t.num_quads))
         if ctx.needs_input_grad[0]:
             ctx.save_for_backward(v)
         ctx.tables, ctx.eps = t, eps
@@ -245,7 +228,6 @@ class _FlatnessLoss(torch.autograd.Function):
     def backward(ctx, grad_loss):
         if not ctx.needs_input_grad[0]:
             return None, None, None
-        lib = _lib.load()
         v, = ctx.saved_tensors
         t = ctx.tables
         dev = v.device
@@ -253,11 +235,9 @@ class _FlatnessLoss(torch.autograd.Function):
         g = _lib.dense(grad_loss)
         grad_v = torch.empty_like(v)
         some = t.num_quads > 0
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_flatness_backward(v.data_ptr(), _lib.ptr(t.quads) if some else None,
-                                                _lib.ptr(t.inc_offsets) if some else None, _lib.ptr(t.inc) if some else None,
-                                                g.data_ptr(), grad_v.data_ptr(), B, Nv, t.num_quads, ctx.eps,
-                                                torch.cuda.current_stream(dev).cuda_stream), 'nr_flatness_backward')
+        _lib.launch('nr_flatness_backward', dev, v.data_ptr(), _lib.ptr(t.quads) if some else None,
+                    _lib.ptr(t.inc_offsets) if some else None, _lib.ptr(t.inc) if some else None, g.data_ptr(),
+                    grad_v.data_ptr(), B, Nv, t.num_quads, ctx.eps)
         return grad_v, None, None
 
 

@@ -87,43 +87,31 @@ def corner_normals_torch(vertices, faces, smooth=False, fill_back=True):
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
-def _workspace(lib, B, Nv, Nf, dev):
-    wsb = lib.nr_normals_workspace_bytes(B, Nv, Nf)
-    return torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev), wsb
-
-
 class _VertexNormals(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], setup) -> n_v [B,Nv,3]; setup = (indices, offsets, entries, idx_per_batch)."""
 
     @staticmethod
     def forward(ctx, vertices, setup):
-        lib = _lib.load()
         idx, off, ent, per_batch = setup
         v = _lib.dense(vertices.detach())
         B, Nv = v.shape[:2]
         out = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            _lib.check(lib.nr_vertex_normals_forward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), out.data_ptr(), B, Nv, idx.shape[1],
-                int(per_batch), torch.cuda.current_stream(v.device).cuda_stream), 'nr_vertex_normals_forward')
+        _lib.launch('nr_vertex_normals_forward', v.device, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    out.data_ptr(), B, Nv, idx.shape[1], int(per_batch))
         ctx.save_for_backward(v)
         ctx.setup = setup
         return out
 
     @staticmethod
     def backward(ctx, grad_normals):
-        lib = _lib.load()
         v, = ctx.saved_tensors
         idx, off, ent, per_batch = ctx.setup
         B, Nv = v.shape[:2]
         g = _lib.dense(grad_normals)
         grad_v = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            ws, wsb = _workspace(lib, B, Nv, idx.shape[1], v.device)
-            _lib.check(lib.nr_vertex_normals_backward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), g.data_ptr(), grad_v.data_ptr(), B, Nv,
-                idx.shape[1], int(per_batch), ws.data_ptr(), wsb, torch.cuda.current_stream(v.device).cuda_stream),
-                'nr_vertex_normals_backward')
+        _lib.launch('nr_vertex_normals_backward', v.device, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    g.data_ptr(), grad_v.data_ptr(), B, Nv, idx.shape[1], int(per_batch),
+                    workspace_bytes=_lib.workspace_bytes('nr_normals_workspace_bytes', B, Nv, idx.shape[1]))
         return grad_v, None
 
 
@@ -132,34 +120,27 @@ class _FaceNormals(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, setup):
-        lib = _lib.load()
         idx, off, ent, per_batch = setup
         v = _lib.dense(vertices.detach())
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
         out = torch.empty((B, Nf, 3), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(lib.nr_face_normals_forward(
-                v.data_ptr(), idx.data_ptr(), out.data_ptr(), B, Nv, Nf, int(per_batch),
-                torch.cuda.current_stream(v.device).cuda_stream), 'nr_face_normals_forward')
+        _lib.launch('nr_face_normals_forward', v.device, v.data_ptr(), idx.data_ptr(), out.data_ptr(), B, Nv, Nf,
+                    int(per_batch))
         ctx.save_for_backward(v)
         ctx.setup = setup
         return out
 
     @staticmethod
     def backward(ctx, grad_normals):
-        lib = _lib.load()
         v, = ctx.saved_tensors
         idx, off, ent, per_batch = ctx.setup
         B, Nv = v.shape[:2]
         g = _lib.dense(grad_normals)
         grad_v = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            ws, wsb = _workspace(lib, B, Nv, idx.shape[1], v.device)
-            _lib.check(lib.nr_face_normals_backward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), g.data_ptr(), grad_v.data_ptr(), B, Nv,
-                idx.shape[1], int(per_batch), ws.data_ptr(), wsb, torch.cuda.current_stream(v.device).cuda_stream),
-                'nr_face_normals_backward')
+        _lib.launch('nr_face_normals_backward', v.device, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    g.data_ptr(), grad_v.data_ptr(), B, Nv, idx.shape[1], int(per_batch),
+                    workspace_bytes=_lib.workspace_bytes('nr_normals_workspace_bytes', B, Nv, idx.shape[1]))
         return grad_v, None
 
 
@@ -169,37 +150,29 @@ class _CornerNormals(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, setup):
-        lib = _lib.load()
         idx, off, ent, per_batch, fill_back, smooth = setup
         v = _lib.dense(vertices.detach())
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
         out = torch.empty((B, 2 * Nf if fill_back else Nf, 3, 3), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            ws, wsb = _workspace(lib, B, Nv, Nf, v.device) if smooth else (torch.empty((1,), dtype=torch.uint8, device=v.device), 0)
-            _lib.check(lib.nr_corner_normals_forward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), out.data_ptr(), B, Nv, Nf, int(per_batch),
-                int(fill_back), int(smooth), ws.data_ptr(), wsb, torch.cuda.current_stream(v.device).cuda_stream),
-                'nr_corner_normals_forward')
+        _lib.launch('nr_corner_normals_forward', v.device, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    out.data_ptr(), B, Nv, Nf, int(per_batch), int(fill_back), int(smooth),
+                    workspace_bytes=_lib.workspace_bytes('nr_normals_workspace_bytes', B, Nv, Nf) if smooth else 0)
         ctx.save_for_backward(v)
         ctx.setup = setup
         return out
 
     @staticmethod
     def backward(ctx, grad_corner):
-        lib = _lib.load()
         v, = ctx.saved_tensors
         idx, off, ent, per_batch, fill_back, smooth = ctx.setup
         B, Nv = v.shape[:2]
         Nf = idx.shape[1]
         g = _lib.dense(grad_corner)
         grad_v = torch.empty_like(v)
-        with torch.cuda.device(v.device):
-            ws, wsb = _workspace(lib, B, Nv, Nf, v.device)
-            _lib.check(lib.nr_corner_normals_backward(
-                v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(), g.data_ptr(), grad_v.data_ptr(), B, Nv, Nf,
-                int(per_batch), int(fill_back), int(smooth), ws.data_ptr(), wsb,
-                torch.cuda.current_stream(v.device).cuda_stream), 'nr_corner_normals_backward')
+        _lib.launch('nr_corner_normals_backward', v.device, v.data_ptr(), idx.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    g.data_ptr(), grad_v.data_ptr(), B, Nv, Nf, int(per_batch), int(fill_back), int(smooth),
+                    workspace_bytes=_lib.workspace_bytes('nr_normals_workspace_bytes', B, Nv, Nf))
         return grad_v, None
 
 
@@ -222,12 +195,9 @@ def _check(name, vertices, faces, implementation):
         raise ValueError('%s: faces have batch size %d, vertices %d' % (name, faces.shape[0], B))
     if faces.device != vertices.device:
         raise ValueError('%s: vertices and faces must be on one device (%s, %s)' % (name, vertices.device, faces.device))
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
     fits = vertices.is_cuda and vertices.dtype == torch.float32 and 1 <= B <= 65535
-    if implementation == 'hip' and not fits:
-        raise ValueError('%s: the HIP kernels take float32 CUDA tensors with a batch size of at most 65535' % name)
-    return vertices, unbatched, fits and implementation != 'torch'
+    return vertices, unbatched, _util.takes_hip(name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a '
+                                                'batch size of at most 65535')
 
 
 def _setup(vertices, faces):

@@ -37,11 +37,8 @@ class Adam(torch.optim.Optimizer):
                 g = p.grad
                 if p.is_cuda and p.dtype == torch.float32 and g.dtype == torch.float32 and p.is_contiguous():
                     g = g.contiguous()
-                    with torch.cuda.device(p.device):
-                        _lib.check(_lib.load().nr_adam_update(
-                            p.data_ptr(), g.data_ptr(), state['m'].data_ptr(), state['v'].data_ptr(), p.numel(),
-                            lr, 1 - b1, 1 - b2, group['eps'], torch.cuda.current_stream(p.device).cuda_stream),
-                            'nr_adam_update')
+                    _lib.launch('nr_adam_update', p.device, p.data_ptr(), g.data_ptr(), state['m'].data_ptr(),
+                                state['v'].data_ptr(), p.numel(), lr, 1 - b1, 1 - b2, group['eps'])
                     continue
                 mask = g != 0  # :26
                 m = torch.where(mask, state['m'] + (1 - b1) * (g - state['m']), state['m'])

@@ -51,10 +51,7 @@ def _clouds(name, x, y):
 
 def _check_implementation(name, implementation):
     """None and 'torch' are the plain-torch path; 'hip' names kernels that this package does not have."""
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
-    if implementation == 'hip':
-        raise ValueError('%s: there are no HIP kernels for the point-cloud losses; use implementation=None' % name)
+    _util.takes_hip(name, implementation, False, 'there are no HIP kernels for the point-cloud losses; use implementation=None')
 
 
 # ---------------------------------------------------------------------------------------------------------------------

@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import on_device as _on_device, stream_ptr as _stream_ptr
 from .uv_textures import UVImages, pack_images, unpack_image_gradients
 from .vertex_colors import CornerColors
 
@@ -51,33 +52,6 @@ EXACT_GRADIENT = bool(int(os.environ.get('NR_EXACT_GRADIENT', '0')))
 _BACKWARD_ORDER_FLAG = _lib.NR_FLAG_SERIAL_BACKWARD if int(os.environ.get('NR_SERIAL_BACKWARD', '0')) else 0
 # (measuring aid, read once: NR_K6_LEGACY=1 keeps K6's default mode on the piece-per-lane band kernel -- NR_FLAG_K6_LEGACY)
 _BACKWARD_ORDER_FLAG |= _lib.NR_FLAG_K6_LEGACY if int(os.environ.get('NR_K6_LEGACY', '0')) else 0
-
-
-_RAW_STREAM = getattr(torch._C, '_cuda_getCurrentRawStream', None)
-
-
-def _stream_ptr(device):
-    """hipStream_t of torch's current stream on `device` (the raw query: no Stream object per call)."""
-    if _RAW_STREAM is not None:
-        return _RAW_STREAM(device.index)
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-class _NoGuard(object):
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *exc):
-        return False
-
-
-_NO_GUARD = _NoGuard()
-
-
-def _on_device(device):
-    """Context that makes `device` the current HIP device for the launches -- nothing at all when it already is (one process
-    per GPU: always), torch.cuda.device otherwise."""
-    return _NO_GUARD if torch.cuda.current_device() == device.index else torch.cuda.device(device)
 
 
 _BG_CACHE = {}
@@ -786,7 +760,6 @@ class _ImageEpilogue(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, rgb_map, alpha_map, depth_map, anti_aliasing):
-        lib = _lib.load()
         maps = [_lib.dense(m.detach()) if m is not None else None for m in (rgb_map, alpha_map, depth_map)]
         ref = next(m for m in maps if m is not None)
         dev = ref.device
@@ -797,17 +770,14 @@ class _ImageEpilogue(torch.autograd.Function):
         outs = [None if maps[0] is None else torch.empty((B, 3, size, size), dtype=torch.float32, device=dev),
                 None if maps[1] is None else torch.empty((B, size, size), dtype=torch.float32, device=dev),
                 None if maps[2] is None else torch.empty((B, size, size), dtype=torch.float32, device=dev)]
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_image_epilogue(_lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(outs[0]),
-                                             _lib.ptr(outs[1]), _lib.ptr(outs[2]), B, S, int(anti_aliasing),
-                                             _stream_ptr(dev)), 'nr_image_epilogue')
+        _lib.launch('nr_image_epilogue', dev, _lib.ptr(maps[0]), _lib.ptr(maps[1]), _lib.ptr(maps[2]), _lib.ptr(outs[0]),
+                    _lib.ptr(outs[1]), _lib.ptr(outs[2]), B, S, int(anti_aliasing))
         ctx.dims = (B, S, bool(anti_aliasing))
         ctx.set_materialize_grads(False)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, g_rgb, g_alpha, g_depth):
-        lib = _lib.load()
         B, S, aa = ctx.dims
         grads = [_lib.dense(g) for g in (g_rgb, g_alpha, g_depth)]
         ref = next((g for g in grads if g is not None), None)
@@ -818,10 +788,8 @@ class _ImageEpilogue(torch.autograd.Function):
         outs = [None if grads[0] is None else torch.empty((B, S, S, 3), dtype=torch.float32, device=dev),
                 None if grads[1] is None else torch.empty((B, S, S), dtype=torch.float32, device=dev),
                 None if grads[2] is None else torch.empty((B, S, S), dtype=torch.float32, device=dev)]
-        with torch.cuda.device(dev):
-            _lib.check(lib.nr_image_epilogue_backward(_lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(grads[2]),
-                                                      _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), B, S,
-                                                      int(aa), _stream_ptr(dev)), 'nr_image_epilogue_backward')
+        _lib.launch('nr_image_epilogue_backward', dev, _lib.ptr(grads[0]), _lib.ptr(grads[1]), _lib.ptr(grads[2]),
+                    _lib.ptr(outs[0]), _lib.ptr(outs[1]), _lib.ptr(outs[2]), B, S, int(aa))
         return outs[0], outs[1], outs[2], None
 
 

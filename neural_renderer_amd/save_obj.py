@@ -31,15 +31,13 @@ def create_texture_image(textures, texture_size_out=16, device='cuda'):
     vertices[:, 2, 0] = (column + 1) * texture_size_out - 1
     vertices[:, 2, 1] = (row + 1) * texture_size_out - 1
 
-    lib = _lib.load()
     dev = torch.device(device)
     with torch.cuda.device(dev):
         image_d = torch.empty((height, width, 3), dtype=torch.float32, device=dev)
         vertices_d = torch.from_numpy(vertices).to(dev)
         textures_d = torch.from_numpy(textures).to(dev)
-        _lib.check(lib.nr_create_texture_image(textures_d.data_ptr(), vertices_d.data_ptr(), image_d.data_ptr(), num_faces,
-                                               texture_size_in, texture_size_out, tile_width, tile_height,
-                                               torch.cuda.current_stream(dev).cuda_stream), 'nr_create_texture_image')
+        _lib.launch('nr_create_texture_image', image_d.device, textures_d.data_ptr(), vertices_d.data_ptr(), image_d.data_ptr(),
+                    num_faces, texture_size_in, texture_size_out, tile_width, tile_height)
         image = image_d.cpu().numpy()
     vertices[:, :, 0] /= (width - 1)   # :140-141
     vertices[:, :, 1] /= (height - 1)

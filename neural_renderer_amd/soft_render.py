@@ -51,8 +51,7 @@ import math
 
 import torch
 
-from . import _lib
-from .soft_silhouette import _MAX_FACES, _MAX_SIZE, _number
+from . import _lib, _util
 
 _CHUNK_ELEMENTS = 2 ** 24   # soft_render_torch: the most elements of one temporary
 REACH = 17.0                # an outside pair is taken up to d2 = REACH sigma
@@ -148,7 +147,6 @@ class _SoftRender(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, faces, colors, image_size, sigma, gamma, near, far, eps, background):
-        lib = _lib.load()
         f, c = _lib.dense(faces.detach()), _lib.dense(colors.detach())
         B, F, S = int(f.shape[0]), int(f.shape[1]), image_size
         per_batch = 1 if int(c.shape[0]) == B else 0   # else [1,F,3]: one set for the batch, read in place
@@ -156,32 +154,24 @@ class _SoftRender(torch.autograd.Function):
         rgba = torch.empty((B, 4, S, S), dtype=torch.float32, device=f.device)
         q = torch.empty((B, S, S), dtype=torch.float32, device=f.device)
         norm = torch.empty((B, 2, S, S), dtype=torch.float32, device=f.device)
-        with torch.cuda.device(f.device):
-            wsb = getattr(lib, entry + '_workspace_bytes')(B, F, S)
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(getattr(lib, entry + '_forward')(
-                f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(), B, F, S, per_batch, sigma, gamma,
-                near, far, eps, background[0], background[1], background[2], ws.data_ptr(), wsb,
-                torch.cuda.current_stream(f.device).cuda_stream), entry + '_forward')
+        _lib.launch(entry + '_forward', f.device, f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(),
+                    B, F, S, per_batch, sigma, gamma, near, far, eps, background[0], background[1], background[2],
+                    workspace_bytes=_lib.workspace_bytes(entry + '_workspace_bytes', B, F, S))
         ctx.save_for_backward(f, c, rgba, q, norm)
         ctx.args = (S, per_batch, sigma, gamma, near, far, eps, background, entry)
         return rgba.flip(2)
 
     @staticmethod
     def backward(ctx, grad_rgba):
-        lib = _lib.load()
         f, c, rgba, q, norm = ctx.saved_tensors
         S, per_batch, sigma, gamma, near, far, eps, background, entry = ctx.args
         B, F = int(f.shape[0]), int(f.shape[1])
         g = _lib.dense(grad_rgba.flip(2))
         grad_faces, grad_colors = torch.empty_like(f), torch.empty_like(c)
-        with torch.cuda.device(f.device):
-            wsb = getattr(lib, entry + '_workspace_bytes')(B, F, S)
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(getattr(lib, entry + '_backward')(
-                f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(), g.data_ptr(), grad_faces.data_ptr(),
-                grad_colors.data_ptr(), B, F, S, per_batch, sigma, gamma, near, far, eps, background[0], background[1],
-                background[2], ws.data_ptr(), wsb, torch.cuda.current_stream(f.device).cuda_stream), entry + '_backward')
+        _lib.launch(entry + '_backward', f.device, f.data_ptr(), c.data_ptr(), rgba.data_ptr(), q.data_ptr(), norm.data_ptr(),
+                    g.data_ptr(), grad_faces.data_ptr(), grad_colors.data_ptr(), B, F, S, per_batch, sigma, gamma, near, far,
+                    eps, background[0], background[1], background[2],
+                    workspace_bytes=_lib.workspace_bytes(entry + '_workspace_bytes', B, F, S))
         return (grad_faces, grad_colors) + (None,) * 7
 
 
@@ -203,11 +193,11 @@ def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, backgr
         raise ValueError('%s: colors on %s, faces on %s' % (name, colors.device, faces.device))
     if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
         raise ValueError('%s: image_size must be a positive integer, got %r' % (name, image_size))
-    sigma, gamma = _number(name, 'sigma', sigma), _number(name, 'gamma', gamma)
+    sigma, gamma = _util.number(name, 'sigma', sigma), _util.number(name, 'gamma', gamma)
     for what, v in (('sigma', sigma), ('gamma', gamma)):
         if not (0 < v < float('inf')):
             raise ValueError('%s: %s must be a finite number greater than 0, got %r' % (name, what, v))
-    near, far, eps = _number(name, 'near', near), _number(name, 'far', far), _number(name, 'eps', eps)
+    near, far, eps = _util.number(name, 'near', near), _util.number(name, 'far', far), _util.number(name, 'eps', eps)
     if not (math.isfinite(near) and math.isfinite(far) and near < far):
         raise ValueError('%s: near and far must be finite numbers with near < far, got %r and %r' % (name, near, far))
     if not math.isfinite(eps):
@@ -218,19 +208,15 @@ def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, backgr
         background = ()
     if len(background) != 3:
         raise ValueError('%s: background_color must be three numbers, got %r' % (name, background_color))
-    background = tuple(_number(name, 'background_color', float(c) if torch.is_tensor(c) else c) for c in background)
+    background = tuple(_util.number(name, 'background_color', float(c) if torch.is_tensor(c) else c) for c in background)
     if not all(math.isfinite(c) for c in background):
         raise ValueError('%s: background_color must be finite, got %r' % (name, background_color))
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
     fits = (faces.is_cuda and faces.dtype == torch.float32 and colors.dtype == torch.float32 and B <= 65535
-            and F <= _MAX_FACES and B * F * 9 < 2 ** 31 and image_size <= _MAX_SIZE and 1e-30 <= sigma <= 1e30
-            and 1e-30 <= gamma <= 1e30)
-    if implementation == 'hip' and not fits:
-        raise ValueError('%s: the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 faces '
-                         '(batch size * faces * 9 < 2^31), an image_size of 16384 at most and sigma, gamma in [1e-30, 1e30]'
-                         % name)
-    return image_size, sigma, gamma, near, far, eps, background, fits and implementation != 'torch'
+            and F <= _util.SOFT_MAX_FACES and B * F * 9 < 2 ** 31 and image_size <= _util.SOFT_MAX_SIZE
+            and 1e-30 <= sigma <= 1e30 and 1e-30 <= gamma <= 1e30)
+    return image_size, sigma, gamma, near, far, eps, background, _util.takes_hip(
+        name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 '
+        'faces (batch size * faces * 9 < 2^31), an image_size of 16384 at most and sigma, gamma in [1e-30, 1e30]')
 
 
 def soft_render(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,

@@ -25,15 +25,11 @@ plain torch with the same definition and tie rule, and leaves nothing out.  No h
 (graph.capture) -- but capture before any eager backward on the same leaves, or make the eager calls under no_grad: a
 capture after a whole eager step ended the process inside torch's capture_end (DESIGN "Soft silhouettes", Stream capture).
 """
-import math
-
 import torch
 
-from . import _lib
+from . import _lib, _util
 
 _CHUNK_ELEMENTS = 2 ** 26   # soft_silhouettes_torch: the most elements of one temporary
-_MAX_FACES = 2 ** 24        # include/nr_hip.h
-_MAX_SIZE = 16384
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -89,46 +85,31 @@ class _SoftSilhouettes(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, faces, image_size, sigma, near, far):
-        lib = _lib.load()
         f = _lib.dense(faces.detach())
         B, F, S = int(f.shape[0]), int(f.shape[1]), image_size
         alpha = torch.empty((B, S, S), dtype=torch.float32, device=f.device)
         q = torch.empty_like(alpha)
-        with torch.cuda.device(f.device):
-            wsb = lib.nr_soft_silhouette_workspace_bytes(B, F, S)
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(lib.nr_soft_silhouette_forward(
-                f.data_ptr(), alpha.data_ptr(), q.data_ptr(), B, F, S, sigma, near, far, ws.data_ptr(), wsb,
-                torch.cuda.current_stream(f.device).cuda_stream), 'nr_soft_silhouette_forward')
+        _lib.launch('nr_soft_silhouette_forward', f.device, f.data_ptr(), alpha.data_ptr(), q.data_ptr(), B, F, S, sigma, near,
+                    far, workspace_bytes=_lib.workspace_bytes('nr_soft_silhouette_workspace_bytes', B, F, S))
         ctx.save_for_backward(f, q)
         ctx.args = (S, sigma, near, far)
         return alpha.flip(1)
 
     @staticmethod
     def backward(ctx, grad_alpha):
-        lib = _lib.load()
         f, q = ctx.saved_tensors
         S, sigma, near, far = ctx.args
         B, F = int(f.shape[0]), int(f.shape[1])
         g = _lib.dense(grad_alpha.flip(1))
         grad_faces = torch.empty_like(f)
-        with torch.cuda.device(f.device):
-            wsb = lib.nr_soft_silhouette_workspace_bytes(B, F, S)
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=f.device)
-            _lib.check(lib.nr_soft_silhouette_backward(
-                f.data_ptr(), q.data_ptr(), g.data_ptr(), grad_faces.data_ptr(), B, F, S, sigma, near, far, ws.data_ptr(), wsb,
-                torch.cuda.current_stream(f.device).cuda_stream), 'nr_soft_silhouette_backward')
+        _lib.launch('nr_soft_silhouette_backward', f.device, f.data_ptr(), q.data_ptr(), g.data_ptr(), grad_faces.data_ptr(),
+                    B, F, S, sigma, near, far,
+                    workspace_bytes=_lib.workspace_bytes('nr_soft_silhouette_workspace_bytes', B, F, S))
         return grad_faces, None, None, None, None
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # the public function
-
-def _number(name, what, v):
-    if isinstance(v, bool) or not isinstance(v, (int, float)) or math.isnan(v):
-        raise ValueError('%s: %s must be a number, got %r' % (name, what, v))
-    return float(v)
-
 
 def _check(name, faces, image_size, sigma, near, far, implementation):
     """Argument checks shared by both implementations -> (image_size, sigma, near, far, takes the HIP path)."""
@@ -137,19 +118,16 @@ def _check(name, faces, image_size, sigma, near, far, implementation):
         raise ValueError('%s: faces must be a non-empty float tensor [batch size, num of faces, 3, 3]' % name)
     if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
         raise ValueError('%s: image_size must be a positive integer, got %r' % (name, image_size))
-    sigma = _number(name, 'sigma', sigma)
+    sigma = _util.number(name, 'sigma', sigma)
     if not (0 < sigma < float('inf')):
         raise ValueError('%s: sigma must be a finite number greater than 0, got %r' % (name, sigma))
-    near, far = _number(name, 'near', near), _number(name, 'far', far)
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("%s: implementation must be None, 'torch' or 'hip'" % name)
+    near, far = _util.number(name, 'near', near), _util.number(name, 'far', far)
     B, F = int(faces.shape[0]), int(faces.shape[1])
-    fits = (faces.is_cuda and faces.dtype == torch.float32 and B <= 65535 and F <= _MAX_FACES and B * F * 9 < 2 ** 31
-            and image_size <= _MAX_SIZE and 1e-30 <= sigma <= 1e30)
-    if implementation == 'hip' and not fits:
-        raise ValueError('%s: the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 faces '
-                         '(batch size * faces * 9 < 2^31), an image_size of 16384 at most and 1e-30 <= sigma <= 1e30' % name)
-    return image_size, sigma, near, far, fits and implementation != 'torch'
+    fits = (faces.is_cuda and faces.dtype == torch.float32 and B <= 65535 and F <= _util.SOFT_MAX_FACES
+            and B * F * 9 < 2 ** 31 and image_size <= _util.SOFT_MAX_SIZE and 1e-30 <= sigma <= 1e30)
+    return image_size, sigma, near, far, _util.takes_hip(
+        name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 '
+        'faces (batch size * faces * 9 < 2^31), an image_size of 16384 at most and 1e-30 <= sigma <= 1e30')
 
 
 def soft_silhouettes(faces, image_size=256, sigma=1e-4, near=0.1, far=100, implementation=None):

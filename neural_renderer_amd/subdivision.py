@@ -170,14 +170,11 @@ def _apply_torch(x, t):
 
 
 def _apply_hip(x, t):
-    lib = _lib.load()
     x = _lib.dense(x)
     B, _, C = x.shape
     y = torch.empty((B, t.num_out, C), dtype=torch.float32, device=x.device)
-    with torch.cuda.device(x.device):
-        _lib.check(lib.nr_stencil_apply(x.data_ptr(), t.offsets.data_ptr(), t.cols.data_ptr(), t.weights.data_ptr(), y.data_ptr(),
-                                        B, t.num_in, t.num_out, C, t.num_entries,
-                                        torch.cuda.current_stream(x.device).cuda_stream), 'nr_stencil_apply')
+    _lib.launch('nr_stencil_apply', x.device, x.data_ptr(), t.offsets.data_ptr(), t.cols.data_ptr(), t.weights.data_ptr(),
+                y.data_ptr(), B, t.num_in, t.num_out, C, t.num_entries)
     return y
 
 
@@ -214,8 +211,7 @@ class Subdivision(object):
         """x [Nv,C] or [B,Nv,C] float -> [..,Nv',C], differentiable (once) in x.  `implementation`: None picks the HIP
         kernel when the call fits it (float32 CUDA, B <= 65535, C <= 16), 'torch' / 'hip' force one ('hip' raises when the
         call does not fit)."""
-        if implementation not in (None, 'torch', 'hip'):
-            raise ValueError("subdivision: implementation must be None, 'torch' or 'hip'")
+        _util.check_implementation('subdivision', implementation)
         if not (torch.is_tensor(x) and x.is_floating_point() and x.dim() in (2, 3) and x.shape[-1] >= 1 and x.shape[0] >= 1):
             raise ValueError('subdivision: the data must be a float tensor [num of vertices, channels] or [batch size, num of '
                              'vertices, channels]')
@@ -230,10 +226,8 @@ class Subdivision(object):
             x = x[None]
         B, C = int(x.shape[0]), int(x.shape[2])
         fits = x.is_cuda and x.dtype == torch.float32 and B <= 65535 and C <= MAX_CHANNELS
-        if implementation == 'hip' and not fits:
-            raise ValueError('subdivision: the HIP kernel takes float32 CUDA tensors with a batch size of 65535 and %d channels '
-                             'at most' % MAX_CHANNELS)
-        hip = fits and implementation != 'torch'
+        hip = _util.takes_hip('subdivision', implementation, fits, 'the HIP kernel takes float32 CUDA tensors with a batch size '
+                              'of 65535 and %d channels at most' % MAX_CHANNELS)
         for level in self._levels:
             x = _ApplyLevel.apply(x, level) if hip else _apply_torch(x, level.forward)
         return x[0] if squeeze else x
@@ -291,8 +285,7 @@ def subdivide(vertices, faces, levels=1, scheme='loop', implementation=None):
     """-> (vertices' [..,Nv',C], faces'): `levels` refinements of vertices [Nv,C] or [B,Nv,C] on faces [F,3] or [B,F,3] (all
     images equal), differentiable (once) in the vertices.  faces' has the batch layout of faces: [4^L F, 3], or an expanded
     view [B, 4^L F, 3].  levels = 0 returns the inputs unchanged."""
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("subdivision: implementation must be None, 'torch' or 'hip'")
+    _util.check_implementation('subdivision', implementation)
     if not (torch.is_tensor(vertices) and vertices.dim() in (2, 3)):
         raise ValueError('subdivision: the data must be a float tensor [num of vertices, channels] or [batch size, num of '
                          'vertices, channels]')

@@ -189,12 +189,9 @@ class _BakeUV(torch.autograd.Function):
         state = layout._tensors(device)
         F, ts = layout.num_faces, layout.texture_size
         textures = torch.empty((Bi, F, ts, ts, ts, 3), dtype=torch.float32, device=device)
-        lib = _lib.load()
-        with torch.cuda.device(device):
-            _lib.check(lib.nr_bake_uv_textures(packed.data_ptr(), state['table'].data_ptr(), state['faces_uv'].data_ptr(),
-                                               state['face_image'].data_ptr(), state['base'].data_ptr(), textures.data_ptr(),
-                                               Bi, F, ts, layout.num_images, layout.num_pixels,
-                                               torch.cuda.current_stream(device).cuda_stream), 'nr_bake_uv_textures')
+        _lib.launch('nr_bake_uv_textures', device, packed.data_ptr(), state['table'].data_ptr(), state['faces_uv'].data_ptr(),
+                    state['face_image'].data_ptr(), state['base'].data_ptr(), textures.data_ptr(), Bi, F, ts,
+                    layout.num_images, layout.num_pixels)
         ctx.layout = layout
         ctx.batch = Bi
         ctx.device = device
@@ -207,13 +204,8 @@ class _BakeUV(torch.autograd.Function):
         grad_textures = _lib.dense(grad_textures)
         P = layout.num_pixels
         grad_packed = torch.empty((Bi, P, 3), dtype=torch.float32, device=device)
-        lib = _lib.load()
-        with torch.cuda.device(device):
-            _lib.check(lib.nr_bake_uv_textures_backward(grad_textures.data_ptr(), row_ptr.data_ptr(), entry_texel.data_ptr(),
-                                                        entry_weight.data_ptr(), grad_packed.data_ptr(), Bi, layout.num_faces,
-                                                        layout.texture_size, P,
-                                                        torch.cuda.current_stream(device).cuda_stream),
-                       'nr_bake_uv_textures_backward')
+        _lib.launch('nr_bake_uv_textures_backward', device, grad_textures.data_ptr(), row_ptr.data_ptr(), entry_texel.data_ptr(),
+                    entry_weight.data_ptr(), grad_packed.data_ptr(), Bi, layout.num_faces, layout.texture_size, P)
         return (None,) + tuple(unpack_image_gradients(layout, grad_packed))
 
 

@@ -21,6 +21,7 @@ import torch
 
 from . import _lib, _util
 from ._util import as_tensor_like
+from .frontend import _is_number, _vec3
 
 
 class VertexColors(object):
@@ -176,7 +177,6 @@ class _VertexShade(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, vertices, colors, setup):
-        lib = _lib.load()
         idx, off, ent, per_batch, light, fill_back, smooth = setup
         v = _lib.dense(vertices.detach())
         c = _lib.dense(colors.detach())
@@ -186,13 +186,9 @@ class _VertexShade(torch.autograd.Function):
         Bc = 1 if c.dim() == 2 else int(c.shape[0])
         F = 2 * Nf if fill_back else Nf
         out = torch.empty((B, F, 3, 3), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            wsb = lib.nr_vertex_shade_workspace_bytes(B, Nv) if smooth else 0
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_vertex_shade_forward(
-                v.data_ptr(), idx.data_ptr(), c.data_ptr(), off.data_ptr(), ent.data_ptr(), out.data_ptr(), B, Nv, Nf, Bc,
-                int(per_batch), int(fill_back), int(smooth), light, ws.data_ptr(), wsb,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_vertex_shade_forward')
+        _lib.launch('nr_vertex_shade_forward', dev, v.data_ptr(), idx.data_ptr(), c.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    out.data_ptr(), B, Nv, Nf, Bc, int(per_batch), int(fill_back), int(smooth), light,
+                    workspace_bytes=_lib.workspace_bytes('nr_vertex_shade_workspace_bytes', B, Nv) if smooth else 0)
         ctx.save_for_backward(v, c)
         ctx.setup = setup
         ctx.colors_dim = colors.dim()
@@ -200,7 +196,6 @@ class _VertexShade(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_corner):
-        lib = _lib.load()
         v, c = ctx.saved_tensors
         idx, off, ent, per_batch, light, fill_back, smooth = ctx.setup
         need_v, need_c = ctx.needs_input_grad[:2]
@@ -213,20 +208,16 @@ class _VertexShade(torch.autograd.Function):
         g = _lib.dense(grad_corner)
         grad_v = torch.empty_like(v) if need_v else None
         grad_c = torch.empty_like(c) if need_c else None
-        with torch.cuda.device(dev):
-            wsb = lib.nr_vertex_shade_workspace_bytes(B, Nv) if (smooth and need_v) else 0
-            ws = torch.empty((max(wsb, 1),), dtype=torch.uint8, device=dev)
-            _lib.check(lib.nr_vertex_shade_backward(
-                v.data_ptr(), idx.data_ptr(), c.data_ptr(), off.data_ptr(), ent.data_ptr(), g.data_ptr(), _lib.ptr(grad_c),
-                _lib.ptr(grad_v), B, Nv, Nf, Bc, int(per_batch), int(fill_back), int(smooth), light, ws.data_ptr(), wsb,
-                torch.cuda.current_stream(dev).cuda_stream), 'nr_vertex_shade_backward')
+        _lib.launch('nr_vertex_shade_backward', dev, v.data_ptr(), idx.data_ptr(), c.data_ptr(), off.data_ptr(), ent.data_ptr(),
+                    g.data_ptr(), _lib.ptr(grad_c), _lib.ptr(grad_v), B, Nv, Nf, Bc, int(per_batch), int(fill_back), int(smooth),
+                    light, workspace_bytes=(_lib.workspace_bytes('nr_vertex_shade_workspace_bytes', B, Nv)
+                                            if (smooth and need_v) else 0))
         return grad_v, grad_c, None
 
 
 def _host_light(ia, idir, ca, cd, direction):
     """The light as host numbers (nr_light), or None when a parameter is a tensor / per-image array."""
-    from .frontend import _number, _vec3
-    if not (_number(ia) and _number(idir)):
+    if not (_is_number(ia) and _is_number(idir)):
         return None
     vecs = [_vec3(x) for x in (ca, cd, direction)]
     if any(x is None for x in vecs):
@@ -271,13 +262,11 @@ def vertex_shade(vertices, faces, colors, intensity_ambient=0.5, intensity_direc
     if isinstance(colors, VertexColors):
         colors = colors.colors
     B, Nv, Nf, Bc = check_vertex_shade(vertices, faces, colors)
-    if implementation not in (None, 'torch', 'hip'):
-        raise ValueError("vertex_shade: implementation must be None, 'torch' or 'hip'")
+    _util.check_implementation('vertex_shade', implementation)
     light = _host_light(intensity_ambient, intensity_directional, color_ambient, color_directional, direction)
     fits = vertices.is_cuda and vertices.dtype == torch.float32 and light is not None and B <= 65535
-    if implementation == 'hip' and not fits:
-        raise ValueError('vertex_shade: the HIP kernels take float32 CUDA tensors and host light parameters')
-    if implementation == 'torch' or not fits:
+    if not _util.takes_hip('vertex_shade', implementation, fits, 'the HIP kernels take float32 CUDA tensors and host light '
+                           'parameters'):
         if vertices.dtype != torch.float32:
             raise ValueError('vertex_shade: float32 tensors expected (vertex_shade_torch takes other float types)')
         return CornerColors(vertex_shade_torch(vertices, faces, colors, intensity_ambient, intensity_directional,

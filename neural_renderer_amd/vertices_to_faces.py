@@ -12,31 +12,24 @@ from . import _lib, _util
 class _VerticesToFaces(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, faces):
-        lib = _lib.load()
         v = _lib.dense(vertices.detach())
         f = _lib.dense(faces.detach().to(torch.int32))
         B, Nv = v.shape[:2]
         Nf = f.shape[1]
         out = torch.empty((B, Nf, 3, 3), dtype=torch.float32, device=v.device)
-        with torch.cuda.device(v.device):
-            _lib.check(lib.nr_vertices_to_faces(v.data_ptr(), f.data_ptr(), out.data_ptr(), B, Nv, Nf, 1,
-                                                torch.cuda.current_stream(v.device).cuda_stream),
-                       'nr_vertices_to_faces')
+        _lib.launch('nr_vertices_to_faces', v.device, v.data_ptr(), f.data_ptr(), out.data_ptr(), B, Nv, Nf, 1)
         ctx.save_for_backward(f)
         ctx.dims = (B, Nv, Nf)
         return out
 
     @staticmethod
     def backward(ctx, grad_faces):
-        lib = _lib.load()
         f, = ctx.saved_tensors
         B, Nv, Nf = ctx.dims
         g = _lib.dense(grad_faces)
         grad_vertices = torch.empty((B, Nv, 3), dtype=torch.float32, device=g.device)
-        with torch.cuda.device(g.device):
-            _lib.check(lib.nr_vertices_to_faces_backward(g.data_ptr(), f.data_ptr(), grad_vertices.data_ptr(), B, Nv, Nf,
-                                                         1, torch.cuda.current_stream(g.device).cuda_stream),
-                       'nr_vertices_to_faces_backward')
+        _lib.launch('nr_vertices_to_faces_backward', g.device, g.data_ptr(), f.data_ptr(), grad_vertices.data_ptr(), B, Nv, Nf,
+                    1)
         return grad_vertices, None
 
 
