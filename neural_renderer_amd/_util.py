@@ -42,6 +42,39 @@ def takes_hip(name, implementation, fits, needs):
     return fits and implementation != 'torch'
 
 
+# what soft_silhouette.py and soft_render.py share
+
+def soft_segment(px, py, ax, ay, bx, by):
+    """(d2, edge function, t for the depth) of the segment a -> b at the pixels.  Inside d2 the nearest point's parameter carries
+    no gradient: d2's derivative through it is 0 (r orthogonal to the segment, or clamped); the t handed out does, where free."""
+    ex, ey, wx, wy = bx - ax, by - ay, px - ax, py - ay
+    dot, ee = wx * ex + wy * ey, ex * ex + ey * ey
+    pos = ee > 0
+    t_raw = torch.where(pos, dot / torch.where(pos, ee, torch.ones_like(ee)), torch.zeros_like(dot))
+    t = t_raw.clamp(0, 1).detach()
+    rx, ry = (1 - t) * wx + t * (px - bx), (1 - t) * wy + t * (py - by)   # p - c; an end takes (1 - t) or t of the gradient
+    return rx * rx + ry * ry, ex * wy - ey * wx, torch.where((t_raw > 0) & (t_raw < 1), t_raw, t)
+
+
+def soft_check_faces(name, faces):
+    """The soft operators' `faces` check -> (batch size, num of faces)."""
+    if not (torch.is_tensor(faces) and faces.is_floating_point() and faces.dim() == 4 and tuple(faces.shape[2:]) == (3, 3)
+            and faces.shape[0] >= 1 and faces.shape[1] >= 1):
+        raise ValueError('%s: faces must be a non-empty float tensor [batch size, num of faces, 3, 3]' % name)
+    return int(faces.shape[0]), int(faces.shape[1])
+
+
+def soft_check_image_size(name, image_size):
+    if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
+        raise ValueError('%s: image_size must be a positive integer, got %r' % (name, image_size))
+
+
+def soft_fits(faces, image_size):
+    """The device, dtype and size part of what the soft HIP kernels take (include/nr_hip.h)."""
+    return (faces.is_cuda and faces.dtype == torch.float32 and faces.shape[0] <= 65535 and faces.shape[1] <= SOFT_MAX_FACES
+            and faces.numel() < 2 ** 31 and image_size <= SOFT_MAX_SIZE)   # (numel: batch size * faces * 9)
+
+
 _INDEX_ATTR = '_nr_index_ok'  # verdict stashed on a tensor OBJECT: it dies with the tensor (a cache keyed on data_ptr would
                                # be hit by an unrelated tensor that the caching allocator places at the same address)
 

@@ -13,11 +13,12 @@
 // Over the taken pairs of p in ascending f, with m = max(eps, max_f zn_f), D = 1 / (1 + e^-x):
 //   w_f = D_f exp((zn_f - m) / gamma),  w_b = exp((eps - m) / gamma),  Z = w_b + sum w_f
 //   rgb = (w_b C_b + sum w_f C_f) / Z,  Q = prod 1 / (1 + e^x_f),  alpha = 1 - Q
-//   k_render_setup     (image, face) -> an 80-byte record: the silhouette record's 48 bytes (the flag with the area rule),
-//                      1 / z_k, the colour
-//   k_render_forward   a workgroup of four waves owns a 16 x 16 pixel tile, a lane a pixel; the records go through LDS in
-//                      chunks of 256 (20 KiB), the compact list ascending in f by ballot + prefix count, a wave-uniform trip
-//                      count.  TWO walks of the image's records: the first finds m, the second sums.  Stores rgba, Q, (m, Z).
+//   k_render_setup     (image, face) -> an 80-byte record: the base record's 48 bytes (soft_record, nr_soft_pair.h: the flag
+//                      with the area rule, the silhouette's box), 1 / z_k, the colour
+//   k_render_forward   a workgroup of four waves owns a 16 x 16 pixel tile, a lane a pixel (soft_tile); the records go
+//                      through LDS in chunks of 256 (20 KiB), the compact list ascending in f by soft_filter_chunk, a
+//                      wave-uniform trip count.  TWO walks of the image's records: the first finds m, the second sums.
+//                      Stores rgba, Q, (m, Z).
 //   k_render_backward  a wave owns an (image, face): it walks the pixels of the box, lanes strided, recomputes the pair, sums
 //                      six xy, three z and three colour gradients per lane, reduces them in the fixed xor tree, one store
 //                      per entry.
@@ -34,21 +35,18 @@
 // the flat terms plus one addition each (sum_k lambda_k dL/dlambda_k taken as diz iz: sum_k u_k E_k = 0 in exact arithmetic).
 // The <false> instantiations are the flat kernels, instruction for instruction.
 // No atomics, no host synchronisation, every output element stored; the same bits in every run and for an image alone or
-// inside a batch: a pixel's sums depend on the set of its taken pairs and their order in f alone.
+// inside a batch: a pixel's sums depend on the set of its taken pairs and their order in f alone.  The base record, the box, the
+// tile, the filter, the pair and the constants are nr_soft_pair.h's, one definition with nr_soft_silhouette.hip.
 #include "nr_soft_pair.h"
 
 using namespace nr;
 
 namespace {
 
-constexpr int RENDER_TILE = 16;       // pixels per side of a workgroup's tile (a wave: 8 x 8)
-constexpr int RENDER_CHUNK = 256;     // face records per LDS chunk, one per thread
-constexpr int RENDER_REC = 5;         // float4 per record
+constexpr int RENDER_REC = 5;         // float4 per record: the base record's SOFT_REC and two more
 constexpr int CORNER_REC = 6;         // ... with corner colours
-constexpr float RENDER_REACH = 17.0f;   // a pair outside is taken up to d2 = RENDER_REACH sigma
-constexpr int RENDER_MAX_F = 1 << 24;
 
-// what a record holds beyond the silhouette's: (1 / z0, 1 / z1, 1 / z2, red), (green, blue, 0, 0)
+// what a record holds beyond the base record: (1 / z0, 1 / z1, 1 / z2, red), (green, blue, 0, 0)
 struct FaceShade {
     float iz0, iz1, iz2, cr, cg, cb;
 };
@@ -143,37 +141,10 @@ __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ 
 {
     const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (f >= F) return;
-    const float *v = faces + ((size_t)b * F + f) * 9;
     const float *col = colors + (size_t)b * color_stride + (size_t)f * (CORNERS ? 9 : 3);
-    float c[9];
-#pragma unroll
-    for (int k = 0; k < 9; k++) c[k] = v[k];
-    bool on = true;
-#pragma unroll
-    for (int k = 0; k < 9; k++) on = on && (fabsf(c[k]) < __builtin_inff());   // false for a NaN too
-#pragma unroll
-    for (int k = 2; k < 9; k += 3) on = on && (double)c[k] >= near && (double)c[k] <= far;
-    // the doubled area in double: the differences and products of floats are exact there, one rounding in the subtraction
-    const double area = ((double)c[3] - (double)c[0]) * ((double)c[7] - (double)c[1]) -
-                        ((double)c[6] - (double)c[0]) * ((double)c[4] - (double)c[1]);
-    on = on && area != 0.0;
-    int ix_lo = S, iy_lo = S, ix_hi = -1, iy_hi = -1;   // empty
-    if (on) {
-        const float fs = (float)S;
-        const float xmin = fminf(fminf(c[0], c[3]), c[6]) - reach, xmax = fmaxf(fmaxf(c[0], c[3]), c[6]) + reach;
-        const float ymin = fminf(fminf(c[1], c[4]), c[7]) - reach, ymax = fmaxf(fmaxf(c[1], c[4]), c[7]) + reach;
-        // as k_soft_setup: floor below and ceil above keep up to a pixel more than needed; clamped before the conversion
-        const float lo_c = -1.0f, hi_c = fs;
-        ix_lo = max((int)floorf(fminf(fmaxf(to_pixel(xmin, fs), lo_c), hi_c)), 0);
-        ix_hi = min((int)ceilf(fminf(fmaxf(to_pixel(xmax, fs), lo_c), hi_c)), S - 1);
-        iy_lo = max((int)floorf(fminf(fmaxf(to_pixel(ymin, fs), lo_c), hi_c)), 0);
-        iy_hi = min((int)ceilf(fminf(fmaxf(to_pixel(ymax, fs), lo_c), hi_c)), S - 1);
-        if (ix_lo > ix_hi || iy_lo > iy_hi) { ix_lo = iy_lo = S; ix_hi = iy_hi = -1; }
-    }
     float4 *o = rec + ((size_t)b * F + f) * (CORNERS ? CORNER_REC : RENDER_REC);
-    o[0] = make_float4(c[0], c[1], c[3], c[4]);
-    o[1] = make_float4(c[6], c[7], __int_as_float(ix_lo), __int_as_float(iy_lo));
-    o[2] = make_float4(__int_as_float(ix_hi), __int_as_float(iy_hi), __int_as_float(on ? 1 : 0), 0.0f);
+    float c[9];
+    soft_record<true>(faces + ((size_t)b * F + f) * 9, o, S, reach, near, far, c);   // the flag with the area rule
     o[3] = make_float4(1.0f / c[2], 1.0f / c[5], 1.0f / c[8], col[0]);
     if constexpr (CORNERS) {
         o[4] = make_float4(col[1], col[2], col[3], col[4]);
@@ -186,61 +157,23 @@ __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ 
 // --------------------------------------------------------------------------------------------------------------------
 // forward
 
-// one chunk of records into the compact LDS list of those whose box meets the tile, ascending in f -> their number
-template <bool CORNERS>
-__device__ __forceinline__ int filter_chunk(const float4 *__restrict__ rb, int c0, int F, int tid, int wave, int lane, int tx0,
-                                            int ty0, int tx1, int ty1, float4 *list, int *wave_count)
-{
-    constexpr int REC = CORNERS ? CORNER_REC : RENDER_REC;
-    const int f = c0 + tid;
-    float4 r0, r1, r2, r3, r4, r5;
-    bool hit = false;
-    if (f < F) {
-        const float4 *src = rb + (size_t)f * REC;
-        r0 = src[0]; r1 = src[1]; r2 = src[2]; r3 = src[3]; r4 = src[4];
-        if constexpr (CORNERS) r5 = src[5];
-        const SoftFace s = unpack(r0, r1, r2);
-        hit = s.on != 0 && s.ix_lo <= tx1 && s.ix_hi >= tx0 && s.iy_lo <= ty1 && s.iy_hi >= ty0;
-    }
-    const unsigned long long m = __ballot(hit);
-    const int before = __popcll(m & ((1ull << lane) - 1ull));
-    if (lane == 0) wave_count[wave] = __popcll(m);
-    __syncthreads();
-    int base = 0, n = 0;
-#pragma unroll
-    for (int w = 0; w < 4; w++) {
-        const int cnt = wave_count[w];
-        base += w < wave ? cnt : 0;
-        n += cnt;
-    }
-    if (hit) {   // thread order is face order: the list stays ascending in f
-        const int at = (base + before) * REC;   // < RENDER_CHUNK * REC: at most one entry per thread
-        list[at] = r0; list[at + 1] = r1; list[at + 2] = r2; list[at + 3] = r3; list[at + 4] = r4;
-        if constexpr (CORNERS) list[at + 5] = r5;
-    }
-    __syncthreads();
-    return rfl(n);
-}
-
 template <bool CORNERS>
 __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict__ rec, float *__restrict__ rgba,
                                                         float *__restrict__ trans, float *__restrict__ norm, int F, int S,
                                                         int tiles_x, RenderArgs a)
 {
     constexpr int REC = CORNERS ? CORNER_REC : RENDER_REC;
-    __shared__ float4 list[RENDER_CHUNK * REC];
+    __shared__ float4 list[SOFT_CHUNK * REC];
     __shared__ int wave_count[4];
-    const int b = blockIdx.y, tile_y = blockIdx.x / tiles_x, tile_x = blockIdx.x - tile_y * tiles_x;
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int tx0 = tile_x * RENDER_TILE, ty0 = tile_y * RENDER_TILE;
-    const int tx1 = min(tx0 + RENDER_TILE - 1, S - 1), ty1 = min(ty0 + RENDER_TILE - 1, S - 1);
-    const int xi = tx0 + (wave & 1) * 8 + (lane & 7), yi = ty0 + (wave >> 1) * 8 + (lane >> 3);
-    const float px = pixel_center(min(xi, S - 1), S), py = pixel_center(min(yi, S - 1), S);
+    const int b = blockIdx.y;
+    const SoftTile T = soft_tile(S, tiles_x);
+    const int xi = T.xi, yi = T.yi;
+    const float px = T.px, py = T.py;
     const float4 *rb = rec + (size_t)b * F * REC;
     // the first walk: m = max(eps, the zn of the taken pairs) -- a maximum of the very floats the second walk subtracts it from
     float m = a.eps;
-    for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
-        const int n = filter_chunk<CORNERS>(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+    for (int c0 = 0; c0 < F; c0 += SOFT_CHUNK) {
+        const int n = soft_filter_chunk<REC>(rb, c0, F, T, list, wave_count);
         for (int j = 0; j < n; j++) {
             const float4 *l = list + j * REC;
             const SoftFace s = unpack(l[0], l[1], l[2]);
@@ -254,8 +187,8 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
     // the second walk
     const float wb = expf((a.eps - m) * a.inv_gamma);
     float Z = wb, cr = wb * a.bg_r, cg = wb * a.bg_g, cb = wb * a.bg_b, Q = 1.0f;
-    for (int c0 = 0; c0 < F; c0 += RENDER_CHUNK) {
-        const int n = filter_chunk<CORNERS>(rb, c0, F, tid, wave, lane, tx0, ty0, tx1, ty1, list, wave_count);
+    for (int c0 = 0; c0 < F; c0 += SOFT_CHUNK) {
+        const int n = soft_filter_chunk<REC>(rb, c0, F, T, list, wave_count);
         for (int j = 0; j < n; j++) {
             const float4 *l = list + j * REC;
             const SoftFace s = unpack(l[0], l[1], l[2]);
@@ -442,8 +375,6 @@ __global__ __launch_bounds__(256) void k_render_colors(const float *__restrict__
 // --------------------------------------------------------------------------------------------------------------------
 // host
 
-bool render_sizes_ok(int B, int F, int S) { return check_sizes(B, F, S) == 0 && F <= RENDER_MAX_F; }
-
 // corners = 0: one colour per face, 1: one per corner
 size_t render_records(int B, int F, int corners)
 {
@@ -469,7 +400,7 @@ struct RenderCall {
 int render_check(const RenderCall &c)
 {
     if (!c.faces || !c.colors) return NR_E_NULL;
-    if (!render_sizes_ok(c.B, c.F, c.S)) return NR_E_SIZE;
+    if (!soft_sizes_ok(c.B, c.F, c.S)) return NR_E_SIZE;
     const auto finite = [](double v) { return v - v == 0.0; };
     if (!(c.sigma >= 1.0e-30 && c.sigma <= 1.0e30) || !(c.gamma >= 1.0e-30 && c.gamma <= 1.0e30)) return NR_E_MODE;
     if (!finite(c.near) || !finite(c.far) || !(c.far > c.near) || !finite(c.eps)) return NR_E_MODE;
@@ -484,7 +415,7 @@ RenderArgs render_args(const RenderCall &c)
     RenderArgs a;
     a.inv_sigma = (float)(1.0 / c.sigma);
     a.inv_gamma = (float)(1.0 / c.gamma);
-    a.cut = (float)((double)RENDER_REACH * c.sigma);
+    a.cut = (float)((double)SOFT_REACH * c.sigma);
     a.far = (float)c.far;
     a.inv_range = (float)(1.0 / (c.far - c.near));
     a.eps = (float)c.eps;
@@ -495,10 +426,9 @@ RenderArgs render_args(const RenderCall &c)
 template <bool CORNERS>
 int render_setup(const RenderCall &c, hipStream_t st)
 {
-    const float reach = sqrtf(RENDER_REACH * (float)c.sigma) * 1.0001f;   // (the margin covers the roundings of this line)
     hipLaunchKernelGGL(k_render_setup<CORNERS>, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces,
                        c.colors, (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * (CORNERS ? 9 : 3) : (size_t)0,
-                       reach, c.near, c.far);
+                       soft_reach(c.sigma), c.near, c.far);
     return launch_status();
 }
 
@@ -509,7 +439,7 @@ int render_forward(const RenderCall &c, float *rgba, float *transmittance, float
     if (int e = render_check(c)) return e;
     hipStream_t st = (hipStream_t)stream;
     if (int rc = render_setup<CORNERS>(c, st)) return rc;
-    const int tiles = (c.S + RENDER_TILE - 1) / RENDER_TILE;
+    const int tiles = (c.S + SOFT_TILE - 1) / SOFT_TILE;
     hipLaunchKernelGGL(k_render_forward<CORNERS>, dim3((unsigned)(tiles * tiles), (unsigned)c.B), dim3(256), 0, st,
                        (const float4 *)c.workspace, rgba, transmittance, normaliser, c.F, c.S, tiles, render_args(c));
     return launch_status();
@@ -539,7 +469,7 @@ int render_backward(const RenderCall &c, const float *rgba, const float *transmi
 
 NR_API size_t nr_soft_render_workspace_bytes(int32_t B, int32_t F, int32_t S)
 {
-    return render_sizes_ok(B, F, S) ? render_workspace(B, F, 0) : 0;
+    return soft_sizes_ok(B, F, S) ? render_workspace(B, F, 0) : 0;
 }
 
 NR_API int nr_soft_render_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,
@@ -565,7 +495,7 @@ NR_API int nr_soft_render_backward(const float *faces, const float *colors, cons
 
 NR_API size_t nr_soft_corners_workspace_bytes(int32_t B, int32_t F, int32_t S)
 {
-    return render_sizes_ok(B, F, S) ? render_workspace(B, F, 1) : 0;
+    return soft_sizes_ok(B, F, S) ? render_workspace(B, F, 1) : 0;
 }
 
 NR_API int nr_soft_corners_forward(const float *faces, const float *colors, float *rgba, float *transmittance, float *normaliser,

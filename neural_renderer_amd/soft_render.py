@@ -60,18 +60,6 @@ REACH = 17.0                # an outside pair is taken up to d2 = REACH sigma
 # ---------------------------------------------------------------------------------------------------------------------
 # plain torch
 
-def _segment(px, py, ax, ay, bx, by):
-    """(d2, edge function, t for the depth) of the segment a -> b at the pixels.  Inside d2 the parameter of the nearest
-    point carries no gradient, as in soft_silhouette._segment; the t handed out for the depth does, where it is free."""
-    ex, ey, wx, wy = bx - ax, by - ay, px - ax, py - ay
-    dot, ee = wx * ex + wy * ey, ex * ex + ey * ey
-    pos = ee > 0
-    t_raw = torch.where(pos, dot / torch.where(pos, ee, torch.ones_like(ee)), torch.zeros_like(dot))
-    t = t_raw.clamp(0, 1).detach()
-    rx, ry = (1 - t) * wx + t * (px - bx), (1 - t) * wy + t * (py - by)
-    return rx * rx + ry * ry, ex * wy - ey * wx, torch.where((t_raw > 0) & (t_raw < 1), t_raw, t)
-
-
 def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
                       background_color=(0, 0, 0)):
     """rgba [B,4,S,S] in plain torch (any device, any float dtype), differentiable by autograd in faces and colors; the
@@ -101,9 +89,9 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
     out = []
     for r0 in range(0, S, rows):
         py = centre[None, r0:r0 + rows, None, None]
-        d0, c0, t0 = _segment(px, py, v[0][0], v[0][1], v[1][0], v[1][1])
-        d1, c1, t1 = _segment(px, py, v[1][0], v[1][1], v[2][0], v[2][1])
-        d2, c2, t2 = _segment(px, py, v[2][0], v[2][1], v[0][0], v[0][1])
+        d0, c0, t0 = _util.soft_segment(px, py, v[0][0], v[0][1], v[1][0], v[1][1])
+        d1, c1, t1 = _util.soft_segment(px, py, v[1][0], v[1][1], v[2][0], v[2][1])
+        d2, c2, t2 = _util.soft_segment(px, py, v[2][0], v[2][1], v[0][0], v[0][1])
         s1 = d1 < d0   # strict: the lowest segment wins a tie
         da = torch.where(s1, d1, d0)
         s2 = d2 < da
@@ -181,18 +169,14 @@ class _SoftRender(torch.autograd.Function):
 def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, background_color, implementation):
     """Argument checks shared by both implementations -> (image_size, sigma, gamma, near, far, eps, background, takes the
     HIP path)."""
-    if not (torch.is_tensor(faces) and faces.is_floating_point() and faces.dim() == 4 and tuple(faces.shape[2:]) == (3, 3)
-            and faces.shape[0] >= 1 and faces.shape[1] >= 1):
-        raise ValueError('%s: faces must be a non-empty float tensor [batch size, num of faces, 3, 3]' % name)
-    B, F = int(faces.shape[0]), int(faces.shape[1])
+    B, F = _util.soft_check_faces(name, faces)
     if not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() in (3, 4)
             and tuple(colors.shape[1:]) in ((F, 3), (F, 3, 3)) and colors.shape[0] in (1, B)):
         raise ValueError('%s: colors must be a float tensor [batch size or 1, num of faces (%d), 3], or [batch size or 1, '
                          'num of faces, 3, 3] for corner colours' % (name, F))
     if colors.device != faces.device:
         raise ValueError('%s: colors on %s, faces on %s' % (name, colors.device, faces.device))
-    if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
-        raise ValueError('%s: image_size must be a positive integer, got %r' % (name, image_size))
+    _util.soft_check_image_size(name, image_size)
     sigma, gamma = _util.number(name, 'sigma', sigma), _util.number(name, 'gamma', gamma)
     for what, v in (('sigma', sigma), ('gamma', gamma)):
         if not (0 < v < float('inf')):
@@ -211,9 +195,7 @@ def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, backgr
     background = tuple(_util.number(name, 'background_color', float(c) if torch.is_tensor(c) else c) for c in background)
     if not all(math.isfinite(c) for c in background):
         raise ValueError('%s: background_color must be finite, got %r' % (name, background_color))
-    fits = (faces.is_cuda and faces.dtype == torch.float32 and colors.dtype == torch.float32 and B <= 65535
-            and F <= _util.SOFT_MAX_FACES and B * F * 9 < 2 ** 31 and image_size <= _util.SOFT_MAX_SIZE
-            and 1e-30 <= sigma <= 1e30 and 1e-30 <= gamma <= 1e30)
+    fits = _util.soft_fits(faces, image_size) and colors.dtype == faces.dtype and 1e-30 <= sigma <= 1e30 and 1e-30 <= gamma <= 1e30
     return image_size, sigma, gamma, near, far, eps, background, _util.takes_hip(
         name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 '
         'faces (batch size * faces * 9 < 2^31), an image_size of 16384 at most and sigma, gamma in [1e-30, 1e30]')

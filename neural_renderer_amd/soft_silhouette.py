@@ -35,17 +35,6 @@ _CHUNK_ELEMENTS = 2 ** 26   # soft_silhouettes_torch: the most elements of one t
 # ---------------------------------------------------------------------------------------------------------------------
 # plain torch
 
-def _segment(px, py, ax, ay, bx, by):
-    """(d2, edge function) of the segment a -> b at the pixels; the parameter of the nearest point carries no gradient: the
-    derivative of d2 through it is 0 (r is orthogonal to the segment, or the parameter is clamped)."""
-    ex, ey, wx, wy = bx - ax, by - ay, px - ax, py - ay
-    dot, ee = wx * ex + wy * ey, ex * ex + ey * ey
-    pos = ee > 0
-    t = torch.where(pos, dot / torch.where(pos, ee, torch.ones_like(ee)), torch.zeros_like(dot)).clamp(0, 1).detach()
-    rx, ry = (1 - t) * wx + t * (px - bx), (1 - t) * wy + t * (py - by)   # p - c; an end takes (1 - t) or t of the gradient
-    return rx * rx + ry * ry, ex * wy - ey * wx
-
-
 def soft_silhouettes_torch(faces, image_size=256, sigma=1e-4, near=0.1, far=100):
     """alpha [B,S,S] in plain torch (any device, any float dtype), differentiable by autograd; the module docstring's
     definition over every (pixel, face) pair, in chunks of pixel rows."""
@@ -62,9 +51,9 @@ def soft_silhouettes_torch(faces, image_size=256, sigma=1e-4, near=0.1, far=100)
     out = []
     for r0 in range(0, S, rows):
         py = centre[None, r0:r0 + rows, None, None]
-        d0, c0 = _segment(px, py, v[0][0], v[0][1], v[1][0], v[1][1])
-        d1, c1 = _segment(px, py, v[1][0], v[1][1], v[2][0], v[2][1])
-        d2, c2 = _segment(px, py, v[2][0], v[2][1], v[0][0], v[0][1])
+        d0, c0, _ = _util.soft_segment(px, py, v[0][0], v[0][1], v[1][0], v[1][1])
+        d1, c1, _ = _util.soft_segment(px, py, v[1][0], v[1][1], v[2][0], v[2][1])
+        d2, c2, _ = _util.soft_segment(px, py, v[2][0], v[2][1], v[0][0], v[0][1])
         d = torch.where(d1 < d0, d1, d0)   # strict: the lowest segment wins a tie
         d = torch.where(d2 < d, d2, d)
         inside = ((c0 > 0) & (c1 > 0) & (c2 > 0)) | ((c0 < 0) & (c1 < 0) & (c2 < 0))
@@ -113,18 +102,13 @@ class _SoftSilhouettes(torch.autograd.Function):
 
 def _check(name, faces, image_size, sigma, near, far, implementation):
     """Argument checks shared by both implementations -> (image_size, sigma, near, far, takes the HIP path)."""
-    if not (torch.is_tensor(faces) and faces.is_floating_point() and faces.dim() == 4 and tuple(faces.shape[2:]) == (3, 3)
-            and faces.shape[0] >= 1 and faces.shape[1] >= 1):
-        raise ValueError('%s: faces must be a non-empty float tensor [batch size, num of faces, 3, 3]' % name)
-    if isinstance(image_size, bool) or not isinstance(image_size, int) or image_size < 1:
-        raise ValueError('%s: image_size must be a positive integer, got %r' % (name, image_size))
+    _util.soft_check_faces(name, faces)
+    _util.soft_check_image_size(name, image_size)
     sigma = _util.number(name, 'sigma', sigma)
     if not (0 < sigma < float('inf')):
         raise ValueError('%s: sigma must be a finite number greater than 0, got %r' % (name, sigma))
     near, far = _util.number(name, 'near', near), _util.number(name, 'far', far)
-    B, F = int(faces.shape[0]), int(faces.shape[1])
-    fits = (faces.is_cuda and faces.dtype == torch.float32 and B <= 65535 and F <= _util.SOFT_MAX_FACES
-            and B * F * 9 < 2 ** 31 and image_size <= _util.SOFT_MAX_SIZE and 1e-30 <= sigma <= 1e30)
+    fits = _util.soft_fits(faces, image_size) and 1e-30 <= sigma <= 1e30
     return image_size, sigma, near, far, _util.takes_hip(
         name, implementation, fits, 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most, at most 2^24 '
         'faces (batch size * faces * 9 < 2^31), an image_size of 16384 at most and 1e-30 <= sigma <= 1e30')

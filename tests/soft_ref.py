@@ -2,14 +2,15 @@
 float64 NumPy: forward, Q and the analytic gradient, with the term magnitudes and the per-entry bounds of a float32 run.
 
   restate(faces, S, sigma, near, far, g, adds)   -> Result: alpha, Q, grad_faces, their magnitudes and bounds, the doubt share
+  geometry(xy, on, S, sigma)                     the pairs' geometry and its rounding terms, also soft_render_ref's front
   sphere_faces(level, B)                         the projected icosphere of the checked cases
   worst_ratio(got, ref, bound)                   max |got - ref| / bound, 0 / 0 = 0, x / 0 = inf
 
 The definition is the header's.  Everything is computed per (pixel, face) pair on arrays [3 segments, S*S pixels, F faces];
 rows are internal (row 0 at the bottom) and flipped on the way in (g) and out (alpha, Q, the bound).
 
-The float32 operation sequence that the bounds count (csrc/nr_soft_silhouette.hip: soft_segment, soft_pair, the two kernels),
-u = 2^-24, first order, every difference and sum propagated with absolute values:
+The float32 operation sequence that the bounds count (csrc/nr_soft_pair.h: soft_segment, soft_pair; csrc/nr_soft_silhouette.hip:
+the two kernels), u = 2^-24, first order, every difference and sum propagated with absolute values:
 
   p        the pixel centre is the float32 rounding of (2 i + 1 - S) / S:                       dp = u |p|
   per segment a -> b:  e = b - a, w = p - a (a rounding each, w also dp);  dot = wx ex + wy ey;  ee = ex ex + ey ey
@@ -47,6 +48,8 @@ segment can have the SAME nearest point and d2 and yet hand the gradient to othe
 happens only at a shared vertex, where both segments give everything to that vertex).  Which of the two wins is decided by the
 last bit of d2: such a pair adds both candidates' gradient terms, as in (2); alpha is the same either way.
 """
+import types
+
 import numpy as np
 
 import vertex_ref
@@ -72,12 +75,13 @@ class Result(object):
     pass
 
 
-def _image(fc, S, sigma, near, far, g, adds):
-    """One image: fc [F,3,3] float64, g [S,S] internal rows or None."""
-    F = fc.shape[0]
-    with np.errstate(all='ignore'):
-        on = np.isfinite(fc).all((1, 2)) & (fc[:, :, 2] >= near).all(1) & (fc[:, :, 2] <= far).all(1)
-    xy = np.where(on[:, None, None], fc[:, :, :2], 0.0)
+def geometry(xy, on, S, sigma):
+    """The front that the three restatements share: xy [F,3,2] of the faces (0 where a face does not contribute), on [F],
+    -> a namespace of arrays [3 segments, P = S*S pixels, F faces] or [P,F]: the segments' geometry (px, py, ex, ey, wx, wy, vx,
+    vy, ee, t_raw, t, cx, cy, rx, ry, d2s, cr), the chosen segment (k, pick(a, kk=k)), the pair (d2, inside, s, x, onp), the
+    chosen segment's rounding terms of the module docstring (tk, rxk, ryk, exk, eyk, eek, t_rawk, apx, apy, ddot, dt_full --
+    before the clamp's exactness --, dt, dr0x, dr0y, dd2, dx), the second candidate (k2, d22, apart: it has another nearest
+    point) and the edge doubt (emag, near0)."""
     c1 = (2.0 * np.arange(S) + 1 - S) / S
     px = np.tile(c1, S)[:, None]       # [P,1], P = yi * S + xi
     py = np.repeat(c1, S)[:, None]
@@ -97,18 +101,12 @@ def _image(fc, S, sigma, near, far, g, adds):
     d2s = rx * rx + ry * ry
     cr = ex * wy - ey * wx
     k = np.argmin(d2s, 0)                                  # the lowest k on a tie
-    pick = lambda a: np.take_along_axis(np.broadcast_to(a, d2s.shape), k[None], 0)[0]
+    pick = lambda a, kk=None: np.take_along_axis(np.broadcast_to(a, d2s.shape), (k if kk is None else kk)[None], 0)[0]
     d2 = pick(d2s)
     inside = (cr > 0).all(0) | (cr < 0).all(0)
     s = np.where(inside, 1.0, -1.0)
     x = s * d2 / sigma
     onp = np.broadcast_to(on[None, :], x.shape)
-    with np.errstate(all='ignore'):
-        D = np.where(onp, 1.0 / (1.0 + np.exp(-x)), 0.0)
-        # Q = the product of 1 / (1 + e^x) and alpha = 1 - Q, through the logarithms: in float64 the plain product and the
-        # subtraction would leave alpha no better than 2^-53 F, which is the size of the far pixels' alpha
-        ln_q = -np.where(onp, np.logaddexp(0.0, x), 0.0).sum(1)
-        Q, alpha = np.exp(ln_q), -np.expm1(ln_q)
 
     # ---- the chosen segment's rounding terms
     tk, rxk, ryk, exk, eyk = pick(t), pick(rx), pick(ry), pick(ex), pick(ey)
@@ -116,24 +114,48 @@ def _image(fc, S, sigma, near, far, g, adds):
     apx, apy = np.abs(px), np.abs(py)
     ddot = 4 * U * pick(np.abs(wx * ex) + np.abs(wy * ey)) + U * (np.abs(exk) * apx + np.abs(eyk) * apy)
     with np.errstate(all='ignore'):
-        dt = np.where(eek > 0, ddot / np.where(eek > 0, eek, 1.0), 0.0) + 5 * U * np.abs(t_rawk)
-    dt = np.where((t_rawk < -dt) | (t_rawk > 1 + dt), 0.0, dt)
+        dt_full = np.where(eek > 0, ddot / np.where(eek > 0, eek, 1.0), 0.0) + 5 * U * np.abs(t_rawk)
+    dt = np.where((t_rawk < -dt_full) | (t_rawk > 1 + dt_full), 0.0, dt_full)
     dr0x = U * (3 * (1 - tk) * np.abs(pick(wx)) + 2 * tk * np.abs(pick(vx)) + np.abs(rxk) + apx)
     dr0y = U * (3 * (1 - tk) * np.abs(pick(wy)) + 2 * tk * np.abs(pick(vy)) + np.abs(ryk) + apy)
     dd2 = 2 * np.abs(rxk) * dr0x + 2 * np.abs(ryk) * dr0y + 2 * U * d2
     dx = dd2 / sigma + 2 * U * np.abs(x)
 
-    # ---- doubt
+    # ---- the second candidate, the edge functions next to 0
     d2_other = np.where(np.arange(3)[:, None, None] == k[None], np.inf, d2s)
     k2 = np.argmin(d2_other, 0)
-    pick2 = lambda a: np.take_along_axis(np.broadcast_to(a, d2s.shape), k2[None], 0)[0]
-    d22 = pick2(d2s)
-    apart = np.hypot(pick2(cx) - pick(cx), pick2(cy) - pick(cy)) > 1e-12 * (1 + np.abs(pick(cx)) + np.abs(pick(cy)))
-    seg_doubt = onp & apart & (d22 - d2 <= SEG_DOUBT * d22)
+    d22 = pick(d2s, k2)
+    apart = np.hypot(pick(cx, k2) - pick(cx), pick(cy, k2) - pick(cy)) > 1e-12 * (1 + np.abs(pick(cx)) + np.abs(pick(cy)))
     # an edge function in doubt: within 1e-6 of its own term magnitude of 0.  A magnitude of exactly 0 (a zero-length
     # segment, a pixel on the segment's first end) is no doubt: the edge function is 0 in every arithmetic, the pair outside
     emag = np.abs(ex * wy) + np.abs(ey * wx)
     near0 = (emag > 0) & (np.abs(cr) <= EDGE_DOUBT * emag)
+    return types.SimpleNamespace(
+        px=px, py=py, ex=ex, ey=ey, wx=wx, wy=wy, vx=vx, vy=vy, ee=ee, t_raw=t_raw, t=t, cx=cx, cy=cy, rx=rx, ry=ry, d2s=d2s,
+        cr=cr, k=k, pick=pick, d2=d2, inside=inside, s=s, x=x, onp=onp, tk=tk, rxk=rxk, ryk=ryk, exk=exk, eyk=eyk, eek=eek,
+        t_rawk=t_rawk, apx=apx, apy=apy, ddot=ddot, dt_full=dt_full, dt=dt, dr0x=dr0x, dr0y=dr0y, dd2=dd2, dx=dx, k2=k2, d22=d22,
+        apart=apart, emag=emag, near0=near0)
+
+
+def _image(fc, S, sigma, near, far, g, adds):
+    """One image: fc [F,3,3] float64, g [S,S] internal rows or None."""
+    F = fc.shape[0]
+    with np.errstate(all='ignore'):
+        on = np.isfinite(fc).all((1, 2)) & (fc[:, :, 2] >= near).all(1) & (fc[:, :, 2] <= far).all(1)
+    G = geometry(np.where(on[:, None, None], fc[:, :, :2], 0.0), on, S, sigma)
+    t, rx, ry, cr, k, d2, s, x, onp = G.t, G.rx, G.ry, G.cr, G.k, G.d2, G.s, G.x, G.onp
+    tk, rxk, ryk, exk, eyk, dt, dr0x, dr0y, dx = G.tk, G.rxk, G.ryk, G.exk, G.eyk, G.dt, G.dr0x, G.dr0y, G.dx
+    k2, d22, apart, emag, near0 = G.k2, G.d22, G.apart, G.emag, G.near0
+    pick2 = lambda a: G.pick(a, k2)
+    with np.errstate(all='ignore'):
+        D = np.where(onp, 1.0 / (1.0 + np.exp(-x)), 0.0)
+        # Q = the product of 1 / (1 + e^x) and alpha = 1 - Q, through the logarithms: in float64 the plain product and the
+        # subtraction would leave alpha no better than 2^-53 F, which is the size of the far pixels' alpha
+        ln_q = -np.where(onp, np.logaddexp(0.0, x), 0.0).sum(1)
+        Q, alpha = np.exp(ln_q), -np.expm1(ln_q)
+
+    # ---- doubt
+    seg_doubt = onp & apart & (d22 - d2 <= SEG_DOUBT * d22)
     edge_doubt = onp & near0.any(0)
     doubt = seg_doubt | edge_doubt
     # ... whose sign decides inside or outside: no edge function is exactly 0 and the ones not in doubt agree in sign

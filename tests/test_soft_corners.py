@@ -1,5 +1,5 @@
 """CPU checks of soft colour rendering with corner colours (soft_render with colors [B|1,F,3,3],
-Renderer.render_soft(per_pixel=True)): soft_render_torch in float64 against the restatement of tests/soft_corners_ref.py, the
+Renderer.render_soft(per_pixel=True)): soft_render_torch in float64 against the restatement of tests/soft_render_ref.py, the
 restatement's analytic gradient against central differences of itself, equal corners against the flat definition, shared
 colours, the sensitivity of the float32 bounds, the masked-pixel and doubt caps of every case the GPU file runs, argument
 errors of the Python function and of the three ABI entries, and the renderer on CPU tensors."""
@@ -7,7 +7,6 @@ import numpy as np
 import pytest
 import torch
 
-import soft_corners_ref as C
 import soft_render_ref as R
 from test_soft_render import TWO
 
@@ -36,7 +35,7 @@ def test_torch_float64_equals_the_restatement(S, sigma, gamma):
     faces = R.sphere_faces(1, 2)
     colors = _colors(2, faces.shape[1])
     g = np.random.default_rng(2).normal(size=(2, 4, S, S))
-    ref = C.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
+    ref = R.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
     out, gf, gc = _torch64(faces, colors, S, sigma, gamma, ref.g)
     assert tuple(gc.shape) == (2, faces.shape[1], 3, 3)
     assert np.abs(out - ref.rgba).max() <= 1e-12
@@ -59,8 +58,8 @@ def test_shared_colors_in_torch():
     assert tuple(colors.grad.shape) == (1, 80, 3, 3)
     assert torch.allclose(colors.grad[0], wide.grad.sum(0), rtol=1e-12, atol=1e-14)
     # the restatement with [1,F,3,3]
-    ref = C.restate(faces.numpy(), colors.detach().numpy(), 16, 1e-3, 1e-2, g=g.numpy())
-    total, _ = C.shared_colors(ref)
+    ref = R.restate(faces.numpy(), colors.detach().numpy(), 16, 1e-3, 1e-2, g=g.numpy())
+    total, _ = R.shared_colors(ref)
     assert tuple(total.shape) == (1, 80, 3, 3) and np.abs(total).max() > 0
     again = torch.tensor(colors.detach().numpy(), requires_grad=True)
     nr.soft_render_torch(faces, again, 16, 1e-3, 1e-2).backward(torch.tensor(ref.g))
@@ -85,7 +84,7 @@ def test_three_equal_corners_are_the_flat_render():
     assert (a - b).abs().max() <= 1e-12
     assert (af - bf).abs().max() <= 1e-12 * max(1.0, float(af.abs().max()))
     assert (ac - bc.sum(2)).abs().max() <= 1e-12 * max(1.0, float(ac.abs().max()))
-    ref_c = C.restate(faces, np.repeat(flat[:, :, None, :], 3, 2), 16, 1e-3, 1e-1, background=BG, g=g)
+    ref_c = R.restate(faces, np.repeat(flat[:, :, None, :], 3, 2), 16, 1e-3, 1e-1, background=BG, g=g)
     ref_f = R.restate(faces, flat, 16, 1e-3, 1e-1, background=BG, g=g)
     assert np.abs(ref_c.rgba - ref_f.rgba).max() <= 1e-12
     assert np.abs(ref_c.grad_faces - ref_f.grad_faces).max() <= 1e-12 * max(1.0, np.abs(ref_f.grad_faces).max())
@@ -102,9 +101,9 @@ def test_analytic_gradient_against_central_differences(sigma, gamma):
     faces, S = TWO, 8
     colors = _colors(1, 2, 4).astype(np.float64)
     g = np.random.default_rng(5).normal(size=(1, 4, S, S))
-    ref = C.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
+    ref = R.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
     assert ref.masked == [0] and ref.doubt == [0]
-    loss = lambda f, c: float((C.restate(f, c, S, sigma, gamma, background=BG).rgba * g).sum())
+    loss = lambda f, c: float((R.restate(f, c, S, sigma, gamma, background=BG).rgba * g).sum())
     hstep = 1e-6
     for idx in np.ndindex(faces.shape):
         up, dn = faces.copy(), faces.copy()
@@ -126,8 +125,8 @@ def test_the_colour_path_reaches_the_geometry():
     another one, in every face entry."""
     colors = _colors(1, 2, 4).astype(np.float64)
     g = np.random.default_rng(5).normal(size=(1, 4, 8, 8))
-    ref = C.restate(TWO, colors, 8, 3e-2, 5e-2, background=BG, g=g)
-    cut = C.restate(TWO, colors, 8, 3e-2, 5e-2, background=BG, g=g, variant='no_colour_path')
+    ref = R.restate(TWO, colors, 8, 3e-2, 5e-2, background=BG, g=g)
+    cut = R.restate(TWO, colors, 8, 3e-2, 5e-2, background=BG, g=g, variant='no_colour_path')
     assert (np.abs(ref.grad_faces - cut.grad_faces) > 1e-6 * ref.grad_faces_mag).all()
     assert np.array_equal(ref.grad_colors, cut.grad_colors) and np.array_equal(ref.rgba, cut.rgba)
 
@@ -141,11 +140,11 @@ def test_bounds_are_not_vacuous(variant, what):
     import test_soft_corners_gpu as G
     mesh, B, S, sigma, gamma = G.CASES[0]
     faces, colors, ref = G.reference(mesh, B, S, sigma, gamma)
-    bad = C.restate(faces, colors, S, sigma, gamma, background=G.BG, g=ref.g, variant=variant)
+    bad = R.restate(faces, colors, S, sigma, gamma, background=G.BG, g=ref.g, variant=variant)
     if what == 'rgba':
-        ratio = C.masked_ratio(bad.rgba, ref.rgba, ref.rgba_bound, ref.mask)
+        ratio = R.masked_ratio(bad.rgba, ref.rgba, ref.rgba_bound, ref.mask)
     else:
-        ratio = C.worst_ratio(bad.grad_faces, ref.grad_faces, ref.grad_faces_bound)
+        ratio = R.worst_ratio(bad.grad_faces, ref.grad_faces, ref.grad_faces_bound)
     assert ratio > 1, ratio
 
 
@@ -160,7 +159,7 @@ def test_caps_of_every_gpu_case():
         key = (mesh, B, S, sigma)
         if key not in seen:   # (no gradient asked: the forward half of the restatement is enough)
             faces = G._faces(mesh, B)
-            seen[key] = C.restate(faces, np.zeros((1, faces.shape[1], 3, 3)), S, sigma, gamma)
+            seen[key] = R.restate(faces, np.zeros((1, faces.shape[1], 3, 3)), S, sigma, gamma)
         ref = seen[key]
         assert ref.masked_share <= 0.01, (key, ref.masked, ref.with_pair)
         assert ref.doubt_share <= 0.02, (key, ref.doubt, ref.pairs)

@@ -1,7 +1,7 @@
 """`-m gpu`: the soft colour kernels with corner colours (csrc/nr_soft_render.hip, the nr_soft_corners_* entries), soft_render
 with colors [B|1,F,3,3] and Renderer.render_soft(per_pixel=True).
 
-rgba, grad_faces and grad_colors against the float64 restatement of tests/soft_corners_ref.py under its derived bounds, on the
+rgba, grad_faces and grad_colors against the float64 restatement of tests/soft_render_ref.py under its derived bounds, on the
 geometry and (S, sigma, gamma) of tests/test_soft_render_gpu.py's cases; shared colours; reproducibility; the tensor boundary
 and a side stream; equal corners against the flat kernels; the renderer end to end, against soft_render of the composition
 and against the hard rasterizer; the example.  "Bit for bit" is torch.equal.  The cases and their references are also read
@@ -16,10 +16,9 @@ import numpy as np
 import pytest
 import torch
 
-import soft_corners_ref as C
 import soft_render_ref as R
 import test_soft_render_gpu as G0
-from test_soft_render_gpu import BG, _cuda, _faces, _host
+from test_soft_render_gpu import BG, _cuda, _faces, _host, _ratios, _run
 
 pytestmark = pytest.mark.gpu
 
@@ -42,22 +41,8 @@ def reference(mesh, B, S, sigma, gamma, adds=None):
         rng = np.random.default_rng(B * 1000 + S + 7)
         colors = rng.uniform(0, 1, (B, faces.shape[1], 3, 3)).astype(np.float32)
         g = rng.normal(size=(B, 4, S, S)).astype(np.float32)
-        _cache[key] = (faces, colors, C.restate(faces, colors, S, sigma, gamma, background=BG, g=g, adds=adds))
+        _cache[key] = (faces, colors, R.restate(faces, colors, S, sigma, gamma, background=BG, g=g, adds=adds))
     return _cache[key]
-
-
-def _run(faces, colors, g, S, sigma, gamma, implementation='hip'):
-    import neural_renderer_amd as nr
-    ft, ct = _cuda(faces, True), _cuda(colors, True)
-    rgba = nr.soft_render(ft, ct, S, sigma, gamma, background_color=BG, implementation=implementation)
-    rgba.backward(_cuda(np.asarray(g, np.float32)))
-    return rgba.detach(), ft.grad, ct.grad
-
-
-def _ratios(ref, rgba, gf, gc):
-    return (C.masked_ratio(_host(rgba), ref.rgba, ref.rgba_bound, ref.mask),
-            C.worst_ratio(_host(gf), ref.grad_faces, ref.grad_faces_bound),
-            C.worst_ratio(_host(gc), ref.grad_colors, ref.grad_colors_bound))
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -66,7 +51,7 @@ def _ratios(ref, rgba, gf, gc):
 @pytest.mark.parametrize('mesh,B,S,sigma,gamma', CASES, ids=IDS)
 def test_forward_and_gradients_within_the_derived_bounds(mesh, B, S, sigma, gamma):
     """rgba (outside the masked pixels), grad_faces and grad_colors from random upstream gradients (0 on the masked pixels)
-    within the per-entry bounds of soft_corners_ref (its docstring); the caps on masked pixels and pairs in doubt."""
+    within the per-entry bounds of soft_render_ref (its docstring); the caps on masked pixels and pairs in doubt."""
     faces, colors, ref = reference(mesh, B, S, sigma, gamma)
     rgba, gf, gc = _run(faces, colors, ref.g, S, sigma, gamma)
     assert tuple(rgba.shape) == (B, 4, S, S) and tuple(gf.shape) == faces.shape and tuple(gc.shape) == colors.shape
@@ -92,14 +77,14 @@ def test_shared_colors():
     rng = np.random.default_rng(11)
     colors = rng.uniform(0, 1, (1, faces.shape[1], 3, 3)).astype(np.float32)
     g = rng.normal(size=(3, 4, S, S)).astype(np.float32)
-    ref = C.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
+    ref = R.restate(faces, colors, S, sigma, gamma, background=BG, g=g)
     assert ref.masked_share <= 0.01
     rgba, gf, gc = _run(faces, colors, ref.g, S, sigma, gamma)
     wide, gfw, gcw = _run(faces, np.repeat(colors, 3, 0), ref.g, S, sigma, gamma)
     assert tuple(gc.shape) == (1, faces.shape[1], 3, 3) and tuple(gcw.shape) == (3, faces.shape[1], 3, 3)
     assert torch.equal(rgba, wide) and torch.equal(gf, gfw)
-    total, bound = C.shared_colors(ref)
-    rc = C.worst_ratio(_host(gc), total, bound)
+    total, bound = R.shared_colors(ref)
+    rc = R.worst_ratio(_host(gc), total, bound)
     print('shared corner colours: grad_colors %.3f of the bound' % rc)
     assert rc <= 1 and np.abs(total).max() > 0
 
@@ -160,14 +145,14 @@ def test_equal_corners_against_the_flat_kernels(case):
     mesh, B, S, sigma, gamma = case
     faces, flat, ref_f = G0.reference(*case)
     wide = np.ascontiguousarray(np.repeat(flat[:, :, None, :], 3, 2))
-    ref_c = C.restate(faces, wide, S, sigma, gamma, background=BG, g=ref_f.g)
+    ref_c = R.restate(faces, wide, S, sigma, gamma, background=BG, g=ref_f.g)
     assert np.array_equal(ref_c.mask, ref_f.mask) and np.array_equal(ref_c.g, ref_f.g)
     a, af, ac = G0._run(faces, flat, ref_f.g, S, sigma, gamma)
     b, bf, bc = _run(faces, wide, ref_f.g, S, sigma, gamma)
     keep = ~np.broadcast_to(ref_f.mask[:, None], ref_f.rgba.shape)
-    rr = C.worst_ratio(_host(b)[keep], _host(a).astype(np.float64)[keep], (ref_c.rgba_bound + ref_f.rgba_bound)[keep])
-    rf = C.worst_ratio(_host(bf), _host(af).astype(np.float64), ref_c.grad_faces_bound + ref_f.grad_faces_bound)
-    rc = C.worst_ratio(_host(bc).astype(np.float64).sum(2), _host(ac).astype(np.float64),
+    rr = R.worst_ratio(_host(b)[keep], _host(a).astype(np.float64)[keep], (ref_c.rgba_bound + ref_f.rgba_bound)[keep])
+    rf = R.worst_ratio(_host(bf), _host(af).astype(np.float64), ref_c.grad_faces_bound + ref_f.grad_faces_bound)
+    rc = R.worst_ratio(_host(bc).astype(np.float64).sum(2), _host(ac).astype(np.float64),
                        ref_c.grad_colors_bound.sum(2) + ref_f.grad_colors_bound)
     print('%s equal corners against flat: rgba %.3f, grad_faces %.3f, grad_colors %.3f of the two bounds' % (mesh, rr, rf, rc))
     assert rr <= 1 and rf <= 1 and rc <= 1, (rr, rf, rc)
@@ -245,13 +230,13 @@ def test_render_soft_per_pixel_against_the_hard_rasterizer():
     # the two definitions in float64, from the very faces and corner colours the kernels got
     proj, corner, _ = r._shade(vertices, faces, vc)
     pf, pc = _host(proj[:, :2]).astype(np.float64), _host(corner.colors[:, :2]).astype(np.float64)
-    ref = C.restate(pf, pc, S, sigma, gamma, r.near, r.far, r.soft_eps, BG)
-    hard64 = C.hard_image(pf, pc, S, BG)
+    ref = R.restate(pf, pc, S, sigma, gamma, r.near, r.far, r.soft_eps, BG)
+    hard64 = R.hard_image(pf, pc, S, BG)
     compared = np.broadcast_to((ref.edge_d2 > 30 * sigma)[:, None], hard64.shape)
     covered = compared & np.broadcast_to((ref.rgba[:, 3:] > 0.5), hard64.shape)
     assert covered.sum() >= 3 * 100 and (compared & ~covered).sum() >= 3 * 100          # the quad and the background
     definitions = np.abs(ref.rgba[:, :3] - hard64)
-    affine = C.restate(pf, pc, S, sigma, gamma, r.near, r.far, r.soft_eps, BG, variant='affine')
+    affine = R.restate(pf, pc, S, sigma, gamma, r.near, r.far, r.soft_eps, BG, variant='affine')
     assert np.abs(affine.rgba[:, :3] - ref.rgba[:, :3])[compared].max() >= 0.05
     got = np.abs(_host(soft[:, :3]).astype(np.float64) - _host(hard).astype(np.float64))
     beyond = (got - definitions)[compared].max()

@@ -14,7 +14,7 @@ import soft_render_ref as R
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 256   # csrc/nr_soft_render.hip: RENDER_CHUNK, the face records per LDS chunk
+CHUNK = 256   # csrc/nr_soft_pair.h: SOFT_CHUNK, the face records per LDS chunk
 BG = (0.2, 0.3, 0.4)
 NAN = float('nan')
 # (the contributing ones at coordinates that are no pixel centres and put no edge through one: the masked-pixel cap)

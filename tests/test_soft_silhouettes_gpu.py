@@ -17,7 +17,7 @@ import soft_ref as R
 
 pytestmark = pytest.mark.gpu
 
-CHUNK = 256   # csrc/nr_soft_silhouette.hip: SOFT_CHUNK, the face records per LDS chunk
+CHUNK = 256   # csrc/nr_soft_pair.h: SOFT_CHUNK, the face records per LDS chunk
 
 
 def _cuda(a, grad=False):
