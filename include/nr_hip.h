@@ -90,7 +90,8 @@ extern "C" {
                           *        nr_normals_workspace_bytes;
                           *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes;
                           *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes;
-                          *        nr_soft_corners_forward, nr_soft_corners_backward, nr_soft_corners_workspace_bytes);
+                          *        nr_soft_corners_forward, nr_soft_corners_backward, nr_soft_corners_workspace_bytes;
+                          *        nr_soft_uv_forward, nr_soft_uv_backward, nr_soft_uv_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -897,6 +898,61 @@ int nr_soft_corners_backward(const float *faces, const float *colors, const floa
                              int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t colors_per_batch, double sigma,
                              double gamma, double near, double far, double eps, double background_r, double background_g,
                              double background_b, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Soft colour rendering with UV texture images: nr_soft_render_* with the images of a UV layout (nr_uv_images above) sampled
+ * at every taken pair.  light [B, F, 3] (light_per_batch = 1) or [F, 3] shared by the batch and read in place
+ * (light_per_batch = 0): one light colour per face; grad_light has its shape.  F is the layout's face count -- uv->faces_uv
+ * [F, 3, 2], uv->face_image [F], uv->base [F, ts, ts, ts, 3]; the struct carries no count, and the soft path has no fill_back
+ * copies -- and uv->image_batch is 1 (images shared by the batch, image batch stride 0) or B.  Everything else -- the
+ * contribution rule, the taken rule, lambda_k, iz, zp, zn, m, w_f, w_b, Z, Q, alpha, the layouts, the ranges -- is
+ * nr_soft_render_*'s, and u_k = lambda_k / z_k, mu_k = u_k zp are nr_soft_corners_*'s, except the colour of a taken pair:
+ *   C_f(p)_c = L_fc T_f(p)_c,  rgb = (w_b background + sum w_f C_f(p)) / Z.
+ *   Face f with an image m = face_image[f] in [0, num_images) whose table row lies inside the num_pixels packed pixels:
+ *     d_k = fminf(fmaxf(mu_k, 0), 1) (the clamp removes rounding excess only; its derivative is taken as 1), and T_f(p) is
+ *     the bilinear lookup nr_bake_uv_textures takes at a texel, at the barycentric point d of faces_uv[f] in image m [H, W]:
+ *     pos_x = (sum_k uvx_fk d_k) (W - 1), pos_y = (sum_k uvy_fk d_k) (H - 1); xi = (int)pos_x, yi = (int)pos_y,
+ *     yi1 = (int)(pos_y + 1); wx1 = pos_x - xi, wx0 = 1 - wx1, wy1 = pos_y - yi, wy0 = 1 - wy1; the four reads (yi, xi),
+ *     (yi1, xi), (yi, xi + 1), (yi1, xi + 1) with the weights wx0 wy0, wx0 wy1, wx1 wy0, wx1 wy1, rows counted from the
+ *     bottom of an image stored top row first, each flat index row * W + col clamped to [0, H W - 1] -- NO READ LEAVES THE
+ *     IMAGE, whatever uv holds (outside [0, 1], infinite, NaN) --, T = ((0 + I[q_0] w_0) + I[q_1] w_1) + ... in read order.
+ *   Any other face: T_f = the mean of its base cube (summed in double, rounded once), a constant without a gradient.
+ *   Inside a face this is the texture nr_forward_rasterize_uv shows, outside the texture at the nearest boundary point:
+ *   continuous across every edge, as the corner colours are.
+ * Backward, per taken pair, with W = w_f / Z and h = g_rgb . (C_f(p) - rgb) as in nr_soft_render_backward.  The read indices
+ * carry no gradient; wx1 and wy1 move with pos_x and pos_y:
+ *   Tx_c = sum_r (dw_r / dwx1) I[q_r]_c = wy0 (I[q_2] - I[q_0])_c + wy1 (I[q_3] - I[q_1])_c,
+ *   Ty_c = sum_r (dw_r / dwy1) I[q_r]_c = wx0 (I[q_1] - I[q_0])_c + wx1 (I[q_3] - I[q_2])_c,
+ *   G_k  = sum_c g_c L_fc (Tx_c uvx_fk (W - 1) + Ty_c uvy_fk (H - 1))     (0 for a face without an image)
+ *   grad_images[b or 0, q_r, c] += W g_c L_fc w_r     (faces with an image; shared images: one sum over the batch)
+ *   grad_light[b or 0, f, c]    += W g_c T_f(p)_c
+ *   E_k = W zp (G_k - sum_j mu_j G_j)
+ * and everything after E_k is nr_soft_corners_backward's: d_k = diz + E_k, the z terms, the free-t term and the inside terms.
+ * faces_uv, face_image and base receive no gradient.
+ * grad_faces and grad_light: fixed order, no atomics, the same bits in every run and for an image alone or inside a batch;
+ * shared light is added over the batch in ascending b in double and rounded once.  grad_images [image_batch, num_pixels, 3]
+ * (every element stored; NULL: not computed): each entry is ROUNDED ONCE FROM A DOUBLE SUM WHOSE ADDITIONS ARRIVE IN NO FIXED
+ * ORDER (double atomics into a zero-filled scratch in the workspace; terms that are 0 are skipped): its bits are not
+ * promised.
+ * NR_E_* before any launch, nr_soft_render_*'s codes in their order with nr_forward_rasterize_uv's checks of *uv added: a
+ * NULL pointer (uv and its five tables included) NR_E_NULL; sizes out of range, texture_size outside [2, 1024], num_images
+ * or num_pixels < 1, image_batch not in {1, B} NR_E_SIZE; the numbers and light_per_batch NR_E_MODE; a NULL or short
+ * workspace NR_E_WORKSPACE.  nr_soft_uv_workspace_bytes reads uv->num_pixels and uv->image_batch only (0 for NULL or sizes out
+ * of range).  No host synchronisation; capturable.
+ */
+size_t nr_soft_uv_workspace_bytes(const nr_uv_images *uv, int32_t batch_size, int32_t num_faces, int32_t image_size);
+
+int nr_soft_uv_forward(const nr_uv_images *uv, const float *faces, const float *light, float *rgba, float *transmittance,
+                       float *normaliser, int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t light_per_batch,
+                       double sigma, double gamma, double near, double far, double eps, double background_r,
+                       double background_g, double background_b, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_soft_uv_backward(const nr_uv_images *uv, const float *faces, const float *light, const float *rgba,
+                        const float *transmittance, const float *normaliser, const float *grad_rgba, float *grad_faces,
+                        float *grad_light, float *grad_images, int32_t batch_size, int32_t num_faces, int32_t image_size,
+                        int32_t light_per_batch, double sigma, double gamma, double near, double far, double eps,
+                        double background_r, double background_g, double background_b, void *workspace, size_t workspace_bytes,
+                        void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

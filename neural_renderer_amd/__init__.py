@@ -44,7 +44,7 @@ from .normals import camera_rotation, corner_normals, face_normals, vertex_norma
 from .soft_silhouette import soft_silhouettes, soft_silhouettes_torch
 # not in the reference: soft colour rendering -- the soft coverage aggregated by a depth-weighted softmax, with its exact
 # gradient to x, y, z and the face colours, HIP in both directions -- for Renderer.render_soft
-from .soft_render import soft_render, soft_render_torch
+from .soft_render import soft_render, soft_render_torch, soft_render_uv, soft_render_uv_torch
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -67,4 +67,5 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
            'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation',
-           'soft_silhouettes', 'soft_silhouettes_torch', 'soft_render', 'soft_render_torch']
+           'soft_silhouettes', 'soft_silhouettes_torch', 'soft_render', 'soft_render_torch', 'soft_render_uv',
+           'soft_render_uv_torch']

@@ -261,7 +261,9 @@ __device__ __forceinline__ int f2i(float x) { return (int)x; }  // v_cvt_i32_f32
 // The four bilinear reads of an [H,W] image stored bottom row first at the barycentric point d of a face's uv triangle
 // (load_obj.py:112-128): the flat pixel indices in the order the sum takes them -- (yi,xi), (yi1,xi), (yi,xi+1), (yi1,xi+1),
 // with the reference's yi1 = (int)(pos_y + 1) -- clamped to [0, H*W-1], and their weights.
-__device__ __forceinline__ void texel_reads(const float *face, const float d[3], int H, int W, long long p[4], float w[4])
+// ax: the weights' factors (wx0, wx1, wy0, wy1), for a caller that differentiates the sample (nr_soft_render.hip).
+__device__ __forceinline__ void texel_reads(const float *face, const float d[3], int H, int W, long long p[4], float w[4],
+                                            float ax[4])
 {
     const float pos_x = (face[0] * d[0] + face[2] * d[1] + face[4] * d[2]) * (float)(W - 1);  // :112-113
     const float pos_y = (face[1] * d[0] + face[3] * d[1] + face[5] * d[2]) * (float)(H - 1);  // :114-115
@@ -281,6 +283,13 @@ __device__ __forceinline__ void texel_reads(const float *face, const float d[3],
     w[1] = wx0 * wy1;
     w[2] = wx1 * wy0;
     w[3] = wx1 * wy1;
+    ax[0] = wx0; ax[1] = wx1; ax[2] = wy0; ax[3] = wy1;
+}
+
+__device__ __forceinline__ void texel_reads(const float *face, const float d[3], int H, int W, long long p[4], float w[4])
+{
+    float ax[4];
+    texel_reads(face, d, H, W, p, w, ax);
 }
 
 // texel_reads' index (bottom row first) -> the same pixel in an image stored top row first (file orientation)

@@ -96,7 +96,7 @@ __device__ __forceinline__ int soft_filter_chunk(const float4 *__restrict__ rb, 
                                                  int *wave_count)
 {
     const int f = c0 + T.tid;
-    float4 r0, r1, r2, r3, r4, r5;   // (named, not an array: an array indexed in a loop ends up in scratch or LDS)
+    float4 r0, r1, r2, r3, r4, r5, r6;   // (named, not an array: an array indexed in a loop ends up in scratch or LDS)
     bool hit = false;
     if (f < F) {
         const float4 *src = rb + (size_t)f * REC;
@@ -104,6 +104,7 @@ __device__ __forceinline__ int soft_filter_chunk(const float4 *__restrict__ rb, 
         if constexpr (REC > 3) r3 = src[3];
         if constexpr (REC > 4) r4 = src[4];
         if constexpr (REC > 5) r5 = src[5];
+        if constexpr (REC > 6) r6 = src[6];
         const SoftFace s = unpack(r0, r1, r2);
         hit = s.on != 0 && s.ix_lo <= T.tx1 && s.ix_hi >= T.tx0 && s.iy_lo <= T.ty1 && s.iy_hi >= T.ty0;
     }
@@ -124,6 +125,7 @@ __device__ __forceinline__ int soft_filter_chunk(const float4 *__restrict__ rb, 
         if constexpr (REC > 3) list[at + 3] = r3;
         if constexpr (REC > 4) list[at + 4] = r4;
         if constexpr (REC > 5) list[at + 5] = r5;
+        if constexpr (REC > 6) list[at + 6] = r6;
     }
     __syncthreads();
     return rfl(n);

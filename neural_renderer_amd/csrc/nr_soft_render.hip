@@ -37,6 +37,22 @@
 // No atomics, no host synchronisation, every output element stored; the same bits in every run and for an image alone or
 // inside a batch: a pixel's sums depend on the set of its taken pairs and their order in f alone.  The base record, the box, the
 // tile, the filter, the pair and the constants are nr_soft_pair.h's, one definition with nr_soft_silhouette.hip.
+// UV images (nr_soft_uv_*; DESIGN "Soft colour rendering", UV images): the colour of a taken pair is a light colour per face
+// times the bake's bilinear lookup of the face's image at the pair's own weights,
+//   d_k = min(max(mu_k, 0), 1),  T_f(p) = texel_reads' four reads of image face_image[f] at d (uv_texel),  C_f(p) = L_f T_f(p)
+// -- the texture render() shows inside, the texture of the nearest boundary point outside; a face without an image shows L_f
+// times the mean of its base cube.  The forward and the backward are the <UV> instantiations of the same two templates (the
+// flat and corner ones are <FLAT> and <CORNER>: the former <false> and <true>, their instructions unchanged), k_uv_setup
+// writes a 112-byte record (the 48 bytes, 1 / z_k, the light colour, six uv floats, the image's first pixel, H and W; 28 KiB
+// per chunk).  Backward, with Tx_c = sum_r (dw_r / dwx1) I[q_r]_c, Ty_c likewise, G_k = sum_c g_c L_c (Tx_c uvx_k (W - 1) +
+// Ty_c uvy_k (H - 1)):  E_k = (W zp) (G_k - sum_j mu_j G_j) stands where the corner colours' E_k stands and every line after it
+// is shared; dL/dL_fc += (W g_c) T_c takes the three colour sums.  These outputs keep the paragraph above: fixed order, the
+// same bits in every run.  The IMAGE gradient does not: dL/dI[q_r]_c += W g_c L_c w_r is formed in double and added with
+// double atomics into a zero-filled scratch (many pairs land on one image pixel; the scheme of nr_uv_pixel.hip, for its
+// reason), zero terms skipped, and k_uv_image_round rounds every sum once -- a double sum whose additions arrive in no fixed
+// order.
+#include <type_traits>
+
 #include "nr_soft_pair.h"
 
 using namespace nr;
@@ -131,6 +147,72 @@ struct RenderArgs {
     float bg_r, bg_g, bg_b;
 };
 
+// the colour of a pair: one per face, three corner colours, or a light colour times a UV image sample
+constexpr int FLAT = 0, CORNER = 1, UV = 2;
+constexpr int UV_REC = 7;             // float4 per record with a UV sample
+constexpr int mode_rec(int mode) { return mode == UV ? UV_REC : (mode == CORNER ? CORNER_REC : RENDER_REC); }
+
+// what the UV kernels take beyond RenderArgs (the flat and corner kernels keep RenderArgs itself: their signatures stay)
+struct UVArgs : RenderArgs {
+    const float *images;     // [image_batch, P, 3], each image top row first
+    size_t image_stride;     // floats between the images of two batch elements, 0 for shared images
+    double *acc;             // backward: the double sums of the image gradient, or nullptr when it is not asked for
+    size_t acc_stride;       // doubles, 0 for shared images
+};
+template <int MODE>
+using ModeArgs = std::conditional_t<MODE == UV, UVArgs, RenderArgs>;
+
+// what a UV record holds beyond FaceShade's 1 / z_k and the light colour (FaceShade's cr, cg, cb):
+// (., ., uvx0, uvy0), (uvx1, uvy1, uvx2, uvy2), (first pixel, H, W, 0); a face without an image has H = 0 and the mean of its
+// base cube in the first three uv slots
+struct UVFace {
+    float uv[6];
+    int off, H, W;
+};
+
+__device__ __forceinline__ UVFace unpack_uv(const float4 &e, const float4 &g, const float4 &i)
+{
+    UVFace u;
+    u.uv[0] = e.z; u.uv[1] = e.w; u.uv[2] = g.x; u.uv[3] = g.y; u.uv[4] = g.z; u.uv[5] = g.w;
+    u.off = __float_as_int(i.x); u.H = __float_as_int(i.y); u.W = __float_as_int(i.z);
+    return u;
+}
+
+// the sample of a taken pair: the four reads q (packed pixels) with their weights w, the weights' factors ax = (wx0, wx1,
+// wy0, wy1), the texels i[read][rgb] and the sum (r, g, b)
+struct UVTexel {
+    int q[4];
+    float w[4], ax[4], i[4][3], r, g, b;
+};
+
+// T_f(p): the bake's own bilinear lookup (texel_reads, nr_device.h) at d_k = min(max(mu_k, 0), 1), the reads summed in read
+// order from 0 as uv_color sums them; the mean base colour for a face without an image.  NO READ LEAVES THE FACE'S IMAGE,
+// whatever uv and mu hold (uv outside [0, 1], infinite, NaN): texel_reads clamps the flat index to [0, H W - 1], mirror_row
+// maps that range onto itself, and k_uv_setup admits an image only when [off, off + H W) lies inside the packed pixels.
+__device__ __forceinline__ void uv_texel(const UVFace &u, const PairColor &pc, const float *__restrict__ images, UVTexel &s)
+{
+    if (u.H == 0) {
+        s.r = u.uv[0]; s.g = u.uv[1]; s.b = u.uv[2];
+        return;
+    }
+    const float d[3] = {fminf(fmaxf(pc.mu0, 0.0f), 1.0f), fminf(fmaxf(pc.mu1, 0.0f), 1.0f), fminf(fmaxf(pc.mu2, 0.0f), 1.0f)};
+    long long p[4];
+    texel_reads(u.uv, d, u.H, u.W, p, s.w, s.ax);
+#pragma unroll
+    for (int r = 0; r < 4; r++) {   // the four texels are requested together
+        s.q[r] = u.off + mirror_row(p[r], u.H, u.W);
+        const float *px = images + (size_t)s.q[r] * 3;
+        s.i[r][0] = px[0]; s.i[r][1] = px[1]; s.i[r][2] = px[2];
+    }
+    s.r = s.g = s.b = 0.0f;
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        s.r += s.i[r][0] * s.w[r];
+        s.g += s.i[r][1] * s.w[r];
+        s.b += s.i[r][2] * s.w[r];
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------------------
 // set-up
 
@@ -154,15 +236,54 @@ __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ 
     }
 }
 
+// UV images: the base record, 1 / z_k and the light colour as above, then the face's uv triangle and its image's place in the
+// packing.  A face whose face_image lies outside [0, M), or whose table row does not lie inside the P packed pixels, is a face
+// without an image: H = 0 and the mean of its base cube (summed in double, rounded once) in the first three uv slots.
+__global__ __launch_bounds__(256) void k_uv_setup(const float *__restrict__ faces, const float *__restrict__ light, UVShade uv,
+                                                  float4 *__restrict__ rec, int F, int S, size_t light_stride, float reach,
+                                                  double near, double far)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (f >= F) return;
+    const float *L = light + (size_t)b * light_stride + (size_t)f * 3;
+    float4 *o = rec + ((size_t)b * F + f) * UV_REC;
+    float c[9];
+    soft_record<true>(faces + ((size_t)b * F + f) * 9, o, S, reach, near, far, c);
+    o[3] = make_float4(1.0f / c[2], 1.0f / c[5], 1.0f / c[8], L[0]);
+    const int m = uv.face_image[f];
+    int off = 0, H = 0, W = 0;
+    if (m >= 0 && m < uv.M) {
+        off = uv.table[3 * m]; H = uv.table[3 * m + 1]; W = uv.table[3 * m + 2];
+        if (off < 0 || H < 1 || W < 1 || (long long)off + (long long)H * W > (long long)uv.P) H = 0;
+    }
+    if (H != 0) {
+        const float *t = uv.faces_uv + (size_t)f * 6;
+        o[4] = make_float4(L[1], L[2], t[0], t[1]);
+        o[5] = make_float4(t[2], t[3], t[4], t[5]);
+        o[6] = make_float4(__int_as_float(off), __int_as_float(H), __int_as_float(W), 0.0f);
+    } else {
+        const int T = uv.ts * uv.ts * uv.ts;
+        const float *tx = uv.base + (size_t)f * T * 3;
+        double sr = 0.0, sg = 0.0, sb = 0.0;
+        for (int i = 0; i < T; i++) {
+            sr += (double)tx[3 * i]; sg += (double)tx[3 * i + 1]; sb += (double)tx[3 * i + 2];
+        }
+        o[4] = make_float4(L[1], L[2], (float)(sr / T), (float)(sg / T));
+        o[5] = make_float4((float)(sb / T), 0.0f, 0.0f, 0.0f);
+        o[6] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------------------
 // forward
 
-template <bool CORNERS>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict__ rec, float *__restrict__ rgba,
                                                         float *__restrict__ trans, float *__restrict__ norm, int F, int S,
-                                                        int tiles_x, RenderArgs a)
+                                                        int tiles_x, ModeArgs<MODE> a)
 {
-    constexpr int REC = CORNERS ? CORNER_REC : RENDER_REC;
+    constexpr bool CORNERS = MODE == CORNER;
+    constexpr int REC = mode_rec(MODE);
     __shared__ float4 list[SOFT_CHUNK * REC];
     __shared__ int wave_count[4];
     const int b = blockIdx.y;
@@ -205,6 +326,13 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
                 cr = take ? cr + w * pc.r : cr;
                 cg = take ? cg + w * pc.g : cg;
                 cb = take ? cb + w * pc.b : cb;
+            } else if constexpr (MODE == UV) {   // the image is read for taken pairs only
+                const PairColor pc = pair_color(q, h, CornerColor{});   // (its mu; the colour part folds away)
+                UVTexel t = {};
+                if (take) uv_texel(unpack_uv(l[4], l[5], l[6]), pc, a.images + (size_t)b * a.image_stride, t);
+                cr = take ? cr + w * (h.cr * t.r) : cr;
+                cg = take ? cg + w * (h.cg * t.g) : cg;
+                cb = take ? cb + w * (h.cb * t.b) : cb;
             } else {
                 cr = take ? cr + w * h.cr : cr;
                 cg = take ? cg + w * h.cg : cg;
@@ -230,20 +358,23 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
 // --------------------------------------------------------------------------------------------------------------------
 // backward
 
-template <bool CORNERS>
+template <int MODE>
 __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restrict__ rec, const float *__restrict__ rgba,
                                                          const float *__restrict__ trans, const float *__restrict__ norm,
                                                          const float *__restrict__ grad_rgba, float *__restrict__ grad_faces,
-                                                         float *__restrict__ grad_colors, int F, int S, RenderArgs a)
+                                                         float *__restrict__ grad_colors, int F, int S, ModeArgs<MODE> a)
 {
+    constexpr bool CORNERS = MODE == CORNER, VARIES = MODE != FLAT;   // VARIES: the colour moves with the pixel, E_k below
     const int b = blockIdx.y, lane = threadIdx.x & 63;
     const int f = rfl(blockIdx.x * 4 + (threadIdx.x >> 6));
     if (f >= F) return;
-    const float4 *r = rec + ((size_t)b * F + f) * (CORNERS ? CORNER_REC : RENDER_REC);
+    const float4 *r = rec + ((size_t)b * F + f) * mode_rec(MODE);
     const SoftFace s = unpack(r[0], r[1], r[2]);
     const FaceShade h = unpack_shade(r[3], r[4]);
     CornerColor cc = {};
     if constexpr (CORNERS) cc = unpack_corners(r[3], r[4], r[5]);
+    UVFace uvf = {};
+    if constexpr (MODE == UV) uvf = unpack_uv(r[4], r[5], r[6]);
     float g0x = 0.0f, g0y = 0.0f, g1x = 0.0f, g1y = 0.0f, g2x = 0.0f, g2y = 0.0f;
     float g0z = 0.0f, g1z = 0.0f, g2z = 0.0f, gcr = 0.0f, gcg = 0.0f, gcb = 0.0f;
     float g1r = 0.0f, g1g = 0.0f, g1b = 0.0f, g2r = 0.0f, g2g = 0.0f, g2b = 0.0f;   // (corners 1 and 2; gcr, gcg, gcb are corner 0's)
@@ -281,6 +412,47 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
                 E0 = Wz * ((gr * (cc.c00 - pc.r) + gg * (cc.c01 - pc.g)) + gb * (cc.c02 - pc.b));
                 E1 = Wz * ((gr * (cc.c10 - pc.r) + gg * (cc.c11 - pc.g)) + gb * (cc.c12 - pc.b));
                 E2 = Wz * ((gr * (cc.c20 - pc.r) + gg * (cc.c21 - pc.g)) + gb * (cc.c22 - pc.b));
+            } else if constexpr (MODE == UV) {
+                const PairColor pc = pair_color(q, h, CornerColor{});   // (its mu)
+                UVTexel t = {};
+                if (q.taken) uv_texel(uvf, pc, a.images + (size_t)b * a.image_stride, t);
+                hh = (gr * (h.cr * t.r - R) + gg * (h.cg * t.g - G)) + gb * (h.cb * t.b - Bl);
+                gcr += (W * gr) * t.r;    // the light colour's sums
+                gcg += (W * gg) * t.g;
+                gcb += (W * gb) * t.b;
+                if (q.taken && uvf.H != 0) {
+                    // the sample moves with wx1 and wy1 alone (the read indices carry no gradient): Tx, Ty per channel, then
+                    // G_k = sum_c g_c L_c (Tx_c uvx_k (W - 1) + Ty_c uvy_k (H - 1)) and E_k = (W zp) (G_k - sum_j mu_j G_j)
+                    const float ar = gr * h.cr, ag = gg * h.cg, ab = gb * h.cb;
+                    const float txr = t.ax[2] * (t.i[2][0] - t.i[0][0]) + t.ax[3] * (t.i[3][0] - t.i[1][0]);
+                    const float txg = t.ax[2] * (t.i[2][1] - t.i[0][1]) + t.ax[3] * (t.i[3][1] - t.i[1][1]);
+                    const float txb = t.ax[2] * (t.i[2][2] - t.i[0][2]) + t.ax[3] * (t.i[3][2] - t.i[1][2]);
+                    const float tyr = t.ax[0] * (t.i[1][0] - t.i[0][0]) + t.ax[1] * (t.i[3][0] - t.i[2][0]);
+                    const float tyg = t.ax[0] * (t.i[1][1] - t.i[0][1]) + t.ax[1] * (t.i[3][1] - t.i[2][1]);
+                    const float tyb = t.ax[0] * (t.i[1][2] - t.i[0][2]) + t.ax[1] * (t.i[3][2] - t.i[2][2]);
+                    const float X = ((ar * txr + ag * txg) + ab * txb) * (float)(uvf.W - 1);
+                    const float Y = ((ar * tyr + ag * tyg) + ab * tyb) * (float)(uvf.H - 1);
+                    const float G0 = X * uvf.uv[0] + Y * uvf.uv[1], G1 = X * uvf.uv[2] + Y * uvf.uv[3];
+                    const float G2 = X * uvf.uv[4] + Y * uvf.uv[5];
+                    const float Gm = (pc.mu0 * G0 + pc.mu1 * G1) + pc.mu2 * G2, Wz = W * q.zp;
+                    E0 = Wz * (G0 - Gm);
+                    E1 = Wz * (G1 - Gm);
+                    E2 = Wz * (G2 - Gm);
+                    if (a.acc) {   // the image terms W g_c L_c w_r, formed and added in double; zero terms are skipped
+                        double *acc = a.acc + (size_t)b * a.acc_stride;
+                        const double gk[3] = {(double)W * ((double)gr * (double)h.cr), (double)W * ((double)gg * (double)h.cg),
+                                              (double)W * ((double)gb * (double)h.cb)};
+#pragma unroll
+                        for (int rd = 0; rd < 4; rd++) {
+                            double *at = acc + (size_t)t.q[rd] * 3;
+#pragma unroll
+                            for (int c = 0; c < 3; c++) {
+                                const double term = gk[c] * (double)t.w[rd];
+                                if (term != 0.0) atomicAdd(at + c, term);
+                            }
+                        }
+                    }
+                }
             } else {
                 hh = (gr * (h.cr - R) + gg * (h.cg - G)) + gb * (h.cb - Bl);
                 gcr += W * gr;
@@ -295,7 +467,7 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             const float ca = (-2.0f * t1) * C, cb = (-2.0f * p.t) * C;
             // zn -> zp -> iz
             const float diz = ((hW * a.inv_gamma) * a.inv_range) * (q.zp * q.zp);
-            if constexpr (CORNERS) {
+            if constexpr (VARIES) {
                 g0z += -((diz + E0) * q.l0) * s0;
                 g1z += -((diz + E1) * q.l1) * s1;
                 g2z += -((diz + E2) * q.l2) * s2;
@@ -312,7 +484,7 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             const float ee = k == 0 ? ee0 : (k == 1 ? ee1 : ee2);
             const bool free_t = !p.inside && p.t > 0.0f && p.t < 1.0f;
             float T;
-            if constexpr (CORNERS) {   // ... and the colour moves along the segment with t
+            if constexpr (VARIES) {   // ... and the colour moves along the segment with t
                 const float Ea = k == 0 ? E0 : (k == 1 ? E1 : E2), Eb = k == 0 ? E1 : (k == 1 ? E2 : E0);
                 T = free_t ? (diz * (izb - iza) + (Eb * izb - Ea * iza)) / ee : 0.0f;
             } else {
@@ -324,7 +496,7 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             // inside, through lambda: d iz / d c_j = (iz of the vertex that c_j weighs - iz) / A, and c_j moves with its two ends
             const float dA = p.inside ? diz * q.rA : 0.0f;
             float q0 = dA * (h.iz2 - q.iz), q1 = dA * (h.iz0 - q.iz), q2 = dA * (h.iz1 - q.iz);
-            if constexpr (CORNERS) {   // ... and the colour with lambda: c_j weighs vertex v(j) = 2, 0, 1
+            if constexpr (VARIES) {   // ... and the colour with lambda: c_j weighs vertex v(j) = 2, 0, 1
                 const float rA = p.inside ? q.rA : 0.0f;
                 q0 += (E2 * h.iz2) * rA;
                 q1 += (E0 * h.iz0) * rA;
@@ -465,7 +637,136 @@ int render_backward(const RenderCall &c, const float *rgba, const float *transmi
     return launch_status();
 }
 
+// UV images: the double sums of the image gradient -> grad_images, each rounded once
+__global__ __launch_bounds__(256) void k_uv_image_round(const double *__restrict__ acc, float *__restrict__ grad_images, size_t n)
+{
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) grad_images[i] = (float)acc[i];
+}
+
+// the workspace of the UV entries: the records, the per-image light gradients of a call with shared light, the double sums
+struct UVWorkspace {
+    size_t part_off, acc_off, acc_bytes, total;
+};
+
+UVWorkspace uv_workspace(int B, int F, int P, int image_batch)
+{
+    UVWorkspace w;
+    w.part_off = (size_t)B * (size_t)F * UV_REC * sizeof(float4);
+    w.acc_off = align_up(w.part_off + (size_t)B * (size_t)F * 3 * sizeof(float), 256);
+    w.acc_bytes = (size_t)image_batch * (size_t)P * 3 * sizeof(double);
+    w.total = w.acc_off + w.acc_bytes;
+    return w;
+}
+
+// render_check's codes in render_check's order, with uv_images_args' checks (nr_forward.hip) in front of the workspace's
+int uv_check(const nr_uv_images *uv, const RenderCall &c, UVShade &us)
+{
+    if (!uv || !c.faces || !c.colors) return NR_E_NULL;
+    if (!soft_sizes_ok(c.B, c.F, c.S)) return NR_E_SIZE;
+    const nr_face_light lit = {c.colors, c.F, nullptr, nullptr};
+    FaceLight fl;
+    if (int e = uv_images_args(&lit, uv, c.B, c.F, fl, us)) return e;
+    if ((size_t)uv->image_batch * (size_t)uv->num_pixels * 3 > 0xffffff00ull) return NR_E_SIZE;   // (k_uv_image_round's 1-D grid)
+    RenderCall flat = c;   // the numbers; the flat workspace is the smaller one
+    flat.workspace_bytes = c.workspace ? render_workspace(c.B, c.F, 0) : 0;
+    if (int e = render_check(flat)) return e;
+    if (c.workspace_bytes < uv_workspace(c.B, c.F, uv->num_pixels, uv->image_batch).total) return NR_E_WORKSPACE;
+    return 0;
+}
+
+UVArgs uv_args(const RenderCall &c, const UVShade &us, double *acc)
+{
+    UVArgs a;
+    static_cast<RenderArgs &>(a) = render_args(c);
+    a.images = us.images;
+    a.image_stride = us.shared ? 0 : (size_t)us.P * 3;
+    a.acc = acc;
+    a.acc_stride = a.image_stride;
+    return a;
+}
+
+int uv_setup(const RenderCall &c, const UVShade &us, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_uv_setup, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces, c.colors, us,
+                       (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * 3 : (size_t)0, soft_reach(c.sigma),
+                       c.near, c.far);
+    return launch_status();
+}
+
+int uv_forward(const nr_uv_images *uv, const RenderCall &c, float *rgba, float *transmittance, float *normaliser, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser) return NR_E_NULL;
+    UVShade us;
+    if (int e = uv_check(uv, c, us)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = uv_setup(c, us, st)) return rc;
+    const int tiles = (c.S + SOFT_TILE - 1) / SOFT_TILE;
+    hipLaunchKernelGGL(k_render_forward<UV>, dim3((unsigned)(tiles * tiles), (unsigned)c.B), dim3(256), 0, st,
+                       (const float4 *)c.workspace, rgba, transmittance, normaliser, c.F, c.S, tiles, uv_args(c, us, nullptr));
+    return launch_status();
+}
+
+int uv_backward(const nr_uv_images *uv, const RenderCall &c, const float *rgba, const float *transmittance,
+                const float *normaliser, const float *grad_rgba, float *grad_faces, float *grad_light, float *grad_images,
+                void *stream)
+{
+    if (!rgba || !transmittance || !normaliser || !grad_rgba || !grad_faces || !grad_light) return NR_E_NULL;
+    UVShade us;
+    if (int e = uv_check(uv, c, us)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = uv_setup(c, us, st)) return rc;   // the caller's workspace holds nothing
+    const UVWorkspace w = uv_workspace(c.B, c.F, us.P, uv->image_batch);
+    double *acc = grad_images ? (double *)((char *)c.workspace + w.acc_off) : nullptr;
+    if (acc)
+        if (int he = fill_bytes(acc, 0, w.acc_bytes, st)) return he;   // (nr_device.h: not a memset node)
+    float *part = c.colors_per_batch ? grad_light : (float *)((char *)c.workspace + w.part_off);
+    hipLaunchKernelGGL(k_render_backward<UV>, dim3((unsigned)((c.F + 3) / 4), (unsigned)c.B), dim3(256), 0, st,
+                       (const float4 *)c.workspace, rgba, transmittance, normaliser, grad_rgba, grad_faces, part, c.F, c.S,
+                       uv_args(c, us, acc));
+    if (int rc = launch_status()) return rc;
+    if (!c.colors_per_batch) {
+        const int n = c.F * 3;
+        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part, grad_light, c.B, n);
+        if (int rc = launch_status()) return rc;
+    }
+    if (acc) {
+        const size_t n = w.acc_bytes / sizeof(double);
+        hipLaunchKernelGGL(k_uv_image_round, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, acc, grad_images, n);
+    }
+    return launch_status();
+}
+
 }  // namespace
+
+NR_API size_t nr_soft_uv_workspace_bytes(const nr_uv_images *uv, int32_t B, int32_t F, int32_t S)
+{
+    if (!uv || !soft_sizes_ok(B, F, S) || uv->num_pixels < 1 || uv->num_pixels > 0x7ffffffe ||
+        (uv->image_batch != 1 && uv->image_batch != B))
+        return 0;
+    return uv_workspace(B, F, uv->num_pixels, uv->image_batch).total;
+}
+
+NR_API int nr_soft_uv_forward(const nr_uv_images *uv, const float *faces, const float *light, float *rgba, float *transmittance,
+                              float *normaliser, int32_t B, int32_t F, int32_t S, int32_t light_per_batch, double sigma,
+                              double gamma, double near, double far, double eps, double background_r, double background_g,
+                              double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, light, B, F, S, light_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    return uv_forward(uv, c, rgba, transmittance, normaliser, stream);
+}
+
+NR_API int nr_soft_uv_backward(const nr_uv_images *uv, const float *faces, const float *light, const float *rgba,
+                               const float *transmittance, const float *normaliser, const float *grad_rgba, float *grad_faces,
+                               float *grad_light, float *grad_images, int32_t B, int32_t F, int32_t S, int32_t light_per_batch,
+                               double sigma, double gamma, double near, double far, double eps, double background_r,
+                               double background_g, double background_b, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, light, B, F, S, light_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    return uv_backward(uv, c, rgba, transmittance, normaliser, grad_rgba, grad_faces, grad_light, grad_images, stream);
+}
 
 NR_API size_t nr_soft_render_workspace_bytes(int32_t B, int32_t F, int32_t S)
 {

@@ -19,7 +19,7 @@ from .normals import camera_rotation, corner_normals
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
-from .soft_render import soft_render
+from .soft_render import soft_render, soft_render_uv
 from .soft_silhouette import soft_silhouettes
 from .uv_textures import UVImages
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
@@ -263,7 +263,29 @@ class Renderer(object):
         from `lights` when set).  A tensor [B,F,3,3] / [1,F,3,3] / [F,3,3] gives the corner colours themselves, a tensor of
         face colours [B,F,3] / [1,F,3] / [F,3] the face colour at all three corners; both are multiplied by the light, per
         face with 'flat', per corner with 'smooth'.  (With exactly three faces a [3,3,3] tensor reads as face colours.)
-        Texture cubes raise ValueError: they are not sampled per pixel."""
+        Texture cubes raise ValueError: they are not sampled per pixel.
+
+        A UVImages (per_pixel=True only; without it ValueError): its images are sampled at every pixel (soft_render_uv), times
+        the per-face light of the face's front copy -- `light_*`, or `lights` when set, as the flat path takes it.  Gradients
+        reach the vertices, the images and the camera.  shading = 'smooth' raises ValueError: a light per corner is not done
+        for UV images in the soft renderer."""
+        if isinstance(colors, UVImages):
+            if not per_pixel:
+                raise ValueError('render_soft: a UVImages is sampled at every pixel: pass per_pixel=True')
+            if self.shading not in ('flat', 'smooth'):
+                raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+            if self.shading == 'smooth':
+                raise ValueError("render_soft: shading = 'smooth' with a UVImages: a light per corner is not done for UV "
+                                 "images in the soft renderer (use 'flat')")
+            nf = faces.shape[1]
+            if self.lights is not None:
+                light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=False)
+                projected, _ = self._frontend(vertices, faces)
+            else:
+                projected, light = self._frontend(vertices, faces, light_colors=True)
+            return soft_render_uv(projected[:, :nf], colors, light[:, :nf], self.image_size,
+                                  self.soft_sigma if sigma is None else sigma, self.soft_gamma if gamma is None else gamma,
+                                  self.near, self.far, self.soft_eps, self.background_color)
         if per_pixel:
             nf = faces.shape[1]
             projected, corner = self._soft_corner_colors(vertices, faces, colors)

@@ -45,7 +45,10 @@ the ranges of include/nr_hip.h both directions are HIP kernels (nr_soft_render_*
 captured (graph.capture) -- but capture before any eager backward on the same leaves, or make the eager calls under no_grad,
 as for soft_silhouettes (DESIGN "Soft silhouettes", Stream capture).
 
-Not done: textures sampled at the pixel, a learnable sigma / gamma, anti-aliasing, a spatial index.
+UV texture images sampled at the pixel: soft_render_uv below (its docstring has the colour of a pair and its gradient).
+
+Not done: a light per corner with UV images, texture cubes sampled at the pixel, gradients to faces_uv, a learnable sigma /
+gamma, anti-aliasing, a spatial index.
 """
 import math
 
@@ -60,10 +63,10 @@ REACH = 17.0                # an outside pair is taken up to d2 = REACH sigma
 # ---------------------------------------------------------------------------------------------------------------------
 # plain torch
 
-def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
-                      background_color=(0, 0, 0)):
-    """rgba [B,4,S,S] in plain torch (any device, any float dtype), differentiable by autograd in faces and colors; the
-    module docstring's definition over every (pixel, face) pair, in chunks of pixel rows."""
+def _render_torch(faces, shade, per_pair, image_size, sigma, gamma, near, far, eps, background_color):
+    """The module docstring's definition over every (pixel, face) pair, in chunks of pixel rows, up to the colour of a pair:
+    `shade(u0, u1, u2, zp)` -- u_k = lambda_k / z_k and zp, each [B,rows,S,F] -- gives the pair's colour as three channel
+    tensors that broadcast against them; `per_pair`: how many elements of that size shade's largest temporary holds."""
     B, F, S = int(faces.shape[0]), int(faces.shape[1]), int(image_size)
     one, zero = torch.ones((), dtype=faces.dtype, device=faces.device), torch.zeros((), dtype=faces.dtype, device=faces.device)
     z = faces[:, :, :, 2]
@@ -75,17 +78,12 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
     iz = 1 / torch.where(on[:, :, None], z, one)
     v = [[xy[:, None, None, :, k, c] for c in range(2)] for k in range(3)]   # [B,1,1,F]
     izv = [iz[:, None, None, :, k] for k in range(3)]
-    corners = colors.dim() == 4
-    if corners:
-        col = colors.to(faces.dtype).expand(B, F, 3, 3)[:, None, None]       # [B,1,1,F,3 corners,3]
-    else:
-        col = colors.to(faces.dtype).expand(B, F, 3)[:, None, None]          # [B,1,1,F,3]
     on = on[:, None, None, :]
     centre = (2 * torch.arange(S, device=faces.device, dtype=torch.float64) + 1 - S) / S
     centre = centre.to(faces.dtype)
     px = centre[None, None, :, None]
     bg = [float(c) for c in background_color]
-    rows = max(1, _CHUNK_ELEMENTS // max(1, B * S * F))
+    rows = max(1, _CHUNK_ELEMENTS // max(1, B * S * F * per_pair))
     out = []
     for r0 in range(0, S, rows):
         py = centre[None, r0:r0 + rows, None, None]
@@ -112,11 +110,7 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
         w = torch.where(taken, torch.sigmoid(x) * torch.exp(torch.where(taken, (zn - m[..., None]) / gamma, zero)), zero)
         wb = torch.exp((eps - m) / gamma)
         Z = wb + w.sum(3)
-        if corners:   # the colour at the pixel: the perspective-correct weights mu_k = u_k zp
-            mu0, mu1, mu2 = u0 * zp, u1 * zp, u2 * zp
-            at = [mu0 * col[..., 0, c] + mu1 * col[..., 1, c] + mu2 * col[..., 2, c] for c in range(3)]
-        else:
-            at = [col[..., c] for c in range(3)]
+        at = shade(u0, u1, u2, zp)
         rgb = [(wb * bg[c] + (w * at[c]).sum(3)) / Z for c in range(3)]
         # alpha = 1 - Q as in soft_silhouettes_torch: the value from the product, the derivative from Q times the logarithms
         q = torch.where(taken, torch.sigmoid(-x), torch.ones_like(x)).prod(3).detach()
@@ -124,6 +118,77 @@ def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, nea
         alpha = (1 - q) + q * torch.where(q > 0, ln_q.detach() - ln_q, torch.zeros_like(ln_q))
         out.append(torch.stack(rgb + [alpha], 1))
     return torch.cat(out, 2).flip(2)
+
+
+def soft_render_torch(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
+                      background_color=(0, 0, 0)):
+    """rgba [B,4,S,S] in plain torch (any device, any float dtype), differentiable by autograd in faces and colors; the
+    module docstring's definition over every (pixel, face) pair, in chunks of pixel rows."""
+    B, F = int(faces.shape[0]), int(faces.shape[1])
+    if colors.dim() == 4:   # the colour at the pixel: the perspective-correct weights mu_k = u_k zp
+        col = colors.to(faces.dtype).expand(B, F, 3, 3)[:, None, None]       # [B,1,1,F,3 corners,3]
+
+        def shade(u0, u1, u2, zp):
+            mu0, mu1, mu2 = u0 * zp, u1 * zp, u2 * zp
+            return [mu0 * col[..., 0, c] + mu1 * col[..., 1, c] + mu2 * col[..., 2, c] for c in range(3)]
+    else:
+        col = colors.to(faces.dtype).expand(B, F, 3)[:, None, None]          # [B,1,1,F,3]
+
+        def shade(u0, u1, u2, zp):
+            return [col[..., c] for c in range(3)]
+    return _render_torch(faces, shade, 1, image_size, sigma, gamma, near, far, eps, background_color)
+
+
+def soft_render_uv_torch(faces, faces_uv, face_image, base_color, image_table, packed_images, light, image_size=256,
+                         sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3, background_color=(0, 0, 0)):
+    """rgba [B,4,S,S] in plain torch (any device, any float dtype) with UV images, on plain tensors: faces [B,F,3,3]; faces_uv
+    [F,3,2]; face_image [F] integers (outside [0, M): no image); base_color [F,3], the colour of a face without an image, or
+    [F,...,3], averaged over the middle dimensions (a base cube); image_table [M,3] integers (first pixel, H, W);
+    packed_images [Bi,P,3] (Bi 1 or B), each image top row first; light [B|1,F,3] or None (ones).  The module docstring's
+    definition with the UV colour of a pair, differentiable by autograd in faces, packed_images and light; in chunks of pixel
+    rows."""
+    B, F = int(faces.shape[0]), int(faces.shape[1])
+    dt, dev = faces.dtype, faces.device
+    uv = torch.as_tensor(faces_uv, device=dev).to(dt)
+    fi = torch.as_tensor(face_image, device=dev).long()
+    table = torch.as_tensor(image_table, device=dev).long().reshape(-1, 3)
+    base = torch.as_tensor(base_color, device=dev).to(dt)
+    base = base.reshape(F, -1, 3).mean(1)                                       # [F,3]
+    packed = packed_images.to(dt)
+    Bi, P = int(packed.shape[0]), int(packed.shape[1])
+    has = (fi >= 0) & (fi < table.shape[0])
+    row = table[torch.where(has, fi, torch.zeros_like(fi))]                     # [F,3]
+    off, H, W = row[:, 0], row[:, 1], row[:, 2]
+    has = has & (off >= 0) & (H >= 1) & (W >= 1) & (off + H * W <= P)
+    off, H, W = [torch.where(has, v, torch.ones_like(v) if i else torch.zeros_like(v)) for i, v in enumerate((off, H, W))]
+    lit = (torch.ones((1, F, 3), dtype=dt, device=dev) if light is None else light.to(dt)).expand(B, F, 3)[:, None, None]
+    Wf, Hf = (W - 1).to(dt), (H - 1).to(dt)
+    last = H * W - 1
+    images = packed.expand(B, P, 3)
+    bidx = torch.arange(B, device=dev)[:, None, None, None]
+
+    def shade(u0, u1, u2, zp):
+        d = []
+        for u in (u0, u1, u2):   # the clamp removes rounding excess only: its derivative is taken as 1
+            mu = u * zp
+            d.append(mu + (mu.clamp(0, 1) - mu).detach())
+        pos_x = (uv[:, 0, 0] * d[0] + uv[:, 1, 0] * d[1] + uv[:, 2, 0] * d[2]) * Wf
+        pos_y = (uv[:, 0, 1] * d[0] + uv[:, 1, 1] * d[1] + uv[:, 2, 1] * d[2]) * Hf
+        xi, yi = pos_x.detach().trunc(), pos_y.detach().trunc()                 # (int): towards 0; no gradient
+        yi1 = (pos_y.detach() + 1).trunc()
+        wx1, wy1 = pos_x - xi, pos_y - yi
+        wx0, wy0 = 1 - wx1, 1 - wy1
+        xi, yi, yi1 = [torch.nan_to_num(v, nan=0.0, posinf=2.0 ** 31, neginf=-2.0 ** 31).long() for v in (xi, yi, yi1)]
+        total = None
+        for r_, c_, w in ((yi, xi, wx0 * wy0), (yi1, xi, wx0 * wy1), (yi, xi + 1, wx1 * wy0), (yi1, xi + 1, wx1 * wy1)):
+            flat = torch.minimum((r_ * W + c_).clamp(min=0), last)               # rows from the bottom, clamped into the image
+            rr = flat // W
+            q = off + (H - 1 - rr) * W + (flat - rr * W)                        # the image is stored top row first
+            term = images[bidx, q] * w[..., None]                               # [B,rows,S,F,3]
+            total = term if total is None else total + term
+        T = torch.where(has[:, None], total, base)
+        return [lit[..., c] * T[..., c] for c in range(3)]
+    return _render_torch(faces, shade, 8, image_size, sigma, gamma, near, far, eps, background_color)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -166,16 +231,20 @@ class _SoftRender(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 # the public function
 
-def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, background_color, implementation):
+def _check(name, faces, colors, image_size, sigma, gamma, near, far, eps, background_color, implementation, light=False):
     """Argument checks shared by both implementations -> (image_size, sigma, gamma, near, far, eps, background, takes the
-    HIP path)."""
+    HIP path).  light: `colors` is soft_render_uv's `light`, one colour per face only."""
     B, F = _util.soft_check_faces(name, faces)
-    if not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() in (3, 4)
-            and tuple(colors.shape[1:]) in ((F, 3), (F, 3, 3)) and colors.shape[0] in (1, B)):
+    if light:
+        if not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() == 3
+                and tuple(colors.shape[1:]) == (F, 3) and colors.shape[0] in (1, B)):
+            raise ValueError('%s: light must be a float tensor [batch size or 1, num of faces (%d), 3]' % (name, F))
+    elif not (torch.is_tensor(colors) and colors.is_floating_point() and colors.dim() in (3, 4)
+              and tuple(colors.shape[1:]) in ((F, 3), (F, 3, 3)) and colors.shape[0] in (1, B)):
         raise ValueError('%s: colors must be a float tensor [batch size or 1, num of faces (%d), 3], or [batch size or 1, '
                          'num of faces, 3, 3] for corner colours' % (name, F))
     if colors.device != faces.device:
-        raise ValueError('%s: colors on %s, faces on %s' % (name, colors.device, faces.device))
+        raise ValueError('%s: %s on %s, faces on %s' % (name, 'light' if light else 'colors', colors.device, faces.device))
     _util.soft_check_image_size(name, image_size)
     sigma, gamma = _util.number(name, 'sigma', sigma), _util.number(name, 'gamma', gamma)
     for what, v in (('sigma', sigma), ('gamma', gamma)):
@@ -215,3 +284,110 @@ def soft_render(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1,
     if hip:
         return _SoftRender.apply(faces, colors, S, sigma, gamma, near, far, eps, background)
     return soft_render_torch(faces, colors, S, sigma, gamma, near, far, eps, background)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# UV images
+
+class _SoftRenderUV(torch.autograd.Function):
+    """forward(ctx, uv (a UVImages), args, faces [B,F,3,3], light [B|1,F,3], *uv.images) -> rgba [B,4,S,S], row 0 the top
+    row: the nr_soft_uv_* entries."""
+
+    @staticmethod
+    def _struct(layout, packed, device):
+        st = layout._tensors(device)
+        return _lib.UVImagesStruct(packed.data_ptr(), st['table'].data_ptr(), st['faces_uv'].data_ptr(),
+                                   st['face_image'].data_ptr(), st['base'].data_ptr(), layout.texture_size, layout.num_images,
+                                   layout.num_pixels, int(packed.shape[0]))
+
+    @staticmethod
+    def forward(ctx, uv, args, faces, light, *images):
+        from .uv_textures import pack_images
+        S, sigma, gamma, near, far, eps, background = args
+        f, lt = _lib.dense(faces.detach()), _lib.dense(light.detach())
+        packed = pack_images([im.detach() for im in images], uv.batch)
+        B, F = int(f.shape[0]), int(f.shape[1])
+        per_batch = 1 if int(lt.shape[0]) == B else 0   # else [1,F,3]: one set for the batch, read in place
+        rgba = torch.empty((B, 4, S, S), dtype=torch.float32, device=f.device)
+        q = torch.empty((B, S, S), dtype=torch.float32, device=f.device)
+        norm = torch.empty((B, 2, S, S), dtype=torch.float32, device=f.device)
+        st = _SoftRenderUV._struct(uv.layout, packed, f.device)
+        _lib.launch('nr_soft_uv_forward', f.device, st, f.data_ptr(), lt.data_ptr(), rgba.data_ptr(), q.data_ptr(),
+                    norm.data_ptr(), B, F, S, per_batch, sigma, gamma, near, far, eps, background[0], background[1],
+                    background[2], workspace_bytes=_lib.workspace_bytes('nr_soft_uv_workspace_bytes', st, B, F, S))
+        ctx.save_for_backward(f, lt, packed, rgba, q, norm)
+        ctx.uv, ctx.args, ctx.per_batch = uv, args, per_batch
+        return rgba.flip(2)
+
+    @staticmethod
+    def backward(ctx, grad_rgba):
+        from .uv_textures import unpack_image_gradients
+        f, lt, packed, rgba, q, norm = ctx.saved_tensors
+        uv, per_batch = ctx.uv, ctx.per_batch
+        S, sigma, gamma, near, far, eps, background = ctx.args
+        B, F = int(f.shape[0]), int(f.shape[1])
+        g = _lib.dense(grad_rgba.flip(2))
+        want_images = True in ctx.needs_input_grad[4:]
+        grad_faces, grad_light = torch.empty_like(f), torch.empty_like(lt)
+        grad_packed = torch.empty_like(packed) if want_images else None
+        st = _SoftRenderUV._struct(uv.layout, packed, f.device)
+        _lib.launch('nr_soft_uv_backward', f.device, st, f.data_ptr(), lt.data_ptr(), rgba.data_ptr(), q.data_ptr(),
+                    norm.data_ptr(), g.data_ptr(), grad_faces.data_ptr(), grad_light.data_ptr(), _lib.ptr(grad_packed), B, F, S,
+                    per_batch, sigma, gamma, near, far, eps, background[0], background[1], background[2],
+                    workspace_bytes=_lib.workspace_bytes('nr_soft_uv_workspace_bytes', st, B, F, S))
+        grads = [None] * len(uv.images)
+        if want_images:
+            for m, (gi, im) in enumerate(zip(unpack_image_gradients(uv.layout, grad_packed), uv.images)):
+                if ctx.needs_input_grad[4 + m]:   # an image shared by the batch: one row when every image is shared, else the rows summed
+                    grads[m] = gi if im.dim() == 4 else (gi[0] if uv.batch is None else gi.sum(0))
+        return (None, None, grad_faces, grad_light) + tuple(grads)
+
+
+def soft_render_uv(faces, uv_images, light=None, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
+                   background_color=(0, 0, 0), implementation=None):
+    """rgba [B,4,S,S] (row 0 the top row): faces [B,F,3,3] -- the rasterizer's input, without fill_back copies -- coloured by
+    the images of a UVImages (uv_textures.py: images [H_m,W_m,3] shared by the batch or [B,H_m,W_m,3] per render), sampled at
+    every taken pair with the bake's bilinear lookup at the pair's perspective-correct weights, times one light colour per
+    face, light [B,F,3] or [1,F,3] (None: ones); aggregated by coverage and depth as soft_render does.
+
+        C_f(p)_c = L_fc T_f(p)_c.  A face with an image m = face_image[f]: d_k = min(max(mu_k, 0), 1) (the clamp only removes
+        rounding excess; its derivative is taken as 1), pos_x = (sum_k uvx_fk d_k)(W_m - 1), pos_y = (sum_k uvy_fk d_k)(H_m - 1),
+        the four reads (yi,xi), (yi1,xi), (yi,xi+1), (yi1,xi+1) with xi = (int)pos_x, yi = (int)pos_y, yi1 = (int)(pos_y + 1),
+        rows counted from the bottom of an image stored top row first, the flat index clamped into the image, weights wx0 wy0,
+        wx0 wy1, wx1 wy0, wx1 wy1, summed in that order from 0.  A face without an image: the mean of its base cube, a constant.
+        Inside a face this is the texture render() shows, outside the texture at the nearest boundary point: continuous
+        across every edge.  Gradient, exact wherever the definition is differentiable (the read indices carry none; wx1 and
+        wy1 move with pos): per taken pair dL/dI[q_r]_c += W g_c L_c w_r, dL/dL_fc += W g_c T_f(p)_c, and with G_k = sum_c g_c
+        L_c (Tx_c uvx_fk (W - 1) + Ty_c uvy_fk (H - 1)), E_k = W zp (G_k - sum_j mu_j G_j) stands where the corner colours' E_k
+        stands (module docstring).
+
+    Differentiable, once, in faces (x, y and z), in every image tensor and in light; faces_uv, face_image and base receive no
+    gradient.  On float32 CUDA tensors inside the ranges of include/nr_hip.h both directions are HIP kernels (nr_soft_uv_*):
+    the gradients of faces and light are summed in a fixed order and repeat bit for bit; each entry of an image's gradient
+    is rounded once from a double sum whose additions arrive in no fixed order -- its last bit may differ between runs.
+    Everything else (`implementation='torch'`, sigma or gamma outside [1e-30, 1e30]) is soft_render_uv_torch on the layout's
+    tensors.  No host tables beyond the layout's (uploaded on first use): a call may be captured (graph.capture) once one
+    eager call has run -- but capture before any eager backward on the same leaves, or make the eager calls under no_grad, as
+    for soft_silhouettes (DESIGN "Soft silhouettes", Stream capture).  The other arguments are soft_render's."""
+    from .uv_textures import UVImages, pack_images
+    name = 'soft_render_uv'
+    B, F = _util.soft_check_faces(name, faces)
+    if not isinstance(uv_images, UVImages):
+        raise ValueError('%s: uv_images must be a UVImages' % name)
+    if uv_images.layout.num_faces != F:
+        raise ValueError('%s: the layout has %d faces, the call %d (the soft renderer takes no fill_back copies)'
+                         % (name, uv_images.layout.num_faces, F))
+    if uv_images.image_batch not in (1, B):
+        raise ValueError('%s: batched images must have the batch size of the faces (%d), got %d' % (name, B, uv_images.image_batch))
+    if uv_images.device != faces.device:
+        raise ValueError('%s: images on %s, faces on %s' % (name, uv_images.device, faces.device))
+    if light is None:
+        light = torch.ones((1, F, 3), dtype=faces.dtype, device=faces.device)
+    S, sigma, gamma, near, far, eps, background, hip = _check(name, faces, light, image_size, sigma, gamma, near, far, eps,
+                                                              background_color, implementation, light=True)
+    if hip:
+        return _SoftRenderUV.apply(uv_images, (S, sigma, gamma, near, far, eps, background), faces, light, *uv_images.images)
+    layout = uv_images.layout
+    st = layout._tensors(faces.device)
+    return soft_render_uv_torch(faces, st['faces_uv'], st['face_image'], st['base'], st['table'],
+                                pack_images(uv_images.images, uv_images.batch), light, S, sigma, gamma, near, far, eps, background)
