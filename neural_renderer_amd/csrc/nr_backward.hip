@@ -60,7 +60,7 @@ int nr::plan_backward(const BackwardCall &c, BackwardPlan &p)
     //   compaction | line setup | band kernel + gather in ONE grid, the gather's workgroups behind the band's | K6's overflow
     //   pass + the faces the gather left out + K6's sums onto grad_faces (one launch: big_overflow below)
     // The gather starts in the slots that the band kernel's last round frees instead of behind a launch boundary on an empty
-    // chip (k_band_gather, nr_backward_pixel_map.hip; measured: nr_k6_tune.h).  The band workgroups zero the unlisted faces'
+    // chip (k_band_gather, nr_k6_row.h; measured: nr_k6_tune.h).  The band workgroups zero the unlisted faces'
     // cubes of grad_textures only: the gather of the same launch stores the listed ones.
     // static taps (TS2 path): valid when the clamp of rasterize.py:402 keeps every index float below 1, i.e. when
     // (ts - 1) - eps still rounds below ts - 1 in float32 (eps > 2^-25); otherwise a coordinate can be exactly 1.0

@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k_backward_depth_face(
         const float w[3] = {weight_map[3 * p], weight_map[3 * p + 1], weight_map[3 * p + 2]};
         const float gd = g_depth[p];
         const float depth2 = depth * depth;
-        // :824-827
+        // [k8-terms] :824-827
 #pragma unroll
         for (int k = 0; k < 3; k++) acc[3 * k + 2] += gd * w[k] * depth2 / dc.zz[k];
         // :830-837

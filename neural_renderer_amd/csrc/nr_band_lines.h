@@ -1,6 +1,6 @@
 // nr_band_lines.h -- the line records of K6's band pipeline and the kernel body that writes them.
 //
-// Shared by nr_backward_pixel_map.hip (k_line_setup, the band kernel's scan path) and nr_backward_gather.hip, whose fused
+// Shared by nr_backward_pixel_map.hip (k_line_setup: nr_k6_lists.h; k_bpm_fast's scan path: nr_k6_fast.h) and nr_backward_gather.hip, whose fused
 // launch k_setup_gather runs the line setup and the K7 / K8 gather side by side: both need only the visible-face lists, both
 // are latency-bound launches that leave most of the chip idle, and the band kernel between them needs the records alone.
 #pragma once
@@ -173,12 +173,7 @@ __device__ __forceinline__ int band_sum_prefix(const int *__restrict__ rows, int
     const int per = (n2 + 255) / 256, i0 = tid * per, i1 = min(n2, i0 + per);
     int local = 0;
     for (int i = i0; i < i1; ++i) local += tot[i];
-    int inc = local;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(inc, o, WAVE);
-        if (lane >= o) inc += t;
-    }
+    const int inc = wave_incl_scan(local, lane);
     if (lane == 63) s_tmp[wave] = inc;
     __syncthreads();
     int run = inc - local;
@@ -284,12 +279,7 @@ __device__ __forceinline__ void line_setup_body(const LineSetupArgs &a, const in
             lines = hi >= lo ? hi - lo + 1 : 0;
         }
         const int lane = tid & 63, wave = tid >> 6;
-        int inc = lines;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int t = __shfl_up(inc, o, WAVE);
-            if (lane >= o) inc += t;
-        }
+        const int inc = wave_incl_scan(lines, lane);
         if (lane == 63) s_tmp[wave] = inc;
         __syncthreads();
         int before = 0;

@@ -55,6 +55,17 @@ __device__ __forceinline__ float wave_sum(float v)
     return v;
 }
 
+// inclusive prefix sum over the 64 lanes of a wave (lane = threadIdx.x & 63): lane l returns v of the lanes 0 .. l
+__device__ __forceinline__ int wave_incl_scan(int v, int lane)
+{
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int t = __shfl_up(v, o, WAVE);
+        if (lane >= o) v += t;
+    }
+    return v;
+}
+
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
 __device__ __forceinline__ int rfl(int v) { return __builtin_amdgcn_readfirstlane(v); }

@@ -1,7 +1,7 @@
 // nr_face_gather.h -- the K7 / K8 face gather's kernel body (one face per group of lanes, walking the pixels the face owns) and
 // what it needs.
 //
-// Shared by nr_backward_gather.hip (k_backward_textures_face, k_setup_gather) and nr_backward_pixel_map.hip, whose merged
+// Shared by nr_backward_gather.hip (k_backward_textures_face, k_setup_gather) and nr_backward_pixel_map.hip (nr_k6_row.h), whose merged
 // launch k_band_gather runs the gather's workgroups behind the band kernel's in ONE grid: both are bound by the workgroups the
 // chip holds, and the gather's fill the slots that the band kernel's last round frees.
 #pragma once
@@ -287,7 +287,7 @@ __device__ __forceinline__ void face_gather_body(const FaceGatherArgs &a, const 
         } else {
             compute_taps(face_z, wk, depth, ts, eps, t, LIT && flip);
         }
-        if (DEPTH) {  // K8 terms of this pixel (rasterize.py:824-837), as in k_backward_depth_face
+        if (DEPTH) {  // [k8-terms] K8 terms of this pixel (rasterize.py:824-837), as in k_backward_depth_face
             const float depth2 = depth * depth;
 #pragma unroll
             for (int k = 0; k < 3; k++) dacc[3 * k + 2] += gd * wk[k] * depth2 / dc.zz[k];
@@ -570,7 +570,7 @@ __device__ __forceinline__ void backward_big_body(const BigArgs &a, const uint3 
         if (finish) {
 #pragma unroll
             for (int v = 0; v < 3; v++) {
-                if (big) {
+                if (big) {  // [k8-atomics] K6's rounded total joins K8's float sums, in any order
                     atomicAdd(gf + 3 * v + 0, k6v[2 * v + 0]);
                     atomicAdd(gf + 3 * v + 1, k6v[2 * v + 1]);
                 } else {

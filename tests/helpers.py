@@ -138,21 +138,22 @@ def entrywise(got, ref_d, mags, mode):
     entries above their bound).  Entries where got, ref_d or the bound is not finite are skipped (the NaN pattern is
     asserted where the tests compare gradients).  u = 2^-24, u_d = 2^-53, gamma_n = n u / (1 - n u).
 
-    grad_faces, by `mode` (K6's kernels: neural_renderer_amd/csrc/nr_backward_pixel_map.hip):
+    grad_faces, by `mode` (K6's kernels: neural_renderer_amd/csrc/nr_k6_global.h, nr_k6_fast.h, nr_k6_row.h, parts of the
+    translation unit nr_backward_pixel_map.hip; `file [anchor]` names a comment `// [anchor]` in that file):
       'exact' -- NR_FLAG_EXACT_GRADIENT on either band kernel (include/nr_hip.h:79-93: the reference's operations one by one,
           every sum in double): the terms are the oracle's bits, so only the two double sums differ, each by <= N u_d A
           (any order), and each side rounds its double to float once:  ulp(ref_d) + 2 u_d N A.
       'global' -- k_bpm_global (NR_FLAG_K6_GLOBAL, rasters whose band does not fit in LDS): the reference's terms
-          (nr_backward_pixel_map.hip:190-195) in per-lane double sums, stored without atomics: the exact mode's bound.
+          (nr_k6_global.h [global-terms]) in per-lane double sums, stored without atomics: the exact mode's bound.
       'row' -- k_bpm_row, default mode.  Per term, against the oracle's float term (first order, S = sum_c (|I_c| + |ref_c| +
           2 kappa) |g_c| of the pixel, so that M = sum S / |dist|):
             diff: P formed in double and rounded once (u S), ref_c - K_c rounded (u S), four fused multiply-adds
-                (:1984-1989, 4 u S) -> 6 u S; the oracle's sum_c (I_c - ref_c) g_c (nr_oracle.c, K6): a subtraction, a
+                (nr_k6_row.h [row-visit], 4 u S) -> 6 u S; the oracle's sum_c (I_c - ref_c) g_c (nr_oracle.c, K6): a subtraction, a
                 product and an add per channel (the first add onto 0 exact) -> 5 u S;
             dist: t = fma(sdir, d1, -sdir cross) is the reference's subtraction (same bits); |c| 2/S (2 u: the product
                 and 2/S when S is no power of two), fma(|c| 2/S, |t|, eps) (u), eps in float (u) -> 4 u; the oracle's c t,
                 x 2/S, +- eps -> 3 u;
-            reciprocal: v_rcp_f32 <= 1 ulp = 2 u (:1996; phase A's recip_n with a Newton step, :1655-1657, less); the
+            reciprocal: v_rcp_f32 <= 1 ulp = 2 u ([row-rcp]; phase A's recip_n with a Newton step, [row-recip-n], less); the
                 oracle's division u.
           |term - term_ref| <= (6 + 5) u S / |dist| + (4 + 3 + 2 + 1) u |term| <= 21 u S / |dist|: C1_ROW = 22 with the
           second-order products.  A visit that one side skips (diff <= 0) and the other keeps has |diff| within those
@@ -161,15 +162,17 @@ def entrywise(got, ref_d, mags, mode):
             ulp(ref_d) + 2 u_d N A + C1_ROW u M + gamma_M_ROW A.
       'fast' -- k_bpm_fast, default mode (NR_FLAG_K6_LEGACY, the scan path NR_FLAG_K6_SCAN, overflow images, rasters above
           k_bpm_row's): the colour difference from b - ref or c - ref, one product and three fused multiply-adds
-          (:1001-1021, 5 u S; the oracle 5 u S); t = (d1 - cross) + k, two roundings of one sign (:1035, :1054: 2 u against the
+          (nr_k6_fast.h [fast-diff], 5 u S; the oracle 5 u S); t = (d1 - cross) + k, two roundings of one sign ([fast-t]: 2 u against the
           reference's one, 3 u apart), c 2/S (2 u), fma (u), eps (u); the oracle 3 u; v_rcp_f32 without a Newton step
-          (:1056-1057: 2 u), the oracle's division (u): (5 + 5) u S / |dist| + (3 + 4 + 3 + 2 + 1) u |term|
-          <= 23 u S / |dist|: C1_FAST = 24.  Float sums of <= M_FAST terms (:1056-1057 and the run sums), double above:
+          ([fast-rcp]: 2 u), the oracle's division (u): (5 + 5) u S / |dist| + (3 + 4 + 3 + 2 + 1) u |term|
+          <= 23 u S / |dist|: C1_FAST = 24.  (The general loop of class G forms t = d1 - cross in one
+          rounding and c t + eps in two, a product and an addition: the same count.)  Float sums of <= M_FAST terms ([fast-rcp]
+          and the run sums), double above:
             ulp(ref_d) + 2 u_d N A + C1_FAST u M + gamma_M_FAST A.
       'default' -- the default mode where either band kernel may serve an image (k_bpm_row hands overflow images to
           k_bpm_fast): the larger of the two.
-    With K8 (depth; `mags` has A8): its terms are the reference's expressions (nr_backward_gather.hip:293-299 against
-    nr_oracle.c K8), added in float in any order together with K6's rounded total (atomics, :548-549), so the bound grows
+    With K8 (depth; `mags` has A8): its terms are the reference's expressions (nr_backward_gather.hip and nr_face_gather.h [k8-terms] against
+    nr_oracle.c K8), added in float in any order together with K6's rounded total (atomics, nr_face_gather.h [k8-atomics]), so the bound grows
     by gamma_{N8+1} (A + X8) + ulp, X8 = M8 for x, y (tmp_l cancels) and A8 for z.
     'textures' (grad_textures, K7): one product per term, the reference's (rasterize.py:780), float partial sums and
     atomics in any order:  ulp(ref) + gamma_Nt At.

@@ -824,6 +824,56 @@ def test_high_resolution_dense_mesh():
     check_backward(faces, textures, 192, 1e-3, (True, True, True), seed=34)
 
 
+def compaction_seam_scene(F, S=33, seed=35):
+    """Two images of F random faces at S x S for the compaction's seams (chunks of 1024 faces): the faces at index 0, 1023, 1024
+    (where the mesh has them) and F - 1 are front-facing triangles in front of all others (z below random_scene's zmin), each
+    over its own quarter of the image, so that they own pixels.  Returns (faces, the indices of those faces)."""
+    rng = np.random.default_rng(seed)
+    faces = H.random_scene(rng, 2, F)
+    seam = sorted({i for i in (0, 1023, 1024, F - 1) if 0 <= i < F})
+    for k, i in enumerate(seam):
+        cx, cy = (-0.5, 0.5)[k & 1], (-0.5, 0.5)[k >> 1]
+        faces[:, i] = np.array([[cx - 0.3, cy - 0.3, 0.5 + 0.1 * k], [cx + 0.3, cy - 0.3, 0.5 + 0.1 * k],
+                                [cx, cy + 0.3, 0.5 + 0.1 * k]], np.float32)
+    return faces, seam
+
+
+@pytest.mark.parametrize('F', [1024, 1025, 16384, 16385])
+def test_compaction_chunk_seams(F):
+    """The three kernels that rank the visible faces (k_compact_par, k_list_visible, k_count_visible + k_compact_visible) at the
+    seams of their chunks of 1024 faces: one chunk, one chunk and a face, SMALL_CHUNKS = 16 chunks (the largest mesh of the
+    one-launch compaction) and the first mesh of the two-launch one.  Faces on both sides of the first seam and the mesh's last
+    face own pixels, and every chunk lists a face -- asserted from the oracle before anything runs on the GPU.  check_backward
+    then runs, per call, the forward's flags and k_mark_visible's (use_visible=False), NR_FLAG_K6_SCAN, NR_FLAG_K6_LEGACY and the
+    exact mode: k_compact_par up to 16 chunks, k_count_visible + k_compact_visible at 17.
+    k_list_visible serves the depth-only FUSED backward alone, when it is handed the forward's flags and a workspace and the mesh
+    has at most 16 chunks (k6_lists_fit; the plan's depth_lists, asserted here through the measurement build): check_backward's
+    stage call nr_backward_depth_map, held to the oracle, walks every face without lists, and the fused call -- K8's gather over
+    k_list_visible's lists, or at F = 16385 over every face -- must give its grad_faces bit for bit (the same per-face walk: a
+    face missing from the lists, listed twice or out of place leaves NaN, a doubled or a missing gradient)."""
+    S = 33
+    faces, seam = compaction_seam_scene(F, S)
+    fi = oracle_forward(faces, None, S, 0.1, 100, 1e-3, (0.2, 0.4, 0.6), False, True, False).face_index_map
+    for b in range(faces.shape[0]):
+        owners = np.unique(fi[b][fi[b] >= 0])
+        assert set(seam) <= set(owners.tolist()), 'image %d: a seam face owns no pixel' % b
+        assert len(np.unique(owners // 1024)) == (F + 1023) // 1024, 'image %d: a chunk without a visible face' % b
+    textures = np.random.default_rng(36).uniform(0, 1, (2, F, 2, 2, 2, 3)).astype(np.float32)
+    check_backward(faces, textures, S, 1e-3, (True, True, False), seed=37)
+    check_backward(faces, textures, S, 1e-3, (False, False, True), seed=38)
+    import backward_plans as P
+    from neural_renderer_amd import _build
+    _build.build_profile()
+    made = P.call(2, F, S, 2, (0, 0, 1), 0, 1e-3, visible=1, ws=0)
+    assert P.named(P.signature(made))['depth_lists'] == (1 if F <= 16 * 1024 else 0)
+    fw = abi.forward(faces, None, S, 0.1, 100.0, 1e-3, (0.2, 0.4, 0.6), 0, False, False, True)
+    g_depth = np.random.default_rng(39).normal(size=(2, S, S)).astype(np.float32)
+    gf_stage, _ = abi.backward(fw, None, None, g_depth)
+    gf_fused, _ = abi.backward_fused(fw, None, None, g_depth)  # (the forward's flags and a workspace of the size asked for)
+    np.testing.assert_array_equal(abi.host(gf_fused), abi.host(gf_stage))
+    assert np.abs(abi.host(gf_stage)[:, seam]).max() > 0  # (the seam faces reach the gradient)
+
+
 @pytest.mark.parametrize('modes', [(True, True, True), (False, True, False), (False, False, True), (True, False, False)],
                          ids=['all', 'alpha', 'depth', 'rgb'])
 def test_fused_backward_equals_stage_calls(modes):
