@@ -91,7 +91,8 @@ extern "C" {
                           *        nr_soft_silhouette_forward, nr_soft_silhouette_backward, nr_soft_silhouette_workspace_bytes;
                           *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes;
                           *        nr_soft_corners_forward, nr_soft_corners_backward, nr_soft_corners_workspace_bytes;
-                          *        nr_soft_uv_forward, nr_soft_uv_backward, nr_soft_uv_workspace_bytes);
+                          *        nr_soft_uv_forward, nr_soft_uv_backward, nr_soft_uv_workspace_bytes;
+                          *        nr_soft_cubes_forward, nr_soft_cubes_backward, nr_soft_cubes_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -953,6 +954,57 @@ int nr_soft_uv_backward(const nr_uv_images *uv, const float *faces, const float 
                         int32_t light_per_batch, double sigma, double gamma, double near, double far, double eps,
                         double background_r, double background_g, double background_b, void *workspace, size_t workspace_bytes,
                         void *stream);
+
+/*
+ * Soft colour rendering with texture cubes sampled at the pixel (not in the reference): textures [B, F, ts, ts, ts, 3]
+ * (textures_per_batch = 1) or [1, F, ts, ts, ts, 3] shared by the batch (textures_per_batch = 0, read in place), the
+ * rasterizer's cubes WITHOUT fill_back copies, 2 <= ts <= 8; light [B, F, 3] (light_per_batch = 1) or [1, F, 3]
+ * (light_per_batch = 0): one light colour per face; grad_textures and grad_light have their shapes.  Everything else -- the
+ * contribution rule, the taken rule, lambda_k, iz, zp, zn, m, w_f, w_b, Z, Q, alpha, the layouts, the ranges -- is
+ * nr_soft_render_*'s, and u_k = lambda_k / z_k, mu_k = u_k zp are nr_soft_corners_*'s, except the colour of a taken pair:
+ *   C_f(p)_c = L_fc T_f(p)_c,  rgb = (w_b background + sum w_f C_f(p)) / Z.
+ *   v_k = mu_k (ts - 1); v_k = fmaxf(v_k, 0) (a NaN becomes 0); v_k = (float)fmin((double)v_k, (double)(ts - 1) - texture_eps):
+ *   the rasterizer's sequence with mu_k where it has w_k (zp / z_k).  i_k = (int)v_k, fr_k = v_k - i_k; eight taps pn = 0..7,
+ *   bit k of pn picks (i_k + 1, fr_k), else (i_k, 1 - fr_k); the weight w_pn = ((1 . f_0) f_1) f_2, the flat index (i_0 ts +
+ *   i_1) ts + i_2 of the picked indices.  A tap whose flat index is >= ts^3 is skipped, never read (its weight is an exact 0):
+ *   NO READ LEAVES THE FACE'S CUBE, whatever mu holds.  T = ((0 + w_0 tex_0) + w_1 tex_1) + ... in tap order.
+ *   Inside a face this is the texture nr_forward_rasterize shows, outside the texture at the nearest boundary point:
+ *   continuous across every edge.  texture_eps, 0 <= texture_eps < 1, is the rasterizer's eps; it is not `eps`, which places
+ *   the background in the depth order.
+ * Backward, per taken pair, with W = w_f / Z and h = g_rgb . (C_f(p) - rgb) as in nr_soft_render_backward.  The tap indices
+ * carry no gradient and both clamps are taken with derivative 1 (the lower one removes rounding excess only; the upper one
+ * acts on a sliver of relative width texture_eps / (ts - 1) at a vertex, where the gradient is the unclamped derivative):
+ *   D_kc = sum_pn (dw_pn / dfr_k) tex[tap_pn]_c   (four differences of the taps with and without bit k, each times the other
+ *          two dimensions' factors; a skipped tap counts as 0)
+ *   G_k  = (ts - 1) sum_c g_c L_fc D_kc
+ *   grad_textures[b or 0, f, tap_pn, c] += W g_c L_fc w_pn   (shared cubes: one sum over the batch)
+ *   grad_light[b or 0, f, c]            += W g_c T_f(p)_c
+ *   E_k = W zp (G_k - sum_j mu_j G_j)
+ * and everything after E_k is nr_soft_corners_backward's.  Every output: fixed order, no atomics, every element stored, the
+ * same bits in every run and for an image alone or inside a batch.  grad_textures (NULL: not computed): the wave that owns
+ * (image, face) adds the terms of its taken pairs in double in the order of its walk and rounds each entry once; the entries
+ * of a dropped face or an untouched texel are exact zeros; no zero fill is expected from the caller.  Shared cubes and shared
+ * light: the per-image results are added over the batch in ascending b in double and rounded once.
+ * NR_E_* before any launch, nr_soft_render_*'s codes in their order: a NULL pointer NR_E_NULL; sizes out of range, ts
+ * outside [2, 8] or F ts^3 3 above 2^31 - 257 NR_E_SIZE; the numbers, texture_eps outside [0, 1), textures_per_batch or
+ * light_per_batch NR_E_MODE; a NULL or short workspace NR_E_WORKSPACE.  nr_soft_cubes_workspace_bytes: 0 for sizes out of
+ * range.  No host synchronisation; capturable.
+ */
+size_t nr_soft_cubes_workspace_bytes(int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t texture_size,
+                                     int32_t textures_per_batch);
+
+int nr_soft_cubes_forward(const float *faces, const float *textures, const float *light, float *rgba, float *transmittance,
+                          float *normaliser, int32_t batch_size, int32_t num_faces, int32_t image_size, int32_t texture_size,
+                          int32_t textures_per_batch, int32_t light_per_batch, double sigma, double gamma, double near,
+                          double far, double eps, double background_r, double background_g, double background_b,
+                          double texture_eps, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_soft_cubes_backward(const float *faces, const float *textures, const float *light, const float *rgba,
+                           const float *transmittance, const float *normaliser, const float *grad_rgba, float *grad_faces,
+                           float *grad_light, float *grad_textures, int32_t batch_size, int32_t num_faces, int32_t image_size,
+                           int32_t texture_size, int32_t textures_per_batch, int32_t light_per_batch, double sigma,
+                           double gamma, double near, double far, double eps, double background_r, double background_g,
+                           double background_b, double texture_eps, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Mesh losses (not in the reference's library; the two shape priors of its paper, section 5): on world-space vertices

@@ -44,7 +44,8 @@ from .normals import camera_rotation, corner_normals, face_normals, vertex_norma
 from .soft_silhouette import soft_silhouettes, soft_silhouettes_torch
 # not in the reference: soft colour rendering -- the soft coverage aggregated by a depth-weighted softmax, with its exact
 # gradient to x, y, z and the face colours, HIP in both directions -- for Renderer.render_soft
-from .soft_render import soft_render, soft_render_torch, soft_render_uv, soft_render_uv_torch
+from .soft_render import (TextureCubes, soft_render, soft_render_cubes, soft_render_cubes_torch, soft_render_torch, soft_render_uv,
+                          soft_render_uv_torch)
 # not in the reference: multi-GPU helpers and the captured-graph helper for fixed-shape loops
 from . import distributed, graph
 
@@ -61,11 +62,11 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'clear_workspace_cache',
            'Renderer', 'cross', 'get_points_from_angles', 'lighting', 'look', 'look_at', 'perspective', 'projection',
            'vertices_to_faces',
-           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'UVLayout', 'UVTextures', 'bake_uv_textures',
+           'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'TextureCubes', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
            'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
            'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation',
            'soft_silhouettes', 'soft_silhouettes_torch', 'soft_render', 'soft_render_torch', 'soft_render_uv',
-           'soft_render_uv_torch']
+           'soft_render_uv_torch', 'soft_render_cubes', 'soft_render_cubes_torch']

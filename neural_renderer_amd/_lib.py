@@ -117,6 +117,9 @@ SIGNATURES = {
     'nr_soft_uv_workspace_bytes': (_sz, [_uv_p] + [_i32] * 3),
     'nr_soft_uv_forward': (_c.c_int, [_uv_p] + [_vp] * 5 + [_i32] * 4 + [_f64] * 8 + [_vp, _sz, _vp]),
     'nr_soft_uv_backward': (_c.c_int, [_uv_p] + [_vp] * 9 + [_i32] * 4 + [_f64] * 8 + [_vp, _sz, _vp]),
+    'nr_soft_cubes_workspace_bytes': (_sz, [_i32] * 5),
+    'nr_soft_cubes_forward': (_c.c_int, [_vp] * 6 + [_i32] * 6 + [_f64] * 9 + [_vp, _sz, _vp]),
+    'nr_soft_cubes_backward': (_c.c_int, [_vp] * 10 + [_i32] * 6 + [_f64] * 9 + [_vp, _sz, _vp]),
     'nr_mesh_loss_workspace_bytes': (_sz, [_i32] * 2),
     'nr_laplacian_forward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp, _sz, _vp]),
     'nr_laplacian_backward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),

@@ -51,6 +51,17 @@
 // double atomics into a zero-filled scratch (many pairs land on one image pixel; the scheme of nr_uv_pixel.hip, for its
 // reason), zero terms skipped, and k_uv_image_round rounds every sum once -- a double sum whose additions arrive in no fixed
 // order.
+// Texture cubes (nr_soft_cubes_*; DESIGN "Soft colour rendering", Texture cubes): the colour of a taken pair is a light colour
+// per face times the rasterizer's trilinear lookup of the face's cube [ts, ts, ts, 3] at the pair's own weights,
+//   v_k = min(max(mu_k (ts - 1), 0), (ts - 1) - texture_eps),  T_f(p) = the eight taps of cube_texel,  C_f(p) = L_f T_f(p)
+// -- compute_taps' sequence and sum_taps' sum (nr_device.h) with mu_k where the rasterizer has w_k (zp / z_k).  The <CUBE>
+// instantiations of the two templates; k_cube_setup writes an 80-byte record (the flat one, with the face's index where the
+// flat record has a 0: the forward's compact list loses a record's position).  Backward, with D_kc = sum_pn (dw_pn / dfr_k)
+// tex[tap_pn]_c (cube_slopes) and G_k = (ts - 1) sum_c g_c L_c D_kc:  E_k = (W zp) (G_k - sum_j mu_j G_j) and everything after it
+// as above; dL/dL_fc += (W g_c) T_c.  THE CUBE GRADIENT TAKES NO ATOMICS: the wave that owns (image, face) owns the face's
+// cube, keeps ts^3 * 3 double sums in LDS that no other wave touches and adds the terms ((W g_c) L_c) w_pn of its taken pairs
+// one pair after the other in the order of its walk (k_render_backward has the scheme); every entry is rounded once and
+// stored, zeros included.  Fixed order, the same bits in every run and for an image alone or inside a batch.
 #include <type_traits>
 
 #include "nr_soft_pair.h"
@@ -147,10 +158,11 @@ struct RenderArgs {
     float bg_r, bg_g, bg_b;
 };
 
-// the colour of a pair: one per face, three corner colours, or a light colour times a UV image sample
-constexpr int FLAT = 0, CORNER = 1, UV = 2;
+// the colour of a pair: one per face, three corner colours, a light colour times a UV image sample, or times a cube sample
+constexpr int FLAT = 0, CORNER = 1, UV = 2, CUBE = 3;
 constexpr int UV_REC = 7;             // float4 per record with a UV sample
 constexpr int mode_rec(int mode) { return mode == UV ? UV_REC : (mode == CORNER ? CORNER_REC : RENDER_REC); }
+constexpr int CUBE_MIN_TS = 2, CUBE_MAX_TS = 8;   // the texture sizes of the cube kernels (48 KiB of LDS per backward workgroup at 8)
 
 // what the UV kernels take beyond RenderArgs (the flat and corner kernels keep RenderArgs itself: their signatures stay)
 struct UVArgs : RenderArgs {
@@ -159,8 +171,16 @@ struct UVArgs : RenderArgs {
     double *acc;             // backward: the double sums of the image gradient, or nullptr when it is not asked for
     size_t acc_stride;       // doubles, 0 for shared images
 };
+// ... and the cube kernels
+struct CubeArgs : RenderArgs {
+    const float *cubes;      // [cube_batch, F, ts, ts, ts, 3]
+    size_t cube_stride;      // floats between the cubes of two batch elements, 0 for shared cubes
+    int ts;
+    double hi;               // the upper clamp of a sample position, (ts - 1) - texture_eps
+    float *grad;             // backward: the cube gradient of every image [B, F, ts^3, 3], or nullptr when it is not asked for
+};
 template <int MODE>
-using ModeArgs = std::conditional_t<MODE == UV, UVArgs, RenderArgs>;
+using ModeArgs = std::conditional_t<MODE == UV, UVArgs, std::conditional_t<MODE == CUBE, CubeArgs, RenderArgs>>;
 
 // what a UV record holds beyond FaceShade's 1 / z_k and the light colour (FaceShade's cr, cg, cb):
 // (., ., uvx0, uvy0), (uvx1, uvy1, uvx2, uvy2), (first pixel, H, W, 0); a face without an image has H = 0 and the mean of its
@@ -213,8 +233,105 @@ __device__ __forceinline__ void uv_texel(const UVFace &u, const PairColor &pc, c
     }
 }
 
+// the sample of a taken pair in its face's cube: the cell i, the fractions fr, the eight taps' weights w and texels tx[tap][rgb]
+// (bit pn of `inside`: tap pn lies inside the cube; the texels of the others are handed back as zeros) and the sum (r, g, b)
+struct CubeTexel {
+    int i[3];
+    float fr[3], w[8], tx[8][3], r, g, b;
+    unsigned inside;
+};
+
+// T_f(p): compute_taps' sequence (nr_device.h) at v_k = mu_k (ts - 1) -- max with 0, which also takes a NaN to 0, then the min
+// with hi in double, rounded --, summed as sum_taps sums: the eight texels requested together, from 0 in tap order, a tap whose
+// flat index leaves the cube skipped (its weight is an exact 0) and its address replaced by the cube's last texel.  NO READ
+// LEAVES THE FACE'S CUBE whatever mu holds: 0 <= v_k <= hi <= ts - 1, so every i_k lies in [0, ts - 1] and every flat index
+// read in [0, ts^3 - 1].
+__device__ __forceinline__ void cube_texel(const float *__restrict__ cube, int ts, double hi, const PairColor &pc, CubeTexel &s)
+{
+    const float mu[3] = {pc.mu0, pc.mu1, pc.mu2};
+    const int T = ts * ts * ts;
+#pragma unroll
+    for (int k = 0; k < 3; k++) {
+        float v = mu[k] * (float)(ts - 1);
+        v = fmaxf(v, 0.0f);
+        v = (float)fmin((double)v, hi);
+        s.i[k] = (int)v;
+        s.fr[k] = v - (float)s.i[k];
+    }
+    s.inside = 0;
+#pragma unroll
+    for (int pn = 0; pn < 8; pn++) {
+        float w = 1.0f;
+        int idx[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            if (((pn >> k) & 1) == 0) {
+                w *= 1.0f - s.fr[k];
+                idx[k] = s.i[k];
+            } else {
+                w *= s.fr[k];
+                idx[k] = s.i[k] + 1;
+            }
+        }
+        const int flat = (idx[0] * ts + idx[1]) * ts + idx[2];
+        s.w[pn] = w;
+        s.inside |= (unsigned)(flat < T) << pn;
+        const float *p = cube + min(flat, T - 1) * 3;
+        s.tx[pn][0] = p[0]; s.tx[pn][1] = p[1]; s.tx[pn][2] = p[2];
+    }
+    float c[3] = {0.0f, 0.0f, 0.0f};
+#pragma unroll
+    for (int pn = 0; pn < 8; pn++) {
+        const bool in = (s.inside >> pn) & 1u;
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float sum = c[k] + s.w[pn] * s.tx[pn][k];
+            c[k] = in ? sum : c[k];
+            s.tx[pn][k] = in ? s.tx[pn][k] : 0.0f;
+        }
+    }
+    s.r = c[0]; s.g = c[1]; s.b = c[2];
+}
+
+// D_k: the derivative of the sum above to fr_k, per channel -- the four differences of the taps with and without bit k, each
+// times the product of the other two dimensions' factors, added in ascending tap order from the first
+__device__ __forceinline__ void cube_slopes(const CubeTexel &s, int k, float d[3])
+{
+    const int ka = k == 0 ? 1 : 0, kb = k == 2 ? 1 : 2;   // the other two dimensions, ascending
+    const float fa[2] = {1.0f - s.fr[ka], s.fr[ka]}, fb[2] = {1.0f - s.fr[kb], s.fr[kb]};
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        float sum = 0.0f;
+#pragma unroll
+        for (int jb = 0; jb < 2; jb++)
+#pragma unroll
+            for (int ja = 0; ja < 2; ja++) {
+                const int lo = (ja << ka) | (jb << kb), up = lo | (1 << k);
+                const float term = (fa[ja] * fb[jb]) * (s.tx[up][c] - s.tx[lo][c]);
+                sum = (ja | jb) == 0 ? term : sum + term;
+            }
+        d[c] = sum;
+    }
+}
+
 // --------------------------------------------------------------------------------------------------------------------
 // set-up
+
+// texture cubes: the base record, 1 / z_k and the light colour as the flat record holds its colour, then the face's own index:
+// the forward's compact list loses a record's position
+__global__ __launch_bounds__(256) void k_cube_setup(const float *__restrict__ faces, const float *__restrict__ light,
+                                                    float4 *__restrict__ rec, int F, int S, size_t light_stride, float reach,
+                                                    double near, double far)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (f >= F) return;
+    const float *L = light + (size_t)b * light_stride + (size_t)f * 3;
+    float4 *o = rec + ((size_t)b * F + f) * RENDER_REC;
+    float c[9];
+    soft_record<true>(faces + ((size_t)b * F + f) * 9, o, S, reach, near, far, c);
+    o[3] = make_float4(1.0f / c[2], 1.0f / c[5], 1.0f / c[8], L[0]);
+    o[4] = make_float4(L[1], L[2], __int_as_float(f), 0.0f);
+}
 
 template <bool CORNERS>
 __global__ __launch_bounds__(256) void k_render_setup(const float *__restrict__ faces, const float *__restrict__ colors,
@@ -333,6 +450,16 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
                 cr = take ? cr + w * (h.cr * t.r) : cr;
                 cg = take ? cg + w * (h.cg * t.g) : cg;
                 cb = take ? cb + w * (h.cb * t.b) : cb;
+            } else if constexpr (MODE == CUBE) {   // the cube is read for taken pairs only
+                const PairColor pc = pair_color(q, h, CornerColor{});   // (its mu)
+                CubeTexel t = {};
+                if (take) {
+                    const int f = min(max(__float_as_int(l[4].z), 0), F - 1);   // (the record's own; clamped, the workspace being the caller's)
+                    cube_texel(a.cubes + (size_t)b * a.cube_stride + (size_t)f * (a.ts * a.ts * a.ts * 3), a.ts, a.hi, pc, t);
+                }
+                cr = take ? cr + w * (h.cr * t.r) : cr;
+                cg = take ? cg + w * (h.cg * t.g) : cg;
+                cb = take ? cb + w * (h.cb * t.b) : cb;
             } else {
                 cr = take ? cr + w * h.cr : cr;
                 cg = take ? cg + w * h.cg : cg;
@@ -358,6 +485,15 @@ __global__ __launch_bounds__(256) void k_render_forward(const float4 *__restrict
 // --------------------------------------------------------------------------------------------------------------------
 // backward
 
+// between LDS accesses of different lanes of ONE wave to the same address: the hardware keeps a wave's LDS operations in order,
+// this keeps the compiler from moving them across
+__device__ __forceinline__ void wave_lds_order()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <int MODE>
 __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restrict__ rec, const float *__restrict__ rgba,
                                                          const float *__restrict__ trans, const float *__restrict__ norm,
@@ -375,6 +511,21 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
     if constexpr (CORNERS) cc = unpack_corners(r[3], r[4], r[5]);
     UVFace uvf = {};
     if constexpr (MODE == UV) uvf = unpack_uv(r[4], r[5], r[6]);
+    // texture cubes: the wave owns its face's cube, so it sums the cube's gradient itself -- in double, in LDS that no other
+    // wave touches, one taken pair after the other in the order of the walk (k_render_backward's comment has the scheme)
+    [[maybe_unused]] double *sums = nullptr;
+    [[maybe_unused]] const float *cube = nullptr;
+    [[maybe_unused]] int T3 = 0;
+    if constexpr (MODE == CUBE) {
+        extern __shared__ double cube_sums[];
+        T3 = a.ts * a.ts * a.ts * 3;
+        cube = a.cubes + (size_t)b * a.cube_stride + (size_t)f * T3;
+        if (a.grad) {
+            sums = cube_sums + (threadIdx.x >> 6) * T3;
+            for (int e = lane; e < T3; e += WAVE) sums[e] = 0.0;
+            wave_lds_order();
+        }
+    }
     float g0x = 0.0f, g0y = 0.0f, g1x = 0.0f, g1y = 0.0f, g2x = 0.0f, g2y = 0.0f;
     float g0z = 0.0f, g1z = 0.0f, g2z = 0.0f, gcr = 0.0f, gcg = 0.0f, gcb = 0.0f;
     float g1r = 0.0f, g1g = 0.0f, g1b = 0.0f, g2r = 0.0f, g2g = 0.0f, g2b = 0.0f;   // (corners 1 and 2; gcr, gcg, gcb are corner 0's)
@@ -388,7 +539,10 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
         const float e0x = s.x1 - s.x0, e0y = s.y1 - s.y0, e1x = s.x2 - s.x1, e1y = s.y2 - s.y1, e2x = s.x0 - s.x2, e2y = s.y0 - s.y2;
         const float ee0 = e0x * e0x + e0y * e0y, ee1 = e1x * e1x + e1y * e1y, ee2 = e2x * e2x + e2y * e2y;   // soft_segment's ee
         const float s0 = h.iz0 * h.iz0, s1 = h.iz1 * h.iz1, s2 = h.iz2 * h.iz2;   // 1 / z_k^2
-        for (int i = lane; i < n; i += WAVE) {
+        // (texture cubes: every lane makes every trip, a lane past the last pixel on the last pixel again with nothing taken)
+        const int n_walk = MODE == CUBE ? (n + WAVE - 1) / WAVE * WAVE : n;
+        for (int i0 = lane; i0 < n_walk; i0 += WAVE) {
+            const int i = MODE == CUBE ? min(i0, n - 1) : i0;
             const int row = i / bw, xi = x_lo + (i - row * bw), yi = y_lo + row;
             const float px = pixel_center(xi, S), py = pixel_center(yi, S);
             const SoftPair p = soft_pair(px, py, s, a.inv_sigma);
@@ -399,8 +553,9 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             const float Qp = qb[o], m = nb[o], Z = nb[SS + o];
             const float D = 1.0f / (1.0f + expf(-p.x)), D1 = 1.0f / (1.0f + expf(p.x));
             float W = (D * expf((q.zn - m) * a.inv_gamma)) / Z;
-            W = q.taken ? W : 0.0f;                        // a pair not taken: every term below is an exact 0
-            const float Ga = q.taken ? ga * Qp : 0.0f;
+            const bool taken = MODE == CUBE ? (q.taken && i0 < n) : q.taken;
+            W = taken ? W : 0.0f;                          // a pair not taken: every term below is an exact 0
+            const float Ga = taken ? ga * Qp : 0.0f;
             float hh, E0 = 0.0f, E1 = 0.0f, E2 = 0.0f;   // E_k: what corner k's colour adds to diz, 0 for a flat colour
             if constexpr (CORNERS) {
                 const PairColor pc = pair_color(q, h, cc);
@@ -415,12 +570,12 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
             } else if constexpr (MODE == UV) {
                 const PairColor pc = pair_color(q, h, CornerColor{});   // (its mu)
                 UVTexel t = {};
-                if (q.taken) uv_texel(uvf, pc, a.images + (size_t)b * a.image_stride, t);
+                if (taken) uv_texel(uvf, pc, a.images + (size_t)b * a.image_stride, t);
                 hh = (gr * (h.cr * t.r - R) + gg * (h.cg * t.g - G)) + gb * (h.cb * t.b - Bl);
                 gcr += (W * gr) * t.r;    // the light colour's sums
                 gcg += (W * gg) * t.g;
                 gcb += (W * gb) * t.b;
-                if (q.taken && uvf.H != 0) {
+                if (taken && uvf.H != 0) {
                     // the sample moves with wx1 and wy1 alone (the read indices carry no gradient): Tx, Ty per channel, then
                     // G_k = sum_c g_c L_c (Tx_c uvx_k (W - 1) + Ty_c uvy_k (H - 1)) and E_k = (W zp) (G_k - sum_j mu_j G_j)
                     const float ar = gr * h.cr, ag = gg * h.cg, ab = gb * h.cb;
@@ -451,6 +606,56 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
                                 if (term != 0.0) atomicAdd(at + c, term);
                             }
                         }
+                    }
+                }
+            } else if constexpr (MODE == CUBE) {
+                const PairColor pc = pair_color(q, h, CornerColor{});   // (its mu)
+                CubeTexel t = {};
+                if (taken) cube_texel(cube, a.ts, a.hi, pc, t);
+                hh = (gr * (h.cr * t.r - R) + gg * (h.cg * t.g - G)) + gb * (h.cb * t.b - Bl);
+                gcr += (W * gr) * t.r;    // the light colour's sums
+                gcg += (W * gg) * t.g;
+                gcb += (W * gb) * t.b;
+                if (taken) {
+                    // the sample moves with fr alone (the cell carries no gradient, both clamps are taken with derivative 1):
+                    // G_k = (ts - 1) sum_c g_c L_c D_kc and E_k = (W zp) (G_k - sum_j mu_j G_j)
+                    const float ar = gr * h.cr, ag = gg * h.cg, ab = gb * h.cb, sc = (float)(a.ts - 1);
+                    float d0[3], d1[3], d2[3];
+                    cube_slopes(t, 0, d0);
+                    cube_slopes(t, 1, d1);
+                    cube_slopes(t, 2, d2);
+                    const float G0 = ((ar * d0[0] + ag * d0[1]) + ab * d0[2]) * sc;
+                    const float G1 = ((ar * d1[0] + ag * d1[1]) + ab * d1[2]) * sc;
+                    const float G2 = ((ar * d2[0] + ag * d2[1]) + ab * d2[2]) * sc;
+                    const float Gm = (pc.mu0 * G0 + pc.mu1 * G1) + pc.mu2 * G2, Wz = W * q.zp;
+                    E0 = Wz * (G0 - Gm);
+                    E1 = Wz * (G1 - Gm);
+                    E2 = Wz * (G2 - Gm);
+                }
+                if (sums) {
+                    // the cube terms (W g_c L_c) w_pn.  The taken pairs of this trip one after the other in ascending lane order:
+                    // the pair's cell, fractions and three factors go to every lane, lane 3 pn + c forms tap pn's weight with the
+                    // forward's own operations and adds channel c's term, an exact double product, to its entry.  A pair's eight
+                    // taps are eight different texels, so no two lanes meet; a tap outside the cube is skipped as in the forward.
+                    const float vr = (W * gr) * h.cr, vg = (W * gg) * h.cg, vb = (W * gb) * h.cb;
+                    const int pn = lane / 3, ch = lane - pn * 3, T = T3 / 3;
+                    unsigned long long todo = __ballot(taken);
+                    while (todo != 0) {
+                        const int src = __ffsll((long long)todo) - 1;
+                        todo &= todo - 1;
+                        const int c0 = bcast_i(t.i[0], src), c1 = bcast_i(t.i[1], src), c2 = bcast_i(t.i[2], src);
+                        const float fr0 = bcast_f(t.fr[0], src), fr1 = bcast_f(t.fr[1], src), fr2 = bcast_f(t.fr[2], src);
+                        const float v0 = bcast_f(vr, src), v1 = bcast_f(vg, src), v2 = bcast_f(vb, src);
+                        if (lane < 24) {
+                            float w = 1.0f;
+                            w *= (pn & 1) ? fr0 : 1.0f - fr0;
+                            w *= (pn & 2) ? fr1 : 1.0f - fr1;
+                            w *= (pn & 4) ? fr2 : 1.0f - fr2;
+                            const int flat = ((c0 + (pn & 1)) * a.ts + (c1 + ((pn >> 1) & 1))) * a.ts + (c2 + (pn >> 2));
+                            const float v = ch == 0 ? v0 : (ch == 1 ? v1 : v2);
+                            if (flat < T) sums[flat * 3 + ch] += (double)v * (double)w;
+                        }
+                        wave_lds_order();
                     }
                 }
             } else {
@@ -529,6 +734,12 @@ __global__ __launch_bounds__(256) void k_render_backward(const float4 *__restric
         if constexpr (CORNERS) {
             c[3] = g1r; c[4] = g1g; c[5] = g1b;
             c[6] = g2r; c[7] = g2g; c[8] = g2b;
+        }
+    }
+    if constexpr (MODE == CUBE) {   // every entry of the face's cube stored, each sum rounded once; zeros for a dropped face
+        if (sums) {
+            float *o = a.grad + ((size_t)b * F + f) * T3;
+            for (int e = lane; e < T3; e += WAVE) o[e] = (float)sums[e];
         }
     }
 }
@@ -737,7 +948,140 @@ int uv_backward(const nr_uv_images *uv, const RenderCall &c, const float *rgba, 
     return launch_status();
 }
 
+// the workspace of the cube entries: the records, the per-image light gradients of a call with shared light, the per-image
+// cube gradients of a call with shared cubes
+struct CubeWorkspace {
+    size_t light_off, cubes_off, total;
+};
+
+CubeWorkspace cube_workspace(int B, int F, int ts, int textures_per_batch)
+{
+    CubeWorkspace w;
+    w.light_off = (size_t)B * (size_t)F * RENDER_REC * sizeof(float4);
+    w.cubes_off = align_up(w.light_off + (size_t)B * (size_t)F * 3 * sizeof(float), 256);
+    w.total = w.cubes_off + (textures_per_batch ? 0 : (size_t)B * (size_t)F * (size_t)(ts * ts * ts * 3) * sizeof(float));
+    return w;
+}
+
+bool cube_sizes_ok(int B, int F, int S, int ts)
+{
+    // (F ts^3 3 is k_render_colors' int n)
+    return soft_sizes_ok(B, F, S) && ts >= CUBE_MIN_TS && ts <= CUBE_MAX_TS && (size_t)F * (size_t)(ts * ts * ts * 3) <= 0x7fffff00ull;
+}
+
+struct CubeCall {
+    const float *textures;
+    int ts, textures_per_batch;
+    double texture_eps;
+};
+
+// render_check's codes in render_check's order, the texture size with the sizes and texture_eps with the numbers
+int cube_check(const CubeCall &t, const RenderCall &c)
+{
+    if (!t.textures || !c.faces || !c.colors) return NR_E_NULL;
+    if (!cube_sizes_ok(c.B, c.F, c.S, t.ts)) return NR_E_SIZE;
+    RenderCall flat = c;   // the numbers; the flat workspace is the smaller one
+    flat.workspace_bytes = c.workspace ? render_workspace(c.B, c.F, 0) : 0;
+    const int e = render_check(flat);
+    if (e != 0 && e != NR_E_WORKSPACE) return e;
+    if (!(t.texture_eps >= 0.0 && t.texture_eps < 1.0)) return NR_E_MODE;
+    if (t.textures_per_batch != 0 && t.textures_per_batch != 1) return NR_E_MODE;
+    if (e != 0 || c.workspace_bytes < cube_workspace(c.B, c.F, t.ts, t.textures_per_batch).total) return NR_E_WORKSPACE;
+    return 0;
+}
+
+CubeArgs cube_args(const CubeCall &t, const RenderCall &c, float *grad)
+{
+    CubeArgs a;
+    static_cast<RenderArgs &>(a) = render_args(c);
+    a.cubes = t.textures;
+    a.cube_stride = t.textures_per_batch ? (size_t)c.F * (size_t)(t.ts * t.ts * t.ts * 3) : (size_t)0;
+    a.ts = t.ts;
+    a.hi = (double)(t.ts - 1) - t.texture_eps;
+    a.grad = grad;
+    return a;
+}
+
+int cube_setup(const RenderCall &c, hipStream_t st)
+{
+    hipLaunchKernelGGL(k_cube_setup, dim3((unsigned)((c.F + 255) / 256), (unsigned)c.B), dim3(256), 0, st, c.faces, c.colors,
+                       (float4 *)c.workspace, c.F, c.S, c.colors_per_batch ? (size_t)c.F * 3 : (size_t)0, soft_reach(c.sigma),
+                       c.near, c.far);
+    return launch_status();
+}
+
+int cube_forward(const CubeCall &t, const RenderCall &c, float *rgba, float *transmittance, float *normaliser, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser) return NR_E_NULL;
+    if (int e = cube_check(t, c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = cube_setup(c, st)) return rc;
+    const int tiles = (c.S + SOFT_TILE - 1) / SOFT_TILE;
+    hipLaunchKernelGGL(k_render_forward<CUBE>, dim3((unsigned)(tiles * tiles), (unsigned)c.B), dim3(256), 0, st,
+                       (const float4 *)c.workspace, rgba, transmittance, normaliser, c.F, c.S, tiles, cube_args(t, c, nullptr));
+    return launch_status();
+}
+
+int cube_backward(const CubeCall &t, const RenderCall &c, const float *rgba, const float *transmittance, const float *normaliser,
+                  const float *grad_rgba, float *grad_faces, float *grad_light, float *grad_textures, void *stream)
+{
+    if (!rgba || !transmittance || !normaliser || !grad_rgba || !grad_faces || !grad_light) return NR_E_NULL;
+    if (int e = cube_check(t, c)) return e;
+    hipStream_t st = (hipStream_t)stream;
+    if (int rc = cube_setup(c, st)) return rc;   // the caller's workspace holds nothing
+    const CubeWorkspace w = cube_workspace(c.B, c.F, t.ts, t.textures_per_batch);
+    const int T3 = t.ts * t.ts * t.ts * 3;
+    float *part_light = c.colors_per_batch ? grad_light : (float *)((char *)c.workspace + w.light_off);
+    float *part_cubes = !grad_textures ? nullptr : (t.textures_per_batch ? grad_textures : (float *)((char *)c.workspace + w.cubes_off));
+    // the cube sums: ts^3 * 3 doubles per wave, four waves
+    hipLaunchKernelGGL(k_render_backward<CUBE>, dim3((unsigned)((c.F + 3) / 4), (unsigned)c.B), dim3(256),
+                       (size_t)4 * T3 * sizeof(double), st, (const float4 *)c.workspace, rgba, transmittance, normaliser,
+                       grad_rgba, grad_faces, part_light, c.F, c.S, cube_args(t, c, part_cubes));
+    if (int rc = launch_status()) return rc;
+    if (!c.colors_per_batch) {
+        const int n = c.F * 3;
+        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part_light, grad_light, c.B, n);
+        if (int rc = launch_status()) return rc;
+    }
+    if (part_cubes && !t.textures_per_batch) {
+        const int n = c.F * T3;
+        hipLaunchKernelGGL(k_render_colors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, part_cubes, grad_textures, c.B, n);
+    }
+    return launch_status();
+}
+
 }  // namespace
+
+NR_API size_t nr_soft_cubes_workspace_bytes(int32_t B, int32_t F, int32_t S, int32_t ts, int32_t textures_per_batch)
+{
+    if (!cube_sizes_ok(B, F, S, ts) || (textures_per_batch != 0 && textures_per_batch != 1)) return 0;
+    return cube_workspace(B, F, ts, textures_per_batch).total;
+}
+
+NR_API int nr_soft_cubes_forward(const float *faces, const float *textures, const float *light, float *rgba, float *transmittance,
+                                 float *normaliser, int32_t B, int32_t F, int32_t S, int32_t ts, int32_t textures_per_batch,
+                                 int32_t light_per_batch, double sigma, double gamma, double near, double far, double eps,
+                                 double background_r, double background_g, double background_b, double texture_eps,
+                                 void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, light, B, F, S, light_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    const CubeCall t = {textures, ts, textures_per_batch, texture_eps};
+    return cube_forward(t, c, rgba, transmittance, normaliser, stream);
+}
+
+NR_API int nr_soft_cubes_backward(const float *faces, const float *textures, const float *light, const float *rgba,
+                                  const float *transmittance, const float *normaliser, const float *grad_rgba, float *grad_faces,
+                                  float *grad_light, float *grad_textures, int32_t B, int32_t F, int32_t S, int32_t ts,
+                                  int32_t textures_per_batch, int32_t light_per_batch, double sigma, double gamma, double near,
+                                  double far, double eps, double background_r, double background_g, double background_b,
+                                  double texture_eps, void *workspace, size_t workspace_bytes, void *stream)
+{
+    const double bg[3] = {background_r, background_g, background_b};
+    const RenderCall c = {faces, light, B, F, S, light_per_batch, sigma, gamma, near, far, eps, bg, workspace, workspace_bytes, 0};
+    const CubeCall t = {textures, ts, textures_per_batch, texture_eps};
+    return cube_backward(t, c, rgba, transmittance, normaliser, grad_rgba, grad_faces, grad_light, grad_textures, stream);
+}
 
 NR_API size_t nr_soft_uv_workspace_bytes(const nr_uv_images *uv, int32_t B, int32_t F, int32_t S)
 {

@@ -19,7 +19,7 @@ from .normals import camera_rotation, corner_normals
 from .perspective import perspective
 from .projection import projection
 from .rasterize import rasterize, rasterize_depth, rasterize_rgbad, rasterize_silhouettes
-from .soft_render import soft_render, soft_render_uv
+from .soft_render import TextureCubes, soft_render, soft_render_cubes, soft_render_uv
 from .soft_silhouette import soft_silhouettes
 from .uv_textures import UVImages
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
@@ -219,7 +219,8 @@ class Renderer(object):
             raise ValueError('render_soft: colors must be a float tensor or a VertexColors')
         if colors.dim() == 6:
             raise ValueError('render_soft: per_pixel=True takes a VertexColors, corner colours [B|1,F,3,3] / [F,3,3] or face '
-                             'colours [B|1,F,3] / [F,3]; texture cubes are not sampled per pixel')
+                             'colours [B|1,F,3] / [F,3]; texture cubes are not sampled per pixel (wrap them in a '
+                             'TextureCubes)')
         shape = tuple(colors.shape)
         if colors.dim() == 4 and shape[1:] == (nf, 3, 3):
             corner = colors
@@ -263,12 +264,35 @@ class Renderer(object):
         from `lights` when set).  A tensor [B,F,3,3] / [1,F,3,3] / [F,3,3] gives the corner colours themselves, a tensor of
         face colours [B,F,3] / [1,F,3] / [F,3] the face colour at all three corners; both are multiplied by the light, per
         face with 'flat', per corner with 'smooth'.  (With exactly three faces a [3,3,3] tensor reads as face colours.)
-        Texture cubes raise ValueError: they are not sampled per pixel.
+        A bare tensor of texture cubes raises ValueError: wrap it in a TextureCubes (below) to have it sampled per pixel.
 
         A UVImages (per_pixel=True only; without it ValueError): its images are sampled at every pixel (soft_render_uv), times
         the per-face light of the face's front copy -- `light_*`, or `lights` when set, as the flat path takes it.  Gradients
         reach the vertices, the images and the camera.  shading = 'smooth' raises ValueError: a light per corner is not done
-        for UV images in the soft renderer."""
+        for UV images in the soft renderer.
+
+        A TextureCubes (per_pixel=True only; without it ValueError): its cubes [B|1,F,ts,ts,ts,3] are sampled at every pixel
+        with the rasterizer's trilinear lookup (soft_render_cubes, texture_eps = `rasterizer_eps`), times the per-face light
+        of the face's front copy, as for a UVImages.  Gradients reach the vertices, the cubes and the camera.  shading =
+        'smooth' raises ValueError."""
+        if isinstance(colors, TextureCubes):
+            if not per_pixel:
+                raise ValueError('render_soft: a TextureCubes is sampled at every pixel: pass per_pixel=True (a bare tensor of '
+                                 'cubes gives the mean of each cube)')
+            if self.shading not in ('flat', 'smooth'):
+                raise ValueError("Renderer.shading must be 'flat' or 'smooth', got %r" % (self.shading,))
+            if self.shading == 'smooth':
+                raise ValueError("render_soft: shading = 'smooth' with a TextureCubes: a light per corner is not done for "
+                                 "texture cubes in the soft renderer (use 'flat')")
+            nf = faces.shape[1]
+            if self.lights is not None:
+                light = light_colors(vertices, faces, self.lights, fill_back=self.fill_back, smooth=False)
+                projected, _ = self._frontend(vertices, faces)
+            else:
+                projected, light = self._frontend(vertices, faces, light_colors=True)
+            return soft_render_cubes(projected[:, :nf], colors.textures, light[:, :nf], self.image_size,
+                                     self.soft_sigma if sigma is None else sigma, self.soft_gamma if gamma is None else gamma,
+                                     self.near, self.far, self.soft_eps, self.background_color, self.rasterizer_eps)
         if isinstance(colors, UVImages):
             if not per_pixel:
                 raise ValueError('render_soft: a UVImages is sampled at every pixel: pass per_pixel=True')

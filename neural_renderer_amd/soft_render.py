@@ -46,9 +46,10 @@ captured (graph.capture) -- but capture before any eager backward on the same le
 as for soft_silhouettes (DESIGN "Soft silhouettes", Stream capture).
 
 UV texture images sampled at the pixel: soft_render_uv below (its docstring has the colour of a pair and its gradient).
+Texture cubes sampled at the pixel: soft_render_cubes below, likewise.
 
-Not done: a light per corner with UV images, texture cubes sampled at the pixel, gradients to faces_uv, a learnable sigma /
-gamma, anti-aliasing, a spatial index.
+Not done: a light per corner with UV images or cubes, fill_back-transposed cubes, cubes larger than 8 in HIP, gradients to
+faces_uv, a learnable sigma / gamma, anti-aliasing, a spatial index.
 """
 import math
 
@@ -391,3 +392,174 @@ def soft_render_uv(faces, uv_images, light=None, image_size=256, sigma=1e-4, gam
     st = layout._tensors(faces.device)
     return soft_render_uv_torch(faces, st['faces_uv'], st['face_image'], st['base'], st['table'],
                                 pack_images(uv_images.images, uv_images.batch), light, S, sigma, gamma, near, far, eps, background)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# texture cubes
+
+CUBE_MIN_TS, CUBE_MAX_TS = 2, 8   # the texture sizes of the HIP kernels (nr_soft_cubes_*)
+
+
+class TextureCubes(object):
+    """Texture cubes [B|1,F,ts,ts,ts,3] (ts >= 2, no fill_back copies) to be SAMPLED AT EVERY PIXEL by the soft renderer:
+    Renderer.render_soft(vertices, faces, TextureCubes(t), per_pixel=True).  A bare 6-dim tensor keeps its meaning there (the
+    mean of each cube); this wrapper only names the tensor, which stays the leaf that receives the gradient."""
+
+    def __init__(self, textures):
+        if not (torch.is_tensor(textures) and textures.is_floating_point() and textures.dim() == 6 and textures.shape[5] == 3
+                and textures.shape[2] == textures.shape[3] == textures.shape[4] and textures.shape[2] >= 2):
+            raise ValueError('TextureCubes: textures must be a float tensor [batch size or 1, num of faces, ts, ts, ts, 3] with '
+                             'ts >= 2, got %s' % (tuple(textures.shape) if torch.is_tensor(textures) else type(textures).__name__,))
+        self.textures = textures
+
+    @property
+    def texture_size(self):
+        return int(self.textures.shape[2])
+
+
+def soft_render_cubes_torch(faces, textures, light=None, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
+                            background_color=(0, 0, 0), texture_eps=1e-3):
+    """rgba [B,4,S,S] in plain torch (any device, any float dtype) with texture cubes sampled at the pixel: faces [B,F,3,3],
+    textures [B|1,F,ts,ts,ts,3], light [B|1,F,3] or None (ones).  soft_render_cubes' definition, differentiable by autograd in
+    faces, textures and light; in chunks of pixel rows."""
+    B, F = int(faces.shape[0]), int(faces.shape[1])
+    dt, dev = faces.dtype, faces.device
+    ts = int(textures.shape[2])
+    T = ts ** 3
+    tex = textures.to(dt).expand(B, F, ts, ts, ts, 3).reshape(B, F, T, 3)
+    lit = (torch.ones((1, F, 3), dtype=dt, device=dev) if light is None else light.to(dt)).expand(B, F, 3)[:, None, None]
+    hi = float(ts - 1) - float(texture_eps)
+    bidx = torch.arange(B, device=dev)[:, None, None, None]
+    fidx = torch.arange(F, device=dev)[None, None, None, :]
+
+    def shade(u0, u1, u2, zp):
+        cell, fr = [], []
+        for u in (u0, u1, u2):   # both clamps with derivative 1; the cell carries no gradient
+            v = (u * zp) * (ts - 1)
+            c = torch.nan_to_num(v.detach(), nan=0.0).clamp(min=0)
+            c = torch.clamp(c.double(), max=hi).to(dt)                         # (the min in double, then rounded)
+            v = v + (c - v).detach()
+            i = c.trunc()
+            cell.append(i.long())
+            fr.append(v - i)
+        total = None
+        for pn in range(8):
+            w, idx = None, []
+            for k in range(3):
+                up = (pn >> k) & 1
+                f_ = fr[k] if up else 1 - fr[k]
+                w = f_ if w is None else w * f_
+                idx.append(cell[k] + up)
+            flat = (idx[0] * ts + idx[1]) * ts + idx[2]
+            inside = flat < T                                                  # a tap outside the cube is skipped
+            texel = tex[bidx, fidx, flat.clamp(max=T - 1)]                     # [B,rows,S,F,3]
+            term = torch.where(inside[..., None], texel * w[..., None], torch.zeros((), dtype=dt, device=dev))
+            total = term if total is None else total + term
+        return [lit[..., c] * total[..., c] for c in range(3)]
+    return _render_torch(faces, shade, 16, image_size, sigma, gamma, near, far, eps, background_color)
+
+
+class _SoftRenderCubes(torch.autograd.Function):
+    """forward(ctx, faces [B,F,3,3], textures [B|1,F,ts,ts,ts,3], light [B|1,F,3], args) -> rgba [B,4,S,S], row 0 the top row:
+    the nr_soft_cubes_* entries."""
+
+    @staticmethod
+    def forward(ctx, faces, textures, light, args):
+        S, sigma, gamma, near, far, eps, background, texture_eps = args
+        f, t, lt = _lib.dense(faces.detach()), _lib.dense(textures.detach()), _lib.dense(light.detach())
+        B, F, ts = int(f.shape[0]), int(f.shape[1]), int(t.shape[2])
+        tex_per_batch = 1 if int(t.shape[0]) == B else 0     # else [1,F,...]: one set for the batch, read in place
+        light_per_batch = 1 if int(lt.shape[0]) == B else 0
+        rgba = torch.empty((B, 4, S, S), dtype=torch.float32, device=f.device)
+        q = torch.empty((B, S, S), dtype=torch.float32, device=f.device)
+        norm = torch.empty((B, 2, S, S), dtype=torch.float32, device=f.device)
+        _lib.launch('nr_soft_cubes_forward', f.device, f.data_ptr(), t.data_ptr(), lt.data_ptr(), rgba.data_ptr(), q.data_ptr(),
+                    norm.data_ptr(), B, F, S, ts, tex_per_batch, light_per_batch, sigma, gamma, near, far, eps, background[0],
+                    background[1], background[2], texture_eps,
+                    workspace_bytes=_lib.workspace_bytes('nr_soft_cubes_workspace_bytes', B, F, S, ts, tex_per_batch))
+        ctx.save_for_backward(f, t, lt, rgba, q, norm)
+        ctx.args, ctx.per_batch = args, (tex_per_batch, light_per_batch)
+        return rgba.flip(2)
+
+    @staticmethod
+    def backward(ctx, grad_rgba):
+        f, t, lt, rgba, q, norm = ctx.saved_tensors
+        S, sigma, gamma, near, far, eps, background, texture_eps = ctx.args
+        tex_per_batch, light_per_batch = ctx.per_batch
+        B, F, ts = int(f.shape[0]), int(f.shape[1]), int(t.shape[2])
+        g = _lib.dense(grad_rgba.flip(2))
+        grad_faces, grad_light = torch.empty_like(f), torch.empty_like(lt)
+        grad_textures = torch.empty_like(t) if ctx.needs_input_grad[1] else None   # (every entry is stored by the kernels)
+        _lib.launch('nr_soft_cubes_backward', f.device, f.data_ptr(), t.data_ptr(), lt.data_ptr(), rgba.data_ptr(), q.data_ptr(),
+                    norm.data_ptr(), g.data_ptr(), grad_faces.data_ptr(), grad_light.data_ptr(), _lib.ptr(grad_textures), B, F, S,
+                    ts, tex_per_batch, light_per_batch, sigma, gamma, near, far, eps, background[0], background[1],
+                    background[2], texture_eps,
+                    workspace_bytes=_lib.workspace_bytes('nr_soft_cubes_workspace_bytes', B, F, S, ts, tex_per_batch))
+        return grad_faces, grad_textures, grad_light, None
+
+
+def soft_render_cubes(faces, textures, light=None, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1, far=100, eps=1e-3,
+                      background_color=(0, 0, 0), texture_eps=1e-3, implementation=None):
+    """rgba [B,4,S,S] (row 0 the top row): faces [B,F,3,3] -- the rasterizer's input, without fill_back copies -- coloured by
+    the rasterizer's texture cubes, textures [B,F,ts,ts,ts,3] or [1,F,ts,ts,ts,3] shared by the batch (ts >= 2, no fill_back
+    copies), sampled at every taken pair with the rasterizer's trilinear lookup at the pair's perspective-correct weights, times
+    one light colour per face, light [B,F,3] or [1,F,3] (None: ones); aggregated by coverage and depth as soft_render does.
+    Everything in the module docstring stands -- u_k, zp, mu_k = u_k zp, m, w_f, Z, Q and alpha -- except the colour of a
+    taken pair:
+
+        C_f(p)_c = L_fc T_f(p)_c.  v_k = mu_k (ts - 1); v_k = max(v_k, 0); v_k = (float)min((double)v_k, (double)(ts - 1) -
+        texture_eps): the rasterizer's sequence with mu_k where it has w_k (zp / z_k).  i_k = (int)v_k, fr_k = v_k - i_k; eight
+        taps pn = 0..7, bit k of pn picks (i_k + 1, fr_k), else (i_k, 1 - fr_k); the weight is the product over k in that
+        order, the flat index (i_0 ts + i_1) ts + i_2 of the picked indices.  A tap whose flat index is >= ts^3 is skipped,
+        never read: its weight is an exact 0, and nothing from outside the cube comes in.  T is the sum from 0 in tap order.
+        Inside a face this is the texture render() shows, outside the texture at the nearest boundary point: continuous
+        across every edge, as the corner colours are.
+        Gradient, exact wherever the definition is differentiable.  The tap indices carry none.  Both clamps are taken with
+        derivative 1, as soft_render_uv takes its clamp: the lower one removes rounding excess only; THE UPPER ONE ACTS ON A
+        SLIVER OF RELATIVE WIDTH texture_eps / (ts - 1) AT A VERTEX, WHERE THE GRADIENT IS THE UNCLAMPED DERIVATIVE; where an
+        outside pair's nearest point is a vertex, mu = (1, 0, 0) and every term that would differ is multiplied by an exact
+        0.  Per taken pair dL/dtex[f][tap_pn]_c += W g_c L_c w_pn, dL/dL_fc += W g_c T_f(p)_c, and with D_kc = sum_pn
+        (dw_pn / dfr_k) tex[tap_pn]_c and G_k = (ts - 1) sum_c g_c L_c D_kc, E_k = W zp (G_k - sum_j mu_j G_j) stands where the
+        corner colours' E_k stands (module docstring).
+
+    texture_eps (the rasterizer's `eps`; a finite host number with 0 <= texture_eps < 1) is not `eps`, which places the
+    background in the depth order.  Differentiable, once, in faces (x, y and z), textures and light.  On float32 CUDA tensors
+    inside the ranges of include/nr_hip.h and with 2 <= ts <= 8 both directions are HIP kernels (nr_soft_cubes_*): every
+    gradient, the cubes' included, is summed in a fixed order without atomics and repeats bit for bit, for an image alone or
+    inside a batch.  Everything else (`implementation='torch'`, a larger ts, sigma or gamma outside [1e-30, 1e30]) is
+    soft_render_cubes_torch.  No host tables: a call may be captured (graph.capture) -- but capture before any eager backward on
+    the same leaves, or make the eager calls under no_grad, as for soft_silhouettes (DESIGN "Soft silhouettes", Stream
+    capture).  Not done: a light per corner, fill_back-transposed cubes, cubes larger than 8 in HIP.  The other arguments are
+    soft_render's."""
+    name = 'soft_render_cubes'
+    B, F = _util.soft_check_faces(name, faces)
+    if isinstance(textures, TextureCubes):
+        textures = textures.textures
+    if not (torch.is_tensor(textures) and textures.is_floating_point() and textures.dim() == 6 and textures.shape[5] == 3
+            and textures.shape[2] == textures.shape[3] == textures.shape[4] and textures.shape[2] >= 2
+            and textures.shape[1] == F and textures.shape[0] in (1, B)):
+        raise ValueError('%s: textures must be a float tensor [batch size or 1, num of faces (%d), ts, ts, ts, 3] with ts >= 2 '
+                         '(the soft renderer takes no fill_back copies), got %s'
+                         % (name, F, tuple(textures.shape) if torch.is_tensor(textures) else type(textures).__name__))
+    if textures.device != faces.device:
+        raise ValueError('%s: textures on %s, faces on %s' % (name, textures.device, faces.device))
+    texture_eps = _util.number(name, 'texture_eps', texture_eps)
+    if not (0 <= texture_eps < 1):
+        raise ValueError('%s: texture_eps must be a finite number with 0 <= texture_eps < 1, got %r' % (name, texture_eps))
+    if light is None:
+        light = torch.ones((1, F, 3), dtype=faces.dtype, device=faces.device)
+    ts = int(textures.shape[2])
+    fits = textures.dtype == faces.dtype and CUBE_MIN_TS <= ts <= CUBE_MAX_TS and F * ts ** 3 * 3 < 2 ** 31 - 256
+    S, sigma, gamma, near, far, eps, background, hip = _check(name, faces, light, image_size, sigma, gamma, near, far, eps,
+                                                              background_color, implementation if fits else
+                                                              _cubes_do_not_fit(name, implementation), light=True)
+    if hip and fits:
+        return _SoftRenderCubes.apply(faces, textures, light, (S, sigma, gamma, near, far, eps, background, texture_eps))
+    return soft_render_cubes_torch(faces, textures, light, S, sigma, gamma, near, far, eps, background, texture_eps)
+
+
+def _cubes_do_not_fit(name, implementation):
+    """takes_hip's sentence for cubes outside the HIP kernels' range -> 'torch' for every implementation that may take it."""
+    _util.takes_hip(name, implementation, False, 'the HIP kernels take float32 CUDA cubes of the faces\' dtype with a texture size '
+                    'from %d to %d (larger cubes run in torch) and num of faces * ts^3 * 3 < 2^31 - 256' % (CUBE_MIN_TS, CUBE_MAX_TS))
+    return 'torch'
