@@ -92,7 +92,9 @@ extern "C" {
                           *        nr_soft_render_forward, nr_soft_render_backward, nr_soft_render_workspace_bytes;
                           *        nr_soft_corners_forward, nr_soft_corners_backward, nr_soft_corners_workspace_bytes;
                           *        nr_soft_uv_forward, nr_soft_uv_backward, nr_soft_uv_workspace_bytes;
-                          *        nr_soft_cubes_forward, nr_soft_cubes_backward, nr_soft_cubes_workspace_bytes);
+                          *        nr_soft_cubes_forward, nr_soft_cubes_backward, nr_soft_cubes_workspace_bytes;
+                          *        nr_point_mesh_points_to_faces, nr_point_mesh_faces_to_points, nr_point_mesh_loss,
+                          *        nr_point_mesh_backward_points, nr_point_mesh_backward_vertices, nr_point_mesh_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -1042,6 +1044,62 @@ int nr_flatness_forward(const float *vertices, const int32_t *quads, float *loss
 int nr_flatness_backward(const float *vertices, const int32_t *quads, const int32_t *inc_offsets, const int32_t *inc,
                          const float *grad_loss, float *grad_vertices, int32_t batch_size, int32_t num_vertices,
                          int32_t num_quads, double eps, void *stream);
+
+/*
+ * Point-to-mesh distance (not in the reference's library; DESIGN "Point-to-mesh distance"): points [B, N, 3] -- or ONE cloud
+ * [N, 3] for the batch with points_per_batch = 0 --, world-space vertices [B, Nv, 3] and ONE topology faces [F, 3] int32.
+ *   nr_point_mesh_points_to_faces: per point the nearest face by a brute-force sweep: dist2 [B, N], face_ids [B, N] int32 (the
+ *     lowest face number among the minimal computed distances), barycentric [B, N, 3] (w0, w1, w2 of the closest point).
+ *   nr_point_mesh_faces_to_points: per face the nearest point: dist2 [B, F], point_ids [B, F] int32 (the lowest point number
+ *     on a tie), barycentric [B, F, 3] of the point of the face nearest to that cloud point.
+ *   The closest point of a triangle: csrc/nr_point_triangle.h, one definition for both (the same bits for the same pair),
+ *   exact on faces without area.  A NaN distance never wins; ids are always in range; a row of NaN pairs reports id 0 and a
+ *   non-finite dist2.  split: 0 lets the call decide whether to cut the streamed side (faces resp. points) over several
+ *   workgroups, n >= 1 asks for n parts (1: none); the result does not depend on it.  The workspace holds the parts' minima:
+ *   nr_point_mesh_workspace_bytes(B, N, F, faces_to_points, split), 0 when the call is not split (workspace may then be NULL).
+ *   nr_point_mesh_loss: loss[b] = weight_points * sum_i dist2_points[b, i] + weight_faces * sum_f dist2_faces[b, f], either
+ *     array may be NULL (its term is left out; both: NR_E_MODE); the sums in double in a fixed order, rounded once.
+ *   Backward, from per-pair upstream gradients grad_dist2_points [B, N] and grad_dist2_faces [B, F]; the pairs of one
+ *   direction are left out by passing its ids as NULL (both: NR_E_MODE).  r = ((p - v0) - w1 (v1 - v0)) - w2 (v2 - v0).
+ *   nr_point_mesh_backward_points (points [B, N, 3]): grad_points[b, i] = 2 g r of its own pair, then 2 g r of the faces that
+ *     chose point i, in the order of order_faces [B, F] (face numbers sorted by point id, stable) between
+ *     offsets_points[b, i] and offsets_points[b, i + 1] ([B, N + 1]).
+ *   nr_point_mesh_backward_vertices: grad_vertices[b, v] = 0, then for each entry (f, k) of v in the vertex -> (face, corner)
+ *     table (adj_offsets [Nv + 1], adj_entries [3 F]: 3 f + k ascending) minus (2 g w_k) r of face f's own pair, then of the
+ *     points that chose f, in the order of order_points [B, N] (point numbers sorted by face id, stable) between
+ *     offsets_faces[b, f] and offsets_faces[b, f + 1] ([B, F + 1]).
+ * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * same bits in every run and for an image alone or inside a batch.  Every output element is stored exactly once; no call
+ * synchronises the host; NR_E_* before any launch (NULL before sizes).
+ */
+size_t nr_point_mesh_workspace_bytes(int32_t batch_size, int32_t num_points, int32_t num_faces, int32_t faces_to_points,
+                                     int32_t split);
+
+int nr_point_mesh_points_to_faces(const float *points, const float *vertices, const int32_t *faces, float *dist2,
+                                  int32_t *face_ids, float *barycentric, int32_t batch_size, int32_t num_points,
+                                  int32_t num_vertices, int32_t num_faces, int32_t points_per_batch, int32_t split,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_point_mesh_faces_to_points(const float *points, const float *vertices, const int32_t *faces, float *dist2,
+                                  int32_t *point_ids, float *barycentric, int32_t batch_size, int32_t num_points,
+                                  int32_t num_vertices, int32_t num_faces, int32_t points_per_batch, int32_t split,
+                                  void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_point_mesh_loss(const float *dist2_points, const float *dist2_faces, float *loss, int32_t batch_size, int32_t num_points,
+                       int32_t num_faces, double weight_points, double weight_faces, void *stream);
+
+int nr_point_mesh_backward_points(const float *points, const float *vertices, const int32_t *faces, const int32_t *face_ids,
+                                  const float *barycentric_points, const float *grad_dist2_points, const int32_t *point_ids,
+                                  const float *barycentric_faces, const float *grad_dist2_faces, const int32_t *order_faces,
+                                  const int32_t *offsets_points, float *grad_points, int32_t batch_size, int32_t num_points,
+                                  int32_t num_vertices, int32_t num_faces, void *stream);
+
+int nr_point_mesh_backward_vertices(const float *points, const float *vertices, const int32_t *faces, const int32_t *adj_offsets,
+                                    const int32_t *adj_entries, const int32_t *face_ids, const float *barycentric_points,
+                                    const float *grad_dist2_points, const int32_t *order_points, const int32_t *offsets_faces,
+                                    const int32_t *point_ids, const float *barycentric_faces, const float *grad_dist2_faces,
+                                    float *grad_vertices, int32_t batch_size, int32_t num_points, int32_t num_vertices,
+                                    int32_t num_faces, int32_t points_per_batch, void *stream);
 
 /*
  * Image losses (not in the reference; DESIGN "Image losses"): the objective of a fit on images, one loss per image, on an

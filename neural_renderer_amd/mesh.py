@@ -49,6 +49,12 @@ class Mesh(nn.Module):
         from .point_losses import sample_surface_points
         return sample_surface_points(self.vertices, self.faces, num_samples, generator)
 
+    def point_mesh_distance(self, points, **kw):
+        """point_mesh.point_mesh_distance of `points` and the module's own vertices and faces (not in the reference);
+        direction, reduction and implementation as keywords."""
+        from .point_mesh import point_mesh_distance
+        return point_mesh_distance(points, self.vertices, self.faces, **kw)
+
     def vertex_normals(self, implementation=None):
         """normals.vertex_normals of the module's own vertices and faces (not in the reference): [num_vertices, 3]."""
         from .normals import vertex_normals
