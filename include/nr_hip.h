@@ -80,6 +80,7 @@ extern "C" {
                           *        NR_FLAG_SHARED_TEXTURES, nr_backward_textures_shared[_workspace_bytes];
                           *        nr_laplacian_forward, nr_laplacian_backward, nr_flatness_forward, nr_flatness_backward,
                           *        nr_mesh_loss_workspace_bytes;
+                          *        nr_edge_length_forward, nr_edge_length_backward, nr_cot_weights, nr_cot_apply;
                           *        nr_lights, nr_lights_grad, nr_light_colors_forward, nr_light_colors_backward,
                           *        nr_light_colors_workspace_bytes;
                           *        nr_iou_loss_forward, nr_iou_loss_backward, nr_squared_error_forward, nr_squared_error_backward,
@@ -1044,6 +1045,44 @@ int nr_flatness_forward(const float *vertices, const int32_t *quads, float *loss
 int nr_flatness_backward(const float *vertices, const int32_t *quads, const int32_t *inc_offsets, const int32_t *inc,
                          const float *grad_loss, float *grad_vertices, int32_t batch_size, int32_t num_vertices,
                          int32_t num_quads, double eps, void *stream);
+
+/*
+ * Edge-length and cotangent Laplacian losses (DESIGN "Mesh losses: edge length and cotangent Laplacian"), on the same vertices,
+ * tables, block sums and workspace query as the two above.
+ *   edges [E, 2]: the distinct undirected pairs (v0 < v1) that share a face -- the pairs of nbr --, ordered by (v0, v1);
+ *   nbr_edge [num_nbr]: the edge number of every entry of nbr.
+ * Edge length: l_e = |x_v1 - x_v0|, loss[b] = sum_e (l_e - t_e)^2.  The target t: `target` [E] (target_per_batch = 0) or [B, E]
+ *   (1), read in place; or, with target NULL, the number target_value >= 0 for every edge, and then target_value = 0 skips the
+ *   square root: loss[b] = sum_e |e|^2.  Workspace: nr_mesh_loss_workspace_bytes(B, E).  E = 0: loss = 0 (edges may be NULL).
+ *   Backward: grad_vertices[b, v] = 2 g_b sum over u in N(v), table order, of ((l - t) / l) (x_v - x_u), every edge recomputed
+ *   from its two vertices and its target read through nbr_edge (which may be NULL with target NULL); a term with l = 0 is
+ *   exactly 0.
+ * Cotangent Laplacian: nr_cot_weights writes cot [B, F, 3] for faces [F, 3]: cot_c = (a . b) / sqrt(|a x b|^2 + eps) with
+ *   a = x_(c+1) - x_c, b = x_(c+2) - x_c (corners mod 3; eps rounded to float); a face with a repeated index stores three zeros.
+ *   nr_cot_apply applies L to field [B, Nv, 3] through the vertex -> (face, corner) table adj_offsets [Nv + 1], adj_entries
+ *   [3 F] (ascending 3 f + c within a vertex; ONE topology):
+ *     L(phi)_v = 1/2 sum over the entries (f, c) of v of cot[f, c+2] (phi_(c+1) - phi_v) + cot[f, c+1] (phi_(c+2) - phi_v),
+ *   out[b, v] = L(field)_v, times 2 scale[b] with scale [B] not NULL; with loss not NULL loss[b] = sum_v |out[b, v]|^2
+ *   (workspace nr_mesh_loss_workspace_bytes(B, Nv); otherwise the workspace is not read) and out may be NULL.
+ *   The loss's forward is L applied to the vertices; its backward, the weights being constants of the step and L symmetric,
+ *   is L applied to the stored H with scale = grad_loss.
+ * No atomics, every output element stored, no host synchronisation, NR_E_* before any launch, as above.
+ */
+int nr_edge_length_forward(const float *vertices, const int32_t *edges, const float *target, float *loss, int32_t batch_size,
+                           int32_t num_vertices, int32_t num_edges, int32_t target_per_batch, double target_value,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_edge_length_backward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *nbr_edge,
+                            const float *target, const float *grad_loss, float *grad_vertices, int32_t batch_size,
+                            int32_t num_vertices, int32_t num_nbr, int32_t num_edges, int32_t target_per_batch,
+                            double target_value, void *stream);
+
+int nr_cot_weights(const float *vertices, const int32_t *faces, float *cot, int32_t batch_size, int32_t num_vertices,
+                   int32_t num_faces, double eps, void *stream);
+
+int nr_cot_apply(const float *field, const float *cot, const int32_t *faces, const int32_t *adj_offsets,
+                 const int32_t *adj_entries, const float *scale, float *out, float *loss, int32_t batch_size,
+                 int32_t num_vertices, int32_t num_faces, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Point-to-mesh distance (not in the reference's library; DESIGN "Point-to-mesh distance"): points [B, N, 3] -- or ONE cloud

@@ -25,6 +25,8 @@ from .uv_textures import UVImages, UVLayout, UVTextures, bake_uv_textures
 from .vertex_colors import CornerColors, VertexColors, vertex_light, vertex_shade
 # not in the reference: the Laplacian and flatness losses of a mesh fit (shape priors), HIP in both directions
 from .mesh_losses import flatness_loss, laplacian_loss
+# ... and the edge-length and the cotangent Laplacian loss, with the edges of a topology and their lengths
+from .mesh_losses import cotangent_laplacian_loss, edge_length_loss, edge_lengths, mesh_edges
 # not in the reference: the light as tensors -- per image, learnable, with spherical-harmonics coefficients -- HIP in both directions
 from .lights import Lights, light_colors
 # not in the reference: the objective of a fit on images -- silhouette IoU and masked squared error, optionally on an image
@@ -67,7 +69,7 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'TextureCubes', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
-           'laplacian_loss', 'flatness_loss', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
+           'laplacian_loss', 'flatness_loss', 'edge_length_loss', 'cotangent_laplacian_loss', 'mesh_edges', 'edge_lengths', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
            'closest_surface_points', 'closest_cloud_points', 'point_mesh_distance',

@@ -125,6 +125,10 @@ SIGNATURES = {
     'nr_laplacian_backward': (_c.c_int, [_vp] * 5 + [_i32] * 3 + [_vp]),
     'nr_flatness_forward': (_c.c_int, [_vp] * 3 + [_i32] * 3 + [_f64, _vp, _sz, _vp]),
     'nr_flatness_backward': (_c.c_int, [_vp] * 6 + [_i32] * 3 + [_f64, _vp]),
+    'nr_edge_length_forward': (_c.c_int, [_vp] * 4 + [_i32] * 4 + [_f64, _vp, _sz, _vp]),
+    'nr_edge_length_backward': (_c.c_int, [_vp] * 7 + [_i32] * 5 + [_f64, _vp]),
+    'nr_cot_weights': (_c.c_int, [_vp] * 3 + [_i32] * 3 + [_f64, _vp]),
+    'nr_cot_apply': (_c.c_int, [_vp] * 8 + [_i32] * 3 + [_vp, _sz, _vp]),
     'nr_point_mesh_workspace_bytes': (_sz, [_i32] * 5),
     'nr_point_mesh_points_to_faces': (_c.c_int, [_vp] * 6 + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_point_mesh_faces_to_points': (_c.c_int, [_vp] * 6 + [_i32] * 6 + [_vp, _sz, _vp]),

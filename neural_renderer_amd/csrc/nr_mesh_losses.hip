@@ -25,6 +25,26 @@
 //       ga = ((((-t1) gc1 - t2 gc2) + gab1 b1) + gab2 b2) + (2 gA) a;   gb_i = gc_i + gab_i a;
 //       slots: x1 <- ga, x2 <- gb1, x3 <- gb2, x0 <- -((ga + gb1) + gb2).
 //     A vertex's gradient: 0, then += its slot's share of each incident quad in table order (ascending 4 q + slot).
+//
+// The edge-length loss and the cotangent Laplacian loss (DESIGN "Mesh losses: edge length and cotangent Laplacian"), on the same
+// block sums and k_loss_finish:
+//   k_edge_length_forward  (image, edge): (l - t)^2 summed per block in double
+//   k_edge_length_backward (image, vertex): the gather over N(v); every edge recomputed from its two vertices, its target read
+//                          through nbr_edge -- no per-edge gradient buffer
+//   k_cot_weights          (image, face): the three cotangents of a face, cot [B, F, 3]
+//   k_cot_apply            (image, vertex): L applied to a field [B, Nv, 3] through the vertex -> (face, corner) table with the
+//                          stored weights; the forward's field is x (|H|^2 summed per block in double), the backward's is H
+//   Edge length, per edge (v0 < v1) with target t:  d = x_v1 - x_v0;  n = dot(d, d);
+//     no target tensor and t = 0: the image's loss adds (double)n;  else l = sqrt(n); r = l - t; the loss adds (double)r r.
+//     Backward, vertex v: s = 0; for u in N(v) in table order: d = x_v - x_u; n = dot(d, d);
+//       t = 0: s += d;  else l = sqrt(n); k = l > 0 ? (l - t) / l : 0; s += k d;     grad = (2 g_b) s.
+//   Cotangents of face (i0, i1, i2) at corner c, eps rounded to float once:  a = x_(c+1) - x_c;  b = x_(c+2) - x_c;
+//     n = (a1 b2 - a2 b1, a2 b0 - a0 b2, a0 b1 - a1 b0);  cot_c = dot(a, b) / sqrt(dot(n, n) + eps);  a face with a repeated
+//     index stores three zeros.
+//   L(phi)_v: h = 0; for each (face, corner c) entry of v in table order (ascending 3 f + c), w = cot of that face:
+//       p = phi_(c+1) - phi_v;  q = phi_(c+2) - phi_v;  h += w_(c+2) p + w_(c+1) q  (per component);
+//     out = 0.5 h, or (0.5 h) (2 s_b) with a scale s.  Forward: H = L(x), the loss adds (double)H0 H0 + (double)H1 H1 +
+//     (double)H2 H2 per vertex.  Backward: grad = L(H) with s = g: the weights are constants of the step, L is symmetric.
 #include "nr_device.h"
 
 using namespace nr;
@@ -301,6 +321,154 @@ float *quad_buffer(size_t bytes)
 #endif
 
 // --------------------------------------------------------------------------------------------------------------------
+// edge length
+
+// the target of edge e of image b: the tensor's entry ([E], or [B, E] with per_batch), or the call's number
+__device__ __forceinline__ float edge_target(const float *__restrict__ target, int per_batch, float value, int b, int e, int E)
+{
+    return target ? target[(per_batch ? (size_t)b * E : (size_t)0) + e] : value;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_edge_length_forward(const float *__restrict__ x, const int32_t *__restrict__ edges,
+                                                               const float *__restrict__ target, double *__restrict__ partial,
+                                                               int Nv, int E, int per_batch, float value)
+{
+    const int e = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    double term = 0.0;
+    if (e < E) {
+        const float *xb = x + (size_t)b * Nv * 3;
+        const float *x0 = xb + (size_t)clampi(edges[2 * (size_t)e], 0, Nv - 1) * 3;
+        const float *x1 = xb + (size_t)clampi(edges[2 * (size_t)e + 1], 0, Nv - 1) * 3;
+        const float d[3] = {x1[0] - x0[0], x1[1] - x0[1], x1[2] - x0[2]};
+        const float n = dot3f(d, d);
+        if (!target && value == 0.0f) {
+            term = (double)n;
+        } else {
+            const float r = sqrtf(n) - edge_target(target, per_batch, value, b, e, E);
+            term = (double)r * (double)r;
+        }
+    }
+    block_sum_store(term, partial + (size_t)b * gridDim.x + blockIdx.x);
+}
+
+__global__ __launch_bounds__(BLOCK) void k_edge_length_backward(const float *__restrict__ x, const int32_t *__restrict__ off,
+                                                                const int32_t *__restrict__ nbr,
+                                                                const int32_t *__restrict__ nbr_edge,
+                                                                const float *__restrict__ target,
+                                                                const float *__restrict__ grad_loss,
+                                                                float *__restrict__ grad_vertices, int Nv, int total, int E,
+                                                                int per_batch, float value)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (v >= Nv) return;
+    const float *xb = x + (size_t)b * Nv * 3;
+    const float *xv = xb + (size_t)v * 3;
+    const bool squared = !target && value == 0.0f;
+    int e0, e1;
+    nbr_range(off, v, total, e0, e1);
+    float s[3] = {0.0f, 0.0f, 0.0f};
+    for (int e = e0; e < e1; e++) {
+        const float *xu = xb + (size_t)clampi(nbr[e], 0, Nv - 1) * 3;
+        const float d[3] = {xv[0] - xu[0], xv[1] - xu[1], xv[2] - xu[2]};
+        if (squared) {
+            s[0] += d[0];
+            s[1] += d[1];
+            s[2] += d[2];
+        } else {
+            const float l = sqrtf(dot3f(d, d));
+            const float t = edge_target(target, per_batch, value, b, target ? clampi(nbr_edge[e], 0, E - 1) : 0, E);
+            const float k = l > 0.0f ? (l - t) / l : 0.0f;
+            s[0] += k * d[0];
+            s[1] += k * d[1];
+            s[2] += k * d[2];
+        }
+    }
+    const float g2 = 2.0f * grad_loss[b];
+    float *o = grad_vertices + ((size_t)b * Nv + v) * 3;
+    o[0] = g2 * s[0];
+    o[1] = g2 * s[1];
+    o[2] = g2 * s[2];
+}
+
+// --------------------------------------------------------------------------------------------------------------------
+// cotangent Laplacian
+
+__global__ __launch_bounds__(BLOCK) void k_cot_weights(const float *__restrict__ x, const int32_t *__restrict__ faces,
+                                                       float *__restrict__ cot, int Nv, int F, float eps)
+{
+    const int f = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    if (f >= F) return;
+    const float *xb = x + (size_t)b * Nv * 3;
+    const int32_t *fi = faces + (size_t)f * 3;
+    const int i[3] = {clampi(fi[0], 0, Nv - 1), clampi(fi[1], 0, Nv - 1), clampi(fi[2], 0, Nv - 1)};
+    float w[3] = {0.0f, 0.0f, 0.0f};
+    if (i[0] != i[1] && i[1] != i[2] && i[0] != i[2]) {
+        float p[3][3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const float *src = xb + (size_t)i[k] * 3;
+            p[k][0] = src[0];
+            p[k][1] = src[1];
+            p[k][2] = src[2];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+            const float a[3] = {p[c1][0] - p[c][0], p[c1][1] - p[c][1], p[c1][2] - p[c][2]};
+            const float q[3] = {p[c2][0] - p[c][0], p[c2][1] - p[c][1], p[c2][2] - p[c][2]};
+            const float n[3] = {a[1] * q[2] - a[2] * q[1], a[2] * q[0] - a[0] * q[2], a[0] * q[1] - a[1] * q[0]};
+            w[c] = dot3f(a, q) / sqrtf(dot3f(n, n) + eps);
+        }
+    }
+    float *o = cot + ((size_t)b * F + f) * 3;
+    o[0] = w[0];
+    o[1] = w[1];
+    o[2] = w[2];
+}
+
+// out[b, v] = L(field)_v (times 2 scale[b] with a scale; out may be NULL); with `partial`, |L(field)_v|^2 goes into the block's
+// sum, and every thread of the block stays to the end
+__global__ __launch_bounds__(BLOCK) void k_cot_apply(const float *__restrict__ field, const float *__restrict__ cot,
+                                                     const int32_t *__restrict__ faces, const int32_t *__restrict__ adj_off,
+                                                     const int32_t *__restrict__ adj_ent, const float *__restrict__ scale,
+                                                     float *__restrict__ out, double *__restrict__ partial, int Nv, int F)
+{
+    const int v = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
+    double sq = 0.0;
+    if (v < Nv) {
+        const float *pb = field + (size_t)b * Nv * 3;
+        const float *wb = cot + (size_t)b * F * 3;
+        const float *pv = pb + (size_t)v * 3;
+        const int total = 3 * F;
+        const int e0 = clampi(adj_off[v], 0, total), e1 = clampi(adj_off[v + 1], e0, total);
+        float h[3] = {0.0f, 0.0f, 0.0f};
+        for (int e = e0; e < e1; e++) {
+            const int fc = clampi(adj_ent[e], 0, total - 1), f = fc / 3, c = fc - 3 * f;
+            const int c1 = c == 2 ? 0 : c + 1, c2 = c == 0 ? 2 : c - 1;
+            const int32_t *fi = faces + (size_t)f * 3;
+            const float *p1 = pb + (size_t)clampi(fi[c1], 0, Nv - 1) * 3, *p2 = pb + (size_t)clampi(fi[c2], 0, Nv - 1) * 3;
+            const float w1 = wb[(size_t)f * 3 + c1], w2 = wb[(size_t)f * 3 + c2];
+#pragma unroll
+            for (int k = 0; k < 3; k++) h[k] += w2 * (p1[k] - pv[k]) + w1 * (p2[k] - pv[k]);
+        }
+        float H[3] = {0.5f * h[0], 0.5f * h[1], 0.5f * h[2]};
+        if (scale) {
+            const float s2 = 2.0f * scale[b];
+#pragma unroll
+            for (int k = 0; k < 3; k++) H[k] *= s2;
+        }
+        if (out) {
+            float *o = out + ((size_t)b * Nv + v) * 3;
+            o[0] = H[0];
+            o[1] = H[1];
+            o[2] = H[2];
+        }
+        sq = ((double)H[0] * (double)H[0] + (double)H[1] * (double)H[1]) + (double)H[2] * (double)H[2];
+    }
+    if (partial) block_sum_store(sq, partial + (size_t)b * gridDim.x + blockIdx.x);
+}
+
+// --------------------------------------------------------------------------------------------------------------------
 // host
 
 inline int n_blocks_of(int n) { return (n + BLOCK - 1) / BLOCK; }
@@ -395,4 +563,66 @@ NR_API int nr_flatness_backward(const float *vertices, const int32_t *quads, con
     hipLaunchKernelGGL(k_flatness_backward, dim3((unsigned)n_blocks_of(Nv), (unsigned)B), dim3(BLOCK), 0, (hipStream_t)stream,
                        vertices, quads, inc_offsets, inc, grad_loss, grad_vertices, Nv, E2, (float)eps);
     return launch_status();
+}
+
+NR_API int nr_edge_length_forward(const float *vertices, const int32_t *edges, const float *target, float *loss, int32_t B,
+                                  int32_t Nv, int32_t E, int32_t target_per_batch, double target_value, void *workspace,
+                                  size_t workspace_bytes, void *stream)
+{
+    if (!vertices || !loss || (E > 0 && !edges)) return NR_E_NULL;
+    if (int e = loss_sizes(B, Nv, E)) return e;
+    if ((size_t)B * (size_t)E > 0x7fffffffull || !(target_value >= 0.0) || target_value > 3.0e38) return NR_E_SIZE;
+    if (!workspace || workspace_bytes < partial_bytes(B, E)) return NR_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    double *partial = (double *)workspace;
+    const int nb = n_blocks_of(E);
+    if (nb > 0) {
+        hipLaunchKernelGGL(k_edge_length_forward, dim3((unsigned)nb, (unsigned)B), dim3(BLOCK), 0, st, vertices, edges, target,
+                           partial, Nv, E, target_per_batch != 0, (float)target_value);
+        if (int rc = launch_status()) return rc;
+    }
+    return finish(partial, loss, B, nb, st);
+}
+
+NR_API int nr_edge_length_backward(const float *vertices, const int32_t *nbr_offsets, const int32_t *nbr, const int32_t *nbr_edge,
+                                   const float *target, const float *grad_loss, float *grad_vertices, int32_t B, int32_t Nv,
+                                   int32_t num_nbr, int32_t E, int32_t target_per_batch, double target_value, void *stream)
+{
+    if (!vertices || !nbr_offsets || !grad_loss || !grad_vertices || (num_nbr > 0 && !nbr)) return NR_E_NULL;
+    if (target && num_nbr > 0 && !nbr_edge) return NR_E_NULL;
+    if (int e = loss_sizes(B, Nv, E)) return e;
+    if (num_nbr < 0 || (size_t)B * (size_t)E > 0x7fffffffull || !(target_value >= 0.0) || target_value > 3.0e38) return NR_E_SIZE;
+    if (target && num_nbr > 0 && E < 1) return NR_E_SIZE;
+    hipLaunchKernelGGL(k_edge_length_backward, dim3((unsigned)n_blocks_of(Nv), (unsigned)B), dim3(BLOCK), 0, (hipStream_t)stream,
+                       vertices, nbr_offsets, nbr, nbr_edge, target, grad_loss, grad_vertices, Nv, num_nbr, E,
+                       target_per_batch != 0, (float)target_value);
+    return launch_status();
+}
+
+NR_API int nr_cot_weights(const float *vertices, const int32_t *faces, float *cot, int32_t B, int32_t Nv, int32_t F, double eps,
+                          void *stream)
+{
+    if (!vertices || !faces || !cot) return NR_E_NULL;
+    if (int e = loss_sizes(B, Nv, F)) return e;
+    if (F < 1 || (size_t)B * (size_t)F > 0x7fffffffull / 3) return NR_E_SIZE;
+    hipLaunchKernelGGL(k_cot_weights, dim3((unsigned)n_blocks_of(F), (unsigned)B), dim3(BLOCK), 0, (hipStream_t)stream, vertices,
+                       faces, cot, Nv, F, (float)eps);
+    return launch_status();
+}
+
+NR_API int nr_cot_apply(const float *field, const float *cot, const int32_t *faces, const int32_t *adj_offsets,
+                        const int32_t *adj_entries, const float *scale, float *out, float *loss, int32_t B, int32_t Nv, int32_t F,
+                        void *workspace, size_t workspace_bytes, void *stream)
+{
+    if (!field || !cot || !faces || !adj_offsets || !adj_entries || (!out && !loss)) return NR_E_NULL;
+    if (int e = loss_sizes(B, Nv, F)) return e;
+    if (F < 1 || (size_t)B * (size_t)F > 0x7fffffffull / 3) return NR_E_SIZE;
+    if (loss && (!workspace || workspace_bytes < partial_bytes(B, Nv))) return NR_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    double *partial = loss ? (double *)workspace : nullptr;
+    const int nb = n_blocks_of(Nv);
+    hipLaunchKernelGGL(k_cot_apply, dim3((unsigned)nb, (unsigned)B), dim3(BLOCK), 0, st, field, cot, faces, adj_offsets,
+                       adj_entries, scale, out, partial, Nv, F);
+    if (int rc = launch_status()) return rc;
+    return loss ? finish(partial, loss, B, nb, st) : 0;
 }

@@ -43,6 +43,16 @@ class Mesh(nn.Module):
         from .mesh_losses import flatness_loss
         return flatness_loss(self.vertices, self.faces, eps, implementation)
 
+    def edge_length_loss(self, target=0.0, implementation=None):
+        """mesh_losses.edge_length_loss of the module's own vertices and faces (not in the reference): a 0-dim tensor."""
+        from .mesh_losses import edge_length_loss
+        return edge_length_loss(self.vertices, self.faces, target, implementation)
+
+    def cotangent_laplacian_loss(self, eps=1e-12, implementation=None):
+        """mesh_losses.cotangent_laplacian_loss of the module's own vertices and faces (not in the reference): a 0-dim tensor."""
+        from .mesh_losses import cotangent_laplacian_loss
+        return cotangent_laplacian_loss(self.vertices, self.faces, eps, implementation)
+
     def sample_points(self, num_samples, generator=None):
         """point_losses.sample_surface_points of the module's own vertices and faces (not in the reference): (points
         [num_samples, 3], differentiable in self.vertices, and their SurfaceSamples)."""

@@ -24,7 +24,12 @@ second yardstick in the tests.
 
 The tables are built on the host in vectorised NumPy the first time a topology is seen and cached on the index tensor, as
 vertex_colors._adjacency caches its table: the build reads the indices back, so it must happen BEFORE a graph capture --
-run one eager step with the same index tensor first (inside a capture an unknown topology raises)."""
+run one eager step with the same index tensor first (inside a capture an unknown topology raises).
+
+`edge_length_loss(vertices, faces, target)` and `cotangent_laplacian_loss(vertices, faces, eps)`, the priors of a 3-D fit --
+every edge near its rest length; the cotangent-weighted Laplacian, which penalises bending and not an irregular triangulation,
+with its weights held constant in the gradient --, and `mesh_edges` / `edge_lengths` are defined in the second half of this
+file, with the same shapes, batching, dispatch and discipline (nr_edge_length_* / nr_cot_*)."""
 import numpy as np
 import torch
 
@@ -257,4 +262,304 @@ def flatness_loss(vertices, faces, eps=1e-6, implementation=None):
     laplacian_loss."""
     vertices, squeeze, t, hip = _prepare('flatness_loss', vertices, faces, implementation)
     loss = _FlatnessLoss.apply(vertices, t, float(eps)) if hip else _flatness_torch(vertices, t, float(eps))
+    return loss[0] if squeeze else loss
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# edge length and cotangent Laplacian (DESIGN "Mesh losses: edge length and cotangent Laplacian")
+#
+# Edges: the distinct undirected pairs {v0 < v1} that share a face -- exactly the pairs of the neighbour CSR above, so an edge
+# in one, two or three faces or in a duplicated face counts once and a repeated index inside a face adds nothing --, ordered by
+# (v0, v1); E their number.
+#     l_e = sqrt(|x_v1 - x_v0|^2),    edge length loss_b = sum_e (l_e - t_e)^2,    d/dx_v1 = 2 g_b (l_e - t_e) (x_v1 - x_v0) / l_e
+# with the gradient exactly 0 where l_e = 0; with the number 0 for a target the square root is skipped: sum_e |e|^2.
+# Cotangents: for a face (i, j, k) without a repeated index  cot_k = (a . b) / sqrt(|a x b|^2 + eps),  a = x_i - x_k,
+# b = x_j - x_k, likewise at the other two corners (finite for every finite input; a face with a repeated index has three zeros;
+# every face counts, a duplicated one twice).  With the corner indices mod 3 inside a face
+#     H_v = 1/2 sum_{(f, c) with f_c = v} [cot_{c+2} (x_{c+1} - x_v) + cot_{c+1} (x_{c+2} - x_v)],    loss_b = sum_v |H_{b,v}|^2
+# -- the corner opposite an edge weights that edge: the usual 1/2 (cot alpha + cot beta), summed face by face.  THE WEIGHTS ARE
+# CONSTANTS OF THE STEP: the gradient does not differentiate cot (the common convention of cotangent smoothing, which keeps the
+# backward linear), and the operator being symmetric, d loss / d x_v = 2 g_b L(H)_v: the same gather applied to H.
+
+_EDGE_ATTR = '_nr_mesh_edge_tables'
+
+
+class EdgeTables(object):
+    """The int32 edge tables of one topology, on one device: edges [E,2] ordered by (v0, v1), v0 < v1; nbr_edge [sum deg]: the
+    edge number of every entry of mesh.nbr; mesh: the MeshTables they were built from."""
+
+    def __init__(self, edges, nbr_edge, mesh):
+        self.edges, self.nbr_edge, self.mesh = edges, nbr_edge, mesh
+        self.num_edges = int(edges.shape[0])
+
+
+def build_edge_tables(nbr_offsets, nbr):
+    """Host arrays (edges [E,2], nbr_edge [sum deg]), int32, from the neighbour CSR of build_tables (see EdgeTables)."""
+    off = np.asarray(nbr_offsets, dtype=np.int64)
+    u = np.asarray(nbr, dtype=np.int64)
+    Nv = off.shape[0] - 1
+    v = np.repeat(np.arange(Nv, dtype=np.int64), off[1:] - off[:-1])
+    # the CSR lists the keys v * Nv + u ascending: its entries with v < u are the edges in (v0, v1) order, and an entry's edge
+    # is the rank of its own key with the ends swapped into that order
+    edge_keys = (v * Nv + u)[v < u]
+    nbr_edge = np.searchsorted(edge_keys, np.minimum(v, u) * Nv + np.maximum(v, u))
+    edges = np.stack((edge_keys // max(Nv, 1), edge_keys % max(Nv, 1)), axis=1).reshape(-1, 2)
+    return np.ascontiguousarray(edges.astype(np.int32)), nbr_edge.astype(np.int32)
+
+
+def _edge_tables(faces, num_vertices):
+    """-> EdgeTables on faces' device, cached on the index tensor as _tables caches its own."""
+    def build():
+        t = _tables(faces, num_vertices)
+        edges, nbr_edge = build_edge_tables(t.nbr_offsets.cpu().numpy(), t.nbr.cpu().numpy())
+        return EdgeTables(torch.from_numpy(edges).to(faces.device), torch.from_numpy(nbr_edge).to(faces.device), t)
+
+    return _util.cached_on_index(faces, _EDGE_ATTR, (int(num_vertices),), build,
+                                 'the edge tables of this index tensor are not built yet, and building them reads the indices '
+                                 'on the host: call edge_length_loss once with it before the capture')
+
+
+def _check_index_only(name, faces, num_vertices):
+    if not (torch.is_tensor(faces) and not faces.is_floating_point() and faces.dtype != torch.bool and faces.dim() in (2, 3)
+            and faces.shape[-1] == 3 and faces.shape[-2] >= 1):
+        raise ValueError('%s: faces must be an integer tensor [num of faces, 3] or [batch size, num of faces, 3]' % name)
+    if isinstance(num_vertices, bool) or not isinstance(num_vertices, int) or num_vertices < 1:
+        raise ValueError('%s: num_vertices must be a positive integer, got %r' % (name, num_vertices))
+    _util.check_face_indices(faces, num_vertices)
+
+
+def mesh_edges(faces, num_vertices):
+    """The edges of a topology: int64 [E,2] on faces' device, every row v0 < v1, ordered by (v0, v1) -- the order of
+    edge_length_loss's target and of edge_lengths.  faces [Nf,3], or [B,Nf,3] whose images are all equal."""
+    _check_index_only('mesh_edges', faces, num_vertices)
+    return _edge_tables(faces, num_vertices).edges.long()
+
+
+def _edge_lengths(x, edges):
+    d = x[:, edges[:, 1].long()] - x[:, edges[:, 0].long()]
+    return torch.sqrt((d * d).sum(2))
+
+
+def edge_lengths(vertices, faces):
+    """The length of every edge in mesh_edges' order: [B,E] from vertices [B,Nv,3], [E] from [Nv,3]; plain torch (any device,
+    any float dtype), differentiable by torch's autograd (not at a zero-length edge: use it for targets,
+    `edge_lengths(rest_vertices, faces).detach()`)."""
+    vertices, squeeze = _check('edge_lengths', vertices, faces)
+    _util.check_face_indices(faces, int(vertices.shape[1]), vertices.device)
+    out = _edge_lengths(vertices, _edge_tables(faces, int(vertices.shape[1])).edges)
+    return out[0] if squeeze else out
+
+
+def _edge_target(name, target, vertices, num_edges):
+    """-> (tensor [E] | [B,E] in vertices' dtype, or None; the number)"""
+    if torch.is_tensor(target):
+        B = int(vertices.shape[0])
+        if not (target.is_floating_point() and tuple(target.shape) in ((num_edges,), (B, num_edges))):
+            raise ValueError('%s: a target tensor must be a float tensor [num of edges] or [batch size, num of edges] = [%d] or '
+                             '[%d, %d] in the order of mesh_edges, got %s %s'
+                             % (name, num_edges, B, num_edges, target.dtype, tuple(target.shape)))
+        if target.device != vertices.device:
+            raise ValueError('%s: vertices and target must be on one device (%s, %s)' % (name, vertices.device, target.device))
+        return target.to(vertices.dtype), 0.0
+    value = _util.number(name, 'target', target)
+    if not (0.0 <= value < float('inf')):
+        raise ValueError('%s: target must be a finite number >= 0 (or a tensor), got %r' % (name, target))
+    return None, value
+
+
+def _edge_length_torch(x, e, target, value):
+    q = e.edges.long()
+    d = x[:, q[:, 1]] - x[:, q[:, 0]]
+    n = (d * d).sum(2)
+    if target is None and value == 0.0:
+        return n.sum(1)
+    pos = n > 0
+    l = torch.sqrt(torch.where(pos, n, torch.ones_like(n)))      # (sqrt has no derivative at 0: the gradient is exactly 0 there)
+    l = torch.where(pos, l, torch.zeros_like(n))
+    r = l - (target if target is not None else value)
+    return (r * r).sum(1)
+
+
+def _cot_weights_torch(x, idx, eps):
+    """cot [B,F,3] (not detached) for idx int64 [F,3]"""
+    p = x[:, idx]                                                 # [B,F,3 corners,3]
+    ok = (idx[:, 0] != idx[:, 1]) & (idx[:, 1] != idx[:, 2]) & (idx[:, 0] != idx[:, 2])
+    cots = []
+    for c in range(3):
+        a, b = p[:, :, (c + 1) % 3] - p[:, :, c], p[:, :, (c + 2) % 3] - p[:, :, c]
+        n = torch.cross(a, b, dim=2)
+        cots.append((a * b).sum(2) / torch.sqrt((n * n).sum(2) + eps))
+    cot = torch.stack(cots, dim=2)
+    return torch.where(ok[None, :, None], cot, torch.zeros_like(cot))
+
+
+def _cot_apply_torch(phi, cot, idx):
+    """L(phi) [B,Nv,3] with the weights cot [B,F,3]"""
+    H = torch.zeros_like(phi)
+    p = phi[:, idx]
+    for c in range(3):
+        c1, c2 = (c + 1) % 3, (c + 2) % 3
+        term = cot[:, :, c2, None] * (p[:, :, c1] - p[:, :, c]) + cot[:, :, c1, None] * (p[:, :, c2] - p[:, :, c])
+        H = H.index_add(1, idx[:, c], term)
+    return 0.5 * H
+
+
+def _one_topology(name, faces):
+    """int64 [F,3] of faces [F,3] or [B,F,3] with equal images (checked on the host by the table builders; here by torch)."""
+    if faces.dim() == 3:
+        if faces.shape[0] > 1 and not bool((faces == faces[0:1]).all()):
+            raise ValueError('%s: the faces of all images must be equal (one topology per call)' % name)
+        faces = faces[0]
+    return faces.long()
+
+
+def _cotangent_laplacian_torch(x, idx, eps):
+    H = _cot_apply_torch(x, _cot_weights_torch(x, idx, eps).detach(), idx)
+    return (H * H).sum((1, 2))
+
+
+def edge_length_loss_torch(vertices, faces, target=0.0):
+    """edge_length_loss in plain torch (any device, any float dtype), differentiable by torch's autograd -- in a target tensor
+    too."""
+    vertices, squeeze = _check('edge_length_loss_torch', vertices, faces)
+    _util.check_face_indices(faces, int(vertices.shape[1]), vertices.device)
+    e = _edge_tables(faces, int(vertices.shape[1]))
+    loss = _edge_length_torch(vertices, e, *_edge_target('edge_length_loss_torch', target, vertices, e.num_edges))
+    return loss[0] if squeeze else loss
+
+
+def cotangent_laplacian_loss_torch(vertices, faces, eps=1e-12):
+    """cotangent_laplacian_loss in plain torch (any device, any float dtype), differentiable by torch's autograd with the
+    cotangent weights under detach(): constants of the step."""
+    vertices, squeeze = _check('cotangent_laplacian_loss_torch', vertices, faces)
+    _util.check_face_indices(faces, int(vertices.shape[1]), vertices.device)
+    loss = _cotangent_laplacian_torch(vertices, _one_topology('cotangent_laplacian_loss_torch', faces), float(eps))
+    return loss[0] if squeeze else loss
+
+
+class _EdgeLengthLoss(torch.autograd.Function):
+    """forward(ctx, vertices [B,Nv,3], edge tables, target tensor or None, target number) -> loss [B]; nothing but the vertices
+    is saved: the backward recomputes every edge."""
+
+    @staticmethod
+    def forward(ctx, vertices, e, target, value):
+        v = _lib.dense(vertices.detach())
+        dev = v.device
+        B, Nv = v.shape[:2]
+        E = e.num_edges
+        loss = torch.empty((B,), dtype=torch.float32, device=dev)
+        per_batch = int(target is not None and target.dim() == 2)
+        _lib.launch('nr_edge_length_forward', dev, v.data_ptr(), _lib.ptr(e.edges) if E else None, _lib.ptr(target),
+                    loss.data_ptr(), B, Nv, E, per_batch, value,
+                    workspace_bytes=_lib.workspace_bytes('nr_mesh_loss_workspace_bytes', B, E))
+        if ctx.needs_input_grad[0]:
+            ctx.save_for_backward(v)
+        ctx.tables, ctx.target, ctx.value, ctx.per_batch = e, target, value, per_batch
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        v, = ctx.saved_tensors
+        e, t = ctx.tables, ctx.tables.mesh
+        dev = v.device
+        B, Nv = v.shape[:2]
+        g = _lib.dense(grad_loss)
+        grad_v = torch.empty_like(v)
+        some = int(t.nbr.shape[0]) > 0
+        _lib.launch('nr_edge_length_backward', dev, v.data_ptr(), t.nbr_offsets.data_ptr(), _lib.ptr(t.nbr) if some else None,
+                    _lib.ptr(e.nbr_edge) if some else None, _lib.ptr(ctx.target), g.data_ptr(), grad_v.data_ptr(), B, Nv,
+                    int(t.nbr.shape[0]), e.num_edges, ctx.per_batch, ctx.value)
+        return grad_v, None, None, None
+
+
+class _CotangentLaplacianLoss(torch.autograd.Function):
+    """forward(ctx, vertices [B,Nv,3], adjacency (vertex_colors._adjacency), eps) -> loss [B]; cot [B,F,3] and H [B,Nv,3] are
+    kept for the backward when one can follow, and only then."""
+
+    @staticmethod
+    def forward(ctx, vertices, adj, eps):
+        v = _lib.dense(vertices.detach())
+        dev = v.device
+        B, Nv = v.shape[:2]
+        idx, offsets, entries = adj[:3]
+        F = int(idx.shape[1])
+        keep = ctx.needs_input_grad[0]
+        loss = torch.empty((B,), dtype=torch.float32, device=dev)
+        cot = torch.empty((B, F, 3), dtype=torch.float32, device=dev)
+        H = torch.empty_like(v) if keep else None
+        _lib.launch('nr_cot_weights', dev, v.data_ptr(), idx.data_ptr(), cot.data_ptr(), B, Nv, F, eps)
+        _lib.launch('nr_cot_apply', dev, v.data_ptr(), cot.data_ptr(), idx.data_ptr(), offsets.data_ptr(), entries.data_ptr(), None,
+                    _lib.ptr(H), loss.data_ptr(), B, Nv, F,
+                    workspace_bytes=_lib.workspace_bytes('nr_mesh_loss_workspace_bytes', B, Nv))
+        if keep:
+            ctx.save_for_backward(cot, H)
+        ctx.adj = adj
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        cot, H = ctx.saved_tensors
+        idx, offsets, entries = ctx.adj[:3]
+        dev = H.device
+        B, Nv = H.shape[:2]
+        g = _lib.dense(grad_loss)
+        grad_v = torch.empty_like(H)
+        _lib.launch('nr_cot_apply', dev, H.data_ptr(), cot.data_ptr(), idx.data_ptr(), offsets.data_ptr(), entries.data_ptr(),
+                    g.data_ptr(), grad_v.data_ptr(), None, B, Nv, int(idx.shape[1]), workspace_bytes=0)
+        return grad_v, None, None
+
+
+_NEEDS = 'the HIP kernels take float32 CUDA tensors with a batch size of 65535 at most'
+
+
+def edge_length_loss(vertices, faces, target=0.0, implementation=None):
+    """sum over the edges of (length - target)^2 per image: [B] from vertices [B,Nv,3], a 0-dim tensor from [Nv,3]; faces
+    [Nf,3], or [B,Nf,3] whose images are all equal.  The edges are the distinct vertex pairs that share a face, in
+    mesh_edges(faces, Nv)'s order.  `target`: a number >= 0 for every edge -- with 0, the default, the loss is the sum of the
+    squared lengths and no square root is taken --, or a float tensor [E] or [B,E] in that order (rest lengths:
+    `edge_lengths(rest_vertices, faces).detach()`), read in place and not differentiated by the kernels: a target that
+    requires a gradient takes the torch path.  Differentiable (once) in vertices; the gradient of an edge of length 0 is
+    exactly 0.  `implementation` as in laplacian_loss."""
+    name = 'edge_length_loss'
+    vertices, squeeze = _check(name, vertices, faces)
+    B, Nv = int(vertices.shape[0]), int(vertices.shape[1])
+    _util.check_implementation(name, implementation)
+    _util.check_face_indices(faces, Nv, vertices.device)
+    e = _edge_tables(faces, Nv)
+    tensor, value = _edge_target(name, target, vertices, e.num_edges)
+    fits = (vertices.is_cuda and vertices.dtype == torch.float32 and B <= 65535
+            and not (tensor is not None and tensor.requires_grad))
+    if _util.takes_hip(name, implementation, fits, _NEEDS + ' and a target that requires no gradient'):
+        loss = _EdgeLengthLoss.apply(vertices, e, _lib.dense(tensor), value)
+    else:
+        loss = _edge_length_torch(vertices, e, tensor, value)
+    return loss[0] if squeeze else loss
+
+
+def cotangent_laplacian_loss(vertices, faces, eps=1e-12, implementation=None):
+    """sum_v |H_v|^2 per image with the cotangent-weighted Laplacian H_v = 1/2 sum over the faces around v of
+    cot_(c+2) (x_(c+1) - x_v) + cot_(c+1) (x_(c+2) - x_v), cot = (a . b) / sqrt(|a x b|^2 + eps) at every corner: [B] from
+    vertices [B,Nv,3], a 0-dim tensor from [Nv,3]; faces as in laplacian_loss (one topology; a face with a repeated index adds
+    nothing, a duplicated face counts twice).  H approximates the mean-curvature normal: the loss penalises bending, not an
+    irregular triangulation.  Differentiable (once) in vertices WITH THE WEIGHTS HELD CONSTANT: the gradient is 2 g L(H), it
+    does not differentiate the cotangents.  `implementation` as in laplacian_loss."""
+    name = 'cotangent_laplacian_loss'
+    vertices, squeeze = _check(name, vertices, faces)
+    B, Nv = int(vertices.shape[0]), int(vertices.shape[1])
+    eps = _util.number(name, 'eps', eps)
+    fits = vertices.is_cuda and vertices.dtype == torch.float32 and B <= 65535
+    hip = _util.takes_hip(name, implementation, fits, _NEEDS)
+    _util.check_face_indices(faces, Nv, vertices.device)
+    if hip:
+        from .vertex_colors import _adjacency
+        adj = _adjacency(faces, Nv)
+        if adj[3]:
+            raise ValueError('%s: the faces of all images must be equal (one topology per call)' % name)
+        loss = _CotangentLaplacianLoss.apply(vertices, adj, eps)
+    else:
+        loss = _cotangent_laplacian_torch(vertices, _one_topology(name, faces), eps)
     return loss[0] if squeeze else loss
