@@ -85,6 +85,7 @@ extern "C" {
                           *        nr_light_colors_workspace_bytes;
                           *        nr_iou_loss_forward, nr_iou_loss_backward, nr_squared_error_forward, nr_squared_error_backward,
                           *        nr_image_loss_workspace_bytes;
+                          *        nr_ssim_loss_forward, nr_ssim_loss_backward, nr_ssim_workspace_bytes;
                           *        nr_stencil_apply;
                           *        nr_vertex_normals_forward, nr_vertex_normals_backward, nr_face_normals_forward,
                           *        nr_face_normals_backward, nr_corner_normals_forward, nr_corner_normals_backward,
@@ -1179,6 +1180,47 @@ int nr_squared_error_backward(const float *images, const float *target, const fl
                               int32_t mask_per_image, const double *level_weights, const float *grad_loss,
                               float *grad_images, int32_t batch_size, int32_t channels, int32_t height, int32_t width,
                               int32_t levels, void *stream);
+
+/*
+ * SSIM loss (not in the reference; DESIGN "Image losses: SSIM"): the structural similarity of images [B, C, H, W] and a target
+ * [B, C, H, W] (target_per_image = 1) or [C, H, W] (0: one target for the batch, read in place) under a mask [B, H, W] or
+ * [H, W] or NULL (= 1) that applies to every channel.  window: a HOST array of window_size = 2R + 1 floats w, window_size odd
+ * in 3 .. 11 (NR_E_SIZE otherwise), read during the call and handed to the kernels by value; the 2-D window is w (x) w and G*z
+ * the windowed sum of z.  valid = 0 ('same'): z reads as 0 outside the image and every pixel is a window centre, Hq x Wq =
+ * H x W; valid = 1: only the windows inside the image, Hq x Wq = (H - 2R) x (W - 2R) (NR_E_SIZE when that is empty).  Per
+ * channel and window centre q, in float32:
+ *     mu_x = G*x, mu_y = G*y, sxx = G*(x x) - mu_x^2, syy = G*(y y) - mu_y^2, sxy = G*(x y) - mu_x mu_y,
+ *     a1 = 2 mu_x mu_y + c1, a2 = 2 sxy + c2, b1 = mu_x^2 + mu_y^2 + c1, b2 = sxx + syy + c2, S = (a1 a2) / (b1 b2)
+ *   (c1, c2 rounded to float32), and
+ *     loss[b] = k sum_(c, q) m_b(q) (1 - S_c(q)),
+ *   m the mask at the window's centre pixel, k = 1 (mean = 0) or 1 / (C sum_q m_b(q)) (mean = 1; 0 when that sum is 0).
+ *   Bit-equal images and target give S = 1 at every window and a loss of exactly 0.
+ * The forward stores S into ssim_map [B, C, Hq, Wq] when that is given, and, when grad_maps [3, B, C, Hq, Wq] and scales [B]
+ * doubles are given (both or neither: NR_E_NULL), what the backward reads: the maps
+ *     M3 = dS/dsxy = 2 a1 / (b1 b2),  M2 = dS/dsxx = -S / b2,
+ *     M1 = 2 mu_y a2 / (b1 b2) - 2 mu_x S / b1 - 2 mu_x M2 - mu_y M3,
+ *   which depend on neither g, k nor the mask, and k per image.  The backward is a gather over the windows that contain a pixel:
+ *     grad_images[b, c, p] = -g_b k_b sum_q m_b(q) w(q - p) (M1(q) + 2 x(p) M2(q) + y(p) M3(q)).
+ * No gradient to target or mask.  The sums of an image: per tile of 64 x 16 window centres a double sum of m (1 - S) and of m
+ * in a fixed order into the workspace (nr_ssim_workspace_bytes; 0 for sizes out of range), the tiles added in tile order in
+ * double by a second kernel, the loss evaluated in double and rounded once.  The backward is one launch.  No atomics in any
+ * kernel: the same bits in every run, and an image alone gives the bits it has in a batch.  16-byte loads and stores where
+ * a plane's width is a multiple of 4 and its pointer is 16-byte aligned.  The float operation order: the header comment of
+ * csrc/nr_ssim.hip.  Every output element is stored; no call synchronises the host or reads device memory on the host;
+ * NR_E_* before any launch.
+ */
+size_t nr_ssim_workspace_bytes(int32_t batch_size, int32_t height, int32_t width, int32_t window_size, int32_t valid);
+
+int nr_ssim_loss_forward(const float *images, const float *target, const float *mask, int32_t target_per_image,
+                         int32_t mask_per_image, const float *window, float *loss, float *ssim_map, float *grad_maps,
+                         double *scales, int32_t batch_size, int32_t channels, int32_t height, int32_t width,
+                         int32_t window_size, int32_t valid, int32_t mean, double c1, double c2, void *workspace,
+                         size_t workspace_bytes, void *stream);
+
+int nr_ssim_loss_backward(const float *images, const float *target, const float *mask, int32_t target_per_image,
+                          int32_t mask_per_image, const float *window, const float *grad_maps, const double *scales,
+                          const float *grad_loss, float *grad_images, int32_t batch_size, int32_t channels, int32_t height,
+                          int32_t width, int32_t window_size, int32_t valid, void *stream);
 
 /*
  * Mesh subdivision (not in the reference; DESIGN "Mesh subdivision"): one level of Loop or midpoint refinement is a sparse

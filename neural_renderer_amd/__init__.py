@@ -31,7 +31,7 @@ from .mesh_losses import cotangent_laplacian_loss, edge_length_loss, edge_length
 from .lights import Lights, light_colors
 # not in the reference: the objective of a fit on images -- silhouette IoU and masked squared error, optionally on an image
 # pyramid -- HIP in both directions
-from .image_losses import silhouette_iou_loss, squared_error_loss
+from .image_losses import silhouette_iou_loss, squared_error_loss, ssim_loss, ssim_index
 # not in the reference: mesh subdivision -- Loop and midpoint refinement of per-vertex data as a differentiable step, a sphere
 # template -- HIP in both directions
 from .subdivision import Subdivision, icosphere, subdivide, subdivision
@@ -69,7 +69,7 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'vertices_to_faces',
            'load_obj', 'Mesh', 'Adam', 'save_obj', 'UVImages', 'TextureCubes', 'UVLayout', 'UVTextures', 'bake_uv_textures',
            'CornerColors', 'VertexColors', 'vertex_shade', 'vertex_light',
-           'laplacian_loss', 'flatness_loss', 'edge_length_loss', 'cotangent_laplacian_loss', 'mesh_edges', 'edge_lengths', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss',
+           'laplacian_loss', 'flatness_loss', 'edge_length_loss', 'cotangent_laplacian_loss', 'mesh_edges', 'edge_lengths', 'Lights', 'light_colors', 'silhouette_iou_loss', 'squared_error_loss', 'ssim_loss', 'ssim_index',
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
            'closest_surface_points', 'closest_cloud_points', 'point_mesh_distance',

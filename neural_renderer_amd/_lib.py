@@ -143,6 +143,9 @@ SIGNATURES = {
     'nr_iou_loss_backward': (_c.c_int, [_vp, _i32] + [_vp] * 4 + [_i32] * 4 + [_f64, _vp]),
     'nr_squared_error_forward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 2 + [_i32] * 5 + [_vp, _sz, _vp]),
     'nr_squared_error_backward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 3 + [_i32] * 5 + [_vp]),
+    'nr_ssim_workspace_bytes': (_sz, [_i32] * 5),
+    'nr_ssim_loss_forward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 5 + [_i32] * 7 + [_f64] * 2 + [_vp, _sz, _vp]),
+    'nr_ssim_loss_backward': (_c.c_int, [_vp] * 3 + [_i32] * 2 + [_vp] * 5 + [_i32] * 6 + [_vp]),
     'nr_stencil_apply': (_c.c_int, [_vp] * 5 + [_i32] * 5 + [_vp]),
     'nr_adam_update': (_c.c_int, [_vp] * 4 + [_sz] + [_c.c_float] * 4 + [_vp]),
     'nr_frontend_workspace_bytes': (_sz, [_i32]),

@@ -21,8 +21,25 @@ level of a tile on chip, sums in double in a fixed order, no atomics -- the resu
 gives the bits it has inside a batch.  The kernels give no gradient to `target` or `mask`: a target or mask that requires
 grad, and everything else that does not fit, takes the plain-torch implementations `silhouette_iou_loss_torch` /
 `squared_error_loss_torch` (any device, any float dtype, avg_pool2d), which are also the kernels' second yardstick in the
-tests.  The functions hold no host tables: a first call inside graph.capture works without an eager step before it."""
+tests.  The functions hold no host tables: a first call inside graph.capture works without an eager step before it.
+
+`ssim_loss(images, target, mask)` is the structural term that a photometric fit pairs with the squared error,
+(1 - lambda) L_pix + lambda (1 - SSIM); `ssim_index` returns the map itself.  Inputs as in squared_error_loss.  The window is
+w[k] ~ exp(-(k - R)^2 / 2 sigma^2), k = 0 .. n - 1, n = window_size = 2R + 1 odd in 3 .. 11, computed in double, normalised to
+sum 1 and rounded to float32 (`ssim_window`); the 2-D window is w (x) w and G*z the windowed sum of z.  padding = 'same': z
+reads as 0 outside the image and every pixel is a window centre (Hq x Wq = H x W); 'valid': only the windows inside the image
+(Hq x Wq = (H - 2R) x (W - 2R)).  Per channel and window centre q
+    mu_x = G*x, mu_y = G*y, sxx = G*(x^2) - mu_x^2, syy = G*(y^2) - mu_y^2, sxy = G*(x y) - mu_x mu_y,
+    a1 = 2 mu_x mu_y + C1, a2 = 2 sxy + C2, b1 = mu_x^2 + mu_y^2 + C1, b2 = sxx + syy + C2,
+    S = (a1 a2) / (b1 b2),  C1 = (k1 data_range)^2,  C2 = (k2 data_range)^2,
+    loss_b = k sum_{c,q} m_b(q) (1 - S_c(q)),
+m the mask at the window's centre pixel (None: 1), k = 1 for reduction = 'sum' and 1 / (C sum_q m_b(q)) for 'mean'; an image
+whose mask sums to 0 has loss 0 and a zero gradient.  On float32 CUDA tensors it runs as HIP kernels in both directions
+(nr_ssim_loss_*, csrc/nr_ssim.hip): one fused pass per direction, sums in double in a fixed order, no atomics; images bit-equal
+to the target give a loss of exactly 0.  With a gradient to follow the forward keeps three float maps [B,C,Hq,Wq] for the
+backward.  `ssim_loss_torch` is the same in plain torch (the windowed sums tap by tap on shifted slices, autograd)."""
 import ctypes
+import math
 
 import torch
 import torch.nn.functional as F
@@ -30,6 +47,7 @@ import torch.nn.functional as F
 from . import _lib, _util
 
 MAX_LEVELS = 5
+MAX_WINDOW = 11
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -250,3 +268,178 @@ def squared_error_loss(images, target, mask=None, levels=1, level_weights=None, 
     if _use_hip(name, implementation, x, (target, mask)):
         return _SquaredError.apply(x, t, m, weights)
     return _se_torch(x, t, m, weights)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# SSIM
+
+def ssim_window(window_size, sigma):
+    """The taps w[k] ~ exp(-(k - R)^2 / 2 sigma^2) of the SSIM window: computed in double, normalised to sum 1, rounded to
+    float32 -- a tuple of `window_size` floats that float32 holds exactly."""
+    R = window_size // 2
+    taps = [math.exp(-((k - R) ** 2) / (2.0 * sigma * sigma)) for k in range(window_size)]
+    total = math.fsum(taps)
+    return tuple(float(torch.tensor(t / total, dtype=torch.float64).to(torch.float32)) for t in taps)
+
+
+def _host_number(name, what, value):
+    if torch.is_tensor(value) or isinstance(value, bool) or not isinstance(value, (int, float)):
+        raise ValueError('%s: %s must be a host number, got %r' % (name, what, type(value).__name__))
+    return float(value)
+
+
+def _ssim_arguments(name, x, window_size, sigma, data_range, k1, k2, padding, reduction):
+    """-> (window: tuple of floats, C1, C2, valid, mean)"""
+    if torch.is_tensor(window_size) or isinstance(window_size, bool) or not isinstance(window_size, int) \
+            or not 3 <= window_size <= MAX_WINDOW or window_size % 2 == 0:
+        raise ValueError('%s: window_size must be an odd integer in 3 .. %d, got %r' % (name, MAX_WINDOW, window_size))
+    sigma, data_range = _host_number(name, 'sigma', sigma), _host_number(name, 'data_range', data_range)
+    k1, k2 = _host_number(name, 'k1', k1), _host_number(name, 'k2', k2)
+    if not sigma > 0:
+        raise ValueError('%s: sigma must be positive, got %r' % (name, sigma))
+    if not data_range > 0:
+        raise ValueError('%s: data_range must be positive, got %r' % (name, data_range))
+    if padding not in ('same', 'valid'):
+        raise ValueError("%s: padding must be 'same' or 'valid', got %r" % (name, padding))
+    if reduction not in ('mean', 'sum'):
+        raise ValueError("%s: reduction must be 'mean' or 'sum', got %r" % (name, reduction))
+    H, W = x.shape[2:]
+    if padding == 'valid' and (H < window_size or W < window_size):
+        raise ValueError("%s: with padding = 'valid' the images must be at least window_size = %d high and wide, got %d x %d"
+                         % (name, window_size, H, W))
+    return ssim_window(window_size, sigma), (k1 * data_range) ** 2, (k2 * data_range) ** 2, padding == 'valid', reduction == 'mean'
+
+
+def _window_sums(z, window, valid):
+    """G*z over the last two axes, tap by tap on shifted slices, rows then columns: sum_k w[k] z(q - R + k).  Not conv2d: on
+    the GPU the backward of a grouped conv2d is not exact where every term is 0 (DESIGN "Image losses: SSIM"), and a pixel
+    out of reach of the mask must get a gradient of exactly 0."""
+    n, R = len(window), len(window) // 2
+    if not valid:
+        z = F.pad(z, (R, R, R, R))
+    Hq, Wq = z.shape[-2] - 2 * R, z.shape[-1] - 2 * R
+    rows = window[0] * z[..., :, 0:Wq]
+    for k in range(1, n):
+        rows = rows + window[k] * z[..., :, k:k + Wq]
+    out = window[0] * rows[..., 0:Hq, :]
+    for k in range(1, n):
+        out = out + window[k] * rows[..., k:k + Hq, :]
+    return out
+
+
+def _ssim_map_torch(x, t, window, c1, c2, valid):
+    """S [B,C,Hq,Wq]: the five windowed sums as one stack."""
+    C = x.shape[1]
+    t = t.expand_as(x)
+    z = _window_sums(torch.cat((x, t, x * x, t * t, x * t), 1), window, valid)
+    mux, muy, gxx, gyy, gxy = z.split(C, 1)
+    pxx, pyy, pxy = mux * mux, muy * muy, mux * muy
+    sxx, syy, sxy = gxx - pxx, gyy - pyy, gxy - pxy
+    return (((pxy + pxy) + c1) * ((sxy + sxy) + c2)) / (((pxx + pyy) + c1) * ((sxx + syy) + c2))
+
+
+def _ssim_torch(x, t, m, window, c1, c2, valid, mean):
+    S = _ssim_map_torch(x, t, window, c1, c2, valid)
+    C, R = x.shape[1], len(window) // 2
+    if m is None:
+        total = (1 - S).sum((1, 2, 3))
+        return total / (C * S.shape[2] * S.shape[3]) if mean else total
+    if valid:
+        m = m[:, :, R:m.shape[2] - R, R:m.shape[3] - R]
+    total = (m * (1 - S)).sum((1, 2, 3))
+    if not mean:
+        return total
+    msum = m.sum((1, 2, 3)).expand(x.shape[0])
+    ok = msum != 0
+    return torch.where(ok, total / (C * torch.where(ok, msum, torch.ones_like(msum))), torch.zeros_like(total))
+
+
+def _ssim_launch(x, t, m, window, c1, c2, valid, mean, want_map, want_grad):
+    """nr_ssim_loss_forward on contiguous x [B,C,H,W], t [B or 1,C,H,W], m [B or 1,1,H,W] or None -> (loss [B], S or None,
+    (maps [3,B,C,Hq,Wq], scales [B]) or None)"""
+    dev = x.device
+    B, C, H, W = x.shape
+    n = len(window)
+    Hq, Wq = (H - n + 1, W - n + 1) if valid else (H, W)
+    loss = torch.empty((B,), dtype=torch.float32, device=dev)
+    smap = torch.empty((B, C, Hq, Wq), dtype=torch.float32, device=dev) if want_map else None
+    maps = torch.empty((3, B, C, Hq, Wq), dtype=torch.float32, device=dev) if want_grad else None
+    scales = torch.empty((B,), dtype=torch.float64, device=dev) if want_grad else None
+    _lib.launch('nr_ssim_loss_forward', dev, x.data_ptr(), t.data_ptr(), _lib.ptr(m), int(t.shape[0] != 1 or B == 1),
+                int(m is not None and (m.shape[0] != 1 or B == 1)), (ctypes.c_float * n)(*window), loss.data_ptr(),
+                _lib.ptr(smap), _lib.ptr(maps), _lib.ptr(scales), B, C, H, W, n, int(valid), int(mean), c1, c2,
+                workspace_bytes=_lib.workspace_bytes('nr_ssim_workspace_bytes', B, H, W, n, int(valid)))
+    return loss, smap, ((maps, scales) if want_grad else None)
+
+
+class _SSIMLoss(torch.autograd.Function):
+    """forward(ctx, images [B,C,H,W], target [B or 1,C,H,W], mask [B or 1,1,H,W] or None, window, c1, c2, valid, mean) ->
+    loss [B]; when a backward can follow, the inputs, the forward's three maps M1, M2, M3 and k per image are kept for it."""
+
+    @staticmethod
+    def forward(ctx, images, target, mask, window, c1, c2, valid, mean):
+        x, t = images.detach().contiguous(), target.detach().contiguous()
+        m = None if mask is None else mask.detach().contiguous()
+        want = ctx.needs_input_grad[0]
+        loss, _, saved = _ssim_launch(x, t, m, window, c1, c2, valid, mean, False, want)
+        if want:
+            ctx.save_for_backward(*((x, t) + saved + (() if m is None else (m,))))
+        ctx.window, ctx.valid = window, valid
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        if not ctx.needs_input_grad[0]:
+            return (None,) * 8
+        x, t, maps, scales = ctx.saved_tensors[:4]
+        m = ctx.saved_tensors[4] if len(ctx.saved_tensors) > 4 else None
+        dev = x.device
+        B, C, H, W = x.shape
+        n = len(ctx.window)
+        g = grad_loss.contiguous()
+        grad = torch.empty_like(x)
+        _lib.launch('nr_ssim_loss_backward', dev, x.data_ptr(), t.data_ptr(), _lib.ptr(m), int(t.shape[0] != 1 or B == 1),
+                    int(m is not None and (m.shape[0] != 1 or B == 1)), (ctypes.c_float * n)(*ctx.window), maps.data_ptr(),
+                    scales.data_ptr(), g.data_ptr(), grad.data_ptr(), B, C, H, W, n, int(ctx.valid))
+        return (grad,) + (None,) * 7
+
+
+def ssim_loss_torch(images, target, mask=None, window_size=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, padding='same',
+                    reduction='mean'):
+    """ssim_loss in plain torch (any device, any float dtype): the windowed sums tap by tap on shifted slices with zero padding
+    or none, differentiable by torch's autograd."""
+    name = 'ssim_loss_torch'
+    x, t, m = _check(name, 'images', images, target, mask)
+    window, c1, c2, valid, mean = _ssim_arguments(name, x, window_size, sigma, data_range, k1, k2, padding, reduction)
+    return _ssim_torch(x, t, m, window, c1, c2, valid, mean)
+
+
+def ssim_loss(images, target, mask=None, window_size=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, padding='same',
+              reduction='mean', implementation=None):
+    """k sum_{c,q} mask(q) (1 - S_c(q)) per image (see the module docstring): [B] from images [B,C,H,W] or [B,H,W], a target
+    of that shape or without its batch axis (shared, read in place), and a mask [B,H,W] or [H,W] (None: 1) taken at the
+    window's centre pixel.  window_size odd in 3 .. 11, sigma, data_range, k1, k2 host numbers; padding 'same' | 'valid';
+    reduction 'mean' (k = 1 / (C sum mask)) | 'sum' (k = 1).  Differentiable (once) in images only; `implementation` as in
+    silhouette_iou_loss.  Graph capture is not tested with this operator; the README's advice applies: capture a whole step
+    with neural_renderer_amd.graph.capture before any eager backward on the same leaves, or make the eager calls under
+    no_grad."""
+    name = 'ssim_loss'
+    x, t, m = _check(name, 'images', images, target, mask)
+    window, c1, c2, valid, mean = _ssim_arguments(name, x, window_size, sigma, data_range, k1, k2, padding, reduction)
+    if _use_hip(name, implementation, x, (target, mask)):
+        return _SSIMLoss.apply(x, t, m, window, c1, c2, valid, mean)
+    return _ssim_torch(x, t, m, window, c1, c2, valid, mean)
+
+
+def ssim_index(images, target, window_size=11, sigma=1.5, data_range=1.0, k1=0.01, k2=0.03, padding='same',
+               implementation=None):
+    """The map S of ssim_loss, [B,C,Hq,Wq] (images [B,H,W]: [B,Hq,Wq]), for evaluation: no gradient."""
+    name = 'ssim_index'
+    x, t, _ = _check(name, 'images', images, target, None)
+    window, c1, c2, valid, _ = _ssim_arguments(name, x, window_size, sigma, data_range, k1, k2, padding, 'mean')
+    with torch.no_grad():
+        if _use_hip(name, implementation, x, ()):
+            S = _ssim_launch(x.contiguous(), t.contiguous(), None, window, c1, c2, valid, True, True, False)[1]
+        else:
+            S = _ssim_map_torch(x, t, window, c1, c2, valid)
+    return S[:, 0] if images.dim() == 3 else S
