@@ -96,7 +96,9 @@ extern "C" {
                           *        nr_soft_uv_forward, nr_soft_uv_backward, nr_soft_uv_workspace_bytes;
                           *        nr_soft_cubes_forward, nr_soft_cubes_backward, nr_soft_cubes_workspace_bytes;
                           *        nr_point_mesh_points_to_faces, nr_point_mesh_faces_to_points, nr_point_mesh_loss,
-                          *        nr_point_mesh_backward_points, nr_point_mesh_backward_vertices, nr_point_mesh_workspace_bytes);
+                          *        nr_point_mesh_backward_points, nr_point_mesh_backward_vertices, nr_point_mesh_workspace_bytes;
+                          *        nr_winding_forward, nr_winding_backward_points, nr_winding_backward_vertices,
+                          *        nr_winding_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -1140,6 +1142,44 @@ int nr_point_mesh_backward_vertices(const float *points, const float *vertices, 
                                     const int32_t *point_ids, const float *barycentric_faces, const float *grad_dist2_faces,
                                     float *grad_vertices, int32_t batch_size, int32_t num_points, int32_t num_vertices,
                                     int32_t num_faces, int32_t points_per_batch, void *stream);
+
+/*
+ * Winding numbers (not in the reference's library; DESIGN "Winding numbers"): points [B, N, 3] -- or ONE cloud [N, 3] for the
+ * batch with points_per_batch = 0 (any value but 0 and 1: NR_E_MODE) --, world-space vertices [B, Nv, 3] and ONE topology
+ * faces [F, 3] int32.  w[b, i] = (1 / 4 pi) sum_f Omega_f(p_bi), Omega = 2 atan2(num, den) the signed solid angle of face f seen
+ * from the point (csrc/nr_solid_angle.h: one definition for the three calls, the same bits for the same pair).  A face with
+ * two corners equal as positions contributes exactly 0 to every output; num = den = 0 gives Omega = 0 and a zero gradient; a
+ * non-finite coordinate gives NaN.  The sums are a two-level definition: the streamed side (faces; for the gradient to the
+ * vertices, points) in fixed tiles of 256; a tile's terms added in double, ascending, from 0; the tile sums added in double,
+ * ascending; the total scaled in double and rounded once.
+ *   nr_winding_forward: winding [B, N].
+ *   nr_winding_backward_points (points [B, N, 3]): grad_points[b, i] = (g_bi / 4 pi) sum_f dOmega_f/dp, g = grad_winding [B, N].
+ *   nr_winding_backward_vertices: per face corner (1 / 4 pi) sum_i g_bi dOmega_f(p_bi)/dv_k into the workspace, then
+ *     grad_vertices[b, v] = the sum of the corners (f, k) of v in the vertex -> (face, corner) table (adj_offsets [Nv + 1],
+ *     adj_entries [3 F]: 3 f + k ascending), in table order, in float32.
+ *   split: 0 lets the call decide whether to cut the streamed side at tile boundaries over several workgroups, n >= 1 asks for
+ *   n parts (1: none); a split call stores its tile sums in the workspace and merges them in the same ascending order, so the
+ *   result does not depend on it, to the bit (tile sums above 256 MiB: the call is not split).
+ *   nr_winding_workspace_bytes(B, N, F, which, split), which = 0 forward, 1 backward_points, 2 backward_vertices (else 0): the
+ *   tile sums of a split call, plus for 2 the corner gradients; 0: workspace may be NULL.
+ * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * same bits in every run, for an image alone or inside a batch, split or not.  Every output element is stored exactly once; no
+ * call synchronises the host; NR_E_* before any launch (NULL before sizes).
+ */
+size_t nr_winding_workspace_bytes(int32_t batch_size, int32_t num_points, int32_t num_faces, int32_t which, int32_t split);
+
+int nr_winding_forward(const float *points, const float *vertices, const int32_t *faces, float *winding, int32_t batch_size,
+                       int32_t num_points, int32_t num_vertices, int32_t num_faces, int32_t points_per_batch, int32_t split,
+                       void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_winding_backward_points(const float *points, const float *vertices, const int32_t *faces, const float *grad_winding,
+                               float *grad_points, int32_t batch_size, int32_t num_points, int32_t num_vertices,
+                               int32_t num_faces, int32_t split, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_winding_backward_vertices(const float *points, const float *vertices, const int32_t *faces, const int32_t *adj_offsets,
+                                 const int32_t *adj_entries, const float *grad_winding, float *grad_vertices, int32_t batch_size,
+                                 int32_t num_points, int32_t num_vertices, int32_t num_faces, int32_t points_per_batch,
+                                 int32_t split, void *workspace, size_t workspace_bytes, void *stream);
 
 /*
  * Image losses (not in the reference; DESIGN "Image losses"): the objective of a fit on images, one loss per image, on an

@@ -41,6 +41,9 @@ from .point_losses import SurfaceSamples, chamfer_distance, nearest_points, samp
 # not in the reference: point-to-mesh distance -- for every point the nearest triangle, for every triangle the nearest point,
 # with exact gradients to points and vertices -- HIP in both directions
 from .point_mesh import closest_cloud_points, closest_surface_points, point_mesh_distance
+# not in the reference: generalized winding numbers -- inside / outside, voxel grids and the sign of the distance, with exact
+# gradients to points and vertices -- HIP in both directions
+from .winding import mesh_occupancy, signed_distance, voxel_centers, voxel_iou, voxelize, winding_number
 # not in the reference: vertex, face and corner normals -- HIP in both directions -- for Renderer.render_normals, and the
 # rotation of a renderer's camera
 from .normals import camera_rotation, corner_normals, face_normals, vertex_normals
@@ -73,6 +76,7 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'Subdivision', 'subdivision', 'subdivide', 'icosphere',
            'SurfaceSamples', 'chamfer_distance', 'nearest_points', 'sample_surface', 'sample_surface_points',
            'closest_surface_points', 'closest_cloud_points', 'point_mesh_distance',
+           'winding_number', 'mesh_occupancy', 'voxel_centers', 'voxelize', 'voxel_iou', 'signed_distance',
            'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation',
            'soft_silhouettes', 'soft_silhouettes_torch', 'soft_render', 'soft_render_torch', 'soft_render_uv',
            'soft_render_uv_torch', 'soft_render_cubes', 'soft_render_cubes_torch']

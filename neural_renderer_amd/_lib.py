@@ -135,6 +135,10 @@ SIGNATURES = {
     'nr_point_mesh_loss': (_c.c_int, [_vp] * 3 + [_i32] * 3 + [_f64] * 2 + [_vp]),
     'nr_point_mesh_backward_points': (_c.c_int, [_vp] * 12 + [_i32] * 4 + [_vp]),
     'nr_point_mesh_backward_vertices': (_c.c_int, [_vp] * 14 + [_i32] * 5 + [_vp]),
+    'nr_winding_workspace_bytes': (_sz, [_i32] * 5),
+    'nr_winding_forward': (_c.c_int, [_vp] * 4 + [_i32] * 6 + [_vp, _sz, _vp]),
+    'nr_winding_backward_points': (_c.c_int, [_vp] * 5 + [_i32] * 5 + [_vp, _sz, _vp]),
+    'nr_winding_backward_vertices': (_c.c_int, [_vp] * 7 + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_light_colors_workspace_bytes': (_sz, [_i32] * 4),
     'nr_light_colors_forward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_light_colors_backward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp, _vp, _lights_grad_p] + [_i32] * 6 + [_vp, _sz, _vp]),

@@ -65,6 +65,22 @@ class Mesh(nn.Module):
         from .point_mesh import point_mesh_distance
         return point_mesh_distance(points, self.vertices, self.faces, **kw)
 
+    def winding_number(self, points, implementation=None):
+        """winding.winding_number of `points` and the module's own vertices and faces (not in the reference)."""
+        from .winding import winding_number
+        return winding_number(points, self.vertices, self.faces, implementation)
+
+    def voxelize(self, grid_size, **kw):
+        """winding.voxelize of the module's own vertices and faces (not in the reference): [G,G,G]; bounds, hard and
+        implementation as keywords."""
+        from .winding import voxelize
+        return voxelize(self.vertices, self.faces, grid_size, **kw)
+
+    def signed_distance(self, points, implementation=None):
+        """winding.signed_distance of `points` and the module's own vertices and faces (not in the reference)."""
+        from .winding import signed_distance
+        return signed_distance(points, self.vertices, self.faces, implementation)
+
     def vertex_normals(self, implementation=None):
         """normals.vertex_normals of the module's own vertices and faces (not in the reference): [num_vertices, 3]."""
         from .normals import vertex_normals

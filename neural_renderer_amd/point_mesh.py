@@ -53,8 +53,9 @@ _DIRECTIONS = ('both', 'points_to_mesh', 'mesh_to_points')
 # ---------------------------------------------------------------------------------------------------------------------
 # checks
 
-def _inputs(name, points, vertices, faces, implementation):
-    """-> (points [B or 1,N,3], vertices [B,Nv,3], faces [F,3], squeeze, use_hip)"""
+def _inputs(name, points, vertices, faces, implementation, needs=None):
+    """-> (points [B or 1,N,3], vertices [B,Nv,3], faces [F,3], squeeze, use_hip); `needs`: the limit sentence of another module
+    whose kernels take the same arguments (winding.py)"""
     if not (torch.is_tensor(points) and points.is_floating_point() and points.dim() in (2, 3) and points.shape[-1] == 3
             and points.shape[-2] >= 1 and points.shape[0] >= 1):
         raise ValueError('%s: points must be a float tensor [num of points, 3] or [batch size, num of points, 3] with at least '
@@ -76,7 +77,7 @@ def _inputs(name, points, vertices, faces, implementation):
     lim = 2 ** 31 - 1
     fits = (points.is_cuda and points.dtype == torch.float32 and B <= 65535 and B * N <= lim // 3 and B * F <= lim // 18
             and B * Nv <= lim // 6 and (Bp == B or not points.requires_grad or not torch.is_grad_enabled()))
-    return points, vertices, faces, no_batch, _util.takes_hip(name, implementation, fits, _NEEDS)
+    return points, vertices, faces, no_batch, _util.takes_hip(name, implementation, fits, needs or _NEEDS)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
