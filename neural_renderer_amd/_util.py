@@ -1,3 +1,4 @@
+import functools
 import math
 
 import numpy as np
@@ -5,6 +6,57 @@ import torch
 
 SOFT_MAX_FACES = 2 ** 24    # the soft operators' limits (include/nr_hip.h)
 SOFT_MAX_SIZE = 16384
+
+
+class _SecondDerivative(torch.autograd.Function):
+    """forward(ctx, n, *tensors) -> the first n tensors, the gradients a backward returned; the others are the inputs of that
+    backward's forward and the upstream gradients that require a gradient.  Their edges put this node on every path from the
+    returned gradients to whatever a second derivative can be asked for, and its backward raises."""
+
+    @staticmethod
+    def forward(ctx, n, *tensors):
+        return tuple(t.view_as(t) for t in tensors[:n])
+
+    @staticmethod
+    def backward(ctx, *grads):
+        raise RuntimeError('trying to differentiate twice a function that was marked with @once_differentiable: the '
+                           'operators of neural_renderer_amd are differentiable once, a second derivative is not implemented')
+
+
+def once_differentiable(cls):
+    """Class decorator of every torch.autograd.Function in this package: a second derivative raises.  The backwards fill
+    fresh buffers through the C ABI (or, in the plain-torch winding path, are written for one derivative), so under
+    create_graph=True their results would pass for constants, and a gradient penalty or a Hessian-vector product would lose
+    that term without a word.  torch.autograd.function.once_differentiable is not enough for that: it puts its error node
+    behind the result only when an upstream gradient requires a gradient -- the plain (out * w).sum() does not -- and with
+    edges to fresh leaves only, so torch.autograd.grad(f(g), x) finds no path from it to x and never runs it.  Here the
+    forward notes its inputs that require a gradient on ctx, the backward runs under no_grad, and while a graph is being
+    recorded its results go through _SecondDerivative with those inputs.  `backward.__wrapped__` is the undecorated one."""
+    forward, backward = cls.forward, cls.backward
+
+    @functools.wraps(forward)
+    def once_forward(ctx, *args):
+        ctx._nr_inputs = tuple(a for a in args if torch.is_tensor(a) and a.requires_grad)
+        return forward(ctx, *args)
+
+    @functools.wraps(backward)
+    def once_backward(ctx, *grads):
+        with torch.no_grad():
+            outs = backward(ctx, *grads)
+        if not torch.is_grad_enabled():
+            return outs
+        anchors = ctx._nr_inputs + tuple(g for g in grads if torch.is_tensor(g) and g.requires_grad)
+        seq = outs if isinstance(outs, tuple) else (outs,)
+        live = [i for i, o in enumerate(seq) if torch.is_tensor(o)]
+        if not anchors or not live:
+            return outs
+        seq = list(seq)
+        for i, o in zip(live, _SecondDerivative.apply(len(live), *([seq[i] for i in live] + list(anchors)))):
+            seq[i] = o
+        return tuple(seq) if isinstance(outs, tuple) else seq[0]
+
+    cls.forward, cls.backward = staticmethod(once_forward), staticmethod(once_backward)
+    return cls
 
 
 def normalize(x, eps=1e-5):

@@ -175,6 +175,7 @@ def _make_light_struct(renderer):
     return light
 
 
+@_util.once_differentiable
 class _FrontEnd(torch.autograd.Function):
     """forward(ctx, vertices, textures | None, faces_idx, setup, *camera)
     -> (faces [B,F,3,3], lit textures [B,F,ts,ts,ts,3] | None), or with `colors` (the front-end for the rasterizer's

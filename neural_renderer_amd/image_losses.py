@@ -171,6 +171,7 @@ def _weights_array(weights):
     return (ctypes.c_double * MAX_LEVELS)(*weights)
 
 
+@_util.once_differentiable
 class _IoULoss(torch.autograd.Function):
     """forward(ctx, alpha [B,1,H,W], target [B or 1,1,H,W], weights, eps) -> loss [B]; the target and the 2 levels sums of
     every image are kept for the backward when one can follow."""
@@ -206,6 +207,7 @@ class _IoULoss(torch.autograd.Function):
         return grad, None, None, None
 
 
+@_util.once_differentiable
 class _SquaredError(torch.autograd.Function):
     """forward(ctx, images [B,C,H,W], target [B or 1,C,H,W], mask [B or 1,1,H,W] or None, weights) -> loss [B]; the backward
     recomputes the differences from the inputs."""
@@ -372,6 +374,7 @@ def _ssim_launch(x, t, m, window, c1, c2, valid, mean, want_map, want_grad):
     return loss, smap, ((maps, scales) if want_grad else None)
 
 
+@_util.once_differentiable
 class _SSIMLoss(torch.autograd.Function):
     """forward(ctx, images [B,C,H,W], target [B or 1,C,H,W], mask [B or 1,1,H,W] or None, window, c1, c2, valid, mean) ->
     loss [B]; when a backward can follow, the inputs, the forward's three maps M1, M2, M3 and k per image are kept for it."""

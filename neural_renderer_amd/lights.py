@@ -184,6 +184,7 @@ def _lights_struct(params, flags):
     return s
 
 
+@_util.once_differentiable
 class _LightColors(torch.autograd.Function):
     """forward(ctx, setup, vertices [B,Nv,3], ia, id, ca, cd, direction, sh | None) -> [B,F,3] | [B,F,3,3];
     setup = (indices, offsets, entries, idx_per_batch, per-image flags, fill_back, smooth)."""

@@ -180,6 +180,7 @@ def flatness_loss_torch(vertices, faces, eps=1e-6):
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
+@_util.once_differentiable
 class _LaplacianLoss(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], tables) -> loss [B]; delta [B,Nv,3] is kept for the backward when one can follow."""
 
@@ -213,6 +214,7 @@ class _LaplacianLoss(torch.autograd.Function):
         return grad_v, None
 
 
+@_util.once_differentiable
 class _FlatnessLoss(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], tables, eps) -> loss [B]"""
 
@@ -437,6 +439,7 @@ def cotangent_laplacian_loss_torch(vertices, faces, eps=1e-12):
     return loss[0] if squeeze else loss
 
 
+@_util.once_differentiable
 class _EdgeLengthLoss(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], edge tables, target tensor or None, target number) -> loss [B]; nothing but the vertices
     is saved: the backward recomputes every edge."""
@@ -474,6 +477,7 @@ class _EdgeLengthLoss(torch.autograd.Function):
         return grad_v, None, None, None
 
 
+@_util.once_differentiable
 class _CotangentLaplacianLoss(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], adjacency (vertex_colors._adjacency), eps) -> loss [B]; cot [B,F,3] and H [B,Nv,3] are
     kept for the backward when one can follow, and only then."""

@@ -87,6 +87,7 @@ def corner_normals_torch(vertices, faces, smooth=False, fill_back=True):
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
+@_util.once_differentiable
 class _VertexNormals(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], setup) -> n_v [B,Nv,3]; setup = (indices, offsets, entries, idx_per_batch)."""
 
@@ -115,6 +116,7 @@ class _VertexNormals(torch.autograd.Function):
         return grad_v, None
 
 
+@_util.once_differentiable
 class _FaceNormals(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], setup) -> n_f [B,Nf,3]; setup as in _VertexNormals."""
 
@@ -144,6 +146,7 @@ class _FaceNormals(torch.autograd.Function):
         return grad_v, None
 
 
+@_util.once_differentiable
 class _CornerNormals(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], setup) -> corner normals [B,F,3,3];
     setup = (indices, offsets, entries, idx_per_batch, fill_back, smooth)."""

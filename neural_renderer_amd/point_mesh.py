@@ -221,6 +221,7 @@ def _sorted_by(ids, count):
     return order.to(torch.int32), torch.searchsorted(sorted_ids.contiguous(), bounds).to(torch.int32)
 
 
+@_util.once_differentiable
 class _PointMesh(torch.autograd.Function):
     """forward(ctx, points [B or 1,N,3], vertices [B,Nv,3], faces, to_faces, to_points, split) -> (dist2_points [B,N],
     face_ids int32, barycentric_points, dist2_faces [B,F], point_ids int32, barycentric_faces); a direction that is not
@@ -284,6 +285,7 @@ class _PointMesh(torch.autograd.Function):
         return grad_points, grad_vertices, None, None, None, None
 
 
+@_util.once_differentiable
 class _LossSum(torch.autograd.Function):
     """forward(ctx, dist2_points [B,N] or None, dist2_faces [B,F] or None, wp, wf) -> loss [B]"""
 

@@ -18,7 +18,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _util
 from ._lib import on_device as _on_device, stream_ptr as _stream_ptr
 from .uv_textures import UVImages, pack_images, unpack_image_gradients
 from .vertex_colors import CornerColors
@@ -557,6 +557,7 @@ def _backward_impl(cfg, r, g_rgb, g_alpha, g_depth, want):
     return grad_faces, grads
 
 
+@_util.once_differentiable
 class _RasterizeFunction(torch.autograd.Function):
     """forward(ctx, faces, cfg, source, *inputs) -> (rgb_map [B,S,S,3] | None, alpha_map [B,S,S] | None,
     depth_map [B,S,S] | None, face_index_map); backward(ctx, g_rgb, g_alpha, g_depth, _) -> (grad_faces, None, None, one
@@ -675,6 +676,7 @@ def clear_graph_replay_cache():
     _GRAPH_CACHE.clear()
 
 
+@_util.once_differentiable
 class _GraphedRasterizeFunction(torch.autograd.Function):
     """The operator replayed from captured graphs (see GRAPH_REPLAY): same results as _RasterizeFunction."""
 
@@ -754,6 +756,7 @@ def _graph_entry(faces, src, inputs, cfg):
     return entry
 
 
+@_util.once_differentiable
 class _ImageEpilogue(torch.autograd.Function):
     """rgb_map [B,S,S,3] -> [B,3,is,is], alpha / depth maps [B,S,S] -> [B,is,is]: NHWC -> NCHW, vertical flip and (with
     anti-aliasing) the 2x2 mean of rasterize.py:953-969, forward and backward each as one kernel (csrc/nr_image.hip)."""

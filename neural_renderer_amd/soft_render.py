@@ -195,6 +195,7 @@ def soft_render_uv_torch(faces, faces_uv, face_image, base_color, image_table, p
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
+@_util.once_differentiable
 class _SoftRender(torch.autograd.Function):
     """forward(ctx, faces [B,F,3,3], colors [B|1,F,3] or [B|1,F,3,3], image_size, sigma, gamma, near, far, eps, background)
     -> rgba [B,4,S,S], row 0 the top row.  4-dim colours take the nr_soft_corners_* entries, 3-dim ones nr_soft_render_*."""
@@ -290,6 +291,7 @@ def soft_render(faces, colors, image_size=256, sigma=1e-4, gamma=1e-4, near=0.1,
 # ---------------------------------------------------------------------------------------------------------------------
 # UV images
 
+@_util.once_differentiable
 class _SoftRenderUV(torch.autograd.Function):
     """forward(ctx, uv (a UVImages), args, faces [B,F,3,3], light [B|1,F,3], *uv.images) -> rgba [B,4,S,S], row 0 the top
     row: the nr_soft_uv_* entries."""
@@ -459,6 +461,7 @@ def soft_render_cubes_torch(faces, textures, light=None, image_size=256, sigma=1
     return _render_torch(faces, shade, 16, image_size, sigma, gamma, near, far, eps, background_color)
 
 
+@_util.once_differentiable
 class _SoftRenderCubes(torch.autograd.Function):
     """forward(ctx, faces [B,F,3,3], textures [B|1,F,ts,ts,ts,3], light [B|1,F,3], args) -> rgba [B,4,S,S], row 0 the top row:
     the nr_soft_cubes_* entries."""

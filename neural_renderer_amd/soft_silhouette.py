@@ -69,6 +69,7 @@ def soft_silhouettes_torch(faces, image_size=256, sigma=1e-4, near=0.1, far=100)
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
+@_util.once_differentiable
 class _SoftSilhouettes(torch.autograd.Function):
     """forward(ctx, faces [B,F,3,3], image_size, sigma, near, far) -> alpha [B,S,S], row 0 the top row."""
 

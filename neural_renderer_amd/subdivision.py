@@ -178,6 +178,7 @@ def _apply_hip(x, t):
     return y
 
 
+@_util.once_differentiable
 class _ApplyLevel(torch.autograd.Function):
     """forward(ctx, x [B,Nin,C], level) -> [B,Nout,C]; the backward applies the transposed table to the gradient."""
 
@@ -187,7 +188,6 @@ class _ApplyLevel(torch.autograd.Function):
         return _apply_hip(x.detach(), level.forward)
 
     @staticmethod
-    @torch.autograd.function.once_differentiable
     def backward(ctx, grad):
         if not ctx.needs_input_grad[0]:
             return None, None

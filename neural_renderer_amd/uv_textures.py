@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _util
 from .load_obj import parse_textures, read_texture_image
 
 
@@ -180,6 +180,7 @@ def unpack_image_gradients(layout, grad_packed):
     return [grad_packed[:, off:off + h * w].view(Bi, h, w, 3) for off, h, w in layout.image_table.tolist()]
 
 
+@_util.once_differentiable
 class _BakeUV(torch.autograd.Function):
     @staticmethod
     def forward(ctx, layout, *images):

@@ -171,6 +171,7 @@ def _light_struct(ia, idir, ca, cd, direction):
     return light
 
 
+@_util.once_differentiable
 class _VertexShade(torch.autograd.Function):
     """forward(ctx, vertices [B,Nv,3], colors [Nv,3] | [Bc,Nv,3], setup) -> corner colours [B,F,3,3];
     setup = (indices, offsets, entries, idx_per_batch, nr_light, fill_back, smooth)."""

@@ -9,6 +9,7 @@ import torch
 from . import _lib, _util
 
 
+@_util.once_differentiable
 class _VerticesToFaces(torch.autograd.Function):
     @staticmethod
     def forward(ctx, vertices, faces):

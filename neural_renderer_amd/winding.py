@@ -123,6 +123,7 @@ def _gradient_torch(pair):
             torch.where(keep, kn * _cross(A, B) - kd * dC, z))
 
 
+@_util.once_differentiable
 class _WindingTorch(torch.autograd.Function):
     """forward(ctx, points [B or 1,N,3], vertices [B,Nv,3], faces) -> w [B,N], in chunks of points; the sums in double"""
 
@@ -177,6 +178,7 @@ class _WindingTorch(torch.autograd.Function):
 # ---------------------------------------------------------------------------------------------------------------------
 # HIP
 
+@_util.once_differentiable
 class _Winding(torch.autograd.Function):
     """forward(ctx, points [B or 1,N,3], vertices [B,Nv,3], faces, split) -> w [B,N]"""
 
