@@ -98,7 +98,8 @@ extern "C" {
                           *        nr_point_mesh_points_to_faces, nr_point_mesh_faces_to_points, nr_point_mesh_loss,
                           *        nr_point_mesh_backward_points, nr_point_mesh_backward_vertices, nr_point_mesh_workspace_bytes;
                           *        nr_winding_forward, nr_winding_backward_points, nr_winding_backward_vertices,
-                          *        nr_winding_workspace_bytes);
+                          *        nr_winding_workspace_bytes;
+                          *        nr_ray_mesh_first_hit, nr_ray_mesh_any_hit, nr_ray_mesh_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -1180,6 +1181,38 @@ int nr_winding_backward_vertices(const float *points, const float *vertices, con
                                  const int32_t *adj_entries, const float *grad_winding, float *grad_vertices, int32_t batch_size,
                                  int32_t num_points, int32_t num_vertices, int32_t num_faces, int32_t points_per_batch,
                                  int32_t split, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Ray casting (not in the reference's library; DESIGN "Ray casting"): rays o + t d with origins and directions [B, R, 3] -- or ONE
+ * bundle [R, 3] each for the batch with rays_per_batch = 0 (any value but 0 and 1: NR_E_MODE) --, d not normalised, world-space
+ * vertices [B, Nv, 3] and ONE topology faces [F, 3] int32.  Whether a ray hits a face is csrc/nr_ray_triangle.h, one definition
+ * (the same bits for the same pair): with e1 = v1 - v0, e2 = v2 - v0, pvec = d x e2, det = e1 . pvec, tvec = o - v0, qvec =
+ * tvec x e1, s = sign(det), D = |det|, U = s (tvec . pvec), V = s (d . qvec), T = s (e2 . qvec) a hit iff D > 0, U >= 0, V >= 0,
+ * U + V <= D, with cull = 1 det > 0 (cull neither 0 nor 1: NR_E_MODE), and near <= t < far for t = T / D (a NaN near or far:
+ * NR_E_MODE; far may be +inf).  A NaN fails every test; a face with a non-finite corner and a face with D = 0 are never hit.
+ *   nr_ray_mesh_first_hit: per ray the smallest t by a brute-force sweep, a strict < over ascending face numbers (the lowest
+ *     face wins a tie): t [B, R], face_ids [B, R] int32, barycentric [B, R, 3] = (max((1 - w1) - w2, 0), w1 = U / D, w2 = V / D).
+ *     A miss reports t = +inf, face_id = -1 and weights 0.
+ *   nr_ray_mesh_any_hit: occluded [B, R] bytes, 1 when any face is hit, else 0.
+ *   split: 0 lets the call decide whether to cut the faces over several workgroups, n >= 1 asks for n parts (1: none); the
+ *   parts are merged in ascending order with the same strict < (with OR), so the result does not depend on it.  The workspace
+ *   holds the parts: nr_ray_mesh_workspace_bytes(B, R, F, any_hit, split), 0 when the call is not split (workspace may then be
+ *   NULL).
+ * Sizes: 1 <= B <= 65535, B R <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * same bits in every run, for an image alone or inside a batch, split or not.  Every output element is stored exactly once; no
+ * call synchronises the host; NR_E_* before any launch (NULL before sizes, sizes before modes).
+ */
+size_t nr_ray_mesh_workspace_bytes(int32_t batch_size, int32_t num_rays, int32_t num_faces, int32_t any_hit, int32_t split);
+
+int nr_ray_mesh_first_hit(const float *origins, const float *directions, const float *vertices, const int32_t *faces, float *t,
+                          int32_t *face_ids, float *barycentric, int32_t batch_size, int32_t num_rays, int32_t num_vertices,
+                          int32_t num_faces, int32_t rays_per_batch, double near, double far, int32_t cull, int32_t split,
+                          void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_ray_mesh_any_hit(const float *origins, const float *directions, const float *vertices, const int32_t *faces,
+                        unsigned char *occluded, int32_t batch_size, int32_t num_rays, int32_t num_vertices, int32_t num_faces,
+                        int32_t rays_per_batch, double near, double far, int32_t cull, int32_t split, void *workspace,
+                        size_t workspace_bytes, void *stream);
 
 /*
  * Image losses (not in the reference; DESIGN "Image losses"): the objective of a fit on images, one loss per image, on an

@@ -81,6 +81,18 @@ class Mesh(nn.Module):
         from .winding import signed_distance
         return signed_distance(points, self.vertices, self.faces, implementation)
 
+    def cast_rays(self, origins, directions, **kw):
+        """ray_mesh.ray_mesh_intersect of the rays and the module's own vertices and faces (not in the reference): (t,
+        face_ids, barycentric); near, far, cull_backfaces and implementation as keywords."""
+        from .ray_mesh import ray_mesh_intersect
+        return ray_mesh_intersect(origins, directions, self.vertices, self.faces, **kw)
+
+    def visible_vertices(self, eye, **kw):
+        """ray_mesh.vertex_visibility of the module's own vertices and faces from `eye` (not in the reference): bool
+        [num_vertices]; eps and implementation as keywords."""
+        from .ray_mesh import vertex_visibility
+        return vertex_visibility(self.vertices, self.faces, eye, **kw)
+
     def vertex_normals(self, implementation=None):
         """normals.vertex_normals of the module's own vertices and faces (not in the reference): [num_vertices, 3]."""
         from .normals import vertex_normals
