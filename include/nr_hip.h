@@ -99,7 +99,8 @@ extern "C" {
                           *        nr_point_mesh_backward_points, nr_point_mesh_backward_vertices, nr_point_mesh_workspace_bytes;
                           *        nr_winding_forward, nr_winding_backward_points, nr_winding_backward_vertices,
                           *        nr_winding_workspace_bytes;
-                          *        nr_ray_mesh_first_hit, nr_ray_mesh_any_hit, nr_ray_mesh_workspace_bytes);
+                          *        nr_ray_mesh_first_hit, nr_ray_mesh_any_hit, nr_ray_mesh_workspace_bytes;
+                          *        nr_isosurface_count, nr_isosurface_emit, nr_isosurface_workspace_bytes);
                           *        K6's two arithmetic modes on ONE band kernel for every call size (k_bpm_row: a line record per 16 lanes,
                           *        the sums of a record on the matrix pipe in double); NR_FLAG_K6_PX is ignored;
                           * 0.5.0: K6's default mode on the lane-parallel band kernel (k_bpm_px; NR_FLAG_K6_LEGACY keeps k_bpm_fast); the
@@ -1213,6 +1214,32 @@ int nr_ray_mesh_any_hit(const float *origins, const float *directions, const flo
                         unsigned char *occluded, int32_t batch_size, int32_t num_rays, int32_t num_vertices, int32_t num_faces,
                         int32_t rays_per_batch, double near, double far, int32_t cull, int32_t split, void *workspace,
                         size_t workspace_bytes, void *stream);
+
+/*
+ * Isosurface extraction (not in the reference's library; DESIGN "Isosurface extraction"): marching tetrahedra on values
+ * [B, D, H, W] at the level iso (rounded to float32), inside = value < iso (above = 0) or value > iso (above = 1; neither: NR_E_MODE,
+ * as a non-finite iso); a node at iso is outside.  The cut of a cell, the triangles of every case, their orientation and the
+ * order of vertices and faces are csrc/nr_marching_tets.h, one definition.  Two calls around ONE readback by the caller:
+ *   nr_isosurface_count: fills the workspace and totals [B, 3] int32 = per image the number of vertices, the number of
+ *     triangles (read it as unsigned) and 1 where the image holds a non-finite value (its counts then mean nothing).
+ *   nr_isosurface_emit: with the SAME workspace, untouched in between, and the same B, D, H, W, run: edge_nodes [num_vertices, 2]
+ *     int32 -- the nodes a < b (linear indices within the image) of each vertex's edge -- and faces [num_faces, 3] int32 -- vertex
+ *     numbers within the image --, the images one behind the other in the order of the batch; num_vertices and num_faces are
+ *     the sums of the totals (the rows the caller allocated: no store goes beyond them; both 0: nothing is launched and the
+ *     pointers may be NULL).  It reads the workspace only, not the values.
+ *   run: the nodes a workgroup walks, 0 = the library's choice, at most 4096 (else NR_E_SIZE); the result does not depend on it.
+ *   nr_isosurface_workspace_bytes(B, D, H, W, run): 6 bytes per node and 20 per workgroup; 0 for sizes out of range.
+ * Sizes: 1 <= B <= 65535, D, H, W >= 2, 7 D H W < 2^31 (NR_E_SIZE).  No atomics and no workgroup that waits for another: the same
+ * bits in every run, for an image alone or inside a batch.  No call synchronises the host; NR_E_* before any launch.
+ */
+size_t nr_isosurface_workspace_bytes(int32_t batch_size, int32_t depth, int32_t height, int32_t width, int32_t run);
+
+int nr_isosurface_count(const float *values, int32_t *totals, int32_t batch_size, int32_t depth, int32_t height, int32_t width,
+                        double iso, int32_t above, int32_t run, void *workspace, size_t workspace_bytes, void *stream);
+
+int nr_isosurface_emit(int32_t *edge_nodes, int32_t *faces, size_t num_vertices, size_t num_faces, int32_t batch_size,
+                       int32_t depth, int32_t height, int32_t width, int32_t run, void *workspace, size_t workspace_bytes,
+                       void *stream);
 
 /*
  * Image losses (not in the reference; DESIGN "Image losses"): the objective of a fit on images, one loss per image, on an

@@ -47,6 +47,9 @@ from .winding import mesh_occupancy, signed_distance, voxel_centers, voxel_iou, 
 # not in the reference: ray casting -- the first hit of every ray on a mesh with a differentiable distance, occlusion, vertex
 # visibility and the rays of a renderer's camera -- the search in HIP
 from .ray_mesh import camera_rays, ray_mesh_intersect, ray_mesh_occluded, vertex_visibility
+# not in the reference: isosurface extraction -- marching tetrahedra from a grid of values to a mesh, the way back from
+# `voxelize` and `signed_distance`, with vertices differentiable in the values -- the extraction in HIP
+from .isosurface import IsoSurface, extract_isosurface, marching_tetrahedra
 # not in the reference: vertex, face and corner normals -- HIP in both directions -- for Renderer.render_normals, and the
 # rotation of a renderer's camera
 from .normals import camera_rotation, corner_normals, face_normals, vertex_normals
@@ -81,6 +84,7 @@ __all__ = ['Rasterize', 'rasterize', 'rasterize_depth', 'rasterize_rgbad', 'rast
            'closest_surface_points', 'closest_cloud_points', 'point_mesh_distance',
            'winding_number', 'mesh_occupancy', 'voxel_centers', 'voxelize', 'voxel_iou', 'signed_distance',
            'ray_mesh_intersect', 'ray_mesh_occluded', 'vertex_visibility', 'camera_rays',
+           'IsoSurface', 'extract_isosurface', 'marching_tetrahedra',
            'vertex_normals', 'face_normals', 'corner_normals', 'camera_rotation',
            'soft_silhouettes', 'soft_silhouettes_torch', 'soft_render', 'soft_render_torch', 'soft_render_uv',
            'soft_render_uv_torch', 'soft_render_cubes', 'soft_render_cubes_torch']

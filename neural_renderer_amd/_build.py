@@ -14,7 +14,7 @@ SOURCES = [os.path.join(HERE, 'csrc', n) for n in ('nr_forward.hip', 'nr_backwar
                                                       'nr_uv_pixel.hip', 'nr_vertex_colors.hip', 'nr_mesh_losses.hip', 'nr_lights.hip',
                                                       'nr_image_losses.hip', 'nr_ssim.hip', 'nr_subdivision.hip', 'nr_normals.hip',
                                                       'nr_soft_silhouette.hip', 'nr_soft_render.hip', 'nr_point_mesh.hip', 'nr_winding.hip',
-                                                      'nr_ray_mesh.hip')]
+                                                      'nr_ray_mesh.hip', 'nr_isosurface.hip')]
 # every header the sources can include: a header missing here would let needs_build() skip a needed rebuild
 HEADERS = [os.path.join(os.path.dirname(HERE), 'include', n) for n in ('nr_hip.h', 'nr_hip_profile.h')] + \
     sorted(glob.glob(os.path.join(HERE, 'csrc', '*.h')))

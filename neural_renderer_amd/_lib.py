@@ -142,6 +142,9 @@ SIGNATURES = {
     'nr_ray_mesh_workspace_bytes': (_sz, [_i32] * 5),
     'nr_ray_mesh_first_hit': (_c.c_int, [_vp] * 7 + [_i32] * 5 + [_f64] * 2 + [_i32] * 2 + [_vp, _sz, _vp]),
     'nr_ray_mesh_any_hit': (_c.c_int, [_vp] * 5 + [_i32] * 5 + [_f64] * 2 + [_i32] * 2 + [_vp, _sz, _vp]),
+    'nr_isosurface_workspace_bytes': (_sz, [_i32] * 5),
+    'nr_isosurface_count': (_c.c_int, [_vp] * 2 + [_i32] * 4 + [_f64] + [_i32] * 2 + [_vp, _sz, _vp]),
+    'nr_isosurface_emit': (_c.c_int, [_vp] * 2 + [_sz] * 2 + [_i32] * 5 + [_vp, _sz, _vp]),
     'nr_light_colors_workspace_bytes': (_sz, [_i32] * 4),
     'nr_light_colors_forward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp] + [_i32] * 6 + [_vp, _sz, _vp]),
     'nr_light_colors_backward': (_c.c_int, [_vp] * 4 + [_lights_p, _vp, _vp, _lights_grad_p] + [_i32] * 6 + [_vp, _sz, _vp]),
