@@ -1112,7 +1112,8 @@ int nr_cot_apply(const float *field, const float *cot, const int32_t *faces, con
  *     table (adj_offsets [Nv + 1], adj_entries [3 F]: 3 f + k ascending) minus (2 g w_k) r of face f's own pair, then of the
  *     points that chose f, in the order of order_points [B, N] (point numbers sorted by face id, stable) between
  *     offsets_faces[b, f] and offsets_faces[b, f + 1] ([B, F + 1]).
- * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE; also a forced
+ * split that asks for more than 2^31 - 1 workgroups; nr_point_mesh_workspace_bytes returns 0 for either).  No atomics: the
  * same bits in every run and for an image alone or inside a batch.  Every output element is stored exactly once; no call
  * synchronises the host; NR_E_* before any launch (NULL before sizes).
  */
@@ -1164,7 +1165,8 @@ int nr_point_mesh_backward_vertices(const float *points, const float *vertices, 
  *   result does not depend on it, to the bit (tile sums above 256 MiB: the call is not split).
  *   nr_winding_workspace_bytes(B, N, F, which, split), which = 0 forward, 1 backward_points, 2 backward_vertices (else 0): the
  *   tile sums of a split call, plus for 2 the corner gradients; 0: workspace may be NULL.
- * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * Sizes: 1 <= B <= 65535, B N <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE; also a forced
+ * split that asks for more than 2^31 - 1 workgroups, for which nr_winding_workspace_bytes returns 0).  No atomics: the
  * same bits in every run, for an image alone or inside a batch, split or not.  Every output element is stored exactly once; no
  * call synchronises the host; NR_E_* before any launch (NULL before sizes).
  */
@@ -1199,7 +1201,8 @@ int nr_winding_backward_vertices(const float *points, const float *vertices, con
  *   parts are merged in ascending order with the same strict < (with OR), so the result does not depend on it.  The workspace
  *   holds the parts: nr_ray_mesh_workspace_bytes(B, R, F, any_hit, split), 0 when the call is not split (workspace may then be
  *   NULL).
- * Sizes: 1 <= B <= 65535, B R <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE).  No atomics: the
+ * Sizes: 1 <= B <= 65535, B R <= (2^31 - 1) / 3, B F <= (2^31 - 1) / 18, B Nv <= (2^31 - 1) / 6 (NR_E_SIZE; also a forced
+ * split that asks for more than 2^31 - 1 workgroups, for which nr_ray_mesh_workspace_bytes returns 0).  No atomics: the
  * same bits in every run, for an image alone or inside a batch, split or not.  Every output element is stored exactly once; no
  * call synchronises the host; NR_E_* before any launch (NULL before sizes, sizes before modes).
  */

@@ -20,7 +20,7 @@
 //
 // A NaN distance never wins a strict <; the minimum starts at +inf with id 0, so ids are always in range and a row whose
 // pairs are all NaN (or +inf) reports id 0 and that pair's own, non-finite, dist2.
-#include "nr_mesh_gather.h"
+#include "nr_pair_sweep.h"
 #include "nr_point_triangle.h"
 
 using namespace nr;
@@ -175,15 +175,7 @@ __global__ __launch_bounds__(BLOCK) void k_merge(SweepArgs a)
     const int rows = FACES ? a.mesh.Nf : a.N;
     const int row = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (row >= rows) return;
-    const int cols = FACES ? a.N : a.mesh.Nf;
-    float best = __builtin_inff();
-    int id = 0;
-    for (int s = 0; s < a.S; s++) {
-        const size_t o = ((size_t)b * a.S + s) * rows + row;
-        const float d = a.part_d[o];
-        if (d < best) { best = d; id = a.part_id[o]; }
-    }
-    id = clampi(id, 0, cols - 1);
+    const int id = merge_argmin(a.part_d, a.part_id, b, a.S, rows, row, 0, (FACES ? a.N : a.mesh.Nf) - 1);
     if (FACES) finish(a, b, rows, row, id, row, id);
     else finish(a, b, rows, row, row, id, id);
 }
@@ -325,26 +317,12 @@ __global__ __launch_bounds__(BLOCK) void k_backward_vertices(BackwardArgs a, flo
 // --------------------------------------------------------------------------------------------------------------------
 // host
 
-// B on grid.y; int32 indexing of [B, n, 3] inside the kernels
-bool sizes_ok(int B, int N, int Nv, int F)
+// the split of a direction (faces: the rows are faces) -> the sweep's workgroups along x, 0: more than a grid holds
+unsigned plan(bool faces, int B, int N, int F, int split, SplitPlan &p)
 {
-    if (B < 1 || B > 65535 || N < 1 || Nv < 1 || F < 1) return false;
-    const size_t lim = 0x7fffffffull / 3;
-    return (size_t)B * (size_t)N <= lim && (size_t)B * (size_t)Nv <= lim && (size_t)B * (size_t)F <= lim;
-}
-
-// The streamed side (cols items) in S parts of `chunk` items for `rows` rows handled `per_block` to a workgroup: one part
-// when the grid fills the machine (or split == 1), else enough parts to reach SPLIT_BELOW workgroups (split > 1: that many),
-// never more than there are tiles, and no part empty.
-void plan_split(int B, int rows, int per_block, int cols, int split, int &S, int &chunk)
-{
-    const long long groups = (long long)((rows + per_block - 1) / per_block) * B;
-    const int tiles = (cols + T - 1) / T;
-    long long want = split > 0 ? split : (groups >= SPLIT_BELOW ? 1 : (SPLIT_BELOW + groups - 1) / groups);
-    if (want > tiles) want = tiles;
-    const int per_part = (tiles + (int)want - 1) / (int)want;
-    S = (tiles + per_part - 1) / per_part;
-    chunk = per_part * T;
+    const int rows = faces ? F : N, per_block = faces ? BLOCK : BLOCK * Q;
+    p = plan_split(B, rows, per_block, faces ? N : F, T, SPLIT_BELOW, split);
+    return grid_x(rows, per_block, p.S);
 }
 
 size_t part_bytes(int B, int S, int rows) { return S > 1 ? (size_t)B * S * rows * (sizeof(float) + sizeof(int32_t)) : 0; }
@@ -355,9 +333,12 @@ int sweep(bool faces, const float *points, const float *vertices, const int32_t 
     if (!points || !dist2 || !ids || !bary) return NR_E_NULL;
     SweepArgs a;
     if (int e = mesh_args(vertices, faces_idx, nullptr, nullptr, B, Nv, F, 0, 0, false, a.mesh)) return e;
-    if (!sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
-    const int rows = faces ? F : N, cols = faces ? N : F, per_block = faces ? BLOCK : BLOCK * Q;
-    plan_split(B, rows, per_block, cols, split, a.S, a.chunk);
+    if (!sweep_sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
+    SplitPlan p;
+    const unsigned groups_x = plan(faces, B, N, F, split, p);
+    if (!groups_x) return NR_E_SIZE;
+    a.S = p.S; a.chunk = p.chunk;
+    const int rows = faces ? F : N;
     const size_t need = part_bytes(B, a.S, rows);
     if (need && (!workspace || workspace_bytes < need)) return NR_E_WORKSPACE;
     a.points = points; a.N = N; a.points_per_batch = points_per_batch != 0;
@@ -365,16 +346,10 @@ int sweep(bool faces, const float *points, const float *vertices, const int32_t 
     a.part_id = need ? (int32_t *)((float *)workspace + (size_t)B * a.S * rows) : nullptr;
     a.dist2 = dist2; a.ids = ids; a.bary = bary;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)((rows + per_block - 1) / per_block * a.S), (unsigned)B);
-    if (faces) hipLaunchKernelGGL(k_faces_to_points, grid, dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(k_points_to_faces, grid, dim3(BLOCK), 0, st, a);
-    if (int rc = launch_status()) return rc;
-    if (a.S > 1) {
-        if (faces) hipLaunchKernelGGL(k_merge<true>, grid_of(rows, B), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_merge<false>, grid_of(rows, B), dim3(BLOCK), 0, st, a);
-        return launch_status();
-    }
-    return 0;
+    void (*const sweep)(SweepArgs) = faces ? k_faces_to_points : k_points_to_faces;
+    void (*const merge)(SweepArgs) = faces ? k_merge<true> : k_merge<false>;
+    return launch_sweep(a.S, [&] { hipLaunchKernelGGL(sweep, dim3(groups_x, (unsigned)B), dim3(BLOCK), 0, st, a); },
+                        [&] { hipLaunchKernelGGL(merge, grid_of(rows, B), dim3(BLOCK), 0, st, a); });
 }
 
 int backward_args(const float *points, const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
@@ -387,7 +362,7 @@ int backward_args(const float *points, const float *vertices, const int32_t *fac
     if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, F, 0, 0, need_adjacency, a.mesh)) return e;
     if (face_ids && (!bary_p || !grad_p || (need_order_p && (!order_p || !offsets_f)))) return NR_E_NULL;
     if (point_ids && (!bary_f || !grad_f || (need_order_f && (!order_f || !offsets_p)))) return NR_E_NULL;
-    if (!sizes_ok(B, N, Nv, F)) return NR_E_SIZE;
+    if (!sweep_sizes_ok(B, N, Nv, F)) return NR_E_SIZE;
     if (!face_ids && !point_ids) return NR_E_MODE;
     a.points = points; a.N = N; a.points_per_batch = points_per_batch != 0;
     a.face_ids = face_ids; a.bary_p = bary_p; a.grad_p = grad_p; a.order_p = order_p; a.offsets_f = offsets_f;
@@ -399,11 +374,9 @@ int backward_args(const float *points, const float *vertices, const int32_t *fac
 
 NR_API size_t nr_point_mesh_workspace_bytes(int32_t B, int32_t N, int32_t F, int32_t faces_to_points, int32_t split)
 {
-    if (!sizes_ok(B, N, 1, F) || split < 0) return 0;
-    const int rows = faces_to_points ? F : N, cols = faces_to_points ? N : F;
-    int S, chunk;
-    plan_split(B, rows, faces_to_points ? BLOCK : BLOCK * Q, cols, split, S, chunk);
-    return part_bytes(B, S, rows);
+    SplitPlan p;
+    if (!sweep_sizes_ok(B, N, 1, F) || split < 0 || !plan(faces_to_points != 0, B, N, F, split, p)) return 0;
+    return part_bytes(B, p.S, faces_to_points ? F : N);
 }
 
 NR_API int nr_point_mesh_points_to_faces(const float *points, const float *vertices, const int32_t *faces, float *dist2,
@@ -429,7 +402,7 @@ NR_API int nr_point_mesh_loss(const float *dist2_points, const float *dist2_face
 {
     if (!loss) return NR_E_NULL;
     if (!dist2_points && !dist2_faces) return NR_E_MODE;
-    if (!sizes_ok(B, dist2_points ? N : 1, 1, dist2_faces ? F : 1)) return NR_E_SIZE;
+    if (!rows_ok(B, dist2_points ? N : 1) || !rows_ok(B, dist2_faces ? F : 1)) return NR_E_SIZE;
     hipLaunchKernelGGL(k_loss, dim3((unsigned)B), dim3(BLOCK), 0, (hipStream_t)stream, dist2_points, dist2_faces, loss, N, F,
                        weight_points, weight_faces);
     return launch_status();

@@ -14,7 +14,7 @@
 //                   and the weights are stored -- every output element exactly once; a miss stores +inf, -1 and zeros
 // No atomics and no scratch beyond the split's parts: the same bits in every run, for an image alone or inside a batch, split
 // or not.  A NaN never wins a strict < and fails the inside test, so ids are always in [-1, F).
-#include "nr_mesh_gather.h"
+#include "nr_pair_sweep.h"
 #include "nr_ray_triangle.h"
 
 using namespace nr;
@@ -160,48 +160,24 @@ __global__ __launch_bounds__(BLOCK) void k_merge(SweepArgs a)
 {
     const int N = a.R, i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     if (i >= N) return;
-    float best = __builtin_inff();
-    int id = ANY ? 0 : -1;
-    for (int s = 0; s < a.S; s++) {
-        const size_t o = ((size_t)b * a.S + s) * N + i;
-        if (ANY) {
-            id |= a.part_id[o];
-        } else {
-            const float t = a.part_t[o];
-            if (t < best) { best = t; id = a.part_id[o]; }
-        }
+    if (ANY) {
+        int flag = 0;
+        for (int s = 0; s < a.S; s++) flag |= a.part_id[((size_t)b * a.S + s) * N + i];
+        a.occluded[(size_t)b * N + i] = (unsigned char)(flag != 0);
+    } else {
+        finish(a, b, i, merge_argmin(a.part_t, a.part_id, b, a.S, N, i, -1, a.mesh.Nf - 1));
     }
-    if (ANY) a.occluded[(size_t)b * N + i] = (unsigned char)(id != 0);
-    else finish(a, b, i, clampi(id, -1, a.mesh.Nf - 1));
 }
 
 // --------------------------------------------------------------------------------------------------------------------
 // host
 
-// B on grid.y; int32 indexing of [B, n, 3] inside the kernels
-bool sizes_ok(int B, int N, int Nv, int F)
+// the split of the faces for N rays, BLOCK * Q to a workgroup -> the sweep's workgroups along x, 0: more than a grid holds
+unsigned plan(int B, int N, int F, int split, SplitPlan &p)
 {
-    if (B < 1 || B > 65535 || N < 1 || Nv < 1 || F < 1) return false;
-    return (size_t)B * (size_t)N <= 0x7fffffffull / 3 && mesh_sizes_ok(B, Nv, F);
+    p = plan_split(B, N, BLOCK * Q, F, T, SPLIT_BELOW, split);
+    return grid_x(N, BLOCK * Q, p.S);
 }
-
-// The faces in S parts of `chunk` faces for N rays handled BLOCK * Q to a workgroup: one part when the grid fills the machine
-// (or split == 1), else enough parts to reach SPLIT_BELOW workgroups (split > 1: that many), never more than there are tiles,
-// and no part empty.
-void plan_split(int B, int N, int F, int split, int &S, int &chunk)
-{
-    const int per_block = BLOCK * Q;
-    const long long groups = (long long)((N + per_block - 1) / per_block) * B;
-    const int tiles = (F + T - 1) / T;
-    long long want = split > 0 ? split : (groups >= SPLIT_BELOW ? 1 : (SPLIT_BELOW + groups - 1) / groups);
-    if (want > tiles) want = tiles;
-    const int per_part = (tiles + (int)want - 1) / (int)want;
-    S = (tiles + per_part - 1) / per_part;
-    chunk = per_part * T;
-}
-
-// the sweep's workgroups along x, in 64 bits: the entry points refuse a count above 2^31 - 1 (NR_E_SIZE)
-long long grid_x(int N, int S) { return (long long)((N + BLOCK * Q - 1) / (BLOCK * Q)) * S; }
 
 size_t part_bytes(int B, int S, int N, bool any)
 {
@@ -216,11 +192,12 @@ int run(bool any, const float *origins, const float *directions, const float *ve
     if (any ? !occluded : (!t || !ids || !bary)) return NR_E_NULL;
     SweepArgs a;
     if (int e = mesh_args(vertices, faces_idx, nullptr, nullptr, B, Nv, F, 0, 0, false, a.mesh)) return e;
-    if (!sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
+    if (!sweep_sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
     if ((rays_per_batch != 0 && rays_per_batch != 1) || (cull != 0 && cull != 1) || near != near || far != far) return NR_E_MODE;
-    plan_split(B, N, F, split, a.S, a.chunk);
-    const long long groups_x = grid_x(N, a.S);
-    if (groups_x > 0x7fffffffll) return NR_E_SIZE;  // (a forced split near the tile count on a very large bundle)
+    SplitPlan p;
+    const unsigned groups_x = plan(B, N, F, split, p);
+    if (!groups_x) return NR_E_SIZE;  // (a forced split near the tile count on a very large bundle)
+    a.S = p.S; a.chunk = p.chunk;
     const size_t need = part_bytes(B, a.S, N, any);
     if (need && (!workspace || workspace_bytes < need)) return NR_E_WORKSPACE;
     a.origins = origins; a.directions = directions; a.R = N; a.rays_per_batch = rays_per_batch;
@@ -229,27 +206,19 @@ int run(bool any, const float *origins, const float *directions, const float *ve
     a.part_t = need && !any ? (float *)((int32_t *)workspace + (size_t)B * a.S * N) : nullptr;
     a.t = t; a.ids = ids; a.bary = bary; a.occluded = occluded;
     hipStream_t st = (hipStream_t)stream;
-    const dim3 grid((unsigned)groups_x, (unsigned)B);
-    if (any) hipLaunchKernelGGL(k_sweep<true>, grid, dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(k_sweep<false>, grid, dim3(BLOCK), 0, st, a);
-    if (int rc = launch_status()) return rc;
-    if (a.S > 1) {
-        if (any) hipLaunchKernelGGL(k_merge<true>, grid_of(N, B), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_merge<false>, grid_of(N, B), dim3(BLOCK), 0, st, a);
-        return launch_status();
-    }
-    return 0;
+    void (*const sweep)(SweepArgs) = any ? k_sweep<true> : k_sweep<false>;
+    void (*const merge)(SweepArgs) = any ? k_merge<true> : k_merge<false>;
+    return launch_sweep(a.S, [&] { hipLaunchKernelGGL(sweep, dim3(groups_x, (unsigned)B), dim3(BLOCK), 0, st, a); },
+                        [&] { hipLaunchKernelGGL(merge, grid_of(N, B), dim3(BLOCK), 0, st, a); });
 }
 
 }  // namespace
 
 NR_API size_t nr_ray_mesh_workspace_bytes(int32_t B, int32_t R, int32_t F, int32_t any_hit, int32_t split)
 {
-    if (!sizes_ok(B, R, 1, F) || split < 0) return 0;
-    int S, chunk;
-    plan_split(B, R, F, split, S, chunk);
-    if (grid_x(R, S) > 0x7fffffffll) return 0;  // (the call itself returns NR_E_SIZE)
-    return part_bytes(B, S, R, any_hit != 0);
+    SplitPlan p;
+    if (!sweep_sizes_ok(B, R, 1, F) || split < 0 || !plan(B, R, F, split, p)) return 0;  // (the call itself: NR_E_SIZE)
+    return part_bytes(B, p.S, R, any_hit != 0);
 }
 
 NR_API int nr_ray_mesh_first_hit(const float *origins, const float *directions, const float *vertices, const int32_t *faces,

@@ -14,7 +14,7 @@
 // the tile sums added in double, ascending, from 0; the total scaled in double and rounded once.  A split call stores the tile
 // sums and k_merge adds them in that order, so the result does not depend on the split, to the bit.
 // No atomics and no scratch: every output stored once, the same bits in every run and for an image alone or inside a batch.
-#include "nr_mesh_gather.h"
+#include "nr_pair_sweep.h"
 #include "nr_solid_angle.h"
 
 using namespace nr;
@@ -234,40 +234,23 @@ __global__ __launch_bounds__(BLOCK) void k_gather(MeshArgs a, const float *__res
 
 enum { FORWARD = 0, BACKWARD_POINTS = 1, BACKWARD_VERTICES = 2 };
 
-// B on grid.y; int32 indexing of [B, n, 3] inside the kernels
-bool sizes_ok(int B, int N, int Nv, int F)
-{
-    if (B < 1 || B > 65535 || N < 1 || Nv < 1 || F < 1) return false;
-    const size_t lim = 0x7fffffffull / 3;
-    return (size_t)B * (size_t)N <= lim && mesh_sizes_ok(B, Nv, F);
-}
-
-// The streamed side (cols items) in S parts of `chunk` items for `rows` rows handled `per_block` to a workgroup: one part
-// when the grid fills the machine (or split == 1), else enough parts to reach SPLIT_BELOW workgroups (split > 1: that many),
-// never more than there are tiles, and no part empty.  A split call stores `values` doubles per row and tile; above PART_CAP
-// bytes it is not split.  -> the bytes of the tile sums
-size_t plan_split(int B, int rows, int per_block, int cols, int split, int values, int &S, int &chunk, int &tiles)
-{
-    const long long groups = (long long)((rows + per_block - 1) / per_block) * B;
-    tiles = (cols + T - 1) / T;
-    long long want = split > 0 ? split : (groups >= SPLIT_BELOW ? 1 : (SPLIT_BELOW + groups - 1) / groups);
-    if (want > tiles) want = tiles;
-    const int per_part = (tiles + (int)want - 1) / (int)want;
-    S = (tiles + per_part - 1) / per_part;
-    chunk = per_part * T;
-    const size_t bytes = (size_t)B * tiles * rows * values * sizeof(double);
-    if (S > 1 && bytes <= PART_CAP) return bytes;
-    S = 1;
-    chunk = tiles * T;
-    return 0;
-}
-
 size_t corner_bytes(int B, int F) { return ((size_t)B * F * 9 * sizeof(float) + 15) / 16 * 16; }
 
-size_t plan(int which, int B, int N, int F, int split, int &S, int &chunk, int &tiles)
+// The split of call `which` -> the sweep's workgroups along x, 0: the split asks for more than a grid holds (judged on the
+// split that was asked for, before the cap).  A split call stores 1, 3 or 9 doubles per row and tile, `bytes` in all; above
+// PART_CAP bytes it is not split.
+unsigned plan(int which, int B, int N, int F, int split, SplitPlan &p, size_t &bytes)
 {
-    if (which == BACKWARD_VERTICES) return plan_split(B, F, BLOCK, N, split, 9, S, chunk, tiles);
-    return plan_split(B, N, BLOCK * Q, F, split, which == FORWARD ? 1 : 3, S, chunk, tiles);
+    const bool faces = which == BACKWARD_VERTICES;
+    const int rows = faces ? F : N, per_block = faces ? BLOCK : BLOCK * Q, values = faces ? 9 : (which == FORWARD ? 1 : 3);
+    p = plan_split(B, rows, per_block, faces ? N : F, T, SPLIT_BELOW, split);
+    const unsigned groups_x = grid_x(rows, per_block, p.S);
+    bytes = (size_t)B * p.tiles * rows * values * sizeof(double);
+    if (!groups_x || (p.S > 1 && bytes <= PART_CAP)) return groups_x;
+    p.S = 1;
+    p.chunk = p.tiles * T;
+    bytes = 0;
+    return grid_x(rows, per_block, 1);
 }
 
 int run(int which, const float *points, const float *vertices, const int32_t *faces_idx, const int32_t *adj_offsets,
@@ -277,27 +260,25 @@ int run(int which, const float *points, const float *vertices, const int32_t *fa
     if (!points || !out || (which != FORWARD && !grad)) return NR_E_NULL;
     SweepArgs a;
     if (int e = mesh_args(vertices, faces_idx, adj_offsets, adj_entries, B, Nv, F, 0, 0, which == BACKWARD_VERTICES, a.mesh)) return e;
-    if (!sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
+    if (!sweep_sizes_ok(B, N, Nv, F) || split < 0) return NR_E_SIZE;
     if (points_per_batch != 0 && points_per_batch != 1) return NR_E_MODE;
-    const size_t parts = plan(which, B, N, F, split, a.S, a.chunk, a.tiles);
+    SplitPlan p;
+    size_t parts;
+    const unsigned groups_x = plan(which, B, N, F, split, p, parts);
+    if (!groups_x) return NR_E_SIZE;
+    a.S = p.S; a.chunk = p.chunk; a.tiles = p.tiles;
     const size_t corners = which == BACKWARD_VERTICES ? corner_bytes(B, F) : 0;
     if (parts + corners && (!workspace || workspace_bytes < parts + corners)) return NR_E_WORKSPACE;
     a.points = points; a.grad = grad; a.N = N; a.points_per_batch = points_per_batch;
     a.part = parts ? (double *)((char *)workspace + corners) : nullptr;
     a.out = which == BACKWARD_VERTICES ? (float *)workspace : out;
     hipStream_t st = (hipStream_t)stream;
-    const int rows = which == BACKWARD_VERTICES ? F : N, per_block = which == BACKWARD_VERTICES ? BLOCK : BLOCK * Q;
-    const dim3 grid((unsigned)((rows + per_block - 1) / per_block * a.S), (unsigned)B);
-    if (which == FORWARD) hipLaunchKernelGGL(k_sweep<1>, grid, dim3(BLOCK), 0, st, a);
-    else if (which == BACKWARD_POINTS) hipLaunchKernelGGL(k_sweep<3>, grid, dim3(BLOCK), 0, st, a);
-    else hipLaunchKernelGGL(k_faces, grid, dim3(BLOCK), 0, st, a);
-    if (int rc = launch_status()) return rc;
-    if (a.S > 1) {
-        if (which == FORWARD) hipLaunchKernelGGL(k_merge<1>, grid_of(rows, B), dim3(BLOCK), 0, st, a);
-        else if (which == BACKWARD_POINTS) hipLaunchKernelGGL(k_merge<3>, grid_of(rows, B), dim3(BLOCK), 0, st, a);
-        else hipLaunchKernelGGL(k_merge<9>, grid_of(rows, B), dim3(BLOCK), 0, st, a);
-        if (int rc = launch_status()) return rc;
-    }
+    const dim3 grid(groups_x, (unsigned)B), per_row = grid_of(which == BACKWARD_VERTICES ? F : N, B);
+    void (*const sweep[])(SweepArgs) = {k_sweep<1>, k_sweep<3>, k_faces};  // by `which`
+    void (*const merge[])(SweepArgs) = {k_merge<1>, k_merge<3>, k_merge<9>};
+    if (int rc = launch_sweep(a.S, [&] { hipLaunchKernelGGL(sweep[which], grid, dim3(BLOCK), 0, st, a); },
+                              [&] { hipLaunchKernelGGL(merge[which], per_row, dim3(BLOCK), 0, st, a); }))
+        return rc;
     if (which == BACKWARD_VERTICES) {
         hipLaunchKernelGGL(k_gather, grid_of(Nv, B), dim3(BLOCK), 0, st, a.mesh, (const float *)a.out, out);
         return launch_status();
@@ -309,9 +290,11 @@ int run(int which, const float *points, const float *vertices, const int32_t *fa
 
 NR_API size_t nr_winding_workspace_bytes(int32_t B, int32_t N, int32_t F, int32_t which, int32_t split)
 {
-    if (!sizes_ok(B, N, 1, F) || split < 0 || which < FORWARD || which > BACKWARD_VERTICES) return 0;
-    int S, chunk, tiles;
-    return plan(which, B, N, F, split, S, chunk, tiles) + (which == BACKWARD_VERTICES ? corner_bytes(B, F) : 0);
+    if (!sweep_sizes_ok(B, N, 1, F) || split < 0 || which < FORWARD || which > BACKWARD_VERTICES) return 0;
+    SplitPlan p;
+    size_t parts;
+    if (!plan(which, B, N, F, split, p, parts)) return 0;  // (the call itself returns NR_E_SIZE)
+    return parts + (which == BACKWARD_VERTICES ? corner_bytes(B, F) : 0);
 }
 
 NR_API int nr_winding_forward(const float *points, const float *vertices, const int32_t *faces, float *winding, int32_t B, int32_t N,

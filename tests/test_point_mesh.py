@@ -149,6 +149,11 @@ def test_argument_errors_do_not_need_a_device():
         assert fn(1, 1, 1, 1, 1, 1, 1, 4, 3, 1, 1, -1, None, 0, None) == SIZE
         assert fn(1, 1, 1, 1, 1, 1, 40000, 40000, 3, 1, 1, 0, None, 0, None) == SIZE   # B N 3 above int32
         assert fn(1, 1, 1, 1, 1, 1, 1, 5000, 3, 5000, 1, 3, None, 0, None) == WS         # a split call without its workspace
+        # a forced split on a very large cloud: more than 2^31 - 1 workgroups along x is a size error, before the workspace
+        assert fn(1, 1, 1, 1, 1, 1, 1, 600000000, 3, 100000000, 1, 7000, None, 0, None) == SIZE
+        assert fn(1, 1, 1, 1, 1, 1, 1, 600000000, 3, 100000000, 1, 1000, None, 0, None) == WS  # (fewer: the workspace is asked for)
+    for faces_to_points in (0, 1):
+        assert lib.nr_point_mesh_workspace_bytes(1, 600000000, 100000000, faces_to_points, 7000) == 0
     assert lib.nr_point_mesh_workspace_bytes(1, 5000, 5000, 0, 1) == 0
     assert lib.nr_point_mesh_workspace_bytes(1, 5000, 5000, 0, 3) == 3 * 5000 * 8
     assert lib.nr_point_mesh_workspace_bytes(1, 70, 5000, 1, 0) == 0     # one tile of points: nothing to split

@@ -144,6 +144,12 @@ def test_argument_errors_do_not_need_a_device():
     assert bv(1, 1, 1, 1, 1, 1, 1, 1, 4, 0, 1, 1, 0, None, 0, None) == SIZE
     assert bv(1, 1, 1, 1, 1, 1, 1, 1, 4, 3, 1, 7, 0, None, 0, None) == MODE
     assert bv(1, 1, 1, 1, 1, 1, 1, 1, 4, 3, 1, 1, 0, None, 0, None) == WS                 # the corner gradients need a workspace
+    # a forced split on a very large cloud: more than 2^31 - 1 workgroups along x is a size error, before the workspace
+    assert fw(1, 1, 1, 1, 1, 600000000, 3, 2000000, 1, 7000, None, 0, None) == SIZE
+    assert bp(1, 1, 1, 1, 1, 1, 600000000, 3, 2000000, 7000, None, 0, None) == SIZE
+    assert bv(1, 1, 1, 1, 1, 1, 1, 1, 600000000, 3, 100000000, 1, 7000, None, 0, None) == SIZE
+    assert all(lib.nr_winding_workspace_bytes(1, 600000000, 2000000, which, 7000) == 0 for which in (0, 1))
+    assert lib.nr_winding_workspace_bytes(1, 600000000, 100000000, 2, 7000) == 0
     size = lib.nr_winding_workspace_bytes
     assert size(1, 5000, 5000, 0, 1) == 0
     tiles = (5000 + T - 1) // T
