@@ -48,23 +48,7 @@ __device__ __forceinline__ void compute_face_inv(const float px[3], const float 
 // pixel centre in NDC: (2. * i + 1 - is) / is evaluated in double, rasterize.py:291-292
 __device__ __forceinline__ float pixel_center(int i, int S) { return (float)((2.0 * i + 1 - S) / S); }
 
-__device__ __forceinline__ float wave_sum(float v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
-// inclusive prefix sum over the 64 lanes of a wave (lane = threadIdx.x & 63): lane l returns v of the lanes 0 .. l
-__device__ __forceinline__ int wave_incl_scan(int v, int lane)
-{
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int t = __shfl_up(v, o, WAVE);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
+// (wave_sum, wave_incl_scan and the other fixed-order sums and scans: nr_reduce.h, included below)
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return min(max(v, lo), hi); }
 
@@ -593,3 +577,5 @@ int uv_images_args(const nr_face_light *lit, const nr_uv_images *uv, int B, int 
 int uv_smooth_args(const nr_corner_light *lit, const nr_uv_images *uv, int B, int F, FaceLight &fl, UVShade &out);
 
 }  // namespace nr
+
+#include "nr_reduce.h"  // fixed-order sums and scans: every kernel file gets them with this header

@@ -180,19 +180,6 @@ struct FaceWaveLds {
     int pix[FR_PIX];
 };
 
-// inclusive prefix sum over the 64 lanes with DPP moves only (no LDS crossbar round trips): Hillis-Steele inside each row of 16
-// lanes, then the row totals are passed on (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
-__device__ __forceinline__ int wave_inclusive_sum(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return v;
-}
-
 // LDS hand-over between the lanes of one wave: the wave's LDS operations execute in order; the fence keeps the compiler from
 // moving accesses across and waits for the writes
 __device__ __forceinline__ void wave_lds_sync()
@@ -318,7 +305,7 @@ __global__ __launch_bounds__(256) void k_face_raster(const float *__restrict__ f
         const int b = i / F;
         L.x_lo[slot] = cd.x_lo; L.y_lo[slot] = cd.y_lo; L.bw[slot] = cd.bw; L.img[slot] = b; L.fn[slot] = i - b * F;
     }
-    const int row_end = wave_inclusive_sum(bh), row0 = row_end - bh;
+    const int row_end = wave_incl_scan_dpp(bh), row0 = row_end - bh;
     const int n_rows = __builtin_amdgcn_readlane(row_end, 63);
     constexpr bool pow2 = POW2;  // (S & (S - 1)) == 0: pixel centres with one multiply, no division in the search loop
     const float inv_s = 1.0f / (float)S;
@@ -356,7 +343,7 @@ __global__ __launch_bounds__(256) void k_face_raster(const float *__restrict__ f
                 }
                 xa -= x_lo;
             }
-            const int pix_end = wave_inclusive_sum(cnt), pix0 = pix_end - cnt;
+            const int pix_end = wave_incl_scan_dpp(cnt), pix0 = pix_end - cnt;
             const int n_pix = __builtin_amdgcn_readlane(pix_end, 63);
             for (int pbase = 0; pbase < n_pix; pbase += FR_PIX) {
                 wave_lds_sync();

@@ -9,10 +9,9 @@
 // hangs over the image's edge is cut along block borders.  Pixels outside read as 0 and add exactly 0 to every sum.  The
 // levels of a tile are formed in LDS: level 0 [16][64] from the registers, level l [16 >> l][64 >> l] by the first
 // 1024 >> 2 l threads, one value each.
-//   k_iou_forward / k_se_forward   (tile, image): every level's sums of the tile in double, reduced over the workgroup in one
-//                                  fixed order -- the wave's butterfly, then the waves' sums from LDS in wave order --, one
-//                                  partial per (image, tile, sum)
-//   k_iou_finish / k_se_finish     (image): the tiles' partials added in tile order in double, the loss evaluated in double
+//   k_iou_forward / k_se_forward   (tile, image): every level's sums of the tile in double, reduced over the workgroup in the
+//                                  fixed order of nr_reduce.h (block_sums), one partial per (image, tile, sum)
+//   k_iou_finish / k_se_finish     (image): the tiles' partials in tile order (ordered_sum), the loss evaluated in double
 //                                  and rounded once; the IoU's I_l, U_l are left as doubles for the backward
 //   k_iou_backward / k_se_backward (tile, image): elementwise over the tile.  The IoU reads the target and the saved sums, not
 //                                  alpha; the squared error recomputes its differences
@@ -113,31 +112,6 @@ __device__ __forceinline__ float level_at(const float *__restrict__ s, int l, in
     return s[level_offset(l) + (ty >> l) * (TW >> l) + (tx >> l)];
 }
 
-// The workgroup's sums of v[0 .. n) in one fixed order: the wave's butterfly (every lane ends with the same bits), then the
-// waves' sums from LDS in wave order.  Every thread of the workgroup must call it; thread k stores sum k.
-template <int N>
-__device__ __forceinline__ void block_sums_store(double (&v)[N], int n, double *__restrict__ dst)
-{
-    __shared__ double wave_sums[N][BLOCK / WAVE];
-#pragma unroll
-    for (int k = 0; k < N; k++) {
-        if (k < n) {
-            double x = v[k];
-#pragma unroll
-            for (int o = WAVE / 2; o > 0; o >>= 1) x += __shfl_xor(x, o, WAVE);
-            if ((threadIdx.x & (WAVE - 1)) == 0) wave_sums[k][threadIdx.x / WAVE] = x;
-        }
-    }
-    __syncthreads();
-    if ((int)threadIdx.x < n) {
-        const double *ws = wave_sums[threadIdx.x];
-        double s = ws[0];
-#pragma unroll
-        for (int w = 1; w < BLOCK / WAVE; w++) s += ws[w];
-        dst[threadIdx.x] = s;
-    }
-}
-
 // --------------------------------------------------------------------------------------------------------------------
 // IoU
 
@@ -181,7 +155,8 @@ __global__ __launch_bounds__(BLOCK) void k_iou_forward(const float *__restrict__
         }
     }
     const int n = 2 * levels;
-    block_sums_store(acc, n, partial + ((size_t)b * gridDim.x + blockIdx.x) * n);
+    const double sum = block_sums<BLOCK>(acc, n);
+    if (tid < n) partial[((size_t)b * gridDim.x + blockIdx.x) * n + tid] = sum;
 }
 
 // partial [B, n_tiles, 2 levels] -> loss [B], sums [B, 2 levels] (or NULL)
@@ -197,11 +172,7 @@ __global__ __launch_bounds__(BLOCK) void k_iou_finish(const double *__restrict__
 #pragma unroll
     for (int l = 0; l < MAXL; l++) {
         if (l < levels) {
-            double I = 0.0, U = 0.0;
-            for (int i = 0; i < n_tiles; i++) {
-                I += p[(size_t)i * n + 2 * l];
-                U += p[(size_t)i * n + 2 * l + 1];
-            }
+            const double I = ordered_sum(p + 2 * l, n_tiles, n), U = ordered_sum(p + 2 * l + 1, n_tiles, n);
             total += lw.w[l] * (1.0 - I / (U + eps));
             if (sums) {
                 sums[(size_t)b * n + 2 * l] = I;
@@ -305,7 +276,8 @@ __global__ __launch_bounds__(BLOCK) void k_se_forward(const float *__restrict__ 
             }
         }
     }
-    block_sums_store(acc, levels, partial + ((size_t)b * gridDim.x + blockIdx.x) * levels);
+    const double sum = block_sums<BLOCK>(acc, levels);
+    if (tid < levels) partial[((size_t)b * gridDim.x + blockIdx.x) * levels + tid] = sum;
 }
 
 // partial [B, n_tiles, levels] -> loss [B]
@@ -319,9 +291,7 @@ __global__ __launch_bounds__(BLOCK) void k_se_finish(const double *__restrict__ 
 #pragma unroll
     for (int l = 0; l < MAXL; l++) {
         if (l < levels) {
-            double S = 0.0;
-            for (int i = 0; i < n_tiles; i++) S += p[(size_t)i * levels + l];
-            total += lw.w[l] * S;
+            total += lw.w[l] * ordered_sum(p + l, n_tiles, levels);
         }
     }
     loss[b] = (float)total;

@@ -48,34 +48,11 @@ struct IsoArgs {
     unsigned long long cap_v, cap_f;
 };
 
+// exclusive prefix of v over the workgroup's threads and the workgroup's total; `part` is WAVES words of LDS (nr_reduce.h)
 template <typename T>
-__device__ __forceinline__ T wave_scan(T v, int lane)
+__device__ __forceinline__ T excl_scan(T v, T *part, T &total)
 {
-#pragma unroll
-    for (int o = 1; o < WAVE; o <<= 1) {
-        const T t = __shfl_up(v, o, WAVE);
-        if (lane >= o) v += t;
-    }
-    return v;
-}
-
-// exclusive prefix of v over the workgroup's threads and the workgroup's total; `part` is WAVES words of LDS (two barriers)
-template <typename T>
-__device__ __forceinline__ T block_scan(T v, T *part, T &total)
-{
-    const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
-    const T incl = wave_scan(v, lane);
-    if (lane == WAVE - 1) part[wave] = incl;
-    __syncthreads();
-    T base = 0;
-    total = 0;
-#pragma unroll
-    for (int w = 0; w < WAVES; w++) {
-        if (w < wave) base += part[w];
-        total += part[w];
-    }
-    __syncthreads();
-    return base + incl - v;
+    return block_excl_scan<BLOCK>(v, wave_incl_scan(v, (int)(threadIdx.x & (WAVE - 1))), part, &total);
 }
 
 // node n + the step of corner / edge `code` (4 di + 2 dj + dk) with the strides of the axes
@@ -116,7 +93,7 @@ __global__ __launch_bounds__(BLOCK) void k_count(IsoArgs a)
             word = cm | (in & 1u);
         }
         unsigned total;
-        const unsigned excl = carry + block_scan(pack, part, total);
+        const unsigned excl = carry + excl_scan(pack, part, total);
         if (valid) {
             const size_t g = (size_t)b * a.N + (size_t)n64;
             a.info[g] = (excl & 0xffffu) << 8 | word;
@@ -149,7 +126,7 @@ __global__ __launch_bounds__(BLOCK) void k_scan(const uint32_t *in, T *off, uint
         const T v0 = valid ? in[(size_t)i * 3] : 0, v1 = valid ? in[(size_t)i * 3 + 1] : 0;
         if (valid && in[(size_t)i * 3 + 2]) flag = 1;
         T t0, t1;
-        const T e0 = block_scan(v0, part, t0), e1 = block_scan(v1, part, t1);
+        const T e0 = excl_scan(v0, part, t0), e1 = excl_scan(v1, part, t1);
         if (valid) {
             off[(size_t)i * 2] = c0 + e0;
             off[(size_t)i * 2 + 1] = c1 + e1;

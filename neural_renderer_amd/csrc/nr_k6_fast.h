@@ -204,19 +204,6 @@ __device__ __forceinline__ void run_sums(int key, T &p0, T &p1)
     if (dpp_row_shl1(-1, key) == key) p0 = p1 = T(0);  // not the last lane of its run
 }
 
-// inclusive prefix sum over the 64 lanes with DPP moves only (no LDS crossbar round trips): Hillis-Steele inside each row of 16
-// lanes, then the row totals are passed on (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3)
-__device__ __forceinline__ int wave_incl_sum_dpp(int v)
-{
-    v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, true);   // row_shr:1
-    v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, true);   // row_shr:2
-    v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, true);   // row_shr:4
-    v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, true);   // row_shr:8
-    v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);  // row_bcast:15
-    v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);  // row_bcast:31
-    return v;
-}
-
 // exclusive scan of one 64-bit word of four 16-bit counters per thread over the workgroup (no field overflows: every total
 // is below 2^16); returns the exclusive prefix, *total = sum.  The two halves are scanned as ints with DPP moves: the LDS is
 // the busiest unit of this kernel and a shuffle-based scan would go through its crossbar twelve times.
@@ -224,21 +211,10 @@ template <int NT>
 __device__ __forceinline__ unsigned long long block_excl_scan64(unsigned long long v, unsigned long long *s_tmp,
                                                                 unsigned long long *total)
 {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
-    const int ilo = wave_incl_sum_dpp(lo), ihi = wave_incl_sum_dpp(hi);
+    const int ilo = wave_incl_scan_dpp(lo), ihi = wave_incl_scan_dpp(hi);
     const unsigned long long inc = (unsigned long long)(unsigned)ilo | ((unsigned long long)(unsigned)ihi << 32);
-    if (lane == 63) s_tmp[wave] = inc;
-    __syncthreads();
-    unsigned long long woff = 0, tot = 0;
-    for (int w = 0; w < NT / 64; ++w) {
-        const unsigned long long c = s_tmp[w];
-        if (w < wave) woff += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
+    return block_excl_scan<NT>(v, inc, s_tmp, total);
 }
 
 template <bool RGB, bool ALPHA, int MODE, int NT>
@@ -705,7 +681,7 @@ __device__ __forceinline__ bool bpm_fast_body(
                 }
             }
             int total_lines = 0;
-            const int line_off = block_excl_scan<NT>(nl, s_tmp, &total_lines);
+            const int line_off = block_excl_scan<NT>(nl, wave_incl_scan(nl, (int)(threadIdx.x & 63)), s_tmp, &total_lines);
             if (win >= total_lines) {  // (uniform) this chunk is done
                 chunk += NT;
                 win = 0;

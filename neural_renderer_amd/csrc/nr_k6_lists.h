@@ -238,8 +238,7 @@ __global__ __launch_bounds__(VIS_CHUNK) void k_compact_visible(const unsigned ch
     // offset of this chunk = sum of the counts of the chunks before it
     int part = 0;
     for (int c = tid; c < chunk; c += VIS_CHUNK) part += chunk_count[(size_t)b * n_chunks + c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, WAVE);
+    part = wave_sum(part);
     const int fn = chunk * VIS_CHUNK + tid;
     const bool v = fn < F && flags[(size_t)b * F + fn] != 0;
     int off, own;
@@ -260,25 +259,6 @@ __global__ __launch_bounds__(VIS_CHUNK) void k_compact_visible(const unsigned ch
         }
     }
     if (chunk == n_chunks - 1 && tid == 0) vis_count[b] = chunk_rank_total(own, s_part);
-}
-
-// exclusive scan of one int per thread over the workgroup of NT threads; returns the exclusive prefix, *total = sum
-template <int NT>
-__device__ __forceinline__ int block_excl_scan(int v, int *s_tmp, int *total)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int inc = wave_incl_scan(v, lane);
-    if (lane == 63) s_tmp[wave] = inc;
-    __syncthreads();
-    int woff = 0, tot = 0;
-    for (int w = 0; w < NT / 64; ++w) {
-        const int c = s_tmp[w];
-        if (w < wave) woff += c;
-        tot += c;
-    }
-    __syncthreads();
-    *total = tot;
-    return woff + inc - v;
 }
 
 // rasterize.py:651 / :656 / :722 / :727: `dist += eps` when 0 < dist, `dist -= eps` otherwise (eps is a double literal there).

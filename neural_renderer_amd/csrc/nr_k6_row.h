@@ -543,7 +543,7 @@ __device__ __forceinline__ void bpm_row_body(
             int rank = 0;
             if (has_b) rank = atomicAdd(&hist[key], 1);
             wave_lds_handover();
-            const int cnt = hist[lane], incl = wave_incl_sum_dpp(cnt);
+            const int cnt = hist[lane], incl = wave_incl_scan_dpp(cnt);
             const int n_out = __builtin_amdgcn_readlane(incl, 63);
             wave_lds_handover();
             hist[lane] = incl - cnt;

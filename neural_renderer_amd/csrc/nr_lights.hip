@@ -4,15 +4,15 @@
 // gradients to the vertices and to every parameter.  The result feeds the rasterizer's face_light input.
 //
 // Every sum around a vertex is a GATHER through the vertex -> (face, corner) table of nr_vertex_colors.hip, every sum over an
-// image is reduced in one fixed order (nr_mesh_losses.hip's scheme): no atomics, the same bits in every run.
+// image is reduced in the fixed order of nr_reduce.h: no atomics, the same bits in every run.
 //   k_face_light           flat forward: (image, face) -> the colours of the face and of its reversed copy
 //   k_vertex_light         smooth forward 1: (image, vertex) -> both colours into the workspace
 //   k_corner_light         smooth forward 2: (image, face) -> the colours of its corners (the reversed copy's flipped)
 //   k_vertex_grad<SMOOTH>  (image, vertex): flat: grad_vertices; smooth: g_m, the gradient of the vertex's normal sum
 //   k_normals_gather<true> smooth 2 (nr_mesh_gather.h): (image, vertex): grad_vertices from g_N(f) = (g_m(v0) + g_m(v1)) + g_m(v2)
 //   k_light_sums<SMOOTH>   (image, block of 256 faces / vertices): the 36 double sums of the block into the workspace
-//   k_light_finish         (image, gradient element): the blocks in block order (a shared parameter: the images in image order),
-//                          the gradient formed in double and rounded once
+//   k_light_finish         (image, gradient element): the blocks in block order (ordered_sum; a shared parameter: the images in
+//                          image order), the gradient formed in double and rounded once
 //
 // The mesh arguments and the geometry helpers (load_face, adjacency, face_normal, normal_sum, normal_to_corner) are
 // nr_mesh_gather.h's, shared with nr_vertex_colors.hip and nr_normals.hip.  With sh = NULL the forward is bit for bit
@@ -308,11 +308,12 @@ __device__ __forceinline__ void add_copy(const Lamp &L, bool has_sh, int need, c
 }
 
 // partial [B, n_blocks, NSUM]: the sums of every block of 256 faces (flat) / vertices (smooth); the sums that `need` leaves
-// out are stored as 0.  The block's sum: the wave's butterfly, then the waves' sums from LDS in wave order.
+// out are stored as 0.  The block's sums are nr_reduce.h's block_sums written out in its two steps (wave_sum, waves_sum),
+// because a group of sums that `need` leaves out -- all zeros -- skips its butterflies, which block_sums has no word for.
 template <bool SMOOTH>
 __global__ __launch_bounds__(BLOCK) void k_light_sums(LArgs a, const float *__restrict__ g, double *__restrict__ partial, int need)
 {
-    __shared__ double wave_sums[BLOCK / WAVE][NSUM];
+    __shared__ double wave_sums[NSUM][BLOCK / WAVE];
     const int i = blockIdx.x * blockDim.x + threadIdx.x, b = blockIdx.y;
     const bool has_sh = a.lights.sh != nullptr;
     double s[NSUM];
@@ -352,44 +353,29 @@ __global__ __launch_bounds__(BLOCK) void k_light_sums(LArgs a, const float *__re
 #pragma unroll
     for (int j = 0; j < NSUM; j++) {
         const int group = j < SUM_COS ? NEED_ONE : (j < SUM_SH ? NEED_COS : (j < SUM_DIR ? NEED_SH : NEED_DIR));
-        double v = s[j];
-        if (need & group) {  // (uniform)
-#pragma unroll
-            for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-        }
-        if (lane == 0) wave_sums[wave][j] = v;
+        const double v = (need & group) ? wave_sum(s[j]) : s[j];  // (uniform)
+        if (lane == 0) wave_sums[j][wave] = v;
     }
     __syncthreads();
-    if (threadIdx.x < NSUM) {
-        double t = wave_sums[0][threadIdx.x];
-#pragma unroll
-        for (int w = 1; w < BLOCK / WAVE; w++) t += wave_sums[w][threadIdx.x];
-        partial[((size_t)b * gridDim.x + blockIdx.x) * NSUM + threadIdx.x] = t;
-    }
-}
-
-// sum j of image b: its blocks in block order
-__device__ __forceinline__ double image_sum(const double *__restrict__ partial, int n_blocks, int b, int j)
-{
-    const double *p = partial + (size_t)b * n_blocks * NSUM + j;
-    double s = 0.0;
-    for (int i = 0; i < n_blocks; i++) s += p[(size_t)i * NSUM];
-    return s;
+    if (threadIdx.x < NSUM)
+        partial[((size_t)b * gridDim.x + blockIdx.x) * NSUM + threadIdx.x] = waves_sum(wave_sums[threadIdx.x]);
 }
 
 // what image b adds to gradient element e (see NELEM)
 __device__ __forceinline__ double element_of(const LArgs &a, const double *__restrict__ partial, int n_blocks, int b, int e)
 {
+    auto S = [&](int j) {  // sum j of image b: its blocks in block order
+        return ordered_sum(partial + (size_t)b * n_blocks * NSUM + j, n_blocks, NSUM);
+    };
     if (e < 2) {  // g_Ia = sum_c S[1, c] Ca_c, g_Id = sum_c S[cos, c] Cd_c
         const float *col = e == 0 ? param(a, a.lights.color_ambient, 2, b, 3) : param(a, a.lights.color_directional, 3, b, 3);
         const int j = e == 0 ? SUM_ONE : SUM_COS;
-        return (image_sum(partial, n_blocks, b, j) * (double)col[0] + image_sum(partial, n_blocks, b, j + 1) * (double)col[1]) +
-               image_sum(partial, n_blocks, b, j + 2) * (double)col[2];
+        return (S(j) * (double)col[0] + S(j + 1) * (double)col[1]) + S(j + 2) * (double)col[2];
     }
-    if (e < 5) return (double)*param(a, a.lights.intensity_ambient, 0, b, 1) * image_sum(partial, n_blocks, b, SUM_ONE + e - 2);
-    if (e < 8) return (double)*param(a, a.lights.intensity_directional, 1, b, 1) * image_sum(partial, n_blocks, b, SUM_COS + e - 5);
-    if (e < 11) return (double)*param(a, a.lights.intensity_directional, 1, b, 1) * image_sum(partial, n_blocks, b, SUM_DIR + e - 8);
-    return image_sum(partial, n_blocks, b, SUM_SH + e - 11);
+    if (e < 5) return (double)*param(a, a.lights.intensity_ambient, 0, b, 1) * S(SUM_ONE + e - 2);
+    if (e < 8) return (double)*param(a, a.lights.intensity_directional, 1, b, 1) * S(SUM_COS + e - 5);
+    if (e < 11) return (double)*param(a, a.lights.intensity_directional, 1, b, 1) * S(SUM_DIR + e - 8);
+    return S(SUM_SH + e - 11);
 }
 
 // one thread per (image, gradient element); a shared parameter is summed over the images, in image order, by image 0's thread

@@ -2,13 +2,14 @@
 // loss and the flatness (dihedral angle) loss on world-space vertices [B, Nv, 3], one topology for the whole call.
 //
 // Every sum over the neighbourhood of a vertex is a GATHER through a host-built table in ascending order, and every sum
-// over an image is reduced in one fixed order: no float or double atomics in either direction, the same bits in every run.
+// over an image is reduced in the fixed order of nr_reduce.h: no float or double atomics in either direction, the same bits in
+// every run.
 //   k_laplacian_forward    (image, vertex): delta_v, stored for the backward; |delta_v|^2 summed per block in double
 //   k_laplacian_backward   (image, vertex): the gather over N(v)
 //   k_flatness_forward     (image, quad): (cos + 1)^2 summed per block in double
 //   k_flatness_backward    (image, vertex): for each incident (quad, slot) in table order the quad's derivative is recomputed
 //                          from its four vertices and the slot's share added -- no per-quad gradient buffer
-//   k_loss_finish          (image): the blocks' partial sums added in block order in double, rounded once to loss[b]
+//   k_loss_finish          (image): the blocks' partial sums in block order (ordered_sum), rounded once to loss[b]
 //
 // The float32 operation order (no contraction, correctly rounded division and square root: _build.HIPCC_FLAGS).
 // dot(p, q) = (p0 q0 + p1 q1) + p2 q2 throughout.
@@ -55,21 +56,11 @@ constexpr int BLOCK = 256;
 
 __device__ __forceinline__ float dot3f(const float *p, const float *q) { return (p[0] * q[0] + p[1] * q[1]) + p[2] * q[2]; }
 
-// The block's sum of v in one fixed order: the wave's butterfly (every lane ends with the same bits), then the waves' sums
-// from LDS in wave order.  Every thread of the block must call it; thread 0 stores.
-__device__ __forceinline__ void block_sum_store(double v, double *__restrict__ dst)
+// block b's sum of v (nr_reduce.h: block_sum) into partial [B, gridDim.x]; every thread of the block must call it
+__device__ __forceinline__ void store_block_sum(double v, double *__restrict__ partial, int b)
 {
-    __shared__ double wave_sums[BLOCK / WAVE];
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) wave_sums[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        double s = wave_sums[0];
-#pragma unroll
-        for (int w = 1; w < BLOCK / WAVE; w++) s += wave_sums[w];
-        *dst = s;
-    }
+    const double s = block_sum<BLOCK>(v);
+    if (threadIdx.x == 0) partial[(size_t)b * gridDim.x + blockIdx.x] = s;
 }
 
 // partial [B, n_blocks] -> loss [B]: one thread per image adds its blocks in block order (n_blocks may be 0: loss = 0)
@@ -78,10 +69,7 @@ __global__ __launch_bounds__(BLOCK) void k_loss_finish(const double *__restrict_
 {
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const double *p = partial + (size_t)b * n_blocks;
-    double s = 0.0;
-    for (int i = 0; i < n_blocks; i++) s += p[i];
-    loss[b] = (float)s;
+    loss[b] = (float)ordered_sum(partial + (size_t)b * n_blocks, n_blocks, 1);
 }
 
 // --------------------------------------------------------------------------------------------------------------------
@@ -125,7 +113,7 @@ __global__ __launch_bounds__(BLOCK) void k_laplacian_forward(const float *__rest
         }
         sq = ((double)d[0] * (double)d[0] + (double)d[1] * (double)d[1]) + (double)d[2] * (double)d[2];
     }
-    block_sum_store(sq, partial + (size_t)b * gridDim.x + blockIdx.x);
+    store_block_sum(sq, partial, b);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_laplacian_backward(const float *__restrict__ delta, const int32_t *__restrict__ off,
@@ -231,7 +219,7 @@ __global__ __launch_bounds__(BLOCK) void k_flatness_forward(const float *__restr
         const float p = Q.cosv + 1.0f;
         term = (double)p * (double)p;
     }
-    block_sum_store(term, partial + (size_t)b * gridDim.x + blockIdx.x);
+    store_block_sum(term, partial, b);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_flatness_backward(const float *__restrict__ x, const int32_t *__restrict__ quads,
@@ -348,7 +336,7 @@ __global__ __launch_bounds__(BLOCK) void k_edge_length_forward(const float *__re
             term = (double)r * (double)r;
         }
     }
-    block_sum_store(term, partial + (size_t)b * gridDim.x + blockIdx.x);
+    store_block_sum(term, partial, b);
 }
 
 __global__ __launch_bounds__(BLOCK) void k_edge_length_backward(const float *__restrict__ x, const int32_t *__restrict__ off,
@@ -465,7 +453,7 @@ __global__ __launch_bounds__(BLOCK) void k_cot_apply(const float *__restrict__ f
         }
         sq = ((double)H[0] * (double)H[0] + (double)H[1] * (double)H[1]) + (double)H[2] * (double)H[2];
     }
-    if (partial) block_sum_store(sq, partial + (size_t)b * gridDim.x + blockIdx.x);
+    if (partial) store_block_sum(sq, partial, b);
 }
 
 // --------------------------------------------------------------------------------------------------------------------

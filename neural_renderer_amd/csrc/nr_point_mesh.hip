@@ -10,8 +10,8 @@
 //                      parts are merged in ascending order with the same strict <, so the result does not depend on S
 //   finish             the winning pair is evaluated once more WITH its weights (the same function, the same bits) and
 //                      dist2, the id and the barycentric weights are stored -- every output element exactly once
-//   k_loss             (image): the sums of both directions in double -- per thread in index order, the wave's butterfly, the
-//                      waves in order -- weighted, added and rounded once
+//   k_loss             (image): the sums of both directions in double -- per thread elements t, t + 256, .. in index order from
+//                      0.0, then the workgroup in the fixed order of nr_reduce.h (block_sum) -- weighted, added, rounded once
 //   k_backward_points  (image, point): its own pair's 2 g r, then the faces that chose the point through a list sorted by
 //                      point id, in list order
 //   k_backward_vertices (image, vertex): the table entries (f, k) of the vertex ascending; per entry face f's own pair,
@@ -183,26 +183,14 @@ __global__ __launch_bounds__(BLOCK) void k_merge(SweepArgs a)
 // --------------------------------------------------------------------------------------------------------------------
 // loss
 
-// the block's sum of v in one fixed order, valid in thread 0; every thread of the block must call it
-__device__ __forceinline__ double block_sum(double v)
-{
-    __shared__ double wave_sums[BLOCK / WAVE];
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) wave_sums[threadIdx.x / WAVE] = v;
-    __syncthreads();
-    double s = wave_sums[0];
-#pragma unroll
-    for (int w = 1; w < BLOCK / WAVE; w++) s += wave_sums[w];
-    __syncthreads();
-    return s;
-}
-
+// the sum of d[0 .. n), valid in thread 0; every thread of the block must call it
 __device__ __forceinline__ double strided_sum(const float *__restrict__ d, int n)
 {
     double s = 0.0;
     for (int i = threadIdx.x; i < n; i += BLOCK) s += (double)d[i];
-    return block_sum(s);
+    const double t = block_sum<BLOCK>(s);
+    __syncthreads();  // k_loss calls twice: block_sum's LDS has been read
+    return t;
 }
 
 __global__ __launch_bounds__(BLOCK) void k_loss(const float *__restrict__ dist2_points, const float *__restrict__ dist2_faces,

@@ -20,11 +20,10 @@
 //             LDS reads; at a pitch of 64 floats the 16 lanes of a read's group cover the 64 banks once), then the pixel
 //             arithmetic in registers.
 //   k_ssim_forward  (tile of the map, image): planes x, y; filters mu_x, mu_y, G*(xx), G*(yy), G*(xy); S and, when a gradient
-//                   can follow, M1, M2, M3 (below) as three float maps; the tile's sums of m (1 - S) and of m in double,
-//                   reduced over the workgroup in one fixed order -- the thread's own order (channel by channel, its four
-//                   pixels left to right), the wave's butterfly, the waves' sums from LDS in wave order --, one partial per
-//                   (image, tile, sum)
-//   k_ssim_finish   (image): the tiles' partials added in tile order in double, k and the loss evaluated in double, the loss
+//                   can follow, M1, M2, M3 (below) as three float maps; the tile's sums of m (1 - S) and of m in double --
+//                   the thread's own order (channel by channel, its four pixels left to right), then the workgroup in the
+//                   fixed order of nr_reduce.h (block_sums) --, one partial per (image, tile, sum)
+//   k_ssim_finish   (image): the tiles' partials in tile order (ordered_sum), k and the loss evaluated in double, the loss
 //                   rounded once; k left as a double for the backward
 //   k_ssim_backward (tile of the image, image): planes M1, M2, M3 and the mask over the map; a gather -- the thread sums
 //                   over the windows q that contain its pixels p --: F_i = sum_q w(q - p) m(q) M_i(q), then
@@ -170,30 +169,6 @@ __device__ __forceinline__ void load_row4(const float *__restrict__ plane, int H
     }
 }
 
-// The workgroup's two sums in one fixed order: the wave's butterfly (every lane ends with the same bits), then the waves'
-// sums from LDS in wave order.  Every thread of the workgroup must call it; thread k < 2 stores sum k.
-__device__ __forceinline__ void block_sums_store(double a, double b, double *__restrict__ dst)
-{
-    __shared__ double wave_sums[2][BLOCK / WAVE];
-#pragma unroll
-    for (int o = WAVE / 2; o > 0; o >>= 1) {
-        a += __shfl_xor(a, o, WAVE);
-        b += __shfl_xor(b, o, WAVE);
-    }
-    if ((threadIdx.x & (WAVE - 1)) == 0) {
-        wave_sums[0][threadIdx.x / WAVE] = a;
-        wave_sums[1][threadIdx.x / WAVE] = b;
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        const double *ws = wave_sums[threadIdx.x];
-        double s = ws[0];
-#pragma unroll
-        for (int w = 1; w < BLOCK / WAVE; w++) s += ws[w];
-        dst[threadIdx.x] = s;
-    }
-}
-
 struct ForwardArgs {
     const float *images, *target, *mask;  // mask may be NULL
     size_t target_stride, mask_stride;    // per image (0: shared)
@@ -283,7 +258,9 @@ void k_ssim_forward(ForwardArgs a, Window win)
             store_row4(a.grad_maps + 2 * each + at, a.Hq, a.Wq, qy, qx, M3, a.vec_out);
         }
     }
-    block_sums_store(loss, msum, a.partial + ((size_t)b * gridDim.x + blockIdx.x) * 2);
+    const double both[2] = {loss, msum};
+    const double sum = block_sums<BLOCK>(both, 2);
+    if (tid < 2) a.partial[((size_t)b * gridDim.x + blockIdx.x) * 2 + tid] = sum;
 }
 
 // partial [B, n_tiles, 2] -> loss [B], scales [B] (or NULL)
@@ -293,11 +270,7 @@ __global__ __launch_bounds__(BLOCK) void k_ssim_finish(const double *__restrict_
     const int b = blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     const double *p = partial + (size_t)b * n_tiles * 2;
-    double L = 0.0, M = 0.0;
-    for (int i = 0; i < n_tiles; i++) {
-        L += p[2 * (size_t)i];
-        M += p[2 * (size_t)i + 1];
-    }
+    const double L = ordered_sum(p, n_tiles, 2), M = ordered_sum(p + 1, n_tiles, 2);
     const double k = mean ? (M != 0.0 ? 1.0 / ((double)C * M) : 0.0) : 1.0;
     loss[b] = (float)(k * L);
     if (scales) scales[b] = k;

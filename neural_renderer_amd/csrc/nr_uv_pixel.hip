@@ -17,13 +17,6 @@ using namespace nr;
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
 // SMOOTH (nr_backward_uv_images_smooth): `light` is [B, F, 3, 3], a colour per corner, and acc_light holds nine sums per face.
 template <bool SMOOTH>
 __global__ __launch_bounds__(256) void k_uv_pixel_backward(UVShade uv, const float *__restrict__ faces,
@@ -127,7 +120,7 @@ __global__ __launch_bounds__(256) void k_uv_pixel_backward(UVShade uv, const flo
         const bool mine = key == k0;
         double s3[3];
 #pragma unroll
-        for (int k = 0; k < 3; k++) s3[k] = wave_sum_d(mine ? gl[k] : 0.0);
+        for (int k = 0; k < 3; k++) s3[k] = wave_sum(mine ? gl[k] : 0.0);
         if ((int)(threadIdx.x & (WAVE - 1)) == leader) {
 #pragma unroll
             for (int k = 0; k < 3; k++)

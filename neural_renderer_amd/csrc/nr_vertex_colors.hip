@@ -30,13 +30,6 @@ using namespace nr;
 
 namespace {
 
-__device__ __forceinline__ double wave_sum_d(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, WAVE);
-    return v;
-}
-
 // --------------------------------------------------------------------------------------------------------------------
 // rasterizer: backward to the corner colours
 
@@ -380,7 +373,7 @@ __global__ __launch_bounds__(256) void k_vs_backward_shared(VSArgs a, const floa
         s[2] += gcol[2];
     }
 #pragma unroll
-    for (int c = 0; c < 3; c++) s[c] = wave_sum_d(s[c]);
+    for (int c = 0; c < 3; c++) s[c] = wave_sum(s[c]);
     if (lane == 0) {
 #pragma unroll
         for (int c = 0; c < 3; c++) grad_colors[(size_t)v * 3 + c] = (float)s[c];
